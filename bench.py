@@ -10,6 +10,9 @@ STEADY STATE of the race, ticks 512..3584):
 bracketed by barrier + synchronize on both sides, max over ranks.  `config.ticks` states the tick range that was timed.
 After the timed region the same process also measures, as labelled secondary fields, the full BASELINE protocol
 (ticks 512..3584 of a fresh race) and the race start (ticks 0..512: everyone within 8 m, 4-player games).
+`ms_per_step` is the wall time of one timed step.  --dump-outputs DIR writes what the timed region computed in its last step
+(the karts' records, observations, actions and episode results of a fixed, seeded sample of envs; lqbatch: the controls) as
+DIR/<name>.npy; every input is seeded, so two builds run with the same arguments can be compared output for output.
 
 --gpus N with N > 1: when WORLD_SIZE is not set, THIS process starts N ranks (python -m torch.distributed.run, one per GPU)
 as a child BEFORE anything touches the GPU, relays the child's JSON line and exits with its code; it fails cleanly when the
@@ -237,6 +240,53 @@ def timed_ticks(D, env, ticks, per_rank=None):
     return D.max_time(dt)
 
 
+DUMP_SAMPLE_ENVS = 4096                # --dump-outputs: envs of a larger batch written out (a fixed, seeded sample)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _as_float(x):
+    import numpy as np
+    return x if x.dtype in (np.float32, np.float64) else x.astype(np.float64)        # (int32 / uint32 / uint8 are exact in float64)
+
+
+def env_outputs(env):
+    """what a caller of the env receives after the timed region's last tick: the karts' records (hk_get_agent_state, field by field), the
+    observations, the latched actions and the episode results; every array [envs, agents, ...] over the same fixed, seeded sample of envs
+    when the batch holds more than DUMP_SAMPLE_ENVS (their ids: sample_env_ids).  Getters only, so the karts do not move; but reading the
+    observations raises the HitWall / HitOpponent reward events (include/hk.h), as it does for any caller, so the reward accumulators the
+    lqng workload's repeat windows run on afterwards differ from those of a run without --dump-outputs (their timing does not)."""
+    import numpy as np
+    E = env.E
+    if E <= DUMP_SAMPLE_ENVS:
+        ids = np.arange(E)
+    else:
+        ids = np.sort(np.random.default_rng(0x5EED0000).choice(E, DUMP_SAMPLE_ENVS, replace=False))
+    out = {"sample_env_ids": ids.astype(np.float64)}
+    st = env.agent_state()[ids]
+    for f in st.dtype.names:
+        out["agent_" + f] = _as_float(st[f])
+    out["observations"] = env.observations()[ids]
+    steer, branch = env.get_actions()
+    out["action_steer"], out["action_branch"] = steer[ids], _as_float(branch[ids])
+    res = env.episode_results()[ids]
+    for f in res.dtype.names:
+        out["result_" + f] = _as_float(res[f])
+    return out
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64, at most DUMP_MAX_BYTES in all) -> the field for the result line"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": dirname, "files": len(arrays), "bytes": int(total)}
+
+
 def selftest_launcher(a):
     """CPU check of the N-rank plumbing (tests/test_bench_launcher.py): rendezvous, shard ranges that do not divide,
     barrier, max-over-ranks, the padded all-gather, one JSON line from rank 0.  No libhk compute, no GPU."""
@@ -341,6 +391,7 @@ def bench_rl(a, D, hk):
     dt = timed_ticks(D, env, a.steps)
     prof = env.prof_read()
     if D.rank == 0:
+        dumped = dump_outputs(a.dump_outputs, env_outputs(env)) if a.dump_outputs else None
         avg = {k: (v[0] / v[1] if v[1] else 0.0) for k, v in prof.items()}
         rows = E * 2                                   # rows per launch (one launch per team policy)
         flop_row = 2.0 * (in_dim * 256 + 2 * 256 * 256 + 4 * 256)
@@ -356,6 +407,8 @@ def bench_rl(a, D, hk):
                             "frac": ach / FP32_MFMA_PEAK_TFLOPS, "traffic": None, "avg_launch_ms": ms, "launches": prof["policy_mlp_kernel"][1],
                             "flop_per_launch": rows * flop_row, "kernel_avg_ms": avg,
                             "kernel_total_ms": {k: v[0] for k, v in prof.items()}}}
+        if dumped:
+            out["dump_outputs"] = dumped
         print(json.dumps(out), flush=True)
     D.close()
 
@@ -389,6 +442,7 @@ def bench_mcts(a, D, hk):
     dt = timed_ticks(D, env, a.steps)
     prof = env.prof_read()
     if D.rank == 0:
+        dumped = dump_outputs(a.dump_outputs, env_outputs(env)) if a.dump_outputs else None
         m = env.mcts_state()
         out = {"metric": "env-steps/sec (8-agent Complex, mixed MCTS-RL vs MCTS-LQNG)" if a8 else
                          ("env-steps/sec (2v2 OvalDuos, MCTS-RL)" if rl else "env-steps/sec (4-agent Complex, MCTS-LQNG)"),
@@ -404,6 +458,8 @@ def bench_mcts(a, D, hk):
                           "searches_per_agent_mean": float(m["searches"].mean())},
                "kernel_total_ms": {k: v[0] for k, v in prof.items()},
                "note": "the planner kernel (mcts_search_kernel) is not bracketed by hk_prof: its share = wall time - the stages above"}
+        if dumped:
+            out["dump_outputs"] = dumped
         print(json.dumps(out), flush=True)
     D.close()
 
@@ -450,6 +506,7 @@ def bench_lqbatch(a, D, hk):
     _lib.check(L.hk_create(None, C.byref(h)), None)
     batch = a.lq_batch
     rows = {}
+    dump = {}
     for N in (2, 4):
         rng = np.random.default_rng(1000 + N)
         base = [random_game(rng, N) for _ in range(256)]
@@ -465,17 +522,19 @@ def bench_lqbatch(a, D, hk):
 
         def run():
             _lib.check(L.hk_lq_solve_batch_device(h, batch, N, ptr(dev[0]), ptr(dev[1]), ptr(dev[2]), ptr(dev[3]), ptr(dev[4]), ptr(dev[5]), 3, ptr(u0), None), h)
-        for _ in range(a.warmup if a.warmup < 50 else 5):
+        for _ in range(a.warmup):
             run()
         _lib.check(L.hk_synchronize(h), h)
         _lib.check(L.hk_prof_enable(h, 1), h)
         _lib.check(L.hk_prof_reset(h), h)
-        iters = a.steps if a.steps < 500 else 20
+        iters = a.steps
         t0 = time.perf_counter()
         for _ in range(iters):
             run()
         _lib.check(L.hk_synchronize(h), h)
         dt = time.perf_counter() - t0
+        if a.dump_outputs:
+            dump["u_N%d" % N] = u0.cpu().numpy()          # the controls of the last timed call
         ms = (C.c_double * _lib.HK_PROF_STAGES)()
         n = (C.c_int64 * _lib.HK_PROF_STAGES)()
         _lib.check(L.hk_prof_read(h, ms, n), h)
@@ -483,18 +542,20 @@ def bench_lqbatch(a, D, hk):
         nn = 4 * N
         bytes_game = 8.0 * (N * 16 + N * 8 + N * nn * nn + N * nn + N * 4 + nn + 2)
         tf = batch * lq_flop(N) / 1e12 / (k_ms * 1e-3)
-        rows["N%d" % N] = {"solves_per_s_wall": batch * iters / dt, "solves_per_s_kernel": batch / (k_ms * 1e-3), "kernel_ms": k_ms,
+        rows["N%d" % N] = {"solves_per_s_wall": batch * iters / dt, "ms_per_step": dt / iters * 1e3, "kernel_launches": int(n[2]), "solves_per_s_kernel": batch / (k_ms * 1e-3), "kernel_ms": k_ms,
                            "dense_flop_per_solve": lq_flop(N), "achieved_tflops": tf, "frac_fp64_vector_peak": tf / FP64_VECTOR_PEAK_TFLOPS,
                            "algorithmic_bytes_per_solve": bytes_game, "achieved_gbs": batch * bytes_game / 1e9 / (k_ms * 1e-3),
                            "frac_hbm_peak": batch * bytes_game / 1e9 / (k_ms * 1e-3) / HBM_PEAK_GBS}
     r4 = rows["N4"]
     out = {"metric": "LQ Nash solves/sec (hk_lq_solve_batch, N = 4 players, batch 262 144)", "value": r4["solves_per_s_wall"], "unit": "solves/s",
-           "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": r4["kernel_ms"], "higher_is_better": True, "scaling": "weak",
+           "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": r4["ms_per_step"], "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
            "config": {"workload": "KartLQR.solveFeedbackLQR batched: %d random games per launch (256 distinct, tiled), horizon 3, dense Q / q / R inputs" % batch},
            "roofline": {"bound": "fp64_valu", "kernel": "lq_batch_kernel<4>", "achieved": r4["achieved_tflops"], "peak": FP64_VECTOR_PEAK_TFLOPS,
                         "unit": "TFLOP/s", "frac": r4["frac_fp64_vector_peak"], "traffic": None},
            "per_N": rows}
+    if a.dump_outputs:
+        out["dump_outputs"] = dump_outputs(a.dump_outputs, dump)
     print(json.dumps(out), flush=True)
     L.hk_destroy(h)
     D.close()
@@ -517,6 +578,7 @@ def bench_lqng(a, D, hk):
     dt = timed_ticks(D, env, a.steps, per_rank_ms)       # THE timed region: hk_prof off (its event records cost ~35 us per call)
     sched = env.schedule_info()                          # what the library ran for that call (hk_schedule_info)
     st = env.agent_state() if D.rank == 0 else None
+    outputs = env_outputs(env) if (a.dump_outputs and D.rank == 0) else None     # what the caller holds after the timed region's last tick
     # the same window again, back to back (up to 15 times while the race stays inside the protocol's steady stretch): how much of `value` is the
     # noise of one short sample.  `value` stays the ONE window above.
     n_rep = max(0, min(15, (STEADY_TICK + 3072 - (a.preroll + a.warmup + a.steps)) // max(a.steps, 1)))
@@ -718,6 +780,8 @@ def bench_lqng(a, D, hk):
                                      "note": "the next %d back-to-back windows of the same %d ticks (race ticks %d..%d), each timed like `value`" % (
                                          len(vals), a.steps, t_first + a.steps, t_first + a.steps * (1 + len(vals)))}
         out.update(secondary)
+        if outputs:
+            out["dump_outputs"] = dump_outputs(a.dump_outputs, outputs)
         if not a.no_cpu_baseline and D.world == 1:          # reported on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(A, seed, a.preroll)
         print(json.dumps(out), flush=True)
@@ -738,6 +802,9 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the labelled secondary measurements (protocol window, race start)")
     ap.add_argument("--mcts-iterations", type=int, default=64)
     ap.add_argument("--lq-batch", type=int, default=262144)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, <= 64 MB; "
+                         "the env workloads: a fixed, seeded sample of %d envs of a larger batch; rank 0's shard at N > 1)" % DUMP_SAMPLE_ENVS)
     ap.add_argument("--selftest-launcher", action="store_true", help="CPU check of the N-rank plumbing (gloo; no GPU, no libhk compute)")
     ap.add_argument("--same-device", action="store_true", help="every rank on GPU 0 with gloo in place of RCCL (a rehearsal of the N-rank code on a 1-GPU box; "
                                                                 "tests/test_two_ranks_one_gpu.py): not a scaling measurement")

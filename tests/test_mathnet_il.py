@@ -1,12 +1,11 @@
 """KartLQR.cs:104-105 `LHS.Solve(...)` is MathNet.Numerics' UserLU; the oracle's lu_solve (oracle/hk_oracle_lq.c) and the kernels
 (csrc/hk_lq_core.h) restate it.  tools/mathnet_il.py reads the IL of the binary the reference ships and checks the pivot rule, the order
 of every accumulation and the substitution order; the facts and the binary's SHA-256 are committed (tests/golden/mathnet_userlu_facts.json).
-Where the reference is present the facts are derived again from the binary."""
-import hashlib
+The binary is not part of this repository, so no test runs the tool's IL reader (Assembly / check()); `python tools/mathnet_il.py`
+derives the facts again where the binary lies."""
 import json
 import os
 import sys
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -41,11 +40,3 @@ def test_the_oracle_states_the_same_algorithm():
     assert body.index("for (int k = 0; k < m; k++)\n        for (int i = k + 1; i < m; i++)") < body.index("for (int k = m - 1; k >= 0; k--)")
     assert "Bm[k * nb + j] /= LU[k * m + k];" in body
     assert "-ffp-contract=off" in open(os.path.join(ROOT, "oracle", "Makefile")).read()
-
-
-@pytest.mark.skipif(not os.path.exists(M.DLL), reason="the reference (and its MathNet.Numerics.dll) is not on this machine")
-def test_facts_rederived_from_the_reference_binary():
-    facts = json.load(open(M.FACTS))
-    asm = M.Assembly(M.DLL)
-    assert hashlib.sha256(asm.d).hexdigest() == facts["sha256"]
-    assert M.check(asm) == facts["facts"]

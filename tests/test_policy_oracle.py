@@ -1,17 +1,20 @@
 """RL low-level policy, CPU side: the ONNX reader and the oracle's actor are checked against an INDEPENDENT
 evaluation of the exported graph (a small numpy interpreter of the ONNX node list, float64), on the reference's own
-trained models when /root/reference is present and on synthetic actors otherwise; plus the runtime pieces around the
-actor (StackingSensor order, zero fill after a reset, DecisionPeriod, action repeat)."""
-import glob
+trained actors (the arrays of tests/golden/reference_actors.npz and reference_actor_312.npz, written as mlagents-learn
+exports them by tests/onnx_write.py) and on synthetic actors; plus the runtime pieces around the actor (StackingSensor
+order, zero fill after a reset, DecisionPeriod, action repeat)."""
 import os
 import numpy as np
 import pytest
 import oracle_lib as O
+import onnx_write
 from hierarchicalkarting_amd import _lib, onnx_read
 from hierarchicalkarting_amd.config import make_config
 from hierarchicalkarting_amd.policy import Policy
 
-REF_MODELS = "/root/reference/Assets/Karting/Prefabs/AI"
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+TRAINED = ["HierarchicalAgent-Team-allscaledown14.onnx", "HierarchicalAgent-NonLSTM-allsolo6.onnx", "FixedHierarchicalAgent-NonLSTM-allsolo10.onnx",
+           "HierarchicalAgent-TeamDOE-all28.onnx", "FixedHierarchicalAgent-Team-all33.onnx"]
 
 
 def run_graph(model, obs, deterministic=True):
@@ -55,16 +58,27 @@ def _oracle_env(A, low_mode):
     return o, b
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference checkout not present on this box")
-@pytest.mark.parametrize("pattern,A", [("HierarchicalAgent-Team-allscaledown14.onnx", 4), ("HierarchicalAgent-NonLSTM-allsolo4.onnx", 2),
-                                       ("FixedHierarchicalAgent-Team-all30.onnx", 4)])
-def test_reference_models_through_the_oracle(pattern, A):
-    path = os.path.join(REF_MODELS, pattern)
+def _trained(pattern):
+    """a trained actor of the reference, from the arrays the repository carries"""
+    for f in ("reference_actors.npz", "reference_actor_312.npz"):
+        d = np.load(os.path.join(GOLD, f))
+        if pattern + "/W0" in d:
+            return Policy.from_arrays(d, pattern + "/")
+    raise KeyError(pattern)
+
+
+@pytest.mark.parametrize("pattern,A", [("HierarchicalAgent-Team-allscaledown14.onnx", 4), ("HierarchicalAgent-NonLSTM-allsolo6.onnx", 2),
+                                       ("FixedHierarchicalAgent-NonLSTM-allsolo10.onnx", 2), ("HierarchicalAgent-TeamDOE-all28.onnx", 4),
+                                       ("FixedHierarchicalAgent-Team-all33.onnx", 4)])
+def test_reference_models_through_the_oracle(pattern, A, tmp_path):
+    src = _trained(pattern)
+    path = onnx_write.write_actor(str(tmp_path / pattern), src)
     model = onnx_read.load(path)
     o, b = _oracle_env(A, [_lib.HK_LOW_RL] * A)
     in_dim = model["inputs"][0][1][1]
     assert in_dim % o.obs_dim == 0 and in_dim // o.obs_dim in (4, 8)      # trained on this observation layout, 4 or 8 stacked
     pol = Policy.from_onnx(path, stack=in_dim // o.obs_dim, deterministic=True)
+    assert all(np.array_equal(pol.arrays()[k], v) for k, v in src.arrays().items())        # every array read back bit for bit
     idx = o.attach_policy(pol, list(range(A)), 2)
     r = np.random.default_rng(5)
     obs = (r.standard_normal((64, pol.in_dim)) * 3.0 + pol.norm_mean).astype(np.float32)
@@ -77,18 +91,18 @@ def test_reference_models_through_the_oracle(pattern, A):
     # deterministic outputs of the graph = what the oracle latches as actions
     det_c = v["deterministic_continuous_actions"][:, 0]
     assert np.abs(np.clip(mu, -3, 3) / 3 - det_c).max() < 1e-5
+    assert (v["deterministic_discrete_actions"][:, 0] == np.argmax(lg, axis=1)).all()
 
 
-def test_every_reference_hka_model_parses():
-    if not os.path.isdir(REF_MODELS):
-        pytest.skip("reference checkout not present on this box")
+def test_every_reference_hka_model_parses(tmp_path):
+    """every trained actor the repository carries, exported and read back"""
     n = 0
-    for path in sorted(glob.glob(os.path.join(REF_MODELS, "*Hierarchical*.onnx"))):
-        pol = Policy.from_onnx(path)
+    for m in TRAINED:
+        pol = Policy.from_onnx(onnx_write.write_actor(str(tmp_path / m), _trained(m)))
         assert pol.in_dim in (212, 216, 312, 624) and pol.hidden in (128, 256) and pol.n_branch == 3 and len(pol.W) in (2, 3)
         assert pol.norm_std.min() > 0
         n += 1
-    assert n >= 40
+    assert n == len(TRAINED)
 
 
 @pytest.mark.parametrize("in_dim,hidden,layers,A", [(216, 128, 3, 2), (312, 256, 3, 4), (216, 64, 1, 2)])
