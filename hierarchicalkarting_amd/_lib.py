@@ -11,6 +11,7 @@ HK_MAX_SECTIONS = 64
 HK_NUM_SENSORS = 9
 HK_ABI_VERSION = 5
 HK_PROF_STAGES = 6
+HK_METER_PARTS = 4
 PROF_STAGE_NAMES = ("env_run_kernel", "lqn_kernel<2,3,4>", "lq_batch_kernel", "policy_mlp_kernel", "observe+stack", "env_b1_kernel")
 HK_COMM_ID_BYTES = 128
 HK_MAX_POLICIES = 4
@@ -199,6 +200,7 @@ SYMBOLS = {
     "hk_prof_reset": (C.c_int, [_H]),
     "hk_prof_read": (C.c_int, [_H, _dp, C.POINTER(C.c_int64)]),
     "hk_prof_games": (C.c_int, [_H, C.POINTER(C.c_int64)]),
+    "hk_prof_meter": (C.c_int, [_H, C.POINTER(C.c_int64)]),
     "hk_gather_count": (C.c_int, [_H, C.POINTER(C.c_int64)]),
 }
 

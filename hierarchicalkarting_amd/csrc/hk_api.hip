@@ -741,9 +741,9 @@ static void record_schedule(hk_handle h, int n_ticks, const char* rounds_mode, i
                                             : (h->dev.lqn_spread ? "queues + lqn_spread_kernel (lqn_round_kernel while the field stands close)" : "queues + lqn_round_kernel"));
     std::snprintf(buf, sizeof(buf),
                   "{\"call_ticks\": %d, \"rounds\": \"%s\", \"rounds_issued\": %d, \"kernel\": \"%s\", \"streams\": %d, \"ticks_per_launch\": %d, "
-                  "\"optimistic_plan\": %s, \"armed_in_first_launch\": %s, \"multi_player_games\": \"%s\", \"games_meter\": \"%s\", \"planner\": %s, \"actors\": %d}",
+                  "\"optimistic_plan\": %s, \"armed_in_first_launch\": %s, \"multi_player_games\": \"%s\", \"games_meter\": \"%s\", \"games_meter_value\": %d, \"planner\": %s, \"actors\": %d}",
                   n_ticks, rounds_mode, rounds, kern, h->split ? SPLIT_WAYS : 1, h->dev.P.run_cap, h->dev.exact_plan ? "true" : "false", fold ? "true" : "false",
-                  games, h->meter_sparse ? "sparse" : (h->meter_dense ? "dense" : "medium"), planner ? "true" : "false", h->n_policies);
+                  games, h->meter_sparse ? "sparse" : (h->meter_dense ? "dense" : "medium"), h->meter_games, planner ? "true" : "false", h->n_policies);
     h->sched = buf;
 }
 
@@ -1534,6 +1534,18 @@ int hk_prof_games(hk_handle h, int64_t* games)
         std::fprintf(stderr, "\n");
     }
 #endif
+    return HK_OK;
+}
+
+int hk_prof_meter(hk_handle h, int64_t* words)
+{
+    HK_NEED_ENV(h);
+    if (!words) return fail(h, HK_ERR_INVALID, "hk_prof_meter: NULL pointer");
+    static_assert(HK_METER_PARTS == hk::GAME_METER_PARTS, "hk.h HK_METER_PARTS");
+    unsigned long long m[4 * hk::GAME_METER_PARTS];
+    HK_HIP(h, hipMemcpyAsync(m, h->dev.game_stats + hk::GAME_METER, sizeof(m), hipMemcpyDeviceToHost, h->stream));
+    HK_HIP(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 4 * hk::GAME_METER_PARTS; k++) words[k] = (int64_t)m[k];
     return HK_OK;
 }
 

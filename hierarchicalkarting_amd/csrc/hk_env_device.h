@@ -551,9 +551,12 @@ __device__ inline void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
 
 // The games-per-launch meter (round 6; the host's choice between in-wave solves and queues + the pair solver's launch, hk_api.hip).  Per part of the batch p
-// (issue_rounds_split; 0 for an unsplit launch) four words at game_stats[GAME_METER + 4 p]: [0 .. 2] the multi-player games the B1 launches of rounds
-// = 0, 1, 2 mod 3 assembled — launch k counts into slot k % 3, clears slot (k + 1) % 3 and reads the finished launch's total from slot (k + 2) % 3 — and
-// [3] a decaying maximum of those totals (x 3/4 per launch: the handful of laggards' launches at the end of a call say nothing about the field).
+// (issue_rounds_split; 0 for an unsplit launch) four words at game_stats[GAME_METER + 4 p]: [0 .. 2] the multi-player games (egos that hold one) the part's
+// B1 launches assembled — the part's launch k (EnvDevice::meter_launches, counted by the host; NOT dev.round, which the tick-only last round of an exact
+// plan advances without a B1 launch) counts into slot k % 3, clears slot (k + 1) % 3 and reads the finished launch k - 1's total from slot (k + 2) % 3 —
+// and [3] a decaying maximum of those totals, m <- max(total of launch k - 1, m - (m >> 2)) (x 3/4 per launch: the handful of laggards' launches at the end
+// of a call say nothing about the field); a launch that starts the part over (the batch changed shape) sets m = 0.  hk_prof_meter reads the words;
+// tests/test_games_meter_reference_gpu.py holds them to the oracle's per-launch totals.
 constexpr int GAME_METER = 160, GAME_METER_PARTS = 4;
 constexpr int GAME_STATS_N = 160 + 4 * GAME_METER_PARTS;      // game_stats: [0, 16) games by player count, [16, 64) cycle stamps, [64, 160) lane-participation probes
 // Diagnostic build only (-DHK_LANEPROF, tools/lane_profile.py): probe k counts the waves that reach it and the lanes switched on when they do

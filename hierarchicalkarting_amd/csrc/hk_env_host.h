@@ -68,6 +68,7 @@ struct EnvDevice {
     bool inwave_ok = false;        // the current call may solve in-wave (hk_api.hip step_ticks: the handle's shape, the switches, the games-per-launch meter)
     bool inwave_always = false;    // HK_INWAVE=1 (tests): also while the field stands close
     unsigned meter_fresh = 0;      // bit p: part p's meter words are old (the batch changed shape): its next B1 launch starts them over
+    unsigned meter_launches[GAME_METER_PARTS] = {};   // B1 launches of part p so far: launch j counts into meter slot j % 3 (not dev.round, which rounds without a B1 launch advance too)
     bool inwave = false;           // the B1 launches of the current rounds solve their multi-player games themselves (hk_lq_spread.h lqs_inwave): no queue, no solver launch
     bool lqn_launched = false;     // the last launch_lqn launched a kernel (or skipped a provably empty one): there is a solver stage to time
     bool b1_small = false;         // the rounds issued while a search launch runs on the side stream in 4-wave workgroups (every CU): B1 reads its tables from global memory, the solver launch is the <= 256-register form (hk_env_launch.h)

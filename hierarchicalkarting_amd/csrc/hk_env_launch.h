@@ -154,13 +154,14 @@ inline int launch_b1(EnvDevice& d, const hk_config& cfg, hipStream_t stream, std
     // holds a game and the queues + the pair solver's 32 games per wave are several times cheaper per game
     const int meter_fresh = ((d.meter_fresh >> (d.qbase >> 1)) & 1u) ? 2 : 0;
     d.meter_fresh &= ~(1u << (d.qbase >> 1));
+    const int meter_slot = (int)(d.meter_launches[d.qbase >> 1]++ % 3u);
     d.inwave = inwave_now(d);      // (HK_INWAVE=1, tests: in every round)
     const int s0 = d.slot1 > d.slot0 ? d.slot0 : 0, s1 = d.slot1 > d.slot0 ? d.slot1 : cfg.num_envs;
     const long long threads = (long long)(s1 - s0) * GA;
     const GameSoA G{d.games, (size_t)cfg.num_envs * cfg.num_agents};
     const unsigned blocks = (unsigned)((threads + 255) / 256);
 #define HK_FIS_B1(TL, MC) hipLaunchKernelGGL((env_b1_kernel<TL, MC>), dim3(blocks), dim3(256), TL ? d.P.o_tmask : 0, stream, d.P, d.agents, d.hot, d.envs, G, d.queue_cnt, d.queue, \
-                           d.round, d.lq_debug, d.status, d.mcts, d.perm, d.game_stats, s0, s1, d.qbase, d.mset, (d.inwave ? 1 : 0) | meter_fresh)
+                           d.round, d.lq_debug, d.status, d.mcts, d.perm, d.game_stats, s0, s1, d.qbase, d.mset, (d.inwave ? 1 : 0) | meter_fresh, meter_slot)
     // (b1_small: beside a search launch whose 4-wave workgroups hold 108.8 KB of EVERY CU's LDS, a B1 block with its 44.5 KB copy of the Complex-track tables
     // — 67 KB with the KartS staging — does not fit; the instantiation that reads the tables through L1 / L2 needs the 22.8 KB of staging only)
     if (d.mcts.st) { if (d.tab_lds && !d.b1_small) HK_FIS_B1(true, true); else HK_FIS_B1(false, true); }

@@ -434,7 +434,7 @@ __global__ __launch_bounds__(256, FISSION ? HK_FIS_OCC : HK_RUN_OCC) void env_ru
 template <bool TAB_LDS, bool HAS_MCTS = false>
 __global__ __launch_bounds__(256, HK_B1_OCC) void env_b1_kernel(EnvParams P, hk_agent_state* agents, uint32_t* hot, hk_env_state* envs, GameSoA games, int* queue_cnt_all,
                                                         int* queue_all, int round, hk_lq_debug* dbg_out, int* status, MctsDev Marg, const int* perm,
-                                                        unsigned long long* stats, int slot0, int slot1, int qbase, int mset, int inwave)
+                                                        unsigned long long* stats, int slot0, int slot1, int qbase, int mset, int inwave, int meter_slot)
 {
     MctsDev M{};
     if (HAS_MCTS) M = Marg;
@@ -464,9 +464,9 @@ __global__ __launch_bounds__(256, HK_B1_OCC) void env_b1_kernel(EnvParams P, hk_
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         // the meter: the launch before this one (same part, same stream) is complete — fold its total into the decaying maximum, clear the next launch's slot
         unsigned long long* mt = stats + GAME_METER + 4 * (qbase >> 1);
-        const unsigned sl = (unsigned)round % 3u;
+        const unsigned sl = (unsigned)meter_slot;
         // (bit 1 of `inwave`: this part has not launched for a long time — the batch changed shape, hk_api.hip step_ticks — and its words are old: start over.
-        // The slot this launch counts into is clean either way: the part's round counter carries on where its last launch, which cleared it, left off)
+        // The slot this launch counts into is clean either way: the part's launch counter carries on where its last launch, which cleared it, left off)
         const unsigned long long prev = mt[(sl + 2u) % 3u], dec = mt[3] - (mt[3] >> 2);
         mt[3] = (inwave & 2) ? 0ull : (prev > dec ? prev : dec);
         mt[(sl + 1u) % 3u] = 0ull;
@@ -495,7 +495,7 @@ __global__ __launch_bounds__(256, HK_B1_OCC) void env_b1_kernel(EnvParams P, hk_
     // the games-per-launch meter of the host's schedule (hk_env_device.h GAME_METER), this launch's share
     {
         const unsigned long long mg = __ballot(qn != 0);
-        if ((threadIdx.x & 63) == 0 && mg != 0ull) atomicAdd(&stats[GAME_METER + 4 * (qbase >> 1) + (unsigned)round % 3u], (unsigned long long)__popcll(mg));
+        if ((threadIdx.x & 63) == 0 && mg != 0ull) atomicAdd(&stats[GAME_METER + 4 * (qbase >> 1) + (unsigned)meter_slot], (unsigned long long)__popcll(mg));
     }
     bool queued = false;
 #ifndef HK_HOST_EMU

@@ -162,6 +162,18 @@ class RacingEnv:
         self._ck(self.L.hk_prof_games(self.h, g))
         return {n: int(g[n]) for n in range(2, _lib.HK_MAX_AGENTS + 1)}
 
+    def prof_games_words(self):
+        """-> (in-wave solver passes, waves that ran any): hk_prof_games words [0], [1] since the last prof_reset"""
+        g = (C.c_int64 * (_lib.HK_MAX_AGENTS + 1))()
+        self._ck(self.L.hk_prof_games(self.h, g))
+        return int(g[0]), int(g[1])
+
+    def prof_meter(self):
+        """-> int64[HK_METER_PARTS, 4]: the games-per-launch meter, per part: slots 0 .. 2 (B1 launch j of the part counts into j % 3), the decaying maximum"""
+        w = (C.c_int64 * (4 * _lib.HK_METER_PARTS))()
+        self._ck(self.L.hk_prof_meter(self.h, w))
+        return [[int(w[4 * p + k]) for k in range(4)] for p in range(_lib.HK_METER_PARTS)]
+
     # ---- the path's one exchange step, natively over RCCL (hk_comm_* / hk_gather_results)
     @staticmethod
     def comm_unique_id():

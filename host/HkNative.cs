@@ -20,6 +20,7 @@ namespace KartGame.AI.Native
         public const int HK_MCTS_MAX_ROOT_PHASES = 3;
         public const int HK_COMM_ID_BYTES = 128;
         public const int HK_PROF_STAGES = 6;
+        public const int HK_METER_PARTS = 4;
         // HierarchicalKartAgent.cs:21-33
         public const int HK_LOW_RL = 0, HK_LOW_MPC = 1, HK_LOW_LQR = 2;
         public const int HK_HIGH_MCTS = 0, HK_HIGH_FIXED = 1;
@@ -405,6 +406,7 @@ namespace KartGame.AI.Native
         [DllImport(Lib)] public static extern int hk_prof_reset(IntPtr h);
         [DllImport(Lib)] public static extern int hk_prof_read(IntPtr h, double* ms, long* launches);
         [DllImport(Lib)] public static extern int hk_prof_games(IntPtr h, long* games);
+        [DllImport(Lib)] public static extern int hk_prof_meter(IntPtr h, long* words);     // [4 * HK_METER_PARTS]
 
         public static void Check(int rc, IntPtr h)
         {

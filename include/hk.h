@@ -479,11 +479,21 @@ int hk_comm_destroy(hk_handle h);
 int hk_prof_enable(hk_handle h, int on);
 int hk_prof_reset(hk_handle h);
 int hk_prof_read(hk_handle h, double* ms /*[HK_PROF_STAGES]*/, int64_t* launches /*[HK_PROF_STAGES]*/);
-/* multi-player LQ games (KartLQR.solveFeedbackLQR calls with N >= 2 players) the solver kernels ran since the last hk_prof_reset,
- * by player count: games[N], N = 2 .. HK_MAX_AGENTS (single-player games are solved inside the tick / B1 kernel and not counted).  games[0], games[1] (round 6):
- * the solver passes the waves of env_b1_kernel ran in-wave, and the waves that ran any — their ratio says how well the regroup keeps the envs that hold
- * games apart (1.00: one pass per wave). */
+/* multi-player LQ games (KartLQR.solveFeedbackLQR calls with N >= 2 players) solved since the last hk_prof_reset, by player count: games[N],
+ * N = 2 .. HK_MAX_AGENTS — one per ego per solve tick that holds one, wherever it is solved (a solver launch or in-wave in env_b1_kernel), counted once
+ * (single-player games are solved inside the tick / B1 kernel and not counted).  The one rule by which they differ from the reference's solves: the
+ * solve ticks of the start hold after its first cadence (cadence < episode step < start_hold_ticks) are skipped — the karts cannot move and each solve
+ * would decode the controls of the one before bit for bit — while the skip is on (no planner, no Training-mode reset, HK_NO_HOLD_DEDUPE unset, and no
+ * hk_set_agent_state / hk_set_env_state since hk_create).  With that rule the counts equal the CPU oracle's tally (hko_game_counts) for every schedule
+ * and call size (tests/test_game_counts_gpu.py).  games[0], games[1] (round 6): the solver passes the waves of env_b1_kernel ran in-wave, and
+ * the waves that ran any — their ratio says how well the regroup keeps the envs that hold games apart (1.00: one pass per wave); passes <= in-wave games. */
 int hk_prof_games(hk_handle h, int64_t* games /*[HK_MAX_AGENTS + 1]*/);
+/* the games-per-launch meter the host picks its schedule from (env_b1_kernel, 4-agent fission handles; hk_prof_games' synchronisation): four words per
+ * part p of the batch (0 unsplit; 0 .. 1 on two streams), words[4 p + k]: k = 0 .. 2 the multi-player games (egos that hold one) of the part's B1
+ * launches, launch j of the part counting into slot j % 3, and k = 3 the decaying maximum of the finished launches' totals (m <- max(total, m - m / 4)).
+ * Read-only; not reset by hk_prof_reset.  The last look at it is hk_schedule_info()'s "games_meter_value". */
+#define HK_METER_PARTS 4
+int hk_prof_meter(hk_handle h, int64_t* words /*[4 * HK_METER_PARTS]*/);
 
 #ifdef __cplusplus
 }

@@ -74,6 +74,9 @@ int hko_policy_forward(hko_env*, int policy, int rows, const float* obs, float* 
 int hko_get_actions(hko_env*, float* steer, int32_t* branch);
 /* debug taps for single-step fixtures: last LQ game assembled for (env, ego) */
 int hko_debug_last_game(hko_env*, int env, int ego, hk_lq_debug* out);
+/* multi-player games (N >= 2 players) the envs [env_lo, env_hi) solved since hko_create / the last reset, by player count: out[HK_MAX_AGENTS + 1] */
+int hko_game_counts(hko_env*, int env_lo, int env_hi, int64_t* out);
+int hko_game_counts_reset(hko_env*);
 /* raycast against the track walls (analytic Physics.Raycast vs TrackMask): returns hit distance or -1 */
 float hko_raycast_track(hko_env*, float ox, float oz, float dx, float dz, float maxdist);
 

@@ -757,6 +757,7 @@ static void solve_lqr(hko_env* e, int env, int ego)
     }
     double u[2] = {0, 0};
     hko_lq_solve(N, Am, Bm, Qm, qm, Rm, x0, 3, u, NULL);                                 /* :1201 */
+    if (N >= 2) e->games[(size_t)env * (HK_MAX_AGENTS + 1) + N] += 1;                   /* the tally hk_prof_games is checked against (one env per thread) */
     if (dbg) { dbg->u0[0] = u[0]; dbg->u0[1] = u[1]; }
     /* :1206-1224 decode */
     const float maxAng = me->final_steer * 0.4f;                                        /* getMaxAngularVelocity AK:505 */
@@ -1367,6 +1368,7 @@ hko_env* hko_create(const hk_config* cfg)
     e->dbg = (hk_lq_debug*)calloc(na, sizeof(hk_lq_debug));
     e->act_steer = (float*)calloc(na, sizeof(float));
     e->act_branch = (int32_t*)calloc(na, sizeof(int32_t));
+    e->games = (int64_t*)calloc((size_t)e->E * (HK_MAX_AGENTS + 1), sizeof(int64_t));
     if (cfg->rewards) {
         const size_t n = na * (size_t)hko_rw_table_len(e);
         e->sec_min_time = (int32_t*)malloc(n * sizeof(int32_t));
@@ -1412,7 +1414,7 @@ void hko_destroy(hko_env* e)
     hko_mcts_trees_free(e);
     free(e->mcts);
     free(e->sec_min_time); free(e->sec_count);
-    free(e->act_steer); free(e->act_branch); free(e->perms); free(e);
+    free(e->act_steer); free(e->act_branch); free(e->perms); free(e->games); free(e);
 }
 
 int hko_reset(hko_env* e, const int32_t* env_ids, int n, int experiment_num)
@@ -1460,6 +1462,24 @@ int hko_step(hko_env* e, int n_ticks)
         for (int env = 0; env < e->E; env++) step_env(e, env);
         e->academy_step += 1;
     }
+    return 0;
+}
+
+/* multi-player games (solves with N >= 2 players; single-player solves are not games, as in hk_prof_games) of envs [env_lo, env_hi) since
+ * hko_create or the last hko_game_counts_reset, summed by player count: out[N], N = 0 .. HK_MAX_AGENTS (out[0], out[1] stay 0) */
+int hko_game_counts(hko_env* e, int env_lo, int env_hi, int64_t* out)
+{
+    if (!e || !out || env_lo < 0 || env_hi > e->E || env_lo > env_hi) return HK_ERR_INVALID;
+    for (int n = 0; n <= HK_MAX_AGENTS; n++) out[n] = 0;
+    for (int env = env_lo; env < env_hi; env++)
+        for (int n = 0; n <= HK_MAX_AGENTS; n++) out[n] += e->games[(size_t)env * (HK_MAX_AGENTS + 1) + n];
+    return 0;
+}
+
+int hko_game_counts_reset(hko_env* e)
+{
+    if (!e) return HK_ERR_INVALID;
+    memset(e->games, 0, sizeof(int64_t) * (size_t)e->E * (HK_MAX_AGENTS + 1));
     return 0;
 }
 

@@ -55,6 +55,7 @@ struct hko_env {
     int decision_period;
     int64_t academy_step;  /* ticks stepped since creation (Academy.StepCount) */
     float* obs_scratch;    /* [E][A][obs_dim] */
+    int64_t* games;        /* [E][HK_MAX_AGENTS + 1] multi-player games solved, by player count (hko_game_counts) */
 };
 
 /* ------------------------------------------------------------------ Philox-4x32-10 (synthetic start jitter) */

@@ -120,6 +120,10 @@ def _env_api():
         L.hko_policy_forward.argtypes = [C.c_void_p, C.c_int, C.c_int, fp, fp, fp]
         L.hko_get_actions.restype = C.c_int
         L.hko_get_actions.argtypes = [C.c_void_p, fp, C.POINTER(C.c_int32)]
+        L.hko_game_counts.restype = C.c_int
+        L.hko_game_counts.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        L.hko_game_counts_reset.restype = C.c_int
+        L.hko_game_counts_reset.argtypes = [C.c_void_p]
         L._env_bound = True
         # The oracle spreads envs over OpenMP threads.  A GPU box shows every host core (256) but grants a share of ~16: with the
         # default team size the per-tick fork / join of the policy tests spins 256 threads on 16 CPUs and a 1-minute suite takes
@@ -239,6 +243,16 @@ class OracleEnv:
         d = HL.LqDebug()
         assert self.L.hko_debug_last_game(self.h, env, ego, C.byref(d)) == 0
         return d
+
+    def game_counts(self, lo=0, hi=None):
+        """multi-player games (N >= 2 players) envs [lo, hi) solved since creation / game_counts_reset, by player count: int64[HK_MAX_AGENTS + 1]
+        (the reference hk_prof_games is compared with)"""
+        out = np.zeros(HL.HK_MAX_AGENTS + 1, np.int64)
+        assert self.L.hko_game_counts(self.h, lo, self.E if hi is None else hi, out.ctypes.data_as(C.POINTER(C.c_int64))) == 0
+        return out
+
+    def game_counts_reset(self):
+        assert self.L.hko_game_counts_reset(self.h) == 0
 
     def raycast_track(self, ox, oz, dx, dz, maxdist):
         return self.L.hko_raycast_track(self.h, ox, oz, dx, dz, maxdist)

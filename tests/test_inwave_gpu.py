@@ -60,6 +60,15 @@ for n in (76, 4, 4, 8, 1, 3, 20, 64, 120, 300):
 games = g.prof_games()
 assert {2, 3, 4} <= seen, seen
 assert games[2] > 0 and games[3] > 0 and games[4] > 0, games
+# every game the kernels solved, wherever, counted once: the oracle's tally (tests/test_game_counts_gpu.py holds the other schedules to it)
+want = o.game_counts()
+assert all(games[n] == want[n] for n in range(2, 9)), (games, want.tolist())
+passes, waves = g.prof_games_words()
+assert waves <= passes <= sum(games.values()), (passes, waves, games)
+if os.environ.get("HK_INWAVE") == "0":
+    assert passes == 0 and waves == 0, (passes, waves)
+if os.environ.get("HK_INWAVE") == "1":
+    assert waves > 0, (passes, waves)
 print("inwave ok", games)
 """
 
