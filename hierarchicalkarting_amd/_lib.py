@@ -20,8 +20,8 @@ HK_POLICY_MAX_IN = 1280
 HK_POLICY_MAX_HIDDEN = 256
 
 HK_OK, HK_ERR_INVALID, HK_ERR_NO_DEVICE, HK_ERR_HIP, HK_ERR_UNSUPPORTED, HK_ERR_SINGULAR = 0, -1, -2, -3, -4, -5
-HK_LOW_RL, HK_LOW_MPC, HK_LOW_LQR = 0, 1, 2
-HK_HIGH_MCTS, HK_HIGH_FIXED = 0, 1
+HK_LOW_RL, HK_LOW_MPC, HK_LOW_LQR, HK_LOW_E2E = 0, 1, 2, 3
+HK_HIGH_MCTS, HK_HIGH_FIXED, HK_HIGH_NONE = 0, 1, 2
 HK_MODE_RACE, HK_MODE_TRAINING, HK_MODE_EXPERIMENT = 0, 1, 2
 HK_F_ACCEL, HK_F_BRAKE, HK_F_ACTIVE, HK_F_FORWARD_COLLISION, HK_F_HAS_COLLISION, HK_F_CAN_MOVE, HK_F_ENABLED = (1 << i for i in range(7))
 

@@ -74,12 +74,18 @@ REWARD_DEFAULTS = dict(
     AccelerationReward=0.002, NotAtGoalPenalty=-0.001)
 
 
-def make_config(num_envs, num_agents=4, track="oval", high_mode=_lib.HK_HIGH_FIXED, low_mode=_lib.HK_LOW_LQR,
-                tree_search_depth=5, jitter_seed=0, jitter_pos=0.5, jitter_yaw=0.05, auto_reset=1, env_id_base=0,
+# EndToEndKartAgent's gameParams constants (E2E:18-22).  make_config gives them to every HK_LOW_E2E slot whose gameParams the caller
+# leaves at None; the HierarchicalKartAgent slots get HIER_GAME_PARAMS (the make_config defaults of every earlier version)
+E2E_GAME_PARAMS = dict(tree_search_depth=8, velocity_bucket_size=1, section_window=2, time_precision=100)
+HIER_GAME_PARAMS = dict(tree_search_depth=5, velocity_bucket_size=2, section_window=2, time_precision=100)
+
+
+def make_config(num_envs, num_agents=4, track="oval", high_mode=None, low_mode=_lib.HK_LOW_LQR,
+                tree_search_depth=None, jitter_seed=0, jitter_pos=0.5, jitter_yaw=0.05, auto_reset=1, env_id_base=0,
                 device_id=0, wiring=None, env_mode=_lib.HK_MODE_EXPERIMENT, max_episode_steps=None, laps=None,
-                stats=None, time_precision=100, section_window=2, mcts_iterations=128, mcts_initial_iterations=None,
+                stats=None, time_precision=None, section_window=None, mcts_iterations=128, mcts_initial_iterations=None,
                 mcts_latency_ticks=45, mcts_initial_latency_ticks=75, mcts_seed=0x4D435453, rewards=0, training_agents=None,
-                reward_params=None, disable_on_end=None, train_seed=0x54524149, velocity_bucket_size=2, max_lane_changes=None,
+                reward_params=None, disable_on_end=None, train_seed=0x54524149, velocity_bucket_size=None, max_lane_changes=None,
                 engine=None, sensors=None):
     tr = load_track(track) if isinstance(track, str) else track
     secs = tr["sections"]
@@ -119,13 +125,17 @@ def make_config(num_envs, num_agents=4, track="oval", high_mode=_lib.HK_HIGH_FIX
         cfg.n_other[i] = len(other[i])
         for j, t in enumerate(other[i]):
             cfg.other_agents[i][j] = t
-        cfg.high_mode[i] = high_mode[i] if isinstance(high_mode, (list, tuple)) else high_mode
-        cfg.low_mode[i] = low_mode[i] if isinstance(low_mode, (list, tuple)) else low_mode
-        cfg.tree_search_depth[i] = tree_search_depth[i] if isinstance(tree_search_depth, (list, tuple)) else tree_search_depth
         per = lambda v: v[i] if isinstance(v, (list, tuple)) else v          # gameParams are per agent (HKA:38-52)
-        cfg.velocity_bucket_size[i] = per(velocity_bucket_size)
-        cfg.time_precision[i] = per(time_precision)
-        cfg.section_window[i] = per(section_window)
+        cfg.low_mode[i] = per(low_mode)
+        e2e = cfg.low_mode[i] == _lib.HK_LOW_E2E
+        # high_mode None: HK_HIGH_FIXED, or for an E2E slot HK_HIGH_MCTS (runQuasiMCTS is on for every E2E agent of the reference's scenes)
+        hm = per(high_mode)
+        cfg.high_mode[i] = hm if hm is not None else (_lib.HK_HIGH_MCTS if e2e else _lib.HK_HIGH_FIXED)
+        gp = E2E_GAME_PARAMS if e2e else HIER_GAME_PARAMS
+        for k, v in (("tree_search_depth", tree_search_depth), ("velocity_bucket_size", velocity_bucket_size),
+                     ("time_precision", time_precision), ("section_window", section_window)):
+            val = per(v)
+            getattr(cfg, k)[i] = gp[k] if val is None else val
     st = dict(KART_STATS)
     if stats:
         st.update(stats)

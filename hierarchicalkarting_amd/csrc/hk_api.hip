@@ -1127,8 +1127,8 @@ int hk_policy_attach(hk_handle h, const hk_policy_desc* desc, const int32_t* age
         return fail(h, HK_ERR_INVALID, "hk_policy_attach: in_dim != hk_obs_dim * stack (a model trained for another agent count / horizon)");
     for (int j = 0; j < n_slots; j++) {
         const int a = agent_slots[j];
-        if (a < 0 || a >= h->cfg.num_agents || h->cfg.low_mode[a] != HK_LOW_RL)
-            return fail(h, HK_ERR_INVALID, "hk_policy_attach: agent slot out of range or not LowMode RL");
+        if (a < 0 || a >= h->cfg.num_agents || (h->cfg.low_mode[a] != HK_LOW_RL && h->cfg.low_mode[a] != HK_LOW_E2E))
+            return fail(h, HK_ERR_INVALID, "hk_policy_attach: agent slot out of range or not LowMode RL / E2E");
         for (int p = 0; p < h->n_policies; p++)
             for (int q = 0; q < h->policy[p].q.n_slots; q++)
                 if (h->policy[p].q.slots[q] == a) return fail(h, HK_ERR_INVALID, "hk_policy_attach: agent slot already has a policy");

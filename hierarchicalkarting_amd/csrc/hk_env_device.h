@@ -120,6 +120,11 @@ struct EnvParams {
     int* guard_flag;
     int tab_stage_bytes;    // bytes of the packed tables a block copies to LDS: all of them, or (a long track) all but the last segment, tmask2, which is
                             // then read from global memory (one 8-byte load per kart and tick)
+    // EndToEndKartAgent slots (hk.h HK_LOW_E2E), bit i = agent i.  Their low_mode is stored as HK_LOW_RL — the action path, the absent LQ game and
+    // every player rule are the RL agent's — and their high_mode as HK_HIGH_MCTS (runQuasiMCTS) or HK_HIGH_NONE; what differs is read from this mask:
+    // the observation layout (env_observe_kernel), the OnActionReceived rewards and unit dividers (hk_env_reward.h), no plan at reset and the
+    // bestStates copy of E2E:57-79 (hk_env_mcts.h).  0 on every handle without one.
+    uint32_t e2e_mask;
 };
 // ---- device buffers of the MCTS planner (hk_env_mcts.h) and of the reward shaping (hk_env_reward.h): the same for every GA
 struct MctsKartSnap { int section, lane, lane_changes, tire_age; int sec_time[HK_MCTS_SECTIME_RING]; };

@@ -110,8 +110,12 @@ __device__ inline void mcts_post_request(const EnvParams& P, const MctsDev& M, i
 // own-plan entries it writes only shrinks as the section index grows, nothing else writes beliefs, and a passed checkpoint
 // clears an entry outside that set), so here it runs when a search is promoted or the section index changed — two loads per
 // tick instead of re-reading the plan and re-storing ~100 B of plan / belief entries per agent and tick.
+// An E2E agent (e2e = 1) copies its own entries of sections beyond m_SectionIndex + 1, without HKA's exception at section 0
+// (EndToEndKartAgent.FixedUpdate E2E:57-79).  It keeps no beliefs in the reference; the belief entries written here for it are never
+// read (beliefs feed the LQ game only) — written rather than skipped because a branch on e2e costs the planner instantiations of the
+// tick kernel VGPR spills, E2E agents or not.
 __device__ inline void mcts_consume(const EnvParams& P, hk_mcts_state* m, hk_agent_state* a, int i, int episode_steps, int section_index,
-                                    MctsReq* r)
+                                    MctsReq* r, int e2e = 0)
 {
     bool promoted = false;
     if (m->ready_step >= 0 && episode_steps >= m->ready_step) {
@@ -130,7 +134,7 @@ __device__ inline void mcts_consume(const EnvParams& P, hk_mcts_state* m, hk_age
         for (int p = 0; p < b.n_players; p++) {
             const int who = b.player_agent[p];
             if (who == i) {
-                if (sec > section_index + (section_index == 0 ? 0 : 1)) {
+                if (sec > section_index + (section_index == 0 ? e2e : 1)) {
                     a->plan_lane[sec % L] = b.lane[q][p];
                     a->plan_vel[sec % L] = (float)b.vel[q][p];
                 }
@@ -161,7 +165,8 @@ __device__ inline void phase_plan(const EnvParams& P, const MctsDev& M, int set,
     fresh = (uint32_t)group_or((int)fresh);
     if (req) mcts_post_request(P, M, set, env, i, req, fresh, es.episode_steps, es.episodes_done, P.mcts_iter, es.episode_steps + P.mcts_lat,
                                section, lane, lane_changes, final_steer, final_steer);
-    if (enabled && P.high_mode[i] == HK_HIGH_MCTS) mcts_consume(P, &M.st[(size_t)env * P.A + i], arec, i, es.episode_steps, section, &mc_reqs(M)[(size_t)env * P.A + i]);
+    if (enabled && P.high_mode[i] == HK_HIGH_MCTS)
+        mcts_consume(P, &M.st[(size_t)env * P.A + i], arec, i, es.episode_steps, section, &mc_reqs(M)[(size_t)env * P.A + i], (int)((P.e2e_mask >> i) & 1u));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

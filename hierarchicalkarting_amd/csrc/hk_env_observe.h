@@ -1,6 +1,8 @@
 // hk_env_observe.h — HierarchicalKartAgent.CollectObservations (HKA:485-604): one thread per (env, agent).
 // Layout = the order the reference calls sensor.AddObservation: 8 own, 12 per teammate, 12 per opponent,
 // 5 per upcoming section (sectionHorizon), 9 ray distances (up to 20 m long: walked through the wall grid).
+// E2E rows (EnvParams.e2e_mask; EndToEndKartAgent.CollectObservations E2E:279-376): the same blocks and rays; the own block ends
+// isStraight, tireWear, section / goal, and the section horizon is always the Trigger, 1, isStraight.
 // (included once per lane-group width by hk_env_ga.h: no include guard, namespace hk::HK_GA_NS)
 #include "hk_env_device.h"
 
@@ -88,15 +90,16 @@ __global__ __launch_bounds__(BLOCK) void env_observe_kernel(EnvParams P, const h
 #pragma unroll
     for (int j = 1; j < GA; j++) if (i == j) { fx = kfx[j]; fz = kfz[j]; }
     if (!valid || !((agent_mask >> i) & 1u)) return;
+    const bool e2e = (P.e2e_mask >> i) & 1u;                                 // EndToEndKartAgent.CollectObservations (E2E:279-376)
     if (l == 14) {                                                           // own block HKA:489-496
         o[0] = local_speed(P, a, fx, fz);
         o[1] = (a.flags() & HK_F_ACCEL) ? 1.0f : 0.0f;
         o[2] = (float)a.lane();
         o[3] = a.lane_changes() * 1.0f / P.max_lane_changes;
         o[4] = (a.flags() & HK_F_ACTIVE) ? 1.0f : 0.0f;
-        o[5] = a.section_index() * 1.0f / goal;
-        o[6] = is_straight(P, T, a.section_index()) ? 1.0f : 0.0f;
-        o[7] = tire_wear(P, a.final_steer());
+        const float sg = a.section_index() * 1.0f / goal, st = is_straight(P, T, a.section_index()) ? 1.0f : 0.0f, tw = tire_wear(P, a.final_steer());
+        if (e2e) { o[5] = st; o[6] = tw; o[7] = sg; }                        // E2E:281-288
+        else { o[5] = sg; o[6] = st; o[7] = tw; }
     }
     // team mates, then opponents HKA:500-527: block q of the list is written by lane q of the group (one kart each, side by side,
     // instead of one lane walking all of them while the other fifteen wait)
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(BLOCK) void env_observe_kernel(EnvParams P, const h
             const int next = (a.section_index() + 1 + q) % L;
             float* os = o + 8 + 12 * (A - 1) + 5 * q;
             float lp[3];
-            const int pl = cold->plan_lane[next];
+            const int pl = e2e ? 0 : cold->plan_lane[next];                 // E2E:318-327: always the Trigger
             if (pl != 0) {
                 float mx, mz;
                 lane_marker(T, next, pl, mx, mz);

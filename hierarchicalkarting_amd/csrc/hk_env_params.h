@@ -62,7 +62,16 @@ inline int env_build_params(hk_config& cfg, std::vector<hk_section>& sections, s
             }
             seen |= 1u << o;
         }
-        if (cfg.high_mode[i] != HK_HIGH_FIXED && cfg.high_mode[i] != HK_HIGH_MCTS) { err = "hk_create: bad high_mode"; return HK_ERR_INVALID; }
+        const bool e2e = cfg.low_mode[i] == HK_LOW_E2E;
+        // an EndToEndKartAgent has no Fixed plan: runQuasiMCTS (HK_HIGH_MCTS) or nothing (HK_HIGH_NONE)
+        if (e2e ? (cfg.high_mode[i] != HK_HIGH_MCTS && cfg.high_mode[i] != HK_HIGH_NONE)
+                : (cfg.high_mode[i] != HK_HIGH_FIXED && cfg.high_mode[i] != HK_HIGH_MCTS)) {
+            err = e2e ? "hk_create: an E2E agent's high_mode is HK_HIGH_MCTS (runQuasiMCTS) or HK_HIGH_NONE"
+                      : "hk_create: bad high_mode (HK_HIGH_NONE is valid only with HK_LOW_E2E)";
+            return HK_ERR_INVALID;
+        }
+        if (e2e && cfg.env_mode == HK_MODE_TRAINING) { err = "hk_create: E2E agents in Training mode (env_mode HK_MODE_TRAINING) are not supported"; return HK_ERR_UNSUPPORTED; }
+        if (e2e && cfg.training_agent[i]) { err = "hk_create: E2E agents with Mode == Training (training_agent) are not supported"; return HK_ERR_UNSUPPORTED; }
         if (cfg.high_mode[i] == HK_HIGH_MCTS) {
             if (cfg.tree_search_depth[i] < 1 || cfg.tree_search_depth[i] > HK_MCTS_MAX_DEPTH || cfg.velocity_bucket_size[i] < 1 ||
                 cfg.time_precision[i] < 1 || cfg.section_window[i] < 1 || cfg.section_window[i] > 4) { err = "hk_create: bad MCTS gameParams (depth 1..8, bucket, precision, window 1..4)"; return HK_ERR_INVALID; }
@@ -73,7 +82,9 @@ inline int env_build_params(hk_config& cfg, std::vector<hk_section>& sections, s
                 err = "hk_create: MCTS budget / latency out of range (iterations >= 1, 40 < latency ticks < 100)"; return HK_ERR_INVALID;
             }
         }
-        if (cfg.low_mode[i] != HK_LOW_LQR && cfg.low_mode[i] != HK_LOW_RL) { err = "hk_create: LowMode MPC is dead code in the reference"; return HK_ERR_UNSUPPORTED; }
+        if (cfg.low_mode[i] == HK_LOW_MPC) { err = "hk_create: LowMode MPC is dead code in the reference"; return HK_ERR_UNSUPPORTED; }
+        if (cfg.low_mode[i] != HK_LOW_LQR && cfg.low_mode[i] != HK_LOW_RL && !e2e) { err = "hk_create: bad low_mode"; return HK_ERR_INVALID; }
+        if (e2e && A > 4) { err = "hk_create: E2E agents on the 8-agent lane-group width are not supported"; return HK_ERR_UNSUPPORTED; }
         if (cfg.tree_search_depth[i] < 0 || cfg.tree_search_depth[i] > L) { err = "hk_create: bad tree_search_depth"; return HK_ERR_INVALID; }
     }
     sections.assign(cfg.sections, cfg.sections + L);
@@ -86,7 +97,9 @@ inline int env_build_params(hk_config& cfg, std::vector<hk_section>& sections, s
     P.laps = cfg.laps; P.max_steps = cfg.max_episode_steps; P.max_lane_changes = cfg.max_lane_changes;
     P.H = cfg.section_horizon; P.disable_on_end = cfg.disable_on_end; P.hold = cfg.start_hold_ticks; P.auto_reset = cfg.auto_reset;
     for (int i = 0; i < A; i++) {
-        P.high_mode[i] = cfg.high_mode[i]; P.low_mode[i] = cfg.low_mode[i]; P.depth[i] = cfg.tree_search_depth[i];
+        // an E2E agent drives through the RL action path: stored as HK_LOW_RL, the difference kept in e2e_mask (hk_env_device.h)
+        P.high_mode[i] = cfg.high_mode[i]; P.low_mode[i] = cfg.low_mode[i] == HK_LOW_E2E ? HK_LOW_RL : cfg.low_mode[i]; P.depth[i] = cfg.tree_search_depth[i];
+        if (cfg.low_mode[i] == HK_LOW_E2E) P.e2e_mask |= 1u << i;
         P.vbucket[i] = cfg.velocity_bucket_size[i];
         P.team_of[i] = cfg.team_of[i]; P.time_precision[i] = cfg.time_precision[i]; P.section_window[i] = cfg.section_window[i];
         if (cfg.high_mode[i] == HK_HIGH_MCTS) P.any_mcts += 1;

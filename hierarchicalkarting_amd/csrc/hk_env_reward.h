@@ -40,27 +40,32 @@ __device__ inline void rw_academy(const EnvParams& P, const TabView& T, const in
         accel = br > 1; brake = br < 1;
     }
     const int next = (h.section_index + 1) % P.L;
-    float cx, cz;
-    lane_marker(T, next, a->plan_lane[next], cx, cz);                // plan lane marker, or the Trigger when there is no entry
-    float dx = cx - h.px, dy = T.sec[next].marker_y - P.kart_y, dz = cz - h.pz;
-    const float dm = sqrtf(dx * dx + dy * dy + dz * dz);
-    if (dm > 1e-5f) { dx = dx / dm; dy = dy / dm; dz = dz / dm; } else { dx = 0.0f; dy = 0.0f; dz = 0.0f; }   // Vector3.normalized
-    float vx = h.vx, vy = 0.0f, vz = h.vz;
-    const float vm = sqrtf(vx * vx + vy * vy + vz * vz);
-    if (vm > 1e-5f) { vx = vx / vm; vy = vy / vm; vz = vz / vm; } else { vx = 0.0f; vy = 0.0f; vz = 0.0f; }
-    const float reward = vx * dx + vy * dy + vz * dz;
-    rw_add(r, reward * P.rw.TowardsCheckpointReward);
-    rw_add(r, (accel && !brake ? 1.0f : 0.0f) * P.rw.AccelerationReward);
-    float ls = 0.0f;                                                 // ArcadeKart.LocalSpeed AK:325-342
-    if (fl & HK_F_CAN_MOVE) {
-        const float dot = hfx * h.vx + hfz * h.vz;
-        if (f_abs(dot) > 0.1f) {
-            const float speed = sqrtf(h.vx * h.vx + 0.0f * 0.0f + h.vz * h.vz);
-            ls = dot < 0 ? -(speed / P.st.ReverseSpeed) : (speed / P.st.TopSpeed);
+    // EndToEndKartAgent.OnActionReceived (E2E:385-415) runs the base method, then decodes the actions again and adds the same three rewards
+    // once more, aimed at the next Trigger whatever the plan holds
+    const int passes = ((P.e2e_mask >> i) & 1u) ? 2 : 1;
+    for (int pass = 0; pass < passes; pass++) {
+        float cx, cz;
+        lane_marker(T, next, pass == 0 ? a->plan_lane[next] : 0, cx, cz);   // plan lane marker, or the Trigger when there is no entry
+        float dx = cx - h.px, dy = T.sec[next].marker_y - P.kart_y, dz = cz - h.pz;
+        const float dm = sqrtf(dx * dx + dy * dy + dz * dz);
+        if (dm > 1e-5f) { dx = dx / dm; dy = dy / dm; dz = dz / dm; } else { dx = 0.0f; dy = 0.0f; dz = 0.0f; }   // Vector3.normalized
+        float vx = h.vx, vy = 0.0f, vz = h.vz;
+        const float vm = sqrtf(vx * vx + vy * vy + vz * vz);
+        if (vm > 1e-5f) { vx = vx / vm; vy = vy / vm; vz = vz / vm; } else { vx = 0.0f; vy = 0.0f; vz = 0.0f; }
+        const float reward = vx * dx + vy * dy + vz * dz;
+        rw_add(r, reward * P.rw.TowardsCheckpointReward);
+        rw_add(r, (accel && !brake ? 1.0f : 0.0f) * P.rw.AccelerationReward);
+        float ls = 0.0f;                                             // ArcadeKart.LocalSpeed AK:325-342
+        if (fl & HK_F_CAN_MOVE) {
+            const float dot = hfx * h.vx + hfz * h.vz;
+            if (f_abs(dot) > 0.1f) {
+                const float speed = sqrtf(h.vx * h.vx + 0.0f * 0.0f + h.vz * h.vz);
+                ls = dot < 0 ? -(speed / P.st.ReverseSpeed) : (speed / P.st.TopSpeed);
+            }
         }
+        const float speedProportion = 0.00f;
+        rw_add(r, (ls - speedProportion) / (1 - speedProportion) * P.rw.SpeedReward);
     }
-    const float speedProportion = 0.00f;
-    rw_add(r, (ls - speedProportion) / (1 - speedProportion) * P.rw.SpeedReward);
 }
 
 __device__ __forceinline__ void rw_not_at_goal(const EnvParams& P, const Hot& h, RwAcc& r)

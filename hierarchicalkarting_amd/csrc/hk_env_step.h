@@ -137,6 +137,7 @@ __global__ __launch_bounds__(256) void env_reset_kernel(EnvParams P, hk_agent_st
         mcts_backfill_section_times<true>(P, T, env, i, ex, esp->episodes_done, ar->section_index, &M.st[(size_t)env * P.A + i]);
         uint32_t req = 0;
         for (int e = 0; e < P.A; e++) if (P.high_mode[e] == HK_HIGH_MCTS && !P.training_agent[e]) req |= 1u << e;
+        req &= ~P.e2e_mask;                     // an E2E agent makes no plan at reset (its quasi-MCTS runs on the 100-tick cadence only)
         mcts_post_request(P, M, set, env, i, req, req, 0, esp->episodes_done, P.mcts_iter0, P.mcts_lat0,
                           ar->section_index, ar->lane, ar->lane_changes, ar->final_steer, old_steer);
     }
@@ -245,6 +246,7 @@ __device__ inline bool phase_begin(const EnvParams& P, const int env, const int 
             }
             uint32_t req = 0;
             for (int e = 0; e < P.A; e++) if (P.high_mode[e] == HK_HIGH_MCTS && !P.training_agent[e]) req |= 1u << e;
+            req &= ~P.e2e_mask;                 // (no plan at reset for E2E agents)
             mcts_post_request(P, M, set, env, i, req, req, 0, es.episodes_done, P.mcts_iter0, P.mcts_lat0,
                               h.section_index, h.lane, h.lane_changes, h.final_steer, old_steer);
         }
@@ -693,7 +695,7 @@ __device__ inline void phase_move(const EnvParams& P, const TabView& T, const in
                     const int pl = pl_t;                                   // (key == t)
                     float lane_div = 1.0f, vel_div = 1.0f;                 // HKA:618-619
                     if (pl != 0) {
-                        if (RW) rw_dividers(P, T, i, key, lane, pl, pv_t, px, pz, vx, vz, lane_div, vel_div);
+                        if (RW && !((P.e2e_mask >> i) & 1u)) rw_dividers(P, T, i, key, lane, pl, pv_t, px, pz, vx, vz, lane_div, vel_div);   // E2E: 1 (E2E:263-277)
                         float lmx, lmz;
                         lane_marker(T, key, pl, lmx, lmz);
                         float dist = mag3(px - lmx, P.kart_y - T.sec[key].marker_y, pz - lmz);

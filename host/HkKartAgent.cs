@@ -19,8 +19,11 @@ using KartGame.AI.Native;
 
 namespace KartGame.AI
 {
-    public enum HkLowLevelMode { RL = HkConst.HK_LOW_RL, MPC = HkConst.HK_LOW_MPC, LQR = HkConst.HK_LOW_LQR }      // HKA:21-26
-    public enum HkHighLevelMode { MCTS = HkConst.HK_HIGH_MCTS, Fixed = HkConst.HK_HIGH_FIXED }                  // HKA:28-33
+    // E2E shim: an EndToEndKartAgent of a scene becomes an HkKartAgent with LowMode = E2E and HighMode = MCTS (runQuasiMCTS) or None, the
+    // E2E gameParams constants (treeSearchDepth 8, velocityBucketSize 1, sectionWindow 2, timePrecision 100; E2E:18-22) and its
+    // BehaviorParameters brain; CollectObservations below copies its row of hk_get_observations, which libhk fills in the E2E layout
+    public enum HkLowLevelMode { RL = HkConst.HK_LOW_RL, MPC = HkConst.HK_LOW_MPC, LQR = HkConst.HK_LOW_LQR, E2E = HkConst.HK_LOW_E2E }   // HKA:21-26
+    public enum HkHighLevelMode { MCTS = HkConst.HK_HIGH_MCTS, Fixed = HkConst.HK_HIGH_FIXED, None = HkConst.HK_HIGH_NONE }           // HKA:28-33
 
     public class HkKartAgent : Agent
     {

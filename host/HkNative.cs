@@ -22,8 +22,8 @@ namespace KartGame.AI.Native
         public const int HK_PROF_STAGES = 6;
         public const int HK_METER_PARTS = 4;
         // HierarchicalKartAgent.cs:21-33
-        public const int HK_LOW_RL = 0, HK_LOW_MPC = 1, HK_LOW_LQR = 2;
-        public const int HK_HIGH_MCTS = 0, HK_HIGH_FIXED = 1;
+        public const int HK_LOW_RL = 0, HK_LOW_MPC = 1, HK_LOW_LQR = 2, HK_LOW_E2E = 3;   // E2E: EndToEndKartAgent
+        public const int HK_HIGH_MCTS = 0, HK_HIGH_FIXED = 1, HK_HIGH_NONE = 2;   // NONE: E2E with runQuasiMCTS off
         // RacingEnvController.cs:24-29
         public const int HK_MODE_RACE = 0, HK_MODE_TRAINING = 1, HK_MODE_EXPERIMENT = 2;
         // hk_agent_state.flags

@@ -33,9 +33,12 @@ typedef enum hk_status {
     HK_ERR_SINGULAR = -5      /* LQ: zero pivot in the m x m solve */
 } hk_status;
 
-/* HierarchicalKartAgent.cs:21-33 */
-enum { HK_LOW_RL = 0, HK_LOW_MPC = 1, HK_LOW_LQR = 2 };
-enum { HK_HIGH_MCTS = 0, HK_HIGH_FIXED = 1 };
+/* HierarchicalKartAgent.cs:21-33.  HK_LOW_E2E: the slot is an EndToEndKartAgent (AI/EndToEndKartAgent.cs) instead — actions from the
+ * ML-Agents brain only (no LQ game, no planFixed), its own observation layout and reward path; its high_mode is then HK_HIGH_MCTS
+ * (runQuasiMCTS on: planWithMCTS every 100 ticks with the agent's own gameParams, no plan at reset; the plan feeds the lane / velocity
+ * difference metrics only) or HK_HIGH_NONE (runQuasiMCTS off).  HK_HIGH_NONE is valid only with HK_LOW_E2E. */
+enum { HK_LOW_RL = 0, HK_LOW_MPC = 1, HK_LOW_LQR = 2, HK_LOW_E2E = 3 };
+enum { HK_HIGH_MCTS = 0, HK_HIGH_FIXED = 1, HK_HIGH_NONE = 2 };
 /* RacingEnvController.cs:24-29 */
 enum { HK_MODE_RACE = 0, HK_MODE_TRAINING = 1, HK_MODE_EXPERIMENT = 2 };
 
@@ -205,7 +208,7 @@ typedef struct hk_mcts_state {
     int32_t root_phases;                               /* searches the current tree has received (set at the request; <= HK_MCTS_MAX_ROOT_PHASES) */
     hk_mcts_plan best, pend;
     /* opponentUpcomingLanes / opponentUpcomingVelocities (HKA:77-78): this agent's belief about every other agent's
-     * plan, keyed by section % L; 0 = no entry */
+     * plan, keyed by section % L; 0 = no entry.  (HK_LOW_E2E rows: filled the same way but never read — the E2E agent keeps no beliefs) */
     uint8_t belief_lane[HK_MAX_AGENTS][HK_MAX_SECTIONS];
     uint8_t belief_vel[HK_MAX_AGENTS][HK_MAX_SECTIONS];
 } hk_mcts_state;
@@ -346,7 +349,9 @@ int hk_set_actions(hk_handle h, const float* steer, const int32_t* branch);
  * default 64), else one per resident search lane with re-searched roots rebuilt by replay; plans are bit-identical either way. */
 int hk_step(hk_handle h, int n_ticks);
 
-/* HierarchicalKartAgent.CollectObservations (HKA:485-604): obs[E][A][hk_obs_dim], order exactly as the reference adds them */
+/* HierarchicalKartAgent.CollectObservations (HKA:485-604): obs[E][A][hk_obs_dim], order exactly as the reference adds them.
+ * HK_LOW_E2E rows hold EndToEndKartAgent.CollectObservations (E2E:279-376) in the same hk_obs_dim: own block speed, accel, lane,
+ * laneChanges / max, is_active, isStraight, tireWear, section / goal; the section horizon is always the Trigger (then 1, isStraight). */
 int hk_obs_dim(hk_handle h);
 int hk_get_observations(hk_handle h, float* obs);
 
@@ -444,7 +449,7 @@ typedef struct hk_policy_desc {
     const float* b_branch;     /* [n_branch] */
 } hk_policy_desc;
 
-/* Upload a policy and bind it to the agent slots listed (all must be LowMode == RL; hk_obs_dim * stack must equal
+/* Upload a policy and bind it to the agent slots listed (all must be LowMode == RL or E2E; hk_obs_dim * stack must equal
  * in_dim).  Returns the policy index (>= 0) or a negative hk_status.  decision_period (DecisionRequester) is per handle:
  * a second attach with a different period is refused with HK_ERR_INVALID. */
 int hk_policy_attach(hk_handle h, const hk_policy_desc* desc, const int32_t* agent_slots, int n_slots, int decision_period);

@@ -1,0 +1,260 @@
+"""EndToEndKartAgent ("E2E", HK_LOW_E2E) slots on the GPU.
+
+The CPU oracle has no E2E agent, so each part is held to something independent of libhk's E2E code:
+  * physics, triggers, telemetry and every other agent: the oracle runs the same race with the E2E slot as an RL agent of the
+    Fixed high level and is fed libhk's actions at every tick (hk_get_actions -> hko_set_actions).  Both drive the kart through
+    the same action path, so every hk_agent_state field must agree bit for bit, except the E2E slot's plan, lane / velocity
+    difference metrics and rewards, which the oracle's Fixed plan changes;
+  * observations: E2E rows against the restatement of E2E CollectObservations in tests/e2e_restate.py (own block, section
+    horizon) and against the oracle's row of the same kart (team / opponent blocks and rays, which are HKA's); HKA rows against
+    the oracle's rows;
+  * quasi-MCTS: the request schedule and root reuse through hk_get_mcts_state; HK_HIGH_NONE never searches;
+  * rewards: the E2E OnActionReceived double reward against tests/e2e_restate.py academy_e2e."""
+import numpy as np
+import pytest
+import oracle_lib as O
+import e2e_restate as R
+import hierarchicalkarting_amd as hk
+from hierarchicalkarting_amd import _lib
+from hierarchicalkarting_amd.policy import Policy
+
+pytestmark = pytest.mark.gpu
+
+E2E, RL, LQR = _lib.HK_LOW_E2E, _lib.HK_LOW_RL, _lib.HK_LOW_LQR
+MCTS, FIXED, NONE = _lib.HK_HIGH_MCTS, _lib.HK_HIGH_FIXED, _lib.HK_HIGH_NONE
+E2E_EXEMPT = ("plan_lane", "plan_vel", "avg_lane_diff", "avg_vel_diff", "cum_reward", "step_reward", "group_reward")
+RESULT_EXEMPT = ("avg_lane_diff", "avg_vel_diff", "reward", "group_reward")
+
+
+def _cfg(E, low, high, track="oval", **kw):
+    """gameParams left to make_config: config.E2E_GAME_PARAMS for the E2E slots (E2E:18-22), the scenes' values for the others"""
+    return hk.make_config(E, len(low), track=track, low_mode=low, high_mode=high, jitter_seed=7, mcts_iterations=48, **kw)
+
+
+def _driver(in_dim, seed, hidden=128, layers=3):
+    """a synthetic actor that mostly accelerates and steers mildly, so that its kart reaches the Triggers (a plain random actor stays on the grid)"""
+    pol = Policy.random(in_dim, hidden, layers, seed=seed)
+    pol.b_branch[2] += 4.0
+    pol.W_mu *= 0.3
+    return pol
+
+
+def _twin_cfg(E, low, high, **kw):
+    """the oracle's stand-in: every E2E slot an RL agent of the Fixed high level"""
+    return _cfg(E, [RL if l == E2E else l for l in low], [FIXED if l == E2E else h for l, h in zip(low, high)], **kw)
+
+
+def _cmp(g, o, e2e, t):
+    gs, os_ = g.agent_state(), o.agent_state()
+    for name in gs.dtype.names:
+        keep = np.ones(gs.shape, bool)
+        if name in E2E_EXEMPT:
+            keep[:, e2e] = False
+        assert np.array_equal(gs[name][keep], os_[name][keep]), (t, name)
+    ge, oe = g.env_state(), o.env_state()
+    for name in ("episode_steps", "inactive_mask", "experiment_num", "episodes_done", "status", "initial_started"):
+        assert np.array_equal(ge[name], oe[name]), (t, name)
+    gr, orr = g.episode_results(), o.episode_results()
+    for name in gr.dtype.names:
+        keep = np.ones(gr.shape, bool)
+        if name in RESULT_EXEMPT:
+            keep[:, e2e] = False
+        assert np.array_equal(gr[name][keep], orr[name][keep]), (t, "result", name)
+    return gs
+
+
+def test_create_and_step_an_e2e_handle():
+    """hk_create accepts HK_LOW_E2E (with and without quasi-MCTS), the handle steps, and the E2E kart drives"""
+    g = hk.RacingEnv(_cfg(8, [E2E, LQR], [MCTS, FIXED]))
+    g.reset()
+    st = np.zeros((8, 2), np.float32)
+    br = np.full((8, 2), 2, np.int32)
+    g.set_actions(st, br)
+    g.step(150)
+    a = g.agent_state()
+    assert (a["section_index"][:, 0] > 0).all()          # accelerating straight ahead from the grid passes the next Trigger
+    assert np.isfinite(g.observations()).all()
+    g2 = hk.RacingEnv(_cfg(4, [E2E, E2E, LQR, LQR], [NONE, NONE, FIXED, FIXED]))
+    g2.reset()
+    g2.step(5)
+    with pytest.raises(hk.HkError) as e:
+        hk.RacingEnv(_cfg(2, [LQR, LQR], [NONE, FIXED]))    # HK_HIGH_NONE is an E2E mode
+    assert e.value.code == _lib.HK_ERR_INVALID
+    with pytest.raises(hk.HkError) as e:
+        hk.RacingEnv(_cfg(2, [E2E, LQR], [FIXED, FIXED]))   # an E2E agent has no Fixed plan
+    assert e.value.code == _lib.HK_ERR_INVALID
+    g3 = hk.RacingEnv(hk.make_config(2, 2, low_mode=[E2E, LQR]))   # make_config's defaults: quasi-MCTS with the E2E gameParams
+    g3.reset()
+    g3.step(3)
+    with pytest.raises(hk.HkError) as e:
+        hk.RacingEnv(_cfg(2, [E2E, LQR], [MCTS, FIXED], env_mode=_lib.HK_MODE_TRAINING))
+    assert e.value.code == _lib.HK_ERR_UNSUPPORTED
+
+
+def _actor_twin(E, low, high, track, ticks, seed, check_obs=True):
+    e2e = [i for i, l in enumerate(low) if l == E2E]
+    g = hk.RacingEnv(_cfg(E, low, high, track=track, max_episode_steps=400))
+    o = O.OracleEnv(_twin_cfg(E, low, high, track=track, max_episode_steps=400))
+    g.reset(); o.reset()
+    rl = [i for i, l in enumerate(low) if l == RL]
+    if rl:            # first, so that it is policy 0 on both sides (the policy index keys its sampling stream)
+        p2 = Policy.random(g.obs_dim * 4, 128, 2, seed=seed + 1)
+        g.attach_policy(p2, rl, 2); o.attach_policy(p2, rl, 2)
+    g.attach_policy(_driver(g.obs_dim * 4, seed), e2e, 2)
+    tr = R.Track(g.built)
+    A = len(low)
+    own, oth, hzn, rays = R.obs_layout(A, tr.H)
+    states = {}
+    for t in range(1, ticks + 1):
+        g.step(1)
+        s, b = g.get_actions()
+        o.set_actions(s, b)
+        o.step(1)
+        gs = _cmp(g, o, e2e, t)
+        if t % 20 == 0:
+            states[t] = gs
+        if check_obs and t % 7 == 0:
+            go, oo = g.observations(), o.observations()
+            for i in range(A):
+                if i not in e2e:
+                    assert np.array_equal(go[:, i].view(np.uint32), oo[:, i].view(np.uint32)), (t, i)
+                    continue
+                assert np.array_equal(go[:, i, oth].view(np.uint32), oo[:, i, oth].view(np.uint32)), (t, i, "others")
+                assert np.array_equal(go[:, i, rays].view(np.uint32), oo[:, i, rays].view(np.uint32)), (t, i, "rays")
+                for env in range(E):
+                    w_own, w_hz = R.observe_e2e(tr, gs[env, i], A - 1)
+                    assert np.array_equal(go[env, i, own].view(np.uint32), w_own.view(np.uint32)), (t, env, i, go[env, i, own], w_own)
+                    assert np.array_equal(go[env, i, hzn].view(np.uint32), w_hz.view(np.uint32)), (t, env, i, "horizon")
+    return g, states, e2e
+
+
+@pytest.mark.parametrize("low,high,track", [
+    ([E2E, LQR], [MCTS, MCTS], "oval"),                          # E2E_vs_MCTS_LQR_Oval: quasi-MCTS against an MCTS-LQR opponent
+    ([LQR, LQR, E2E, E2E], [FIXED, FIXED, NONE, MCTS], "complex"),  # E2E_vs_Fixed_LQR_ComplexDuos, one E2E with quasi-MCTS off
+    ([RL, E2E], [FIXED, MCTS], "complex"),                       # E2E_vs_Fixed_RL_Complex: two actors on one handle
+])
+def test_e2e_twin_bit_exact_against_the_oracle(low, high, track):
+    """tick by tick against the oracle fed libhk's actions (850 ticks: two time-outs at 400 and their resets); then the same race in
+    calls of 20 ticks on a second handle must reach the same states (the oracle has no E2E actor to decide inside such a call)"""
+    E = 24
+    g, states, e2e = _actor_twin(E, low, high, track, 850, seed=11 + len(low))
+    assert (g.env_state()["episodes_done"] >= 2).all()
+    moved = states[380][:, e2e]["section_index"] - states[20][:, e2e]["section_index"]
+    assert (moved > 0).any()                                     # the E2E karts pass Triggers
+    g2 = hk.RacingEnv(_cfg(E, low, high, track=track, max_episode_steps=400))
+    g2.reset()
+    rl = [i for i, l in enumerate(low) if l == RL]
+    if rl:
+        g2.attach_policy(Policy.random(g2.obs_dim * 4, 128, 2, seed=12 + len(low)), rl, 2)
+    g2.attach_policy(_driver(g2.obs_dim * 4, 11 + len(low)), e2e, 2)
+    for t in range(20, 841, 20):
+        g2.step(20)
+        s2 = g2.agent_state()
+        for name in s2.dtype.names:
+            assert np.array_equal(s2[name], states[t][name]), (t, name)
+
+
+def test_e2e_plain_handle_split_halves_against_the_oracle(monkeypatch):
+    """no actor, no planner: host-set actions, a batch run as two halves on two streams (HK_SPLIT=1), in calls of 1 and of 20 ticks"""
+    monkeypatch.setenv("HK_SPLIT", "1")
+    low, high = [E2E, E2E, LQR, LQR], [NONE, NONE, FIXED, FIXED]
+    E = 64
+    g = hk.RacingEnv(_cfg(E, low, high, max_episode_steps=300))
+    o = O.OracleEnv(_twin_cfg(E, low, high, max_episode_steps=300))
+    g.reset(); o.reset()
+    r = np.random.default_rng(3)
+    t = 0
+    for n in [1] * 60 + [20] * 30:
+        s = (r.standard_normal((E, 4)) * 0.3).astype(np.float32)
+        b = r.choice([0, 1, 2, 2, 2], size=(E, 4)).astype(np.int32)
+        g.set_actions(s, b); o.set_actions(s, b)
+        g.step(n); o.step(n); t += n
+        _cmp(g, o, [0, 1], t)
+    assert (g.env_state()["episodes_done"] >= 2).all()
+    a = g.agent_state()
+    assert (a["plan_lane"][:, :2] == 0).all() and (a["avg_lane_diff"][:, :2] == 0).all()   # quasi-MCTS off: no plan, no metric
+
+
+def test_quasi_mcts_schedule():
+    """no search before episode step 100, one request at every later multiple of 100 while the kart is active, none at reset;
+    root reuse as in HKA (CyclesRootProcessed < 3, a new tree after a section entry); HK_HIGH_NONE never searches"""
+    low, high = [E2E, LQR, E2E, LQR], [MCTS, MCTS, NONE, FIXED]
+    E = 16
+    lat = 45
+    g = hk.RacingEnv(_cfg(E, low, high, max_episode_steps=700, mcts_latency_ticks=lat))
+    g.reset()
+    r = np.random.default_rng(5)
+    prev = g.mcts_state()
+    assert (prev["searches"][:, 0] == 0).all()                  # no plan at reset for the E2E agent ...
+    assert (prev["searches"][:, 1] == 1).all()                  # ... while the MCTS-LQR agent makes its initial plan
+    seen_kinds = set()
+    promoted = np.zeros(E, bool)
+    for t in range(1, 681):
+        s = (r.standard_normal((E, 4)) * 0.05).astype(np.float32)
+        g.set_actions(s, np.full((E, 4), 2, np.int32))
+        g.step(1)
+        m, es = g.mcts_state(), g.env_state()
+        a = g.agent_state()
+        ds = m["searches"][:, 0] - prev["searches"][:, 0]
+        assert ((ds == 0) | (ds == 1)).all()
+        for env in np.nonzero(ds)[0]:
+            step = int(m["ready_step"][env, 0]) - lat              # the episode step the request was posted on
+            assert step > 0 and step % 100 == 0, (t, env, step)
+            assert abs(int(es["episode_steps"][env]) - step) <= 1, (t, env, step)
+            kind = int(m["pend_kind"][env, 0])
+            seen_kinds.add(kind)
+            if kind == 2:                                           # the existing root again: no section entered since that plan
+                assert prev["root_live"][env, 0] == 1 and prev["root_cycles"][env, 0] < 3
+            else:
+                assert kind == 1
+        promoted |= (m["best"]["n_states"][:, 0] > 0)
+        assert (m["searches"][:, 2] == 0).all() and (a["plan_lane"][:, 2] == 0).all()   # HK_HIGH_NONE
+        prev = m
+    # steps 100 .. 600 of a 700-step episode; a request is skipped only when the tree already had its three searches (HKA:265)
+    assert (m["searches"][:, 0] <= 6).all() and (m["searches"][:, 0] >= 3).all() and (m["searches"][:, 0] == 6).any()
+    assert promoted.all() and 1 in seen_kinds and 2 in seen_kinds
+    assert (g.agent_state()["plan_lane"][:, 0] > 0).any()
+
+
+def test_e2e_rewards_double_academy_and_unit_dividers():
+    """cfg.rewards with every term zeroed but the three OnActionReceived rewards and the two PassCheckpoint rewards: an E2E agent's
+    step_reward over one tick equals the restated E2E OnActionReceived (base method aimed at the planned lane box, then again at the
+    Trigger) on the state before the tick, plus, on a tick that enters the next section, PassCheckpointLaneReward / 1 and
+    PassCheckpointVelocityReward / 1 — E2E pins both dividers to 1 (E2E:263-277), where an HKA agent divides by 1.3^d / 1.1^dv of its plan"""
+    low, high = [E2E, LQR], [MCTS, MCTS]
+    keep = ("TowardsCheckpointReward", "AccelerationReward", "SpeedReward", "PassCheckpointLaneReward", "PassCheckpointVelocityReward")
+    zero = {k: 0.0 for k in hk.config.REWARD_DEFAULTS if k not in keep}
+    E = 12
+    g = hk.RacingEnv(_cfg(E, low, high, rewards=1, reward_params=zero, max_episode_steps=400))
+    g.reset()
+    pol = _driver(g.obs_dim * 4, 4)
+    g.attach_policy(pol, [0], 2)
+    tr = R.Track(g.built)
+    lane_rw = np.float32(g.built.cfg.rw.PassCheckpointLaneReward)
+    vel_rw = np.float32(g.built.cfg.rw.PassCheckpointVelocityReward)
+    assert lane_rw != 0 and vel_rw != 0
+    g.rewards()
+    pre, pre_steps = g.agent_state(), g.env_state()["episode_steps"]
+    with_plan = planned_passes = 0
+    for t in range(1, 451):
+        g.step(1)
+        _, br = g.get_actions()
+        rw, _grp = g.rewards()
+        post, steps = g.agent_state(), g.env_state()["episode_steps"]
+        for env in range(E):
+            if steps[env] != pre_steps[env] + 1:                # the time-out tick ends the episode instead (not restated here)
+                continue
+            a0, a1 = pre[env, 0], post[env, 0]
+            want = R.academy_e2e(tr, a0, int(br[env, 0]))
+            s0, s1 = int(a0["section_index"]), int(a1["section_index"])
+            if s1 == s0 + 1:                                    # OnTriggerEnter of the next section: dividers 1
+                want = np.float32(want + np.float32(lane_rw / np.float32(1.0)))
+                want = np.float32(want + np.float32(vel_rw / np.float32(1.0)))
+                planned_passes += int(a0["plan_lane"][s1 % tr.L] != 0)
+            elif s1 != s0:
+                continue                                        # (driving back through a Trigger: not restated here)
+            assert rw[env, 0].view(np.uint32) == want.view(np.uint32), (t, env, s0, s1, rw[env, 0], want)
+            with_plan += int(a0["plan_lane"][(s0 + 1) % tr.L] != 0)
+        pre, pre_steps = post, steps
+    assert with_plan > 0                                         # some ticks aimed the first pass at a planned lane box
+    assert planned_passes > 0                                    # and some section entries had a plan entry an HKA divider would read
