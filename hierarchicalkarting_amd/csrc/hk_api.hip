@@ -86,17 +86,16 @@ struct Prof {
 // Scheduling switches: read from the environment ONCE, in hk_create, into the handle (listed in include/hk.h).  None of them changes a result bit; they
 // exist for the same-box A/B measurements under profiles/ and for the parity tests that run every schedule against the oracle.  Round 6 retired the ones whose
 // A/B is settled (HK_PARK, HK_NO_EAGER, HK_TAIL_WORST_CASE, HK_KEEP_LAST_SOLVE, HK_RUN_CAP_SHORT / _SPREAD, HK_SPLIT_WAYS, HK_SPLIT_MIN_TICKS, HK_LAZY_MIN_TICKS,
-// HK_REGROUP_ROUNDS, HK_LQN_SPARSE_BLOCKS, HK_NO_SPLIT, HK_NO_FISSION_SHAPED / _MCTS / _CHUNKS, HK_DEBUG_NO_CHECK, HK_STAMPS_DUMP) with their code paths; the numbers
-// they were settled with are in profiles/README.md.  hk_schedule_info() reports what a call ran.
+// HK_REGROUP_ROUNDS, HK_LQN_SPARSE_BLOCKS, HK_NO_SPLIT, HK_NO_FISSION_SHAPED / _MCTS / _CHUNKS, HK_DEBUG_NO_CHECK, HK_STAMPS_DUMP, HK_LAZY_JOIN, HK_DEBUG_MAX_ROUNDS) with
+// their code paths; the numbers they were settled with are in profiles/README.md.  hk_schedule_info() reports what a call ran.
 constexpr int LAZY_MIN_TICKS = 64;        // calls at least this long issue the rounds a spread field needs and finish the laggards after a look at the device
-constexpr int SPLIT_MIN_TICKS = 8;        // with HK_LAZY_JOIN=0: calls of plain handles at least this long run as two halves on two streams (a 20-tick call: 1 050 -> 1 120 M env-steps/s, round 4).
-                                          // Since round 6 the parts are joined lazily (split_join) and EVERY call of a plain handle of >= 8 192 envs is split: hk_step(1) 57.5 -> 45.7 us
-                                          // per call, hk_step(2) 98.3 -> 81.0 (joined at the end of every call the one-tick call took 72.6 us: the reason for the threshold)
+// Every call of a plain handle of >= 8 192 envs is split, and a short folded call leaves its parts open for the next one (split_join): hk_step(1) 57.5 us
+// on one stream, 72.6 us on two streams joined at the end of every call, 45.7 us joined lazily; hk_step(2) 98.3 / 107.9 / 81.0 us (round 6)
 constexpr int SPLIT_WAYS = 2;             // parts of a split batch (three / four parts on as many streams: 1 504 / 1 107 M against 1 532, round 4; three with round 6's in-wave solves: 1 410 against 2 270)
 constexpr int LQN_SPARSE_BLOCKS = 1024;   // workgroups per queue of a solver launch once the field has spread
 struct Tuning {
     bool fission = true;         // HK_FISSION=0: every handle on the fused tick kernel (phase B1 inside the tick loop) instead of tick kernel + env_b1_kernel per solve cadence
-    int split = -1;              // HK_SPLIT=1: the batch as two halves on two streams in EVERY call of a plain handle; 0: one stream always; unset: every call of a plain handle of >= 8 192 envs (with HK_LAZY_JOIN=0: calls of >= SPLIT_MIN_TICKS ticks, and while the field stands close)
+    int split = -1;              // HK_SPLIT=0: one stream always; unset (or 1): every call of a plain handle of >= 8 192 envs runs the batch as two halves on two streams
     int inwave = -1;             // HK_INWAVE=0: multi-player games always go through the queues and a solver launch (the schedule before round 6); 1: env_b1_kernel solves them in-wave in every round (tests); unset: in-wave while the games-per-launch meter says the field has spread
     bool lqn_spread = true;      // HK_LQN=pair: the solver launch of a spread field stays on the pair / matrix-core kernel (the schedule before round 6)
     bool lazy = true;            // HK_FIXED_ROUNDS=1: every call issues the worst-case round count up front (no look at the device)
@@ -105,7 +104,6 @@ struct Tuning {
     bool mcts_pause = true;      // HK_MCTS_NO_PAUSE=1: long calls of planner handles keep the deadline schedule
     bool mcts_overlap = true;    // HK_MCTS_NO_OVERLAP=1: long calls of planner handles launch a replan's searches when its stretch of rounds has ended, on the handle's stream (the schedule before round 5)
     int mcts_side_waves = -1;    // HK_MCTS_SIDE_WAVES=4 / 8 / 0: waves per workgroup of a search launch that runs beside tick launches (unset: 4 where a tick block fits beside one, else 8)
-    int debug_max_rounds = 0;    // HK_DEBUG_MAX_ROUNDS (diagnostic): cap on the rounds of a call, to look at the state in between
     void read()
     {
         auto flag = [](const char* n) { return std::getenv(n) != nullptr; };
@@ -118,7 +116,6 @@ struct Tuning {
         optimistic = !flag("HK_NO_OPTIMISTIC"); optimistic_skew = num("HK_OPTIMISTIC_SKEW", 0, 0, 3);
         mcts_pause = !flag("HK_MCTS_NO_PAUSE"); mcts_overlap = !flag("HK_MCTS_NO_OVERLAP");
         { const char* e = std::getenv("HK_MCTS_SIDE_WAVES"); mcts_side_waves = e ? (std::atoi(e) == 4 ? 4 : (std::atoi(e) == 0 ? 0 : 8)) : -1; }
-        debug_max_rounds = num("HK_DEBUG_MAX_ROUNDS", 0, 0, 1 << 20);
     }
 };
 
@@ -170,12 +167,12 @@ struct hk_context {
     hipStream_t meter_stream = nullptr;
     int meter_ticks = 0;           // ticks issued since the last copy of a short call
     // Long lazily completed calls (hk_step of thousands of ticks): the host issues far ahead of the GPU and would hold the schedule it chose on entry through
-    // whatever the field turns into (second episodes: the resets bring every pack back at once).  It therefore stays at most THROTTLE_AHEAD rounds ahead — a
-    // marker event every THROTTLE_EVERY rounds, a wait for the marker two back — and looks at the meter at every marker.  The GPU never drains.
+    // whatever the field turns into (second episodes: the resets bring every pack back at once).  A call of >= THROTTLE_MIN_TICKS (64) ticks therefore
+    // stays about 8 rounds ahead at most — a marker event every THROTTLE_EVERY (4) rounds, a wait for the marker two back — and looks at the meter at
+    // every marker.  The GPU never drains.
     bool throttle = false;
     hipEvent_t ev_thr[4] = {};
     bool thr_valid[4] = {};
-    bool lazy_join = true;         // HK_LAZY_JOIN=0: every split call joins its parts at its end (the schedule before)
     bool split_open = false;       // the parts of the last split call have not been joined into the handle's stream yet (short folded calls: split_join)
     bool meter_was_split = false;  // the call before ran as SPLIT_WAYS parts (their words are the current ones)
     bool meter_looked = false;     // meter_look has run (its band needs a previous answer)
@@ -310,6 +307,12 @@ int hk_create(const hk_config* cfg, hk_handle* out)
     if (cfg) {
         h->cfg = *cfg;
         h->dev.regroup_rounds = hk::REGROUP_ROUNDS;
+        // the tick kernel without phase B1 + env_b1_kernel per solve cadence for every handle of 3 or 4 agents (hk_env_run.h FISSION).  2-agent fields
+        // (cadence 1: every tick is a solve tick and both egos hold the 2-player game, HKA:317,709) stay on the fused kernel: round 6 measured the fission
+        // schedule for them (bit-equal; three launches per tick, no eager assembly) at 303 M env-steps/s against the fused kernel's 331 M — with a game
+        // per ego and tick the round is the pair solver's 131 072 games (98 us) and the GameSoA round trip of the assembly (B1 82 us), which a split does
+        // not shrink.  The 8-lane groups run the older loop.
+        h->dev.fission = h->tune.fission && cfg->num_agents > 2 && cfg->num_agents <= 4;
         rc = hk::env_create(h->cfg, h->sections, h->walls, h->dev, h->stream, h->err);
         if (rc) { g_last_error = h->err; hk_destroy(h); return rc; }
         h->env_ready = true;
@@ -602,7 +605,7 @@ static int issue_rounds_split(hk_handle h, int rounds)
     h->dev.slot0 = 0; h->dev.slot1 = 0; h->dev.qbase = 0; h->dev.round = h->round_half[0];
     if (first) for (int k = 0; k < K; k++) if (e[k]) h->prof.pool.push_back(e[k]);
     // a folded call (nothing follows its rounds on the handle's stream: no guard kernel, no report) leaves its parts open for the next one
-    if (!(h->dev.fold_split && h->lazy_join) || rc) { if (split_join(h) && !rc) rc = fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)"); }
+    if (!h->dev.fold_split || rc) { if (split_join(h) && !rc) rc = fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)"); }
     if (rc) g_last_error = h->err;
     return rc;
 }
@@ -622,7 +625,6 @@ static int issue_check(hk_handle h, bool lazy)
 // of which costs it a round), issue the rounds the laggard needs and look again.
 static int finish_ticks(hk_handle h)
 {
-    const int cadence = h->cfg.num_agents > 2 ? 4 : 1;
     h->dev.last_solve_skippable = false; h->dev.guard_rounds_left = 0; h->dev.exact_plan = false; h->throttle = false;      // (the laggards' rounds are plain rounds)
     bool packed = false;
     for (int guard = 0; guard < 1024 && h->step_pending; guard++) {
@@ -636,7 +638,7 @@ static int finish_ticks(hk_handle h)
         // Rounds for the slowest env if it met no further multi-player game (+ 1), not for the worst case (a round per cadence): the
         // batch ends with a look at the device anyway, and two thirds of the worst-case rounds used to find nothing to do (94 of 141 in
         // the headline's 3 072-tick call, ~18 us each).  An env that does park on every solve tick still gets a third of its ticks per batch.
-        const int cap = (h->dev.fission && cadence == 1) ? 1 : std::max(h->dev.P.run_cap, cadence);      // (2-agent fission: a tick per round)
+        const int cap = std::max(h->dev.P.run_cap, hk::solve_cadence(h->cfg));
         rc = issue_rounds(h, (maxleft + cap - 1) / cap + 1);
         if (rc) return rc;
         rc = issue_check(h, true);
@@ -656,7 +658,7 @@ static int finish_ticks(hk_handle h)
 // the queues while the field stands close after a reset of every env)
 static bool inwave_allowed(hk_handle h)
 {
-    if (!h->dev.fission || h->dev.P.any_lqr == 0 || h->cfg.num_agents < 3 || h->cfg.num_agents > 4 || h->tune.inwave == 0) return false;
+    if (!h->dev.fission || h->dev.P.any_lqr == 0 || h->tune.inwave == 0) return false;
     return h->tune.inwave == 1 || h->meter_sparse;
 }
 constexpr int METER_TICKS = 16;
@@ -696,7 +698,6 @@ static void meter_look(hk_handle h)
     h->meter_games = (int)std::min<unsigned long long>(worst, 1u << 30);
 }
 
-static bool inwave_allowed(hk_handle h);
 // what the meter's last look means for the launches from here on: where the multi-player games are solved, and — the two are coupled — how the regroup
 // orders the envs that hold them.  Queues want such envs PACKED (they leave their tick launches together), in-wave solves want them APART (a wave solves
 // its games a pass at a time; hk_regroup_pos.h): when the schedule changes sides the order of the last regroup is the wrong one, so the next round regroups.
@@ -730,9 +731,107 @@ static int throttle_mark(hk_handle h, int r)
     return meter_copy(h, false);
 }
 
-// hk_schedule_info: what step_ticks decided for the call it just issued, in one place (the decisions themselves are spread over the function for
-// historical reasons; this record is what bench.py prints, so a measured number names its schedule)
-static void record_schedule(hk_handle h, int n_ticks, const char* rounds_mode, int rounds, bool fold, bool planner)
+// Everything one hk_step call of n_ticks runs, decided in one place from the handle as the call finds it (plan_call writes nothing; step_ticks
+// applies the plan and issues it):
+//   planner            the handle has MCTS agents; lat_min the smaller of its two latencies; a short_call (n_ticks <= defer) shares one search launch
+//                      with the calls around it; T0 the episode step the field is believed to stand on before the call (-1: not known); t_req >= 0: a
+//                      short call of a planner + actor handle that holds the replan step t_req — its searches go to the side stream
+//   pause              long call of a planner handle without actors: stretches of rounds between search launches (step_pause)
+//   lazy               the rounds a field without multi-player games needs; the laggards are finished by the next entry point (finish_ticks)
+//   fold               the first tick launch arms and the last one is the completion guard (no env_arm_kernel, no env_check_kernel)
+//   split              two halves on two streams (issue_rounds_split); fold_split: each part's last tick launch is its guard; continue_split: a short
+//                      folded split call continues the parts the call before left open
+//   eager, run_cap     P.eager (the eager assembly, hk_env_run.h) and P.run_cap (ticks an env may run per launch)
+//   throttle           stay a bounded number of rounds ahead of the GPU and look at the meter (throttle_mark)
+//   rounds             rounds issued up front (pause: 0, the stretches decide); exact_plan: the optimistic plan, exactly `rounds` launches
+//   last_solve_skippable, guard_rounds_left    -> EnvDevice (hk_env_host.h); rounds_mode: hk_schedule_info's "rounds"
+struct CallPlan {
+    int n_ticks = 0, lat_min = 0, defer = 0;
+    long long T0 = -1, t_req = -1;
+    bool planner = false, short_call = false, pause = false, lazy = false, fold = false, split = false, fold_split = false, continue_split = false;
+    bool eager = false, throttle = false, exact_plan = false, last_solve_skippable = false;
+    int run_cap = hk::RUN_CAP, rounds = 0, guard_rounds_left = 0;
+    const char* rounds_mode = "";
+};
+
+static CallPlan plan_call(const hk_context* h, int n_ticks)
+{
+    const hk_config& cfg = h->cfg;
+    const bool quad = cfg.num_agents > 2 && cfg.num_agents <= 4, fission = h->dev.fission, any_lqr = h->dev.P.any_lqr != 0;
+    CallPlan p;
+    p.n_ticks = n_ticks;
+    // Planner searches: a launch of the search kernel lasts as long as one search however few it holds, so requests are batched.  A long call launches
+    // them every MCTS_FLUSH_ROUNDS rounds and once more before it returns; short calls (a Unity host stepping tick by tick, or the chunks between two RL
+    // decisions) share ONE launch until `defer` ticks have been armed since the last one — early enough, because a plan is due > MCTS_MIN_LATENCY ticks
+    // after its request.  (hk_get_mcts_state launches what is pending before it reads.)  A request posted on armed tick 1 is searched before armed
+    // tick defer + 1 runs, and its plan is due `latency` ticks after the request: defer = the handle's smaller latency - 1, at least MCTS_DEFER_TICKS.
+    p.planner = h->dev.mcts.st != nullptr;
+    const bool plain = !p.planner && h->n_policies == 0;
+    p.lat_min = std::min(cfg.mcts_latency_ticks, cfg.mcts_initial_latency_ticks);
+    p.defer = std::max(hk::MCTS_DEFER_TICKS, p.lat_min - 1);
+    p.short_call = p.planner && n_ticks <= p.defer;
+    p.T0 = h->lock_tick;
+    // Round 5: the searches of a replan beside the CHUNKS that follow it (handles with attached actors step in decision chunks; round 4 launched a replan's
+    // searches up to `defer` ticks late, on the handle's stream, and every chunk behind them waited ~10 - 100 ms).  If the field is believed to be in lock-step
+    // the host knows the chunk that holds the replan step (a multiple of 100): whatever is queued is searched BEFORE that chunk, so that the launch after it
+    // holds that chunk's requests only — none older than the chunk — and may therefore run on the side stream until the chunk that reaches request +
+    // latency.  A wrong belief costs the overlap only: requests posted at other times are served by the `defer` rule exactly as before, and every
+    // search launch first waits for the one in flight (they share the tree arena).
+    if (p.short_call && p.T0 >= 0 && h->tune.mcts_overlap && h->n_policies > 0 && (p.T0 / 100 + 1) * 100 <= p.T0 + n_ticks) p.t_req = (p.T0 / 100 + 1) * 100;
+    // Long calls of a planner handle without attached actors run in PAUSE mode: an env that requests a search stops at the next tick boundary until the
+    // search has run, the host runs a stretch of rounds (every env reaches its replan tick or the end of the call), launches ALL the searches of the stretch
+    // in one batch, looks at what is left and repeats.  Without the pause the requests of one replan wave trickle in over many rounds (envs that queue
+    // multi-player games advance 4 ticks a round, the others 8) and every partial batch costs a full search latency: 4-agent Complex, 16 384 envs: 11.8 -> see profiles/.
+    p.pause = p.planner && !p.short_call && h->n_policies == 0 && h->done_host != nullptr && h->tune.mcts_pause;
+    // Rounds.  An env that meets no multi-player game retires RUN_CAP ticks per round; one that does retires at least a solve cadence.  Handles with a
+    // planner or attached actors issue the worst-case count up front (they step in short chunks and must not stall on the host).  Everything else — the
+    // LQNG races of the headline — issues what a field without multi-player games needs, and the stragglers are finished lazily by the next call that
+    // touches the state (finish_ticks): most of the worst-case rounds found nothing to do, and on a 20-tick call they were 5 launches of 8.  (Short calls —
+    // a host stepping tick by tick — keep the fixed count too: a handful of rounds, no host sync.)
+    p.lazy = plain && h->done_host != nullptr && n_ticks >= LAZY_MIN_TICKS && h->tune.lazy;
+    // Arming: a kernel of its own for pause and lazy calls; in the others the first tick launch adds the ticks itself and the last one raises the "did not
+    // complete" flag the guard kernel would (a one-tick call: 4 launches instead of 9 with round 2's tail regroup; split calls fold too since round 6)
+    p.fold = !p.pause && !p.lazy;
+    // the eager assembly (hk_env_run.h) for plain quad handles, and in pause mode too: requests are posted on the same ticks, a round earlier at most
+    // (configs[2]: 61.4 -> 63.6 M env-steps/s).  Planner / actor handles outside pause mode keep their deadline arithmetic as it was.
+    p.eager = quad && (plain || p.pause);
+    // Two halves on two streams (issue_rounds_split) for every call of a plain handle of >= 8 192 envs: round 4 split the long calls (1 472 vs 1 392 M
+    // env-steps/s in round 3's protocol window; headline 1 221 -> 1 292 M, race start 439 -> 458 M), round 6 every call, with the parts joined lazily.
+    p.split = plain && p.eager && h->tune.split != 0 && cfg.num_envs >= 8192;
+    p.fold_split = p.fold && p.split;
+    p.continue_split = p.fold_split && h->tune.lazy && n_ticks < LAZY_MIN_TICKS;
+    p.throttle = p.lazy && n_ticks >= THROTTLE_MIN_TICKS && fission && any_lqr;
+    // ticks per launch: FISSION — every env parks at every solve tick, so a round retires exactly one cadence; longer launches once the field has spread
+    // out (RUN_CAP_SPREAD); short calls of plain LQNG handles one solve cadence per launch — with the eager assembly every env, in a pack or not, retires
+    // it, so a 20-tick call is 6 equal rounds and no tail (at 8 ticks per launch: 3 rounds + a regroup + 5 rounds for the laggards)
+    const long long since_reset = h->dev.ticks_since_reset + h->dev.call_ticks;        // (the call before counts from here on)
+    if (p.pause) p.run_cap = fission ? 4 : hk::RUN_CAP;
+    else if (fission && any_lqr) p.run_cap = 4;
+    else if (p.lazy && cfg.num_agents > 2 && since_reset >= hk::BULK_TICKS) p.run_cap = hk::RUN_CAP_SPREAD;
+    else if (!p.lazy && p.eager) p.run_cap = 4;
+    if (p.pause) p.rounds = 0;
+    else if (p.lazy) p.rounds = hk::env_rounds_min(n_ticks, p.run_cap);
+    else p.rounds = hk::env_rounds_for(cfg, n_ticks, p.run_cap, p.eager);
+    // The optimistic plan of a fixed-round call (round 5).  If every env stands on episode step T0, the call's ticks T0 + 1 .. T0 + n hold S solve ticks
+    // (multiples of the cadence) and the field needs exactly S rounds of {tick launch up to the solve tick, B1, solver} and one more tick launch: a one-tick
+    // call off a solve tick is ONE launch, the driver's 20-tick window 6 + 5 + 5 launches per half instead of 7 + 7 + 7.  The plan is a belief, not a proof
+    // (envs finish and reset on their own; a time-out inside the call would add a solve tick): the call's completion guard verifies it, an env the plan
+    // missed keeps its ticks (and stays parked at its solve tick: hk_env_run.h `stuck`), and the next entry point that looks at the state drops the belief
+    // and finishes it (verify_optimistic).  Nothing is ever wrong, a wrong belief is only slow — so it is used only where it is cheap to check.
+    if (!p.lazy && plain && fission && any_lqr && h->tune.optimistic && p.T0 >= 0 && p.T0 + n_ticks < cfg.max_episode_steps) {
+        const long long Tb = p.T0 + h->tune.optimistic_skew;
+        const int cad = hk::solve_cadence(cfg);
+        p.rounds = (int)((Tb + n_ticks) / cad - Tb / cad) + 1;               // the multiples of the cadence in (Tb, Tb + n], + 1
+        p.exact_plan = true;
+    }
+    p.guard_rounds_left = p.fold && !p.split ? p.rounds : 0;         // the tick launch that brings this to 0 is the call's last: it is the guard
+    p.last_solve_skippable = p.fold && plain && !p.split;
+    p.rounds_mode = p.pause ? "pause (stretches of rounds between search launches)" : p.lazy ? "lazy" : "fixed";
+    return p;
+}
+
+// hk_schedule_info: what the call just issued ran (bench.py prints it, so a measured number names its schedule)
+static void record_schedule(hk_handle h, const CallPlan& p)
 {
     char buf[640];
     const char* kern = h->dev.fission ? "fission (tick kernel + env_b1_kernel per solve cadence)" : "fused";
@@ -742,292 +841,186 @@ static void record_schedule(hk_handle h, int n_ticks, const char* rounds_mode, i
     std::snprintf(buf, sizeof(buf),
                   "{\"call_ticks\": %d, \"rounds\": \"%s\", \"rounds_issued\": %d, \"kernel\": \"%s\", \"streams\": %d, \"ticks_per_launch\": %d, "
                   "\"optimistic_plan\": %s, \"armed_in_first_launch\": %s, \"multi_player_games\": \"%s\", \"games_meter\": \"%s\", \"games_meter_value\": %d, \"planner\": %s, \"actors\": %d}",
-                  n_ticks, rounds_mode, rounds, kern, h->split ? SPLIT_WAYS : 1, h->dev.P.run_cap, h->dev.exact_plan ? "true" : "false", fold ? "true" : "false",
-                  games, h->meter_sparse ? "sparse" : (h->meter_dense ? "dense" : "medium"), h->meter_games, planner ? "true" : "false", h->n_policies);
+                  p.n_ticks, p.rounds_mode, p.rounds, kern, p.split ? SPLIT_WAYS : 1, p.run_cap, p.exact_plan ? "true" : "false", p.fold ? "true" : "false",
+                  games, h->meter_sparse ? "sparse" : (h->meter_dense ? "dense" : "medium"), h->meter_games, p.planner ? "true" : "false", h->n_policies);
     h->sched = buf;
 }
 
-// n_ticks of every env: arm, rounds of {fused tick kernel, queued multi-player solves}, check
-static int step_ticks(hk_handle h, int n_ticks)
+// the plan into the handle (the order matters where noted)
+static void apply_plan(hk_handle h, const CallPlan& p)
 {
-    int rc;
-    meter_look(h);
-    // Planner searches: a launch of the search kernel lasts as long as one search however few it holds, so requests are
-    // batched.  A long call launches them every MCTS_FLUSH_ROUNDS rounds and once more before it returns; short calls (a
-    // Unity host stepping tick by tick, or the chunks between two RL decisions) share ONE launch until MCTS_DEFER_TICKS
-    // ticks have been armed since the last one — early enough, because a plan is due > MCTS_MIN_LATENCY ticks after its
-    // request.  (hk_get_mcts_state launches what is pending before it reads.)
-    const bool planner = h->dev.mcts.st != nullptr;
-    // (the parts of the call before are still open — split_join: only a short folded call of a plain handle may continue them; whether THIS one is split
-    // and folded is known further down, everything else joins here, before it puts anything on the handle's stream)
-    if (h->split_open && (planner || h->n_policies > 0 || n_ticks >= LAZY_MIN_TICKS || !h->tune.lazy)) { if (split_join(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)"); }
-    const long long T0 = h->lock_tick;                           // the episode step the field is believed to stand on before this call (-1: not known)
-    if (h->lock_tick >= 0) h->lock_tick += n_ticks;
-    h->dev.exact_plan = false;
-    // (how long a request may wait for its launch: a request posted on armed tick 1 is searched before armed tick defer + 1 runs, and its
-    // plan is due `latency` ticks after the request — so defer = the handle's smaller latency - 1, at least MCTS_DEFER_TICKS)
-    const int defer = std::max(hk::MCTS_DEFER_TICKS, std::min(h->cfg.mcts_latency_ticks, h->cfg.mcts_initial_latency_ticks) - 1);
-    const bool short_call = planner && n_ticks <= defer;
-    // Round 5: the searches of a replan beside the CHUNKS that follow it (handles with attached actors step in decision chunks; round 4 launched a replan's
-    // searches up to `defer` ticks late, on the handle's stream, and every chunk behind them waited ~10 - 100 ms).  If the field is believed to be in lock-step
-    // the host knows the chunk that holds the replan step (a multiple of 100): whatever is queued is searched BEFORE that chunk, so that the launch after it
-    // holds that chunk's requests only — none older than the chunk — and may therefore run on the side stream until the chunk that reaches request +
-    // latency.  A wrong belief costs the overlap only: requests posted at other times are served by the `defer` rule exactly as before, and every
-    // search launch first waits for the one in flight (they share the tree arena).
-    const int lat_min = std::min(h->cfg.mcts_latency_ticks, h->cfg.mcts_initial_latency_ticks);
-    long long t_req = -1;
-    if (short_call && T0 >= 0 && h->tune.mcts_overlap && h->n_policies > 0) { t_req = (T0 / 100 + 1) * 100; if (t_req > T0 + n_ticks) t_req = -1; }
-    if (h->mcts_async_deadline >= 0 && (!short_call || T0 < 0 || T0 + n_ticks >= h->mcts_async_deadline)) { if (mcts_join_async(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (planner side stream)"); }
-    if (planner && h->dev.mcts_ticks > 0 && (!short_call || h->dev.mcts_ticks + n_ticks > defer || t_req >= 0)) {
-        if (mcts_join_async(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (planner side stream)");
-        rc = hk::env_flush_mcts(h->dev, h->stream, h->err);
-        if (rc) { g_last_error = h->err; return rc; }
-    }
-    if (short_call) h->dev.mcts_ticks += n_ticks;
-    h->dev.mcts_defer = short_call;
+    if (h->lock_tick >= 0) h->lock_tick += p.n_ticks;
+    if (p.short_call) h->dev.mcts_ticks += p.n_ticks;
+    h->dev.mcts_defer = p.short_call || p.pause;            // (pause: the host launches the searches between the stretches, the rounds do not)
     h->dev.ticks_since_reset += h->dev.call_ticks;      // the previous call's ticks
-    h->dev.lqn_sparse_blocks = LQN_SPARSE_BLOCKS;
     h->dev.lqn_spread = h->tune.lqn_spread;
     h->dev.inwave_always = h->tune.inwave == 1;
-    { const char* e = std::getenv("HK_LAZY_JOIN"); h->lazy_join = !(e && std::atoi(e) == 0); }
-    h->dev.call_ticks = n_ticks; h->dev.call_ticks_issued = 0;
-    // Long calls of a planner handle without attached actors run in PAUSE mode: an env that requests a search stops at the next
-    // tick boundary until the search has run, the host runs a stretch of rounds (every env reaches its replan tick or the end of
-    // the call), launches ALL the searches of the stretch in one batch, looks at what is left and repeats.  Without the pause
-    // the requests of one replan wave trickle in over many rounds (envs that queue multi-player games advance 4 ticks a round,
-    // the others 8) and every partial batch costs a full search latency: 4-agent Complex, 16 384 envs: 11.8 -> see profiles/.
-    const bool pause = planner && !short_call && h->n_policies == 0 && h->done_host != nullptr && h->tune.mcts_pause;
-    h->dev.P.mcts_pause = pause ? 1 : 0;
-    // the eager assembly (hk_env_run.h) in pause mode too: requests are posted on the same ticks, a round earlier at most
-    // (configs[2]: 61.4 -> 63.6 M env-steps/s)
-    if (planner) h->dev.P.eager = (pause && h->cfg.num_agents > 2 && h->cfg.num_agents <= 4) ? 1 : 0;
-    // Arming: a kernel of its own, except in fixed-round calls that are not split, where the first tick launch adds the ticks itself and the
-    // last one raises the "did not complete" flag the guard kernel would (a one-tick call: 4 launches instead of 9 with round 2's tail regroup)
-    const bool lazy_call = !planner && h->n_policies == 0 && h->done_host != nullptr && n_ticks >= LAZY_MIN_TICKS && h->tune.lazy;
-    const bool split_req = h->tune.split == 1 || (h->tune.split < 0 && (lazy_call || (!planner && h->n_policies == 0 && n_ticks >= (h->lazy_join ? 1 : SPLIT_MIN_TICKS))));      // (HK_SPLIT=1: every call)
-    // (round 6: split calls fold too — each part's first tick launch arms its lane groups, each part's last one is the guard: issue_rounds_split)
-    const bool fold = !pause && !lazy_call;
-    if (fold) h->dev.arm_ticks = n_ticks;
-    else {
-        rc = hk::env_launch_arm(h->dev, h->cfg, n_ticks, h->stream, h->err);
-        if (rc) { g_last_error = h->err; return rc; }
-    }
-    if (pause) {
-        h->throttle = false;
-        // the fission schedule for planner handles too (long calls, LQNG low levels; round 4): the same two kernels with the planner hooks
-        bool shaped_p = h->cfg.rewards != 0 || h->cfg.env_mode == HK_MODE_TRAINING;
-        for (int i = 0; i < h->cfg.num_agents; i++) shaped_p = shaped_p || h->cfg.training_agent[i] != 0;
-        shaped_p = false;      // (reward shaping and the Training-mode reset live in phases A / C: the tick kernel's instantiations carry them)
-        h->dev.fission = h->tune.fission && !shaped_p && h->dev.P.eager && h->cfg.num_agents > 2 && h->cfg.num_agents <= 4;
-        if (h->dev.fission) h->dev.P.run_cap = 4;
-        apply_meter(h);
-        h->dev.mcts_defer = true;                       // the rounds do not launch searches themselves
-        const int cadence = h->cfg.num_agents > 2 ? 4 : 1;
-        int maxleft = n_ticks;
-        for (int guard = 0; guard < 4096; guard++) {
-            // a stretch: enough rounds for EVERY env to reach its next replan (<= 100 ticks away) or the end of the call, also one
-            // that meets a multi-player game on every solve tick (a solve cadence per round).  The rounds in which most envs already
-            // wait cost tens of microseconds; a second search launch for the late ones would cost a full search latency
-            int reach = std::min(maxleft, 100);
-            // Round 5: a replan's searches run BESIDE the ticks that follow it.  The reference's search thread works for T = 0.9 s while FixedUpdate
-            // goes on (HKA:172-284) and its plan is used mcts_latency_ticks after the request; an env with an outstanding search now steps on until
-            // that tick (hk_env_run.h held_now) instead of stopping at once, so the search launch — as long as ONE search whatever the batch, ~10 ms —
-            // can share the GPU with up to 44 ticks of every env.  The host does not know when requests are posted; it guesses from the ticks since the
-            // last reset of every env (a field that was reset together replans together, on episode steps that are multiples of 100): the stretch is cut
-            // to end 40 ticks after the next such step, the searches are launched on a side stream right after the round that is expected to post the
-            // requests, and the handle's stream waits for them only before the rounds that could reach the deadline.  A wrong guess costs the overlap,
-            // nothing else: every stretch still ends with a search launch for whatever is queued, and no env passes its deadline unserved (device side).
-            const int lat = std::min(h->cfg.mcts_latency_ticks, h->cfg.mcts_initial_latency_ticks);
-            {
-                // Search workgroups beside the ticks: 4 waves (one per SIMD) on EVERY CU when a tick block still fits a CU's LDS beside one — the searches then run
-                // a wave to a SIMD (~7 ms instead of ~10.6 at two waves per SIMD on half the CUs); phase B1 reads its tables from global memory and the solver
-                // launch takes its <= 256-register form for those rounds (b1_small; hk_env_launch.h).  Otherwise 8 waves on half the CUs (round 5's first form).
-                int sw = 4;
-                for (int c = 0; c < h->dev.n_mcls; c++) {
-                    const auto& K = h->dev.mcls[c];
-                    if (hk::ga_ops(h->dev).mcts_lds_bytes(K.ntab, h->dev.P.L, K.na, K.lds_tier, 4) + (size_t)h->dev.tab_lds + 1024 > 160 * 1024) sw = 8;
-                }
-                if (!h->dev.tab_lds) sw = 8;
-                if (h->tune.mcts_side_waves >= 0) sw = h->tune.mcts_side_waves;
-                h->dev.mcts_side_waves = sw;
-            }
-            const bool overlap = h->tune.mcts_overlap && h->dev.fission && cadence == 4 && lat >= 24;
-            int r_post = -1, r_free = 0;
-            if (overlap) {
-                const long long T = (long long)h->dev.ticks_since_reset + (n_ticks - maxleft);      // episode step of a field in lock-step
-                const int k = 100 - (int)(T % 100);                                                 // ticks to the next replan step (1 .. 100)
-                const int after = ((lat - 1) / cadence - 1) * cadence;                              // whole rounds an env runs on before its deadline (45 -> 40 ticks)
-                reach = std::min(maxleft, (k + after - 1) % 100 + 1);
-                if (k <= reach) { r_post = (k + cadence - 1) / cadence + 1; r_free = after / cadence; }
-            }
-            const int stretch_rounds = (reach + cadence - 1) / cadence + 2;
-            if (r_post > 0 && r_post < stretch_rounds) {
-                if (!h->mcts_stream) HK_HIP(h, hipStreamCreateWithFlags(&h->mcts_stream, hipStreamNonBlocking));
-                if (!h->ev_mcts_go) HK_HIP(h, hipEventCreateWithFlags(&h->ev_mcts_go, hipEventDisableTiming));
-                if (!h->ev_mcts_done) HK_HIP(h, hipEventCreateWithFlags(&h->ev_mcts_done, hipEventDisableTiming));
-                rc = issue_rounds(h, r_post);
-                if (rc) return rc;
-                HK_HIP(h, hipEventRecord(h->ev_mcts_go, h->stream));
-                HK_HIP(h, hipStreamWaitEvent(h->mcts_stream, h->ev_mcts_go, 0));
-                rc = hk::env_flush_mcts_on(h->dev, h->stream, h->mcts_stream, h->err);
-                if (rc) { g_last_error = h->err; return rc; }
-                HK_HIP(h, hipEventRecord(h->ev_mcts_done, h->mcts_stream));
-                const int r2 = std::min(stretch_rounds - r_post, r_free);
-                h->dev.b1_small = h->dev.mcts_side_waves == 4;      // (4-wave search workgroups sit on EVERY CU: what runs beside them must share its LDS and registers)
-                rc = issue_rounds(h, r2);
-                h->dev.b1_small = false;
-                if (rc) return rc;
-                HK_HIP(h, hipStreamWaitEvent(h->stream, h->ev_mcts_done, 0));
-                rc = issue_rounds(h, stretch_rounds - r_post - r2);
-                if (rc) return rc;
-            } else {
-                rc = issue_rounds(h, stretch_rounds);
-                if (rc) return rc;
-            }
-            rc = hk::env_flush_mcts(h->dev, h->stream, h->err);
-            if (rc) { g_last_error = h->err; return rc; }
-            rc = issue_check(h, true);
-            if (rc) return rc;
-            HK_HIP(h, hipStreamSynchronize(h->stream));
-            maxleft = h->done_host[0];
-            if (maxleft <= 0 && !h->done_host[1]) break;
-            meter_look(h); apply_meter(h);      // (the copy of this stretch's check is current)
-        }
-        h->dev.mcts_defer = false;
-        h->dev.P.mcts_pause = 0;
-        record_schedule(h, n_ticks, "pause (stretches of rounds between search launches)", 0, false, true);
-        if (maxleft > 0) return fail(h, HK_ERR_HIP, "hk_step: an env did not complete its ticks (internal scheduling error)");
-        return HK_OK;
-    }
-    // Rounds.  An env that meets no multi-player game retires RUN_CAP ticks per round; one that does retires at least a solve
-    // cadence.  Handles with a planner or attached actors issue the worst-case count up front (they step in short chunks and
-    // must not stall on the host).  Everything else — the LQNG races of the headline — issues what a field without
-    // multi-player games needs, and the stragglers are finished lazily by the next call that touches the state
-    // (finish_ticks): most of the worst-case rounds found nothing to do, and on a 20-tick call they were 5 launches of 8.
-    // (short calls — a host stepping tick by tick — keep the fixed count too: a handful of rounds, no host sync)
-    const bool lazy = !planner && h->n_policies == 0 && h->done_host != nullptr && n_ticks >= LAZY_MIN_TICKS && h->tune.lazy;
-    // ticks per launch: longer launches once the field has spread out (see RUN_CAP_SPREAD)
-    const int spread_cap = hk::RUN_CAP_SPREAD;
-    // short calls of plain LQNG handles: one solve cadence per launch — with the eager assembly every env, in a pack or not, retires
-    // it, so a 20-tick call is 6 equal rounds and no tail (at 8 ticks per launch: 3 rounds + a regroup + 5 rounds for the laggards)
-    const int short_cap = 4;
-    const bool eager = true;
-    const bool plain = !planner && h->n_policies == 0;
-    // (planner / actor handles keep their deadline arithmetic as it was; the 8-lane groups run the older loop without it)
-    h->dev.P.eager = (eager && plain && h->cfg.num_agents > 2 && h->cfg.num_agents <= 4) ? 1 : 0;
-    // FISSION: every env parks at every solve tick, so a round retires exactly one cadence
-    bool shaped = h->cfg.rewards != 0 || h->cfg.env_mode == HK_MODE_TRAINING;       // reward shaping / Training mode: their own instantiations of the fused kernel
-    for (int i = 0; i < h->cfg.num_agents; i++) shaped = shaped || h->cfg.training_agent[i] != 0;
-    shaped = false;    // round 5: reward shaping and the Training-mode reset live in phases A / C — the tick kernel's <.., HAS_RW, HAS_TRAIN, .., FISSION> instantiations carry them
-    h->dev.fission = h->tune.fission && plain && !shaped && h->dev.P.eager && h->cfg.num_agents > 2 && h->cfg.num_agents <= 4;
-    // handles without an LQ agent (every low level an RL actor, attached or driven through hk_set_actions): the tick kernel of the fission
-    // schedule alone — phase B1 has nothing to solve, no env parks for it, no B1 launch
-    if (h->tune.fission && !shaped && h->dev.P.any_lqr == 0 && h->cfg.num_agents > 2 && h->cfg.num_agents <= 4) h->dev.fission = true;     // (with a planner too: its hook stays in the tick loop)
-    // handles that step in short fixed-round chunks (attached actors: a chunk per decision; planners outside their long calls): the same two
-    // kernels without the eager assembly — an env parks at its solve tick, B1 + solver run, the next round resumes it; the rounds issued
-    // are the worst case the fused kernel was given too (a round per solve tick of the chunk + 1)
-    if (h->tune.fission && !shaped && (planner || h->n_policies > 0) && h->cfg.num_agents > 2 && h->cfg.num_agents <= 4) h->dev.fission = true;
-    // 2-agent fields (cadence 1: every tick is a solve tick and both egos hold the 2-player game, HKA:317,709) stay on the fused kernel.  Round 6 measured
-    // the fission schedule for them (bit-equal; three launches per tick, no eager assembly): 303 M env-steps/s against the fused kernel's 331 M — with a game per
-    // ego and tick the round is the pair solver's 131 072 games (98 us) and the GameSoA round trip of the assembly (B1 82 us), which a split does not shrink.
-    const bool fission_a2 = false;
-    apply_meter(h);
-    h->throttle = lazy && n_ticks >= THROTTLE_MIN_TICKS && h->dev.fission && h->dev.P.any_lqr != 0;
+    h->dev.call_ticks = p.n_ticks; h->dev.call_ticks_issued = 0;
+    h->dev.P.mcts_pause = p.pause ? 1 : 0;
+    h->dev.P.eager = p.eager ? 1 : 0;
+    h->dev.P.run_cap = p.run_cap;
+    h->throttle = p.throttle;
     for (bool& v : h->thr_valid) v = false;
-    const int run_cap = (h->dev.fission && h->dev.P.any_lqr != 0) ? 4 : (lazy && h->cfg.num_agents > 2 && h->dev.ticks_since_reset >= hk::BULK_TICKS) ? spread_cap
-                        : (!lazy && plain && h->dev.P.eager) ? short_cap : hk::RUN_CAP;
-    h->dev.P.run_cap = run_cap;
-    // two halves on two streams (issue_rounds_split): the default for the long calls of plain handles since round 4 (1 472 vs 1 392 M
-    // env-steps/s in round 3's protocol window; bench.py then reports the roofline fraction of the whole job, see there), on request
-    // (HK_SPLIT=1) for every call.  The notes of the rounds before:  Measured: headline 1 221 -> 1 292 M env-steps/s, race start 439 -> 458 M,
-    // a 20-tick call unchanged (the solver kernel needs a SIMD's whole register file and finds none while the other half's tick kernel
-    // fills the GPU, so on short launches its latency is not hidden but moved).  On a spread field it is off unless HK_SPLIT=1: two tick
-    // kernels that share the GPU each take longer, and bench.py's per-launch roofline (bytes of a launch / its duration) would no longer
-    // describe the kernel (hk_prof's stage totals then add up the spans of two concurrent streams).  While the field stands close (BULK_TICKS after a reset of every env: every ego holds a multi-player game and a round's solver
-    // launch lasts hundreds of microseconds) the split is used without being asked: race start 440 -> 458 M.
-    const bool want_split = split_req, no_split = h->tune.split == 0;
-    const bool close_field = h->dev.ticks_since_reset < hk::BULK_TICKS;
-    h->split = (want_split || (close_field && !no_split)) && h->dev.P.eager && h->cfg.num_envs >= 8192;
+    h->split = p.split;
     if (h->split != h->meter_was_split && h->dev.game_stats) {
         // the batch changes shape: the parts that stop launching (or start again after a long time) must not be read with their old words
         // (no launch for it: the parts' next B1 launches start their words over, the host reads only the parts a call ran as — meter_look)
         h->dev.meter_fresh |= ((1u << hk::GAME_METER_PARTS) - 1u) & ~1u;
         h->meter_was_split = h->split;
     }
-    // (2-agent fission: a round retires exactly one tick whatever the launch's budget)
-    int rounds = lazy ? hk::env_rounds_min(h->cfg, n_ticks, fission_a2 ? 1 : run_cap) : hk::env_rounds_for(h->cfg, n_ticks, run_cap, h->dev.P.eager != 0 || fission_a2);
-    // The optimistic plan of a fixed-round call (round 5).  If every env stands on episode step T0, the call's ticks T0 + 1 .. T0 + n hold S solve ticks
-    // (multiples of the cadence) and the field needs exactly S rounds of {tick launch up to the solve tick, B1, solver} and one more tick launch: a one-tick
-    // call off a solve tick is ONE launch, the driver's 20-tick window 6 + 5 + 5 launches per half instead of 7 + 7 + 7.  The plan is a belief, not a proof
-    // (envs finish and reset on their own; a time-out inside the call would add a solve tick): the call's completion guard verifies it, an env the plan
-    // missed keeps its ticks (and stays parked at its solve tick: hk_env_run.h `stuck`), and the next entry point that looks at the state drops the belief
-    // and finishes it (verify_optimistic).  Nothing is ever wrong, a wrong belief is only slow — so it is used only where it is cheap to check.
-    if (!lazy && plain && h->dev.fission && h->dev.P.any_lqr != 0 && h->tune.optimistic && T0 >= 0 && T0 + n_ticks < h->cfg.max_episode_steps && h->tune.debug_max_rounds == 0) {
-        const long long Tb = T0 + h->tune.optimistic_skew;
-        const int cad = h->cfg.num_agents > 2 ? 4 : 1;
-        const int S = (int)((Tb + n_ticks) / cad - Tb / cad);               // multiples of the cadence in (Tb, Tb + n]
-        rounds = S + 1;
-        h->dev.exact_plan = true;
-        h->exact_idx = 0; h->exact_total = rounds;
+    apply_meter(h);                                     // (after P.eager and the previous call's ticks)
+    h->dev.exact_plan = p.exact_plan;
+    h->exact_idx = 0; h->exact_total = p.rounds;           // (read only while dev.exact_plan is set)
+    h->dev.guard_rounds_left = p.guard_rounds_left;
+    h->dev.fold_split = p.fold_split;
+    h->dev.last_solve_skippable = p.last_solve_skippable;
+}
+
+// A search launch on the side stream, behind everything issued so far on the handle's stream; the handle's stream waits for ev_mcts_done before anything
+// uses its plans (mcts_join_async, or step_pause itself)
+static int launch_side_search(hk_handle h, int side_waves)
+{
+    if (!h->mcts_stream) HK_HIP(h, hipStreamCreateWithFlags(&h->mcts_stream, hipStreamNonBlocking));
+    if (!h->ev_mcts_go) HK_HIP(h, hipEventCreateWithFlags(&h->ev_mcts_go, hipEventDisableTiming));
+    if (!h->ev_mcts_done) HK_HIP(h, hipEventCreateWithFlags(&h->ev_mcts_done, hipEventDisableTiming));
+    HK_HIP(h, hipEventRecord(h->ev_mcts_go, h->stream));
+    HK_HIP(h, hipStreamWaitEvent(h->mcts_stream, h->ev_mcts_go, 0));
+    h->dev.mcts_side_waves = side_waves;
+    const int rc = hk::env_flush_mcts_on(h->dev, h->stream, h->mcts_stream, h->err);
+    if (rc) { g_last_error = h->err; return rc; }
+    HK_HIP(h, hipEventRecord(h->ev_mcts_done, h->mcts_stream));
+    return HK_OK;
+}
+
+// Pause mode: stretches of rounds, each ended by a search launch and a look at what is left (the fission schedule for planner handles too: the same two
+// kernels with the planner hooks, round 4)
+static int step_pause(hk_handle h, const CallPlan& p)
+{
+    const int cadence = hk::solve_cadence(h->cfg);
+    // Search workgroups beside the ticks: 4 waves (one per SIMD) on EVERY CU when a tick block still fits a CU's LDS beside one — the searches then run
+    // a wave to a SIMD (~7 ms instead of ~10.6 at two waves per SIMD on half the CUs); phase B1 reads its tables from global memory and the solver
+    // launch takes its <= 256-register form for those rounds (b1_small; hk_env_launch.h).  Otherwise 8 waves on half the CUs (round 5's first form).
+    int sw = h->dev.tab_lds ? 4 : 8;
+    for (int c = 0; c < h->dev.n_mcls; c++) {
+        const auto& K = h->dev.mcls[c];
+        if (hk::ga_ops(h->dev).mcts_lds_bytes(K.ntab, h->dev.P.L, K.na, K.lds_tier, 4) + (size_t)h->dev.tab_lds + 1024 > 160 * 1024) sw = 8;
     }
-    if (h->tune.debug_max_rounds > 0) rounds = std::min(rounds, h->tune.debug_max_rounds);     // (diagnostic: look at the state between two rounds)
-    {
-        // the rounds every env needs at RUN_CAP ticks a round, then — the laggards packed into the first lane groups — the tail
-        const int main_rounds = std::min(rounds, fission_a2 ? n_ticks : (n_ticks + run_cap - 1) / run_cap);
-        h->dev.guard_rounds_left = (fold && !h->split) ? rounds : 0;          // the tick launch that brings this to 0 is the call's last: it is the guard
-        h->dev.fold_split = fold && h->split;
-        if (h->split_open && !h->dev.fold_split) { if (split_join(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)"); }
-        h->dev.last_solve_skippable = fold && plain && !h->split && h->tune.debug_max_rounds == 0;
-        // (with the eager assembly there is nothing to regroup between the two: ONE issue — a split call used to join its streams and fork them again for
-        // the tail, which left the first stream idle for ~100 us of the driver's 20-tick call)
-        rc = issue_rounds(h, h->dev.P.eager ? rounds : main_rounds);
-        if (rc) return rc;
-        if (rounds > main_rounds && !h->dev.P.eager) {
-            // (with the eager assembly every env retires a cadence per round: there are no laggards to pack, and a one-tick call
-            // would pay three more GPU operations for the regroup than for its tick)
-            if (!planner && h->n_policies == 0 && !h->dev.P.eager) {
-                rc = hk::env_launch_regroup(h->dev, h->cfg, h->stream, h->err);
-                if (rc) { g_last_error = h->err; return rc; }
-            }
-            rc = issue_rounds(h, rounds - main_rounds);
-            if (rc) return rc;
+    if (h->tune.mcts_side_waves >= 0) sw = h->tune.mcts_side_waves;
+    // Round 5: a replan's searches run BESIDE the ticks that follow it.  The reference's search thread works for T = 0.9 s while FixedUpdate goes on
+    // (HKA:172-284) and its plan is used mcts_latency_ticks after the request; an env with an outstanding search now steps on until that tick
+    // (hk_env_run.h held_now) instead of stopping at once, so the search launch — as long as ONE search whatever the batch, ~10 ms — can share the GPU
+    // with up to 44 ticks of every env.  The host does not know when requests are posted; it guesses from the ticks since the last reset of every env
+    // (a field that was reset together replans together, on episode steps that are multiples of 100): the stretch is cut to end 40 ticks after the next
+    // such step, the searches are launched on a side stream right after the round that is expected to post the requests, and the handle's stream waits
+    // for them only before the rounds that could reach the deadline.  A wrong guess costs the overlap, nothing else: every stretch still ends with a
+    // search launch for whatever is queued, and no env passes its deadline unserved (device side).
+    const bool overlap = h->tune.mcts_overlap && h->dev.fission && cadence == 4 && p.lat_min >= 24;
+    int rc, maxleft = p.n_ticks;
+    for (int guard = 0; guard < 4096; guard++) {
+        // a stretch: enough rounds for EVERY env to reach its next replan (<= 100 ticks away) or the end of the call, also one that meets a multi-player
+        // game on every solve tick (a solve cadence per round).  The rounds in which most envs already wait cost tens of microseconds; a second search
+        // launch for the late ones would cost a full search latency
+        int reach = std::min(maxleft, 100);
+        int r_post = -1, r_free = 0;
+        if (overlap) {
+            const long long T = (long long)h->dev.ticks_since_reset + (p.n_ticks - maxleft);      // episode step of a field in lock-step
+            const int k = 100 - (int)(T % 100);                                                   // ticks to the next replan step (1 .. 100)
+            const int after = ((p.lat_min - 1) / cadence - 1) * cadence;                          // whole rounds an env runs on before its deadline (45 -> 40 ticks)
+            reach = std::min(maxleft, (k + after - 1) % 100 + 1);
+            if (k <= reach) { r_post = (k + cadence - 1) / cadence + 1; r_free = after / cadence; }
         }
-    }
-    if (t_req >= 0) {
-        // this chunk held the replan step: its requests (and nothing older) go to the side stream
-        if (mcts_join_async(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (planner side stream)");
-        if (!h->mcts_stream) HK_HIP(h, hipStreamCreateWithFlags(&h->mcts_stream, hipStreamNonBlocking));
-        if (!h->ev_mcts_go) HK_HIP(h, hipEventCreateWithFlags(&h->ev_mcts_go, hipEventDisableTiming));
-        if (!h->ev_mcts_done) HK_HIP(h, hipEventCreateWithFlags(&h->ev_mcts_done, hipEventDisableTiming));
-        HK_HIP(h, hipEventRecord(h->ev_mcts_go, h->stream));
-        HK_HIP(h, hipStreamWaitEvent(h->mcts_stream, h->ev_mcts_go, 0));
-        h->dev.mcts_side_waves = h->tune.mcts_side_waves >= 0 ? h->tune.mcts_side_waves : 8;      // (decision chunks: 8-wave workgroups on half the CUs)
-        rc = hk::env_flush_mcts_on(h->dev, h->stream, h->mcts_stream, h->err);
+        const int stretch_rounds = (reach + cadence - 1) / cadence + 2;
+        if (r_post > 0 && r_post < stretch_rounds) {
+            if ((rc = issue_rounds(h, r_post)) || (rc = launch_side_search(h, sw))) return rc;
+            const int r2 = std::min(stretch_rounds - r_post, r_free);
+            h->dev.b1_small = sw == 4;      // (4-wave search workgroups sit on EVERY CU: what runs beside them must share its LDS and registers)
+            rc = issue_rounds(h, r2);
+            h->dev.b1_small = false;
+            if (rc) return rc;
+            HK_HIP(h, hipStreamWaitEvent(h->stream, h->ev_mcts_done, 0));
+            rc = issue_rounds(h, stretch_rounds - r_post - r2);
+        } else {
+            rc = issue_rounds(h, stretch_rounds);
+        }
+        if (rc) return rc;
+        rc = hk::env_flush_mcts(h->dev, h->stream, h->err);
         if (rc) { g_last_error = h->err; return rc; }
-        HK_HIP(h, hipEventRecord(h->ev_mcts_done, h->mcts_stream));
-        // the oldest request in that launch was posted on step T0 + 1 at the earliest: its plan is first used on that step + the smaller latency
-        h->mcts_async_deadline = T0 + 1 + lat_min;
+        if ((rc = issue_check(h, true))) return rc;
+        HK_HIP(h, hipStreamSynchronize(h->stream));
+        maxleft = h->done_host[0];
+        if (maxleft <= 0 && !h->done_host[1]) break;
+        meter_look(h); apply_meter(h);      // (the copy of this stretch's check is current)
     }
-    if (planner && !short_call) {
+    h->dev.mcts_defer = false;
+    h->dev.P.mcts_pause = 0;
+    record_schedule(h, p);
+    if (maxleft > 0) return fail(h, HK_ERR_HIP, "hk_step: an env did not complete its ticks (internal scheduling error)");
+    return HK_OK;
+}
+
+// Fixed and lazy calls: the rounds issued up front, then the guard (or, folded, none: the last tick launch is the guard)
+static int step_rounds(hk_handle h, const CallPlan& p)
+{
+    // the rounds every env needs at run_cap ticks a round, then — the laggards packed into the first lane groups — the tail.  With the eager assembly
+    // every env retires a cadence per round: there are no laggards to pack, ONE issue (a one-tick call would pay three more GPU operations for the
+    // regroup than for its tick; a split call used to join its streams and fork them again for the tail, which left the first stream idle for ~100 us
+    // of the driver's 20-tick call)
+    const int main_rounds = p.eager ? p.rounds : std::min(p.rounds, (p.n_ticks + p.run_cap - 1) / p.run_cap);
+    int rc = issue_rounds(h, main_rounds);
+    if (rc) return rc;
+    if (p.rounds > main_rounds) {
+        if (!p.planner && h->n_policies == 0) {
+            rc = hk::env_launch_regroup(h->dev, h->cfg, h->stream, h->err);
+            if (rc) { g_last_error = h->err; return rc; }
+        }
+        if ((rc = issue_rounds(h, p.rounds - main_rounds))) return rc;
+    }
+    if (p.t_req >= 0) {
+        // this chunk held the replan step: its requests (and nothing older) go to the side stream, in 8-wave workgroups on half the CUs
+        if (mcts_join_async(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (planner side stream)");
+        if ((rc = launch_side_search(h, h->tune.mcts_side_waves >= 0 ? h->tune.mcts_side_waves : 8))) return rc;
+        // the oldest request in that launch was posted on step T0 + 1 at the earliest: its plan is first used on that step + the smaller latency
+        h->mcts_async_deadline = p.T0 + 1 + p.lat_min;
+    }
+    if (p.planner && !p.short_call) {
         // searches requested in the last rounds of a long call run before it returns
         rc = hk::env_flush_mcts(h->dev, h->stream, h->err);
         if (rc) { g_last_error = h->err; return rc; }
     }
-    if (!fold) {
-        rc = issue_check(h, lazy);
-        if (rc) return rc;
-    }
-    h->step_pending = lazy;
-    if (!lazy && h->dev.fission && (h->meter_ticks += n_ticks) >= METER_TICKS) { h->meter_ticks = 0; if ((rc = meter_copy(h, false))) return rc; }
-    record_schedule(h, n_ticks, lazy ? "lazy" : "fixed", rounds, fold, planner);
-    if (h->dev.exact_plan) h->opt_pending = true;
-    h->dev.exact_plan = false;
+    if (!p.fold && (rc = issue_check(h, p.lazy))) return rc;
+    h->step_pending = p.lazy;
+    if (!p.lazy && h->dev.fission && (h->meter_ticks += p.n_ticks) >= METER_TICKS) { h->meter_ticks = 0; if ((rc = meter_copy(h, false))) return rc; }
+    record_schedule(h, p);
+    if (p.exact_plan) h->opt_pending = true;
     // (an exact plan's last round is the tick launch alone and never reaches the solver launch that consumes this flag: left set, the first solver launch
     // of the rounds that finish a missed env — verify_optimistic — would be skipped and the env would resume on stale controls; found by the fold + skew
     // modes of tests/test_optimistic_plan_gpu.py, round 6)
+    h->dev.exact_plan = false;
     h->dev.last_solve_skippable = false;
     h->dev.guard_rounds_left = 0;
     return HK_OK;
+}
+
+// n_ticks of every env: settle what the call before left open, plan, apply the plan, issue it
+static int step_ticks(hk_handle h, int n_ticks)
+{
+    meter_look(h);
+    const CallPlan p = plan_call(h, n_ticks);
+    // the parts of a split call are still open (split_join): only a short folded split call continues them, everything else joins before it puts
+    // anything on the handle's stream
+    if (h->split_open && !p.continue_split && split_join(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)");
+    if (h->mcts_async_deadline >= 0 && (!p.short_call || p.T0 < 0 || p.T0 + n_ticks >= h->mcts_async_deadline) && mcts_join_async(h))
+        return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (planner side stream)");
+    int rc;
+    if (p.planner && h->dev.mcts_ticks > 0 && (!p.short_call || h->dev.mcts_ticks + n_ticks > p.defer || p.t_req >= 0)) {
+        if (mcts_join_async(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (planner side stream)");
+        rc = hk::env_flush_mcts(h->dev, h->stream, h->err);
+        if (rc) { g_last_error = h->err; return rc; }
+    }
+    apply_plan(h, p);
+    if (p.fold) h->dev.arm_ticks = n_ticks;
+    else if ((rc = hk::env_launch_arm(h->dev, h->cfg, n_ticks, h->stream, h->err))) { g_last_error = h->err; return rc; }
+    return p.pause ? step_pause(h, p) : step_rounds(h, p);
 }
 
 // The completion guard of the optimistic fixed-round calls issued since the last look (status bit 2: the last tick launch of a folded call, env_check_kernel

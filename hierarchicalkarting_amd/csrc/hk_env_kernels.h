@@ -261,9 +261,12 @@ inline int env_launch_check(EnvDevice& d, const hk_config& cfg, bool lazy, hipSt
 // start hold or, in Training mode, the ride to its first Trigger).  Budget ends: with the eager assembly (cap = cadence) they ARE
 // parks; otherwise at most ceil(n / cap) - 1.  A one-tick call is 2 rounds, a 20-tick call of a plain handle 7 (round 2 issued 4 and 8
 // by a looser bound).  env_check_kernel still guards the result.
+// every env meets its multi-player games on the ticks whose episode step is a multiple of the cadence (HKA:317; 2 agents: every tick)
+inline int solve_cadence(const hk_config& cfg) { return cfg.num_agents > 2 ? 4 : 1; }
+
 inline int env_rounds_for(const hk_config& cfg, int n_ticks, int cap = RUN_CAP, bool eager = false)
 {
-    const int cadence = cfg.num_agents > 2 ? 4 : 1;
+    const int cadence = solve_cadence(cfg);
     static_assert(RUN_CAP > 4, "RUN_CAP must exceed the solve cadence");
     const int solve_ticks = std::min(n_ticks, (n_ticks + cadence - 1) / cadence + 1 + n_ticks / 32);
     return eager ? solve_ticks + 1 : solve_ticks + (n_ticks + cap - 1) / cap;
@@ -271,11 +274,7 @@ inline int env_rounds_for(const hk_config& cfg, int n_ticks, int cap = RUN_CAP, 
 
 // Rounds a field needs for n ticks when nothing is queued: every env retires the launch's budget of ticks per round (long calls of
 // plain handles issue these, look at the device and finish the laggards: hk_api.hip finish_ticks).
-inline int env_rounds_min(const hk_config& cfg, int n_ticks, int cfg_run_cap = RUN_CAP)
-{
-    (void)cfg;
-    return (n_ticks + cfg_run_cap - 1) / cfg_run_cap;
-}
+inline int env_rounds_min(int n_ticks, int cap) { return (n_ticks + cap - 1) / cap; }
 
 inline int env_launch_run(EnvDevice& d, const hk_config& cfg, hipStream_t stream, std::string& err)
 {

@@ -319,9 +319,9 @@ int hk_set_actions(hk_handle h, const float* steer, const int32_t* branch);
  * touches the state (any hk_get_* / hk_set_* / hk_reset / hk_step / hk_prof_read / hk_gather_results, or hk_synchronize): it waits
  * for a two-word report of the device and issues what the laggard envs still need ("lazy completion").  hk_synchronize is the
  * completion point: a host that overlaps its own work with hk_step, or times it, calls hk_synchronize where it needs the ticks done.
- * Round 6: a lazily completed call of >= 512 ticks paces itself: the host stays at most 32 rounds (128 ticks) of launches ahead of the GPU (a marker event
- * every 16 rounds, a wait for the marker two back) so that it can look at the games meter and change where multi-player games are solved while the call runs —
- * such a call returns when its LAST 32 rounds are issued, not at once.  Shorter calls return as soon as they are issued, as before.
+ * A lazily completed call (>= 64 ticks) paces itself: the host stays about 8 rounds (32 ticks) of launches ahead of the GPU at most (a marker event
+ * every 4 rounds, a wait for the marker two back) so that it can look at the games meter and change where multi-player games are solved while the call runs —
+ * such a call returns when its LAST ~8 rounds are issued, not at once.  Shorter calls return as soon as they are issued.
  * Round 5: a fixed-round call of a plain handle whose envs are all believed to stand on the same episode step (a reset of every env, then only hk_step
  * calls) issues exactly the launches such a field needs — a one-tick call off a solve tick is one launch — and the completion guard verifies the
  * belief: the next entry point other than hk_step looks at it and, if an env fell behind (it finished its race, a time-out), finishes that env the
@@ -333,13 +333,13 @@ int hk_set_actions(hk_handle h, const float* steer, const int32_t* branch);
  * sticky in the same way (status bit 0) but does not fail the getters: the reference throws nothing there either (MathNet returns
  * inf / NaN), and hk_env_state.status bit 0 flags the karts whose state went non-finite.
  * Scheduling switches, read from the environment ONCE in hk_create (none changes a result bit; hk_schedule_info() reports what a call ran):
- * HK_FISSION (0: every handle on the fused tick kernel instead of the tick kernel without phase B1 + env_b1_kernel per solve cadence), HK_SPLIT (1: two halves on
- * two streams in every call of a plain handle whatever its size, 0: one stream always; unset: every call of a plain handle of >= 8 192 envs), HK_LAZY_JOIN (0: the
- * halves of a split call are joined into hk_stream at the end of every call instead of by the next entry point that needs the whole state), HK_INWAVE (0: multi-player games through the queues and a solver launch, 1: solved by the
+ * HK_FISSION (0: every handle on the fused tick kernel instead of the tick kernel without phase B1 + env_b1_kernel per solve cadence), HK_SPLIT (0: one stream
+ * always; unset: every call of a plain handle of >= 8 192 envs as two halves on two streams, joined into hk_stream by the next entry point that needs the whole
+ * state), HK_INWAVE (0: multi-player games through the queues and a solver launch, 1: solved by the
  * B1 waves that assembled them in every round; unset: in-wave once the field has spread), HK_LQN (pair: the pair / matrix-core solver launch also for a spread
  * field), HK_FIXED_ROUNDS, HK_NO_OPTIMISTIC (fixed-round calls issue the worst-case round count instead of the verified plan of a field in lock-step),
  * HK_OPTIMISTIC_SKEW (tests), HK_MCTS_NO_PAUSE, HK_MCTS_NO_OVERLAP / HK_MCTS_SIDE_WAVES (a replan's searches on the handle's stream after the stretch / search
- * workgroup size beside the ticks), HK_DEBUG_MAX_ROUNDS (diagnostic); read at table / buffer set-up: HK_MCTS_PERSIST_GB, HK_NO_HOLD_DEDUPE, HK_LQ_DEBUG,
+ * workgroup size beside the ticks); read at table / buffer set-up: HK_MCTS_PERSIST_GB, HK_NO_HOLD_DEDUPE, HK_LQ_DEBUG,
  * HK_TAB_GLOBAL (track tables read from global memory, as for tracks that exceed the LDS budget).  Round 6 retired the switches whose A/B was settled
  * (profiles/README.md keeps their numbers).
  * Planner handles (any HighMode MCTS agent): a call of more than 38 ticks without attached actors synchronises with the host

@@ -2,11 +2,7 @@
 
 Default: every call of a plain handle of >= 8 192 envs runs as two halves on two streams whose parts stay open from call to call (hk_api.hip split_join) —
 a host that steps tick by tick keeps both halves' meter words current, reaches the sparse (in-wave) schedule once the field has spread, and sees the same
-state, bit for bit, as a host that steps in long calls, whatever schedule each was given; a getter in between joins the parts.
-
-HK_LAZY_JOIN=0 (the schedule before): one-tick calls of a spread field run as ONE batch, so the second half's meter word stops being written after the
-race start.  Read for ever with its last value — the start's counts — it would keep such a host on the dense schedule for the rest of the race: the host
-only reads the parts the call before ran as, and a part that launches again after a change of shape starts its words over."""
+state, bit for bit, as a host that steps in long calls, whatever schedule each was given; a getter in between joins the parts."""
 import os
 import subprocess
 import sys
@@ -28,7 +24,6 @@ def same(a, r):
             x = x.view(np.uint32); y = y.view(np.uint32)
         assert np.array_equal(x, y), name
 
-lazy_join = os.environ.get("HK_LAZY_JOIN") != "0"
 b = hk.make_config(8192, 4, jitter_seed=5, laps=3, max_episode_steps=4000)
 g = hk.RacingEnv(b); ref = hk.RacingEnv(b)
 g.reset(); ref.reset()
@@ -41,12 +36,12 @@ for k in range(899):
         ref.step(302)
         same(g.agent_state(), ref.agent_state())
 last = g.schedule_info()
-assert last["call_ticks"] == 1 and last["streams"] == (2 if lazy_join else 1), last
+assert last["call_ticks"] == 1 and last["streams"] == 2, last
 assert last["games_meter"] == "sparse", last
 assert "in-wave" in last["multi_player_games"], last
 ref.step(598)
 same(g.agent_state(), ref.agent_state())
-# and on: a long call after the tick-by-tick stretch (with HK_LAZY_JOIN=0: two halves again, from words started over, not from the race start's)
+# and on: a long call after the tick-by-tick stretch
 g.step(64); ref.step(64)
 again = g.schedule_info()
 assert again["streams"] == 2 and again["games_meter"] in ("sparse", "medium"), again
@@ -62,10 +57,8 @@ print("meter ok")
 """
 
 
-@pytest.mark.parametrize("mode", ["default", "joined_every_call"])
+@pytest.mark.parametrize("mode", ["default"])
 def test_tick_by_tick_host_after_a_split_start(mode):
     env = {k: v for k, v in os.environ.items() if not k.startswith("HK_") or k in ("HK_LIB_PATH",)}
-    if mode == "joined_every_call":
-        env["HK_LAZY_JOIN"] = "0"
     r = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT}], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "meter ok" in r.stdout, r.stdout[-1500:] + r.stderr[-4000:]
