@@ -11,8 +11,18 @@ Method = SURVEY.md App. A: scene documents split on '--- !u!<class> &<id>'; an a
 m_PrefabInstance carries m_Modifications (target fileID in the source prefab, propertyPath, value | objectReference); values
 not overridden come from the prefab document itself.
 
+The EndToEndKartAgent ("E2E") karts of the *All scenes are not stripped: each is a KartClassic_HierarchicalMLAgent prefab instance
+whose HierarchicalKartAgent component is removed (m_RemovedComponents) and an EndToEndKartAgent added as a plain scene document on the
+instance's stripped GameObject.  For those the resolver reads the scene document itself (Mode, MaxStep, runQuasiMCTS, Sensors[], team
+wiring, reward dividers) and the rest from the instance as above (BehaviorParameters, DecisionRequester, the ArcadeKart's baseStats).
+An E2E kart placed as a stripped MonoBehaviour of a prefab of its own goes the HierarchicalKartAgent way, with the E2E fields kept.
+The E2E records go to a file of their own, and only the set-ups hk_config can hold are written: one Sensors[] layout, one kart stats
+block and one MaxStep per set-up, E2E karts in Inferencing mode.  Anything else stops the resolver with an error.
+
   python tools/extract_experiments.py            # prints a table
-  python tools/extract_experiments.py --update   # writes tests/golden/reference_experiments.json (data; no reference text)
+  python tools/extract_experiments.py --update   # writes tests/golden/reference_experiments.json (the set-ups with their E2E karts
+                                                 # unresolved, as before) and tests/golden/reference_e2e_experiments.json (the
+                                                 # latest-generation set-ups that hold an E2E kart, every kart resolved); data only
 """
 import argparse, glob, json, os, sys
 sys.path.insert(0, os.path.dirname(__file__))
@@ -26,6 +36,8 @@ GUID_REC = "b83c52cfa72e3b04aaada8bc4075b0e8"
 GUID_HKA = "e8765d53e046ef74898109def269b8cb"
 GUID_BP = "5d1c4e0b1822b495aa52bc52839ecb30"      # Unity.MLAgents.Policies.BehaviorParameters
 GUID_DR = "3a5c9d521e5ef4759a8246a07d52221e"      # DecisionRequester
+GUID_E2E = "28d8af8b732215b4ab548cff34d7ff02"     # EndToEndKartAgent
+E2E_KEYS = ("Mode", "MaxStep", "runQuasiMCTS", "is_active", "LaneDifferenceRewardDivider", "VelocityDifferenceRewardDivider")
 HIGH = {0: "MCTS", 1: "Fixed", 2: "Random"}       # HKA:21-33 enum order is checked in main()
 LOW = {0: "RL", 1: "MPC", 2: "LQR"}
 
@@ -104,10 +116,85 @@ class SceneExperiments:
                 return fid, doc
         return None, None
 
-    def agent(self, agent_fid):
+    def component_on(self, go_fid, inst, prefab_guid, script_guid_wanted):
+        """the doc of the component with that script on a scene GameObject: one added in the scene, else the instance's prefab's"""
+        for fid, (cid, stripped, kind, body) in self.scene.docs.items():
+            if (kind == "MonoBehaviour" and not stripped and isinstance(body, dict) and script_guid(body) == script_guid_wanted
+                    and (body.get("m_GameObject") or {}).get("fileID") == go_fid):
+                return body
+        return self.component_of_instance(inst, prefab_guid, script_guid_wanted)[1]
+
+    def behavior(self, bp):
+        model = bp.get("m_Model") or {}
+        mg = model.get("guid") if isinstance(model, dict) else None
+        return {
+            "model": os.path.basename(self.guid[mg]) if mg in self.guid else None,
+            "vector_observation_size": num((bp.get("m_BrainParameters") or {}).get("VectorObservationSize")),
+            "stacked": num((bp.get("m_BrainParameters") or {}).get("NumStackedVectorObservations")),
+            "team_id": num(bp.get("TeamId")), "behavior_type": num(bp.get("m_BehaviorType")),
+            "behavior_name": bp.get("m_BehaviorName"),
+        }
+
+    def kart_stats(self, prefab_guid, overrides):
+        """ArcadeKart.baseStats as the kart drives with them: the BaseKartClassic document, then the baseStats modifications of each nested
+        prefab instance from the innermost out, then the scene's (fields no document serializes keep ArcadeKart's class default, the
+        same for every kart)"""
+        def walk(g):
+            pf = uy.load(self.guid[g])
+            st = {}
+            for fid, (cid, stripped, kind, body) in pf.docs.items():
+                if kind == "MonoBehaviour" and isinstance(body, dict) and isinstance(body.get("baseStats"), dict):
+                    st.update({k: num(v) for k, v in body["baseStats"].items()})
+            for fid, (cid, stripped, kind, body) in pf.docs.items():
+                if kind == "PrefabInstance" and isinstance(body, dict):
+                    st.update(walk(body["m_SourcePrefab"]["guid"]))
+                    st.update({m["propertyPath"][len("baseStats."):]: num(m["value"]) for m in body["m_Modification"]["m_Modifications"]
+                               if m["propertyPath"].startswith("baseStats.")})
+            return st
+        st = walk(prefab_guid)
+        st.update(overrides)
+        return st
+
+    def placed_e2e(self, agent_fid, d):
+        """an EndToEndKartAgent added as a plain scene document to the GameObject of a kart prefab instance"""
+        go_fid = d["m_GameObject"]["fileID"]
+        go = self.scene.docs[go_fid]
+        if not go[1]:
+            sys.exit("%s: E2E agent %d sits on a GameObject made in the scene; not resolved" % (self.path, agent_fid))
+        inst_id = go[3]["m_PrefabInstance"]["fileID"]
+        inst = self.scene.docs[inst_id][3]
+        prefab_guid = inst["m_SourcePrefab"]["guid"]
+        mods = inst["m_Modification"]["m_Modifications"]
+        removed = {(r or {}).get("fileID") for r in inst["m_Modification"].get("m_RemovedComponents") or []}
+        hka, _ = self.component_of_instance(inst, prefab_guid, GUID_HKA)
+        if hka is not None and hka not in removed:
+            sys.exit("%s: E2E agent %d shares its kart with a HierarchicalKartAgent" % (self.path, agent_fid))
+        src_go = go[3]["m_CorrespondingSourceObject"]["fileID"]
+        out = {"scene_id": agent_fid, "prefab": os.path.basename(self.guid.get(prefab_guid, "?")),
+               "script": os.path.basename(self.guid[GUID_E2E]),
+               "name": next((m["value"] for m in mods if m["propertyPath"] == "m_Name" and m["target"]["fileID"] == src_go), None)}
+        for k in d:
+            if k in E2E_KEYS or k.lower().endswith(("reward", "penalty", "divider")):
+                out[k] = num(d[k])
+        out["teamAgents"], out["otherAgents"] = d.get("teamAgents"), d.get("otherAgents")
+        out["sensors"] = self.sensors(d.get("Sensors") or [], prefab_guid)
+        bp = self.component_on(go_fid, inst, prefab_guid, GUID_BP)
+        if bp:
+            out["behavior"] = self.behavior(bp)
+        dr = self.component_on(go_fid, inst, prefab_guid, GUID_DR)
+        if dr:
+            out["decision_period"] = num(dr.get("DecisionPeriod"))
+            out["take_actions_between_decisions"] = num(dr.get("TakeActionsBetweenDecisions"))
+        out["baseStats_overrides"] = {m["propertyPath"][len("baseStats."):]: num(m["value"]) for m in mods if m["propertyPath"].startswith("baseStats.")}
+        out["kart_stats"] = self.kart_stats(prefab_guid, out["baseStats_overrides"])
+        return out
+
+    def agent(self, agent_fid, e2e=False):
         cid, stripped, kind, d = self.scene.docs[agent_fid]
         out = {"scene_id": agent_fid}
-        if not stripped:          # a kart placed in the scene without a prefab (not seen in the Compete scenes)
+        if not stripped:          # a kart placed in the scene without a prefab: the E2E karts of the *All scenes
+            if e2e and script_guid(d) == GUID_E2E:
+                return self.placed_e2e(agent_fid, d)
             out["unresolved"] = True
             return out
         inst_id = d["m_PrefabInstance"]["fileID"]
@@ -143,15 +230,7 @@ class SceneExperiments:
         out["sensors"] = self.sensors(agent_doc.get("Sensors") or [], src["guid"])
         _, bp = self.component_of_instance(inst, prefab_guid, GUID_BP)
         if bp:
-            model = bp.get("m_Model") or {}
-            mg = model.get("guid") if isinstance(model, dict) else None
-            out["behavior"] = {
-                "model": os.path.basename(self.guid[mg]) if mg in self.guid else None,
-                "vector_observation_size": num((bp.get("m_BrainParameters") or {}).get("VectorObservationSize")),
-                "stacked": num((bp.get("m_BrainParameters") or {}).get("NumStackedVectorObservations")),
-                "team_id": num(bp.get("TeamId")), "behavior_type": num(bp.get("m_BehaviorType")),
-                "behavior_name": bp.get("m_BehaviorName"),
-            }
+            out["behavior"] = self.behavior(bp)
         _, dr = self.component_of_instance(inst, prefab_guid, GUID_DR)
         if dr:
             out["decision_period"] = num(dr.get("DecisionPeriod"))
@@ -160,6 +239,13 @@ class SceneExperiments:
         # the chained-XOR id, so its overrides are recognised by their property path instead
         out["baseStats_overrides"] = {m["propertyPath"][len("baseStats."):]: num(m["value"])
                                       for m in inst["m_Modification"]["m_Modifications"] if m["propertyPath"].startswith("baseStats.")}
+        if e2e:
+            if sg == GUID_E2E:
+                out.update({k: num(agent_doc.get(k)) for k in E2E_KEYS})
+                out["kart_stats"] = self.kart_stats(prefab_guid, out["baseStats_overrides"])
+            else:             # what an E2E scene-mate is checked against, dropped from the record in envs()
+                out["_kart_stats"] = self.kart_stats(prefab_guid, out["baseStats_overrides"])
+                out["_MaxStep"] = num(agent_doc.get("MaxStep"))
         return out
 
     def sensors(self, sens, agent_prefab_guid):
@@ -191,7 +277,8 @@ class SceneExperiments:
                         "AgentHitValidationDistance": num(s.get("AgentHitValidationDistance"))})
         return out
 
-    def envs(self):
+    def envs(self, e2e=False):
+        """the scene's RacingEnvControllers; e2e: the ones that hold an EndToEndKartAgent, every kart resolved and checked"""
         res = []
         for fid, (cid, stripped, kind, body) in self.scene.docs.items():
             if kind != "MonoBehaviour" or not isinstance(body, dict) or script_guid(body) != GUID_REC or stripped:
@@ -207,7 +294,7 @@ class SceneExperiments:
                     env[k] = v
             ids = [a["fileID"] for a in body.get("Agents", [])]
             env["n_sections"] = len(body.get("Sections", []))
-            agents = [self.agent(a) for a in ids]
+            agents = [self.agent(a, e2e) for a in ids]
             idx = {a: i for i, a in enumerate(ids)}
 
             def refs(lst):
@@ -217,8 +304,39 @@ class SceneExperiments:
                 a["otherAgents"] = refs(a.get("otherAgents"))
             env["agents"] = agents
             env["teams"] = [[idx.get(r["fileID"], -1) for r in t.get("Racers", [])] for t in body.get("Teams", [])]
+            if e2e:
+                if not any(a.get("script") == "EndToEndKartAgent.cs" for a in agents):
+                    continue
+                self.check_e2e(env)
             res.append(env)
         return res
+
+    def check_e2e(self, env):
+        """stop unless hk_config can hold the set-up as the scene has it (one Sensors[] layout, one kart stats block, one MaxStep, E2E
+        karts in Inferencing mode); add E2E:247's VectorObservationSize (Awake overwrites the serialized one, which is 3)"""
+        ag = env["agents"]
+        where = "%s %s" % (env["scene"], env.get("ExperimentName"))
+        mates = [a for a in ag if a.get("script") == "HierarchicalKartAgent.cs"]
+        for i, a in enumerate(ag):
+            if a.get("unresolved") or any(r < 0 for r in a["teamAgents"] + a["otherAgents"]):
+                sys.exit("%s: agent %d not resolved" % (where, i))
+            if a["sensors"] != ag[0]["sensors"]:
+                sys.exit("%s: agent %d has Sensors[] of its own; hk_config holds one layout" % (where, i))
+            if a.get("script") != "EndToEndKartAgent.cs":
+                continue
+            if a.get("Mode") != 1:
+                sys.exit("%s: E2E agent %d is not in Inferencing mode" % (where, i))
+            if not a.get("behavior") or not a["behavior"].get("model") or not a.get("decision_period"):
+                sys.exit("%s: E2E agent %d has no actor or DecisionRequester" % (where, i))
+            for m in mates:
+                if a["kart_stats"] != m["_kart_stats"]:
+                    sys.exit("%s: E2E agent %d drives other ArcadeKart stats than %s: %s / %s" % (where, i, m["name"], a["kart_stats"], m["_kart_stats"]))
+                if a["MaxStep"] != m["_MaxStep"]:
+                    sys.exit("%s: E2E agent %d has MaxStep %s, %s has %s" % (where, i, a["MaxStep"], m["name"], m["_MaxStep"]))
+            a["behavior"]["e2e_vector_observation_size"] = (len(a["sensors"]) + 5 * env["sectionHorizon"] + 8
+                                                           + 12 * (len(a["teamAgents"]) + len(a["otherAgents"])))
+        for m in mates:
+            m.pop("_kart_stats"), m.pop("_MaxStep")
 
 
 def optimal_lanes(scene, env_id):
@@ -239,26 +357,45 @@ def main():
     ap.add_argument("--scenes", default="*")
     a = ap.parse_args()
     guid = uy.build_guid_index(ASSETS)
-    allenv = []
+    allenv, e2eenv = [], []
     for p in sorted(glob.glob(os.path.join(SCENES, "CompeteAgents-%s.unity" % a.scenes))):
-        allenv += SceneExperiments(p, guid).envs()
+        sx = SceneExperiments(p, guid)
+        allenv += sx.envs()
+        if p.endswith("All.unity"):          # the latest generation
+            e2eenv += sx.envs(e2e=True)
     for e in allenv:
         e["optimal_lanes"] = optimal_lanes(e["scene"], e["env_id"])
-        print("%-34s %-36s active=%s laps=%s maxSteps=%s MaxLaneChanges=%s mode=%s sections=%d H=%s" % (
-            e["scene"], e.get("ExperimentName"), e["game_object_active"], e.get("laps"), e.get("maxEpisodeSteps"),
-            e.get("MaxLaneChanges"), e.get("mode"), e["n_sections"], e.get("sectionHorizon")))
-        print("        optimal lanes " + "".join(str(x) for x in e["optimal_lanes"]))
-        for i, ag in enumerate(e["agents"]):
-            b = ag.get("behavior") or {}
-            print("        sensors yaw %s ray %s wall %s agent %s" % tuple([x.get(k) for x in ag.get("sensors", [])] for k in ("yaw_deg", "RayDistance", "WallHitValidationDistance", "AgentHitValidationDistance")))
-            print("    [%d] %-14s %-26s high=%s low=%s H=%s depth=%s team=%s others=%s model=%s obs=%sx%s teamId=%s" % (
-                i, ag.get("name"), ag.get("script"), HIGH.get(ag.get("HighMode"), ag.get("HighMode")), LOW.get(ag.get("LowMode"), ag.get("LowMode")),
-                ag.get("sectionHorizon"), (ag.get("gameParams") or {}).get("treeSearchDepth"), ag.get("teamAgents"), ag.get("otherAgents"),
-                b.get("model"), b.get("vector_observation_size"), b.get("stacked"), b.get("team_id")))
+        print_env(e)
+    lanes = {(e["scene"], e["env_id"]): e["optimal_lanes"] for e in allenv}
+    print("\nEndToEndKartAgent set-ups of the *All scenes (%d), every kart resolved" % len(e2eenv))
+    for e in e2eenv:
+        e["optimal_lanes"] = lanes[(e["scene"], e["env_id"])]
+        print_env(e)
     if a.update:
         out = os.path.join(ROOT, "tests", "golden", "reference_experiments.json")
         json.dump(allenv, open(out, "w"), indent=1, sort_keys=True)
         print("wrote", out)
+        out = os.path.join(ROOT, "tests", "golden", "reference_e2e_experiments.json")
+        json.dump(e2eenv, open(out, "w"), indent=1, sort_keys=True)
+        print("wrote", out)
+
+
+def print_env(e):
+    print("%-34s %-36s active=%s laps=%s maxSteps=%s MaxLaneChanges=%s mode=%s sections=%d H=%s" % (
+        e["scene"], e.get("ExperimentName"), e["game_object_active"], e.get("laps"), e.get("maxEpisodeSteps"),
+        e.get("MaxLaneChanges"), e.get("mode"), e["n_sections"], e.get("sectionHorizon")))
+    print("        optimal lanes " + "".join(str(x) for x in e["optimal_lanes"]))
+    for i, ag in enumerate(e["agents"]):
+        b = ag.get("behavior") or {}
+        print("        sensors yaw %s ray %s wall %s agent %s" % tuple([x.get(k) for x in ag.get("sensors", [])] for k in ("yaw_deg", "RayDistance", "WallHitValidationDistance", "AgentHitValidationDistance")))
+        if ag.get("script") == "EndToEndKartAgent.cs":
+            high, low = ("quasi-MCTS" if ag["runQuasiMCTS"] else "none"), "E2E"
+        else:
+            high, low = HIGH.get(ag.get("HighMode"), ag.get("HighMode")), LOW.get(ag.get("LowMode"), ag.get("LowMode"))
+        print("    [%d] %-14s %-26s high=%s low=%s H=%s depth=%s team=%s others=%s model=%s obs=%sx%s teamId=%s period=%s" % (
+            i, ag.get("name"), ag.get("script"), high, low, ag.get("sectionHorizon"), (ag.get("gameParams") or {}).get("treeSearchDepth"),
+            ag.get("teamAgents"), ag.get("otherAgents"), b.get("model"), b.get("e2e_vector_observation_size", b.get("vector_observation_size")),
+            b.get("stacked"), b.get("team_id"), ag.get("decision_period")))
 
 
 if __name__ == "__main__":
