@@ -23,6 +23,12 @@ HK_OK, HK_ERR_INVALID, HK_ERR_NO_DEVICE, HK_ERR_HIP, HK_ERR_UNSUPPORTED, HK_ERR_
 HK_LOW_RL, HK_LOW_MPC, HK_LOW_LQR, HK_LOW_E2E = 0, 1, 2, 3
 HK_HIGH_MCTS, HK_HIGH_FIXED, HK_HIGH_NONE = 0, 1, 2
 HK_MODE_RACE, HK_MODE_TRAINING, HK_MODE_EXPERIMENT = 0, 1, 2
+# rollout recorder fields (hk_rollout_field): name -> (index, numpy dtype)
+RO_FIELDS = {n: (i, dt) for i, (n, dt) in enumerate([
+    ("obs", "<f4"), ("first", "<i4"), ("steer", "<f4"), ("branch", "<i4"), ("raw", "<f4"), ("mu", "<f4"), ("logits", "<f4"),
+    ("logp_cont", "<f4"), ("logp_disc", "<f4"), ("reward", "<f4"), ("group_reward", "<f4"), ("term_reward", "<f4"),
+    ("term_group_reward", "<f4"), ("done", "<i4"), ("ring0", "<f4"), ("next_obs", "<f4")])}
+HK_RO_FIELDS = len(RO_FIELDS)
 HK_F_ACCEL, HK_F_BRAKE, HK_F_ACTIVE, HK_F_FORWARD_COLLISION, HK_F_HAS_COLLISION, HK_F_CAN_MOVE, HK_F_ENABLED = (1 << i for i in range(7))
 
 
@@ -192,6 +198,10 @@ SYMBOLS = {
     "hk_policy_attach": (C.c_int, [_H, C.POINTER(PolicyDesc), C.POINTER(C.c_int32), C.c_int, C.c_int]),
     "hk_policy_forward": (C.c_int, [_H, C.c_int, C.c_int, _fp, _fp, _fp]),
     "hk_get_actions": (C.c_int, [_H, _fp, C.POINTER(C.c_int32)]),
+    "hk_rollout_begin": (C.c_int, [_H, C.c_int]),
+    "hk_rollout_rows": (C.c_int, [_H]),
+    "hk_rollout_close": (C.c_int, [_H]),
+    "hk_rollout_ptr": (C.c_void_p, [_H, C.c_int]),
     "hk_comm_unique_id": (C.c_int, [C.c_void_p]),
     "hk_comm_init": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
     "hk_gather_results": (C.c_int, [_H, C.POINTER(EpisodeResult)]),
@@ -234,3 +244,13 @@ def check(rc, h=None):
         msg = load().hk_last_error(h)
         raise HkError(rc, msg.decode() if msg else "")
     return rc
+
+
+def copy_device_to_host(dst, src, nbytes):
+    """hipMemcpy device -> host through the HIP runtime libhk.so itself is linked against (dlsym on its handle searches its
+    dependencies), so that a process where torch loaded the runtime first copies with the same one"""
+    f = load().hipMemcpy
+    f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    rc = f(C.c_void_p(dst), C.c_void_p(src), C.c_size_t(nbytes), 2)      # hipMemcpyDeviceToHost
+    if rc != 0:
+        raise RuntimeError("hipMemcpy (device -> host) failed: hipError_t %d" % rc)

@@ -13,6 +13,7 @@
 #include "hk_lq_core.h"
 #include "hk_env_kernels.h"
 #include "hk_policy.h"
+#include "hk_rollout.h"
 #include <dlfcn.h>
 
 namespace hk {
@@ -182,6 +183,20 @@ struct hk_context {
     std::string sched;             // hk_schedule_info: the schedule of the last hk_step (written by step_ticks)
     void* pol_scratch = nullptr;   // hk_policy_forward staging
     size_t pol_scratch_bytes = 0;
+    // the rollout recorder (hk_rollout_begin ... hk_rollout_close; hk_rollout.h): one allocation behind every HK_RO_* field, then ep_prev[E], bad[1]
+    struct Rollout {
+        bool open = false;
+        int R = 0;                     // rows of the current / last rollout (0: none yet)
+        int started = 0, rows = 0;     // decisions taken / intervals completed since begin
+        int obs_dim = 0, nbm = 0, smax = 1;
+        uint32_t driven = 0;           // agent slots an actor drives
+        void* buf = nullptr;
+        size_t bytes = 0;
+        size_t off[HK_RO_FIELDS + 2] = {};    // byte offsets; [HK_RO_FIELDS] ep_prev, [HK_RO_FIELDS + 1] bad
+        template <typename T> T* at(int f) const { return (T*)((char*)buf + off[f]); }
+        // row t of a [R][E][A][k] field
+        template <typename T> T* row(int f, int t, size_t ea, int k = 1) const { return at<T>(f) + (size_t)t * ea * k; }
+    } ro;
     // RCCL communicator for hk_gather_results (librccl.so loaded lazily)
     void* comm = nullptr;
     int comm_world = 0, comm_rank = 0;
@@ -348,6 +363,7 @@ void hk_destroy(hk_handle h)
     if (h->gather_buf) (void)hipFree(h->gather_buf);
     if (h->gather_cnt) (void)hipFree(h->gather_cnt);
     if (h->pol_scratch) (void)hipFree(h->pol_scratch);
+    if (h->ro.buf) (void)hipFree(h->ro.buf);
     for (int p = 0; p < HK_MAX_POLICIES; p++) hk::policy_free(h->policy[p]);
     h->prof.fold();
     for (hipEvent_t e : h->prof.pool) (void)hipEventDestroy(e);
@@ -469,6 +485,7 @@ int hk_lq_solve_batch(hk_handle h, int batch, int N, const double* A, const doub
 int hk_reset(hk_handle h, const int32_t* env_ids, int n, int experiment_num)
 {
     HK_NEED_ENV(h);
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_reset: refused while a rollout is open (hk_rollout_close first)");
     int rc = hk::env_reset(h->dev, h->cfg, env_ids, n, experiment_num, h->stream, h->err);
     if (rc) { g_last_error = h->err; return rc; }
     h->lock_tick = env_ids ? -1 : 0;            // every env stands on episode step 0 again / some do: the field is no longer known to be in lock-step
@@ -1062,25 +1079,50 @@ static int policy_decide(hk_handle h)
     if (rc) { g_last_error = h->err; return rc; }
     const unsigned long long decision = (unsigned long long)(h->academy_step / h->decision_period);
     const int E = h->cfg.num_envs, A = h->cfg.num_agents;
+    // an open rollout: this decision writes row t (hk_rollout.h)
+    const auto& ro = h->ro;
+    const int t = ro.started;
+    const size_t ea = (size_t)E * A;
     for (int p = 0; p < h->n_policies; p++) {
         const hk::PolicyDevice& pd = h->policy[p];
         const int pairs = E * pd.q.n_slots;
         const int w = (int)(decision % (unsigned long long)pd.q.stack);
         hipLaunchKernelGGL(hk::policy_stack_kernel, dim3((pairs + 3) / 4), dim3(256), 0, h->stream, pd.q, E, A, h->dev.envs, h->dev.slot_of,
-                           h->dev.obs, w);
+                           h->dev.obs, w, ro.open ? ro.row<float>(HK_RO_OBS, t, ea, ro.obs_dim) : nullptr, ro.open ? ro.row<int>(HK_RO_FIRST, t, ea) : nullptr);
         HK_HIP(h, hipGetLastError());
     }
     h->prof.end(4, eo, h->stream);
+    hk::PolicyRec rec{};
+    if (ro.open) {
+        rec.steer = ro.row<float>(HK_RO_STEER, t, ea); rec.branch = ro.row<int>(HK_RO_BRANCH, t, ea); rec.raw = ro.row<float>(HK_RO_RAW, t, ea);
+        rec.mu = ro.row<float>(HK_RO_MU, t, ea); rec.logits = ro.row<float>(HK_RO_LOGITS, t, ea, ro.nbm); rec.nbm = ro.nbm;
+        rec.logp_c = ro.row<float>(HK_RO_LOGP_CONT, t, ea); rec.logp_d = ro.row<float>(HK_RO_LOGP_DISC, t, ea);
+    }
     for (int p = 0; p < h->n_policies; p++) {
         const hk::PolicyDevice& pd = h->policy[p];
         const int pairs = E * pd.q.n_slots;
         const int w = (int)(decision % (unsigned long long)pd.q.stack);
         hipEvent_t e = h->prof.begin(h->stream);
         rc = hk::policy_launch_mlp(pd, pairs, pd.q.ring, w, decision, h->cfg.env_id_base, A, nullptr, nullptr, h->dev.act_steer,
-                                   h->dev.act_branch, h->stream, h->err);
+                                   h->dev.act_branch, rec, h->stream, h->err);
         if (rc) { g_last_error = h->err; return rc; }
         h->prof.end(3, e, h->stream);
     }
+    if (ro.open) h->ro.started += 1;
+    return HK_OK;
+}
+
+// the end of an open rollout's interval t: the accumulators into row t, its DONE flags
+static int rollout_close_interval(hk_handle h, int t)
+{
+    const auto& ro = h->ro;
+    const int E = h->cfg.num_envs, A = h->cfg.num_agents;
+    const size_t ea = (size_t)E * A;
+    hipLaunchKernelGGL(hk::rollout_close_kernel, dim3((unsigned)((ea + 255) / 256)), dim3(256), 0, h->stream, h->dev.agents, h->dev.envs, h->dev.slot_of, E, A,
+                       ro.driven, ro.row<float>(HK_RO_REWARD, t, ea), ro.row<float>(HK_RO_GROUP_REWARD, t, ea), ro.row<int>(HK_RO_DONE, t, (size_t)E),
+                       ro.at<int>(HK_RO_FIELDS), ro.at<int>(HK_RO_FIELDS + 1));
+    HK_HIP(h, hipGetLastError());
+    h->ro.rows = t + 1;
     return HK_OK;
 }
 
@@ -1093,6 +1135,14 @@ int hk_step(hk_handle h, int n_ticks)
         h->academy_step += n_ticks;
         return step_ticks(h, n_ticks);
     }
+    if (h->ro.open) {
+        // the decisions this call takes: the multiples of decision_period in [academy_step, academy_step + n_ticks)
+        const long long a = h->academy_step, P = h->decision_period;
+        const long long decisions = (a + n_ticks - 1) / P - (a + P - 1) / P + 1;
+        if (decisions > h->ro.R - h->ro.started)
+            return fail(h, HK_ERR_INVALID, "hk_step: the open rollout has " + std::to_string(h->ro.R - h->ro.started) + " rows left, the call takes " +
+                                               std::to_string(decisions) + " decisions");
+    }
     // with policies attached the Academy steps first in a decision tick; the ticks up to the next decision run fused
     int left = n_ticks;
     while (left > 0) {
@@ -1100,10 +1150,18 @@ int hk_step(hk_handle h, int n_ticks)
         if (phase == 0) { int rc = policy_decide(h); if (rc) return rc; }
         int chunk = h->decision_period - phase;
         if (chunk > left) chunk = left;
+        const bool rec_term = h->ro.open && h->dev.rw.sec_time;       // the terminal rewards of this chunk's resets go to the open row
+        if (rec_term) {
+            const size_t ea = (size_t)h->cfg.num_envs * h->cfg.num_agents;
+            h->dev.rw.term_step = h->ro.row<float>(HK_RO_TERM_REWARD, h->ro.started - 1, ea);
+            h->dev.rw.term_group = h->ro.row<float>(HK_RO_TERM_GROUP_REWARD, h->ro.started - 1, ea);
+        }
         int rc = step_ticks(h, chunk);
+        h->dev.rw.term_step = nullptr; h->dev.rw.term_group = nullptr;
         if (rc) return rc;
         h->academy_step += chunk;
         left -= chunk;
+        if (h->ro.open && h->academy_step % h->decision_period == 0 && (rc = rollout_close_interval(h, h->ro.started - 1))) return rc;
     }
     return HK_OK;
 }
@@ -1111,6 +1169,7 @@ int hk_step(hk_handle h, int n_ticks)
 int hk_policy_attach(hk_handle h, const hk_policy_desc* desc, const int32_t* agent_slots, int n_slots, int decision_period)
 {
     HK_NEED_ENV(h);
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_policy_attach: refused while a rollout is open (hk_rollout_close first)");
     int rc = hk::policy_validate(desc, h->err);
     if (rc) { g_last_error = h->err; return rc; }
     if (!agent_slots || n_slots < 1 || n_slots > h->cfg.num_agents || decision_period < 1)
@@ -1157,7 +1216,7 @@ int hk_policy_forward(hk_handle h, int policy, int rows, const float* obs, float
     float* d_lg = d_mu + rows;
     HK_HIP(h, hipMemcpyAsync(d_in, obs, n_in * sizeof(float), hipMemcpyHostToDevice, h->stream));
     hipEvent_t e = h->prof.begin(h->stream);
-    int rc = hk::policy_launch_mlp(pd, rows, d_in, pd.q.stack - 1, 0ull, 0, h->cfg.num_agents, d_mu, d_lg, nullptr, nullptr, h->stream, h->err);
+    int rc = hk::policy_launch_mlp(pd, rows, d_in, pd.q.stack - 1, 0ull, 0, h->cfg.num_agents, d_mu, d_lg, nullptr, nullptr, hk::PolicyRec{}, h->stream, h->err);
     if (rc) { g_last_error = h->err; return rc; }
     h->prof.end(3, e, h->stream);
     HK_HIP(h, hipMemcpyAsync(mu, d_mu, rows * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -1175,6 +1234,87 @@ int hk_get_actions(hk_handle h, float* steer, int32_t* branch)
     HK_HIP(h, hipMemcpyAsync(branch, h->dev.act_branch, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipStreamSynchronize(h->stream));
     return HK_OK;
+}
+
+// ------------------------------------------------------------------ rollout recorder (hk.h; device side in hk_rollout.h)
+int hk_rollout_begin(hk_handle h, int rows)
+{
+    HK_NEED_ENV(h);
+    if (h->n_policies == 0) return fail(h, HK_ERR_INVALID, "hk_rollout_begin: no actor attached");
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_rollout_begin: a rollout is already open");
+    if (rows < 1) return fail(h, HK_ERR_INVALID, "hk_rollout_begin: rows < 1");
+    if (h->academy_step % h->decision_period != 0) return fail(h, HK_ERR_INVALID, "hk_rollout_begin: the Academy step is not on a decision (mid-interval)");
+    if (!h->cfg.auto_reset) return fail(h, HK_ERR_UNSUPPORTED, "hk_rollout_begin: auto_reset == 0 (an ended episode is parked, never reset)");
+    auto& ro = h->ro;
+    const int E = h->cfg.num_envs, A = h->cfg.num_agents, D = hk_obs_dim(h);
+    int nbm = 1, smax = 1;
+    uint32_t driven = 0;
+    for (int p = 0; p < h->n_policies; p++) {
+        nbm = std::max(nbm, h->policy[p].q.n_branch);
+        smax = std::max(smax, h->policy[p].q.stack);
+        for (int j = 0; j < h->policy[p].q.n_slots; j++) driven |= 1u << h->policy[p].q.slots[j];
+    }
+    const size_t ra = (size_t)rows * E * A, ea = (size_t)E * A;
+    size_t elems[HK_RO_FIELDS + 2];
+    for (int f = 0; f < HK_RO_FIELDS; f++) elems[f] = ra;
+    elems[HK_RO_OBS] = ra * D; elems[HK_RO_LOGITS] = ra * nbm; elems[HK_RO_DONE] = (size_t)rows * E;
+    elems[HK_RO_RING0] = ea * (smax - 1) * D; elems[HK_RO_NEXT_OBS] = ea * D;
+    elems[HK_RO_FIELDS] = E; elems[HK_RO_FIELDS + 1] = 1;
+    size_t off[HK_RO_FIELDS + 2], total = 0;
+    for (int f = 0; f < HK_RO_FIELDS + 2; f++) { off[f] = total; total += (elems[f] * 4 + 255) & ~(size_t)255; }
+    if (total > ro.bytes) {
+        if (ro.buf) HK_HIP(h, hipFree(ro.buf));
+        ro.buf = nullptr; ro.bytes = 0; ro.R = 0;
+        HK_HIP(h, hipMalloc(&ro.buf, total));
+        ro.bytes = total;
+    }
+    std::memcpy(ro.off, off, sizeof(off));
+    ro.R = rows; ro.started = 0; ro.rows = 0; ro.obs_dim = D; ro.nbm = nbm; ro.smax = smax; ro.driven = driven;
+    HK_HIP(h, hipMemsetAsync(ro.buf, 0, total, h->stream));
+    const unsigned long long decision = (unsigned long long)(h->academy_step / h->decision_period);
+    for (int p = 0; p < h->n_policies; p++) {
+        const hk::PolicyParams& q = h->policy[p].q;
+        const size_t n = (size_t)E * q.n_slots * (q.stack - 1) * D;
+        if (n == 0) continue;
+        hipLaunchKernelGGL(hk::rollout_ring0_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, q, E, A, (int)(decision % (unsigned long long)q.stack),
+                           smax, ro.at<float>(HK_RO_RING0));
+        HK_HIP(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(hk::rollout_epoch_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, h->dev.envs, h->dev.slot_of, E, ro.at<int>(HK_RO_FIELDS));
+    HK_HIP(h, hipGetLastError());
+    ro.open = true;
+    return HK_OK;
+}
+
+int hk_rollout_rows(hk_handle h)
+{
+    if (!h) return fail(nullptr, HK_ERR_INVALID, "NULL handle");
+    return h->ro.rows;
+}
+
+int hk_rollout_close(hk_handle h)
+{
+    HK_NEED_ENV(h);
+    auto& ro = h->ro;
+    if (!ro.open) return fail(h, HK_ERR_INVALID, "hk_rollout_close: no rollout is open");
+    if (h->academy_step % h->decision_period != 0) return fail(h, HK_ERR_INVALID, "hk_rollout_close: mid-interval (step to the next decision first)");
+    // the bootstrap observation: the observe kernel without its reward events, so that the next decision raises them as usual
+    int rc = hk::env_launch_observe_quiet(h->dev, h->cfg, ro.driven, ro.at<float>(HK_RO_NEXT_OBS), h->stream, h->err);
+    if (rc) { g_last_error = h->err; return rc; }
+    ro.open = false;
+    int bad = 0;
+    HK_HIP(h, hipMemcpyAsync(&bad, ro.at<int>(HK_RO_FIELDS + 1), sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HK_HIP(h, hipStreamSynchronize(h->stream));
+    if (bad) return fail(h, HK_ERR_INVALID, "hk_rollout_close: an env ended more than one episode inside one decision interval; the rows cannot express it");
+    return HK_OK;
+}
+
+void* hk_rollout_ptr(hk_handle h, int field)
+{
+    if (!h) { fail(nullptr, HK_ERR_INVALID, "NULL handle"); return nullptr; }
+    if (field < 0 || field >= HK_RO_FIELDS) { fail(h, HK_ERR_INVALID, "hk_rollout_ptr: bad field"); return nullptr; }
+    if (!h->ro.buf || h->ro.R == 0) { fail(h, HK_ERR_INVALID, "hk_rollout_ptr: no rollout yet (hk_rollout_begin)"); return nullptr; }
+    return h->ro.at<void>(field);
 }
 
 int hk_obs_dim(hk_handle h)
@@ -1228,6 +1368,7 @@ int hk_get_agent_state(hk_handle h, hk_agent_state* out)
 int hk_set_agent_state(hk_handle h, const hk_agent_state* in)
 {
     HK_NEED_ENV(h);
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_set_agent_state: refused while a rollout is open (hk_rollout_close first)");
     if (!in) return fail(h, HK_ERR_INVALID, "NULL pointer");
     const size_t cnt = (size_t)h->cfg.num_envs * h->cfg.num_agents;
     // the device divides by the section count with a multiply-shift that is exact for 0 <= x < 2^32 / L (hk_env_device.h div_L): a rewound or
@@ -1260,6 +1401,7 @@ int hk_get_env_state(hk_handle h, hk_env_state* out)
 int hk_set_env_state(hk_handle h, const hk_env_state* in)
 {
     HK_NEED_ENV(h);
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_set_env_state: refused while a rollout is open (hk_rollout_close first)");
     if (!in) return fail(h, HK_ERR_INVALID, "NULL pointer");
     h->dev.P.hold_dedupe = 0;          // (as hk_set_agent_state: episode_steps may be rewound into a hold whose solves were skipped)
     h->lock_tick = -1;                 // (the host wrote episode steps)
@@ -1400,6 +1542,7 @@ int hk_comm_destroy(hk_handle h)
 int hk_get_rewards(hk_handle h, float* reward, float* group_reward)
 {
     HK_NEED_ENV(h);
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_get_rewards: refused while a rollout is open (hk_rollout_close first)");
     if (!reward || !group_reward) return fail(h, HK_ERR_INVALID, "NULL pointer");
     { int rc = check_device_status(h); if (rc) return rc; }
     const size_t cnt = (size_t)h->cfg.num_envs * h->cfg.num_agents;
@@ -1482,6 +1625,7 @@ int hk_observe(hk_handle h)
 int hk_rewards_device(hk_handle h)
 {
     HK_NEED_ENV(h);
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_rewards_device: refused while a rollout is open (hk_rollout_close first)");
     const size_t cnt = (size_t)h->cfg.num_envs * h->cfg.num_agents;
     int rc = hk::ga_ops(h->dev).launch_rewards_read(h->dev, (int)cnt, h->dev.reward_out, h->dev.reward_out + cnt, h->stream, h->err);
     if (rc) g_last_error = h->err;

@@ -170,6 +170,8 @@ struct RwDev {
     int S;              // laps * L + 2
     unsigned char* hit_code;   // [E][A][sensors]: what the last CollectObservations saw closer than the validation distance
                                // (0 nothing, 1 wall, 2 + j agent j); replayed by reward_hits_kernel
+    float* term_step;          // [E][A] the open rollout row's TERM_REWARD / TERM_GROUP_REWARD (hk_api.hip rollout recorder; set per decision
+    float* term_group;         // chunk, constant over its launches); nullptr: not recording
 };
 
 constexpr float TRIG_CELL = 8.0f;       // coarse cell of the Trigger candidate masks

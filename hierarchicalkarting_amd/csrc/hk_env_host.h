@@ -130,6 +130,7 @@ struct GaOps {
     int (*launch_b1)(EnvDevice& d, const hk_config& cfg, hipStream_t stream, std::string& err);
     int (*launch_lqn)(EnvDevice& d, const hk_config& cfg, hipStream_t stream, std::string& err);
     int (*launch_observe)(EnvDevice& d, const hk_config& cfg, uint32_t agent_mask, hipStream_t stream, std::string& err);
+    int (*launch_observe_quiet)(EnvDevice& d, const hk_config& cfg, uint32_t agent_mask, float* obs, hipStream_t stream, std::string& err);   // into `obs`, no reward events
     int (*launch_arm)(EnvDevice& d, const hk_config& cfg, int n_ticks, hipStream_t stream, std::string& err);
     int (*launch_done_check)(EnvDevice& d, const hk_config& cfg, int lazy, hipStream_t stream, std::string& err);
     int (*launch_rewards_read)(EnvDevice& d, int cnt, float* reward, float* group_reward, hipStream_t stream, std::string& err);

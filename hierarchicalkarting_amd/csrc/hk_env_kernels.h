@@ -297,5 +297,7 @@ inline int env_launch_regroup(EnvDevice& d, const hk_config& cfg, hipStream_t st
 }
 // agent_mask: the agent slots whose observations are needed (all of them for the host's hk_get_observations / hk_observe)
 inline int env_launch_observe(EnvDevice& d, const hk_config& cfg, uint32_t agent_mask, hipStream_t stream, std::string& err) { return HK_GA_CALL(d, launch_observe(d, cfg, agent_mask, stream, err)); }
+// the same observations written to obs[E][A][hk_obs_dim] instead of the handle's buffer, WITHOUT the HitWall / HitOpponent events (the kernel is otherwise pure)
+inline int env_launch_observe_quiet(EnvDevice& d, const hk_config& cfg, uint32_t agent_mask, float* obs, hipStream_t stream, std::string& err) { return HK_GA_CALL(d, launch_observe_quiet(d, cfg, agent_mask, obs, stream, err)); }
 
 }  // namespace hk

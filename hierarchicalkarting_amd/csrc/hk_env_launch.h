@@ -250,7 +250,8 @@ inline int launch_lqn(EnvDevice& d, const hk_config& cfg, hipStream_t stream, st
     return HK_OK;
 }
 
-inline int launch_observe(EnvDevice& d, const hk_config& cfg, uint32_t agent_mask, hipStream_t stream, std::string& err)
+// CollectObservations into obs; hit_code == nullptr: no reward events are recorded
+inline int observe_into(EnvDevice& d, const hk_config& cfg, uint32_t mask, float* obs, unsigned char* hit_code, hipStream_t stream, std::string& err)
 {
     const long long threads = (long long)cfg.num_envs * cfg.num_agents * OBS_LANES;
     // a block is only 16 agents: copying the tables into LDS pays for the Oval's 20 KB (+3 % on the RL workload), not for the
@@ -259,7 +260,6 @@ inline int launch_observe(EnvDevice& d, const hk_config& cfg, uint32_t agent_mas
 #define HK_OBS_LDS_MAX (32 * 1024)     /* round 5: the Oval tables are 29 KB now; in LDS 71.2 -> 72.8 M on the RL workload */
 #endif
     const int lds = (d.tab_lds && d.tab_lds <= HK_OBS_LDS_MAX) ? d.tab_lds : 0;
-    const uint32_t mask = d.rw.hit_code ? 0xFFFFFFFFu : agent_mask;                  // the reward replay needs every agent's hit codes
 #ifndef HK_OBS_BIG_BLOCK
 #define HK_OBS_BIG_BLOCK 1024
 #endif
@@ -267,16 +267,27 @@ inline int launch_observe(EnvDevice& d, const hk_config& cfg, uint32_t agent_mas
 #define HK_OBS_LDS_BLOCK 512      /* one copy of the staged tables per 32 agents: RL workload 75.5 -> 77.5 M (256: a copy per 16; 1 024: 76.0) */
 #endif
     if (lds) hipLaunchKernelGGL((env_observe_kernel<true, HK_OBS_LDS_BLOCK>), dim3((unsigned)((threads + HK_OBS_LDS_BLOCK - 1) / HK_OBS_LDS_BLOCK)), dim3(HK_OBS_LDS_BLOCK), lds, stream, d.P, d.agents, d.hot, d.slot_of,
-                                d.obs, d.rw.hit_code, mask);
+                                obs, hit_code, mask);
     else if (d.tab_lds && d.tab_lds <= 60 * 1024)      // a long track: one copy of the tables per 64 agents
         hipLaunchKernelGGL((env_observe_kernel<true, HK_OBS_BIG_BLOCK>), dim3((unsigned)((threads + HK_OBS_BIG_BLOCK - 1) / HK_OBS_BIG_BLOCK)), dim3(HK_OBS_BIG_BLOCK), d.tab_lds, stream, d.P, d.agents, d.hot,
-                           d.slot_of, d.obs, d.rw.hit_code, mask);
-    else hipLaunchKernelGGL(env_observe_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, d.P, d.agents, d.hot, d.slot_of, d.obs, d.rw.hit_code, mask);
-    int rc = launch_check(err, "env_observe_kernel");
+                           d.slot_of, obs, hit_code, mask);
+    else hipLaunchKernelGGL(env_observe_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, d.P, d.agents, d.hot, d.slot_of, obs, hit_code, mask);
+    return launch_check(err, "env_observe_kernel");
+}
+
+inline int launch_observe(EnvDevice& d, const hk_config& cfg, uint32_t agent_mask, hipStream_t stream, std::string& err)
+{
+    const uint32_t mask = d.rw.hit_code ? 0xFFFFFFFFu : agent_mask;                  // the reward replay needs every agent's hit codes
+    int rc = observe_into(d, cfg, mask, d.obs, d.rw.hit_code, stream, err);
     if (rc || !d.rw.hit_code) return rc;
     // CollectObservations raised HitWall / HitOpponent events (HKA:580-598): replayed per env in agent / sensor order
     hipLaunchKernelGGL(reward_hits_kernel, dim3((cfg.num_envs + 127) / 128), dim3(128), 0, stream, d.P, d.agents, d.hot, d.slot_of, d.rw.hit_code);
     return launch_check(err, "reward_hits_kernel");
+}
+
+inline int launch_observe_quiet(EnvDevice& d, const hk_config& cfg, uint32_t agent_mask, float* obs, hipStream_t stream, std::string& err)
+{
+    return observe_into(d, cfg, agent_mask, obs, nullptr, stream, err);
 }
 
 inline int launch_arm(EnvDevice& d, const hk_config& cfg, int n_ticks, hipStream_t stream, std::string& err)
@@ -326,7 +337,7 @@ inline const GaOps& make_ops()
 {
     static const GaOps ops = {mcts_req_bytes, mcts_searches_per_wave, mcts_lds_bytes, mcts_root_words, game_doubles_per_ego, queue_ints_per_set,
                               launch_mcts_table, launch_mcts_invalidate, flush_mcts, flush_mcts_on, launch_reset, launch_regroup, launch_run, launch_b1, launch_lqn,
-                              launch_observe, launch_arm, launch_done_check, launch_rewards_read, launch_hot_gather, launch_hot_scatter, launch_envs_gather,
+                              launch_observe, launch_observe_quiet, launch_arm, launch_done_check, launch_rewards_read, launch_hot_gather, launch_hot_scatter, launch_envs_gather,
                               launch_envs_scatter, hot_tile_words};
     return ops;
 }

@@ -214,6 +214,11 @@ __device__ inline bool phase_begin(const EnvParams& P, const int env, const int 
             // AddGoalTimingRewards (REC:267 / :306) before ResetGame; then ResetGame clears the section tables (:508-512)
             rw_goal_timing(P, i, me ? h.time_steps : 0, me && (h.flags & HK_F_ENABLED), rwv);
             if (me) results[(size_t)env * P.A + i].group_reward = rwv.group;
+            // rollout recorder: the terminal rewards EndGroupEpisode sends, before the zeroing below (only for an episode that counts)
+            if (me && RD.term_step && (es.initial_started || timeout)) {
+                RD.term_step[(size_t)env * P.A + i] = rwv.step;
+                RD.term_group[(size_t)env * P.A + i] = rwv.group;
+            }
             if (env_ok) {
                 const int n = P.A * RD.S;
                 for (int q = i; q < n; q += GA) { RD.sec_time[(size_t)env * n + q] = -1; RD.sec_cnt[(size_t)env * n + q] = 0; }

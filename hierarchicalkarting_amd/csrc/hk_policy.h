@@ -56,6 +56,13 @@ struct PolicyParams {
     int32_t* epoch;                          // [E][n_slots]
 };
 
+// One rollout row's slices, [E][A] (logits [E][A][nbm]), written beside the latched actions (hk_rollout.h; all nullptr: not recording)
+struct PolicyRec {
+    float *steer, *raw, *mu, *logits, *logp_c, *logp_d;
+    int* branch;
+    int nbm;                                 // logits per agent in the row (the largest n_branch of the handle's actors)
+};
+
 struct PolicyDevice {
     PolicyParams q{};
     float* weights = nullptr;                // one allocation behind every const float* above
@@ -68,8 +75,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // StackingSensor.  One wave per (env, slot), four to a block; w = ring slot that receives the newest observation.  (Round 5: a wave needs no block
 // barrier — the epoch word is read by every lane before lane 0 rewrites it, the zero fill precedes the copy in program order — and a pair moves
 // obs_dim <= 126 floats: with 128 threads and two __syncthreads per pair the kernel took 1.9 ms per decision beside the planner's searches.)
+// rec_obs / rec_first (an open rollout's row, [E][A][obs_dim] / [E][A]; nullptr: not recording): the slice pushed and the clear
 __global__ __launch_bounds__(256) void policy_stack_kernel(PolicyParams Q, int E, int A, const hk_env_state* envs_by_slot, const int* slot_of,
-                                                           const float* obs, int w)
+                                                           const float* obs, int w, float* rec_obs, int* rec_first)
 {
     const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int t = threadIdx.x & 63;
@@ -84,8 +92,13 @@ __global__ __launch_bounds__(256) void policy_stack_kernel(PolicyParams Q, int E
         if (t == 0) Q.epoch[pair] = ep;
     }
     // (the copy of slot w lands on addresses the zero fill may have written from other lanes of this wave: a wave's stores reach memory in program order)
-    const float* o = obs + ((size_t)env * A + Q.slots[j]) * Q.obs_dim;
+    const size_t ea = (size_t)env * A + Q.slots[j];
+    const float* o = obs + ea * Q.obs_dim;
     for (int k = t; k < Q.obs_dim; k += 64) ring[(size_t)w * Q.obs_dim + k] = o[k];
+    if (rec_obs) {
+        for (int k = t; k < Q.obs_dim; k += 64) rec_obs[ea * Q.obs_dim + k] = o[k];
+        if (t == 0) rec_first[ea] = stale ? 1 : 0;
+    }
 }
 
 // hk_reset: force the rings of the listed envs (all when env_ids == nullptr) to be cleared at the next decision
@@ -170,14 +183,14 @@ __device__ __forceinline__ void pm_gemm(f32x16& acc0, f32x16& acc1, const float*
 // ---------------------------------------------------------------------------------------------------------------------
 // src: [rows][in_dim]; logical element k of a row lives at ((w + 1 + k / obs_dim) % stack) * obs_dim + k % obs_dim
 // (w = stack - 1 for plain oldest-first rows).  Outputs: mu_out / logit_out when non-null; act_steer / act_branch
-// (indexed [env][agent], row = env * n_slots + j) when non-null.
+// (indexed [env][agent], row = env * n_slots + j) when non-null, and then the rollout row `rec` when rec.raw is non-null.
 // MODE: how the (H / 32) x 2 blocks of a layer fall on the 8 waves — 0: one block per wave (H <= 128), 1: two blocks per
 // wave sharing their B columns (H = 256), 2: mixed (other H), decided per wave — three inlined forms of the gemm: held to two waves per SIMD
 // instead of four (at 128 registers it spills 85), i.e. one workgroup per CU.
 template <int MODE>
 __global__ __launch_bounds__(PM_THREADS, MODE == 2 ? 2 : 4) void policy_mlp_kernel(PolicyParams Q, int rows, const float* src, int w,
                                                                    unsigned long long decision, int env_id_base, int A,
-                                                                   float* mu_out, float* logit_out, float* act_steer, int* act_branch)
+                                                                   float* mu_out, float* logit_out, float* act_steer, int* act_branch, PolicyRec rec)
 {
     extern __shared__ __align__(16) float At[];        // [max(kc, hidden)][PM_LD] then head[PM_MAX_OUT][PM_TILE]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -308,8 +321,8 @@ __global__ __launch_bounds__(PM_THREADS, MODE == 2 ? 2 : 4) void policy_mlp_kern
                 eps = sqrtf(-2.0f * hk_logf(u1)) * hk_cosf((2.0f * HK_PI_F) * u2);
             }
             const float sigma = hk_expf(Q.log_sigma[0]);
-            float v = mu + eps * sigma;
-            v = v < -3.0f ? -3.0f : (v > 3.0f ? 3.0f : v);
+            const float raw = mu + eps * sigma;
+            const float v = raw < -3.0f ? -3.0f : (raw > 3.0f ? 3.0f : raw);
             int best = 0;
             for (int b = 1; b < Q.n_branch; b++) if (lg[b] > lg[best]) best = b;
             int pick = best;
@@ -321,8 +334,22 @@ __global__ __launch_bounds__(PM_THREADS, MODE == 2 ? 2 : 4) void policy_mlp_kern
                 pick = Q.n_branch - 1;
                 for (int b = 0; b < Q.n_branch; b++) { cum += ex[b]; if (thr < cum) { pick = b; break; } }
             }
-            act_steer[(size_t)env * A + agent] = v / 3.0f;
-            act_branch[(size_t)env * A + agent] = pick;
+            const size_t ea = (size_t)env * A + agent;
+            act_steer[ea] = v / 3.0f;
+            act_branch[ea] = pick;
+            if (rec.raw) {              // (a kernel argument: wave-uniform)
+                // ML-Agents' log-probabilities: the Gaussian's at the unclipped sample, and log_softmax of the logits at the pick
+                const float z = (raw - mu) / sigma;
+                float tot = 0.0f;
+                for (int b = 0; b < Q.n_branch; b++) tot += hk_expf(lg[b] - lg[best]);
+                rec.steer[ea] = v / 3.0f;
+                rec.branch[ea] = pick;
+                rec.raw[ea] = raw;
+                rec.mu[ea] = mu;
+                for (int b = 0; b < Q.n_branch; b++) rec.logits[ea * rec.nbm + b] = lg[b];
+                rec.logp_c[ea] = -0.5f * z * z - Q.log_sigma[0] - 0.918938533204672742f;      // 0.5 log(2 pi)
+                rec.logp_d[ea] = (lg[pick] - lg[best]) - hk_logf(tot);
+            }
         }
     }
 }
@@ -432,7 +459,7 @@ inline void policy_free(PolicyDevice& pd)
 
 inline int policy_launch_mlp(const PolicyDevice& pd, int rows, const float* src, int w, unsigned long long decision,
                              int env_id_base, int A, float* mu_out, float* logit_out, float* act_steer, int* act_branch,
-                             hipStream_t stream, std::string& err)
+                             const PolicyRec& rec, hipStream_t stream, std::string& err)
 {
     if (rows <= 0) return HK_OK;
     const size_t lds = policy_lds_bytes(pd.q);
@@ -454,11 +481,11 @@ inline int policy_launch_mlp(const PolicyDevice& pd, int rows, const float* src,
     }
     const dim3 grid((rows + PM_TILE - 1) / PM_TILE), block(PM_THREADS);
     if (pd.q.hidden <= 128)
-        hipLaunchKernelGGL(policy_mlp_kernel<0>, grid, block, lds, stream, pd.q, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch);
+        hipLaunchKernelGGL(policy_mlp_kernel<0>, grid, block, lds, stream, pd.q, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
     else if (pd.q.hidden == 256)
-        hipLaunchKernelGGL(policy_mlp_kernel<1>, grid, block, lds, stream, pd.q, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch);
+        hipLaunchKernelGGL(policy_mlp_kernel<1>, grid, block, lds, stream, pd.q, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
     else
-        hipLaunchKernelGGL(policy_mlp_kernel<2>, grid, block, lds, stream, pd.q, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch);
+        hipLaunchKernelGGL(policy_mlp_kernel<2>, grid, block, lds, stream, pd.q, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { err = std::string("policy_mlp_kernel: ") + hipGetErrorString(e); return HK_ERR_HIP; }
     return HK_OK;

@@ -6,6 +6,7 @@ RacingEnv  <->  RacingEnvController (+ its KartAgents / ArcadeKarts), E independ
     observations()                   HierarchicalKartAgent.CollectObservations (HKA:485-604)
     set_actions(steer, branch)       KartAgent.OnActionReceived (KA:440-478) for LowMode == RL agents
     attach_policy(policy, slots)     BehaviorParameters.Model: the ML-Agents actor runs on device every DecisionPeriod ticks
+    rollout_begin / rollout_close    record what the attached actors did (obs, actions, log-probs, rewards) on the device
     agent_state() / set_agent_state  snapshot / restore of every KartAgent + ArcadeKart + Rigidbody field
     episode_results()                TelemetryViewer quantities of the last finished episode
 All arrays are numpy views of the ABI structs; all compute happens in the HIP kernels."""
@@ -221,6 +222,65 @@ class RacingEnv:
                 "group_reward": mk(self.L.hk_device_group_reward_ptr(self.h), (E, A), "<f4"),
                 "act_steer": mk(self.L.hk_device_act_steer_ptr(self.h), (E, A), "<f4"),
                 "act_branch": mk(self.L.hk_device_act_branch_ptr(self.h), (E, A), "<i4")}
+
+    # ---- rollout recorder (hk.h hk_rollout_*): every decision of the attached actors writes a row of device buffers
+    def rollout_begin(self, rows):
+        self._ck(self.L.hk_rollout_begin(self.h, int(rows)))
+        self._ro_rows = int(rows)
+
+    def rollout_close(self):
+        self._ck(self.L.hk_rollout_close(self.h))
+
+    def rollout_rows(self):
+        """completed rows: decisions whose interval has run"""
+        n = self.L.hk_rollout_rows(self.h)
+        if n < 0:
+            self._ck(n)
+        return n
+
+    def _rollout_shapes(self):
+        R, E, A, D = self._ro_rows, self.E, self.A, self.obs_dim
+        pols = getattr(self, "_policies", [])
+        nbm = max([p.n_branch for p in pols] + [1])
+        smax = max([p.stack for p in pols] + [1])
+        sh = {n: (R, E, A) for n in _lib.RO_FIELDS}
+        sh.update(obs=(R, E, A, D), logits=(R, E, A, nbm), done=(R, E), ring0=(E, A, smax - 1, D), next_obs=(E, A, D))
+        return sh
+
+    def rollout_views(self):
+        """-> dict field -> torch CUDA tensor ALIASING the recorder's buffer (shapes: hk.h hk_rollout_field; all rows R of the last
+        rollout_begin, of which rollout_rows() are complete).  The same caveats as torch_views: synchronize() before reading, and torch
+        must have touched the GPU before the first RacingEnv of the process.  Valid until the next rollout_begin or close()."""
+        import torch
+
+        class _Ext:
+            def __init__(self, ptr, shape, typestr):
+                self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr), False), "version": 3, "strides": None}
+
+        dev = "cuda:%d" % self.built.cfg.device_id
+        out = {}
+        for name, shape in self._rollout_shapes().items():
+            idx, ts = _lib.RO_FIELDS[name]
+            ptr = self.L.hk_rollout_ptr(self.h, idx)
+            if not ptr:
+                self._ck(_lib.HK_ERR_INVALID)
+            out[name] = torch.as_tensor(_Ext(ptr, shape, ts), device=dev)
+        return out
+
+    def rollout(self):
+        """-> dict field -> numpy copy of the recorder's buffers (the handle's stream is synchronised first)"""
+        self.synchronize()
+        out = {}
+        for name, shape in self._rollout_shapes().items():
+            idx, ts = _lib.RO_FIELDS[name]
+            ptr = self.L.hk_rollout_ptr(self.h, idx)
+            if not ptr:
+                self._ck(_lib.HK_ERR_INVALID)
+            a = np.zeros(shape, np.dtype(ts))
+            if a.size:
+                _lib.copy_device_to_host(a.ctypes.data, ptr, a.nbytes)
+            out[name] = a
+        return out
 
     def observe(self):
         self._ck(self.L.hk_observe(self.h))

@@ -21,6 +21,10 @@ namespace KartGame.AI.Native
         public const int HK_COMM_ID_BYTES = 128;
         public const int HK_PROF_STAGES = 6;
         public const int HK_METER_PARTS = 4;
+        // hk_rollout_field: the buffers of the rollout recorder (hk_rollout_ptr)
+        public const int HK_RO_OBS = 0, HK_RO_FIRST = 1, HK_RO_STEER = 2, HK_RO_BRANCH = 3, HK_RO_RAW = 4, HK_RO_MU = 5, HK_RO_LOGITS = 6,
+                         HK_RO_LOGP_CONT = 7, HK_RO_LOGP_DISC = 8, HK_RO_REWARD = 9, HK_RO_GROUP_REWARD = 10, HK_RO_TERM_REWARD = 11,
+                         HK_RO_TERM_GROUP_REWARD = 12, HK_RO_DONE = 13, HK_RO_RING0 = 14, HK_RO_NEXT_OBS = 15, HK_RO_FIELDS = 16;
         // HierarchicalKartAgent.cs:21-33
         public const int HK_LOW_RL = 0, HK_LOW_MPC = 1, HK_LOW_LQR = 2, HK_LOW_E2E = 3;   // E2E: EndToEndKartAgent
         public const int HK_HIGH_MCTS = 0, HK_HIGH_FIXED = 1, HK_HIGH_NONE = 2;   // NONE: E2E with runQuasiMCTS off
@@ -395,6 +399,11 @@ namespace KartGame.AI.Native
         [DllImport(Lib)] public static extern int hk_policy_attach(IntPtr h, HkPolicyDesc* desc, int* agentSlots, int nSlots, int decisionPeriod);
         [DllImport(Lib)] public static extern int hk_policy_forward(IntPtr h, int policy, int rows, float* obs, float* mu, float* logits);
         [DllImport(Lib)] public static extern int hk_get_actions(IntPtr h, float* steer, int* branch);
+        // rollout recorder: every decision of the attached actors writes a row of device buffers (fields: hk.h hk_rollout_field)
+        [DllImport(Lib)] public static extern int hk_rollout_begin(IntPtr h, int rows);
+        [DllImport(Lib)] public static extern int hk_rollout_rows(IntPtr h);
+        [DllImport(Lib)] public static extern int hk_rollout_close(IntPtr h);
+        [DllImport(Lib)] public static extern IntPtr hk_rollout_ptr(IntPtr h, int field);
         // multi-GPU: one process per GPU, envs sharded by HkConfig.env_id_base; the only exchange is this all-gather over RCCL
         [DllImport(Lib)] public static extern int hk_comm_unique_id(byte* id128);
         [DllImport(Lib)] public static extern int hk_comm_init(IntPtr h, int worldSize, int rank, byte* id128);

@@ -458,6 +458,47 @@ int hk_policy_forward(hk_handle h, int policy, int rows, const float* obs /*[row
 /* The actions currently latched for every agent (what the policies / hk_set_actions wrote): steer[E][A], branch[E][A] */
 int hk_get_actions(hk_handle h, float* steer, int32_t* branch);
 
+/* ---- rollout recorder: what the attached actors did, gathered on the device ---------------------------------------------
+ * While a rollout is open, decision t (the t-th since hk_rollout_begin) writes ROW t of library-owned device buffers, and the
+ * ticks that follow it up to the next decision (interval t) complete the row's rewards and done flag.  Recording changes no
+ * result bit of the simulation.  Layouts are [R][E][A] (R = the rows given to hk_rollout_begin) unless noted; entries of agent
+ * slots no actor drives stay 0.  Every field is 4 bytes per element (f32 or i32).
+ *   OBS [R][E][A][obs_dim]     the observation decision t pushed into the agent's stack (the newest slice)
+ *   FIRST i32                  1: the stack was cleared at decision t (first decision of an episode, or after a reset)
+ *   STEER f32, BRANCH i32      the actions latched at decision t (what hk_get_actions returns after it)
+ *   RAW f32                    the continuous sample before the clip, mu + eps * sigma: STEER == clip(RAW, -3, 3) / 3; RAW == MU when deterministic
+ *   MU f32, LOGITS f32 [R][E][A][n_branch_max]    the actor's heads
+ *   LOGP_CONT, LOGP_DISC f32   -0.5 ((RAW - mu) / sigma)^2 - log_sigma - 0.5 log(2 pi) and log_softmax(logits)[BRANCH] (ML-Agents: the
+ *                              log-probability of the UNCLIPPED sample, continuous and discrete kept apart)
+ *   REWARD, GROUP_REWARD f32   m_Reward / m_GroupReward moved out (and zeroed) at the end of interval t: what hk_get_rewards would return
+ *                              then.  That includes the HitWall / HitOpponent events decision t's CollectObservations raised (ML-Agents would
+ *                              count them toward the row before).  If an episode ended inside the interval: only the part after the reset.
+ *   TERM_REWARD, TERM_GROUP_REWARD f32   an episode ended inside interval t: m_Reward / m_GroupReward at ResetGame, after the goal-timing
+ *                              rewards, just before they are zeroed (what EndGroupEpisode sends); 0 otherwise and without hk_config.rewards
+ *   DONE i32 [R][E]            0, 1 (an episode ended inside interval t) or 2 (... by the time-out)
+ *   RING0 f32 [E][A][stack_max - 1][obs_dim]   the stack contents before decision 0, oldest first, right-aligned (an actor of stack s uses
+ *                              the last s - 1 entries; zeros where empty): with OBS and FIRST every stacked input of the rollout can be rebuilt
+ *   NEXT_OBS f32 [E][A][obs_dim]   written by hk_rollout_close: the observation of the decision after the last row (bootstrap input)
+ * A trainer's transition reward of row t is DONE ? TERM_REWARD : REWARD; TERM_REWARD + REWARD is every AddReward of the interval.
+ * hk_rollout_begin allocates (or reuses) and zeroes the buffers, snapshots RING0 and the episode counters.  Refused (HK_ERR_INVALID):
+ * no actor attached, a rollout already open, the Academy step not on a decision (a multiple of decision_period), rows < 1;
+ * HK_ERR_UNSUPPORTED with hk_config.auto_reset == 0 (an ended episode is parked, never reset).  While a rollout is open an hk_step that
+ * would take more decisions than rows remain is refused before anything is issued, and hk_reset, hk_set_agent_state, hk_set_env_state,
+ * hk_get_rewards, hk_rewards_device and hk_policy_attach are refused (the two reward reads would take the accumulators the rows are made of).
+ * hk_rollout_close is refused mid-interval; it writes NEXT_OBS with an observe launch that raises no reward events (the next decision
+ * raises them as usual) and fails (HK_ERR_INVALID; the rollout is closed all the same) if an env ended more than one episode inside one
+ * interval, which the rows cannot express.  The buffers stay readable until the next hk_rollout_begin or hk_destroy.  Everything is
+ * asynchronous on hk_stream: synchronise before reading. */
+typedef enum hk_rollout_field {
+    HK_RO_OBS = 0, HK_RO_FIRST, HK_RO_STEER, HK_RO_BRANCH, HK_RO_RAW, HK_RO_MU, HK_RO_LOGITS, HK_RO_LOGP_CONT, HK_RO_LOGP_DISC,
+    HK_RO_REWARD, HK_RO_GROUP_REWARD, HK_RO_TERM_REWARD, HK_RO_TERM_GROUP_REWARD, HK_RO_DONE, HK_RO_RING0, HK_RO_NEXT_OBS,
+    HK_RO_FIELDS
+} hk_rollout_field;
+int hk_rollout_begin(hk_handle h, int rows);
+int hk_rollout_rows(hk_handle h);               /* completed rows: decisions whose interval has fully been issued */
+int hk_rollout_close(hk_handle h);
+void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* field; NULL (hk_last_error) on a bad field or before any rollout */
+
 /* ---- multi-GPU: the path's ONE exchange step ---------------------------------------------------------------
  * Race instances are independent (one RacingEnvController owns its own Agents[] / Sections[], REC:46-52): every rank steps its
  * own contiguous env-id range (hk_config.env_id_base) and nothing crosses GPUs on the data path.  What a host wants at the end
