@@ -8,6 +8,7 @@ import pytest
 import oracle_lib as O
 from hierarchicalkarting_amd import _lib
 from hierarchicalkarting_amd.env import AGENT_DT
+from parity import assert_bits_equal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -57,6 +58,5 @@ def test_c_host_matches_the_oracle(tmp_path):
         st = chunk[:E * A * AGENT_DT.itemsize].view(AGENT_DT).reshape(E, A)
         ob = chunk[E * A * AGENT_DT.itemsize:].view(np.float32).reshape(E, A, obs_dim)
         os_ = o.agent_state()
-        for name in AGENT_DT.names:
-            assert np.array_equal(st[name], os_[name]), (c, name)
-        assert np.array_equal(ob.view(np.uint32), o.observations().view(np.uint32)), c
+        assert_bits_equal(st, os_, (c, "agent_state"))
+        assert_bits_equal(ob, o.observations(), (c, "observations"))

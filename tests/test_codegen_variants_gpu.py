@@ -14,63 +14,40 @@ import os
 import subprocess
 import sys
 import pytest
+from parity import run_child, step_both, twin
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CHILD = r"""
-import sys, os
-sys.path.insert(0, %r); sys.path.insert(0, os.path.join(%r, "tests"))
-import numpy as np
-import oracle_lib as O
-import hierarchicalkarting_amd as hk
-from hierarchicalkarting_amd import _lib
-from hierarchicalkarting_amd.policy import Policy
-assert os.path.samefile(_lib.LIB_PATH, %r)
-
-def cmp(g, o, t):
-    gs, os_ = g.agent_state(), o.agent_state()
-    for name in gs.dtype.names:
-        x, y = gs[name], os_[name]
-        if x.dtype.kind == "f":
-            x = x.view(np.uint32); y = y.view(np.uint32)
-        assert np.array_equal(x, y), (t, name, np.argwhere(x != y)[:3].tolist())
-
-def run(b, calls, attach=None):
-    g = hk.RacingEnv(b); o = O.OracleEnv(b)
-    if attach:
-        for e in (g, o): e.attach_policy(*attach)
-    g.reset(); o.reset()
-    t = 0
-    for n in calls:
-        g.step(n); o.step(n); t += n
-        cmp(g, o, t)
-    return g, o
-
-# the headline instantiation, tick by tick through the start, then the call shapes of every schedule (fixed rounds, lazy, split is off at this size)
-run(hk.make_config(96, 4, jitter_seed=0x5EED0000, laps=1), [1] * 90 + [4, 3, 20, 7, 64, 130, 300, 700])
-# ... on the Complex track (Trigger masks in global memory) and with 3 agents
-run(hk.make_config(64, 4, jitter_seed=3, laps=1, track="complex"), (80, 1, 1, 2, 20, 200, 400))
-run(hk.make_config(64, 3, jitter_seed=5, laps=1), (80, 20, 200, 300))
-# two agents (cadence 1, the fused kernel) and eight (the 8-lane unit)
-run(hk.make_config(128, 2, jitter_seed=7, laps=1), (80, 1, 20, 200, 300))
-run(hk.make_config(96, 8, jitter_seed=0x5EED0000, laps=1), (130, 70, 20, 7, 1, 300))
-# Training mode + rewards (the <true, true, true> instantiation), time-outs
-run(hk.make_config(24, 4, env_mode=_lib.HK_MODE_TRAINING, training_agents=[1, 1, 0, 0], laps=1, max_episode_steps=300, rewards=1, jitter_seed=0, track="complex"),
-    (100, 1, 199, 57, 243))
-# planner + attached actor + rewards (the planner and chunk schedules), and the plans themselves
-b = hk.make_config(16, 4, jitter_seed=7, rewards=1, mcts_iterations=16, tree_search_depth=[8, 8, 5, 5],
-                   high_mode=[_lib.HK_HIGH_MCTS, _lib.HK_HIGH_MCTS, _lib.HK_HIGH_FIXED, _lib.HK_HIGH_FIXED],
-                   low_mode=[_lib.HK_LOW_RL, _lib.HK_LOW_LQR, _lib.HK_LOW_LQR, _lib.HK_LOW_LQR])
-g, o = run(b, (130, 40, 131), attach=(Policy.random(hk.RacingEnv(b).obs_dim * 4, 128, 3, seed=1), [0], 2))
-assert np.array_equal(g.mcts_state()["best"]["lane"], o.mcts_state()["best"]["lane"])
-# a planner handle's long call (pause mode: searches beside the ticks up to the plans' deadline)
-b = hk.make_config(32, 4, jitter_seed=9, mcts_iterations=16, tree_search_depth=8, high_mode=_lib.HK_HIGH_MCTS, track="complex", laps=1)
-g, o = run(b, (300, 260))
-assert np.array_equal(g.mcts_state()["best"]["lane"], o.mcts_state()["best"]["lane"])
-print("variant ok")
-"""
+def _child_variant(lib):
+    import numpy as np
+    import hierarchicalkarting_amd as hk
+    from hierarchicalkarting_amd import _lib
+    from hierarchicalkarting_amd.policy import Policy
+    assert os.path.samefile(_lib.LIB_PATH, lib)
+    # the headline instantiation, tick by tick through the start, then the call shapes of every schedule (fixed rounds, lazy, split is off at this size)
+    step_both(*twin(hk.make_config(96, 4, jitter_seed=0x5EED0000, laps=1)), [1] * 90 + [4, 3, 20, 7, 64, 130, 300, 700])
+    # ... on the Complex track (Trigger masks in global memory) and with 3 agents
+    step_both(*twin(hk.make_config(64, 4, jitter_seed=3, laps=1, track="complex")), (80, 1, 1, 2, 20, 200, 400))
+    step_both(*twin(hk.make_config(64, 3, jitter_seed=5, laps=1)), (80, 20, 200, 300))
+    # two agents (cadence 1, the fused kernel) and eight (the 8-lane unit)
+    step_both(*twin(hk.make_config(128, 2, jitter_seed=7, laps=1)), (80, 1, 20, 200, 300))
+    step_both(*twin(hk.make_config(96, 8, jitter_seed=0x5EED0000, laps=1)), (130, 70, 20, 7, 1, 300))
+    # Training mode + rewards (the <true, true, true> instantiation), time-outs
+    step_both(*twin(hk.make_config(24, 4, env_mode=_lib.HK_MODE_TRAINING, training_agents=[1, 1, 0, 0], laps=1, max_episode_steps=300, rewards=1,
+                                   jitter_seed=0, track="complex")), (100, 1, 199, 57, 243))
+    # planner + attached actor + rewards (the planner and chunk schedules), and the plans themselves
+    b = hk.make_config(16, 4, jitter_seed=7, rewards=1, mcts_iterations=16, tree_search_depth=[8, 8, 5, 5],
+                       high_mode=[_lib.HK_HIGH_MCTS, _lib.HK_HIGH_MCTS, _lib.HK_HIGH_FIXED, _lib.HK_HIGH_FIXED],
+                       low_mode=[_lib.HK_LOW_RL, _lib.HK_LOW_LQR, _lib.HK_LOW_LQR, _lib.HK_LOW_LQR])
+    g, o = twin(b, attach=lambda D: (Policy.random(D * 4, 128, 3, seed=1), [0], 2))
+    step_both(g, o, (130, 40, 131))
+    assert np.array_equal(g.mcts_state()["best"]["lane"], o.mcts_state()["best"]["lane"])
+    # a planner handle's long call (pause mode: searches beside the ticks up to the plans' deadline)
+    g, o = twin(hk.make_config(32, 4, jitter_seed=9, mcts_iterations=16, tree_search_depth=8, high_mode=_lib.HK_HIGH_MCTS, track="complex", laps=1))
+    step_both(g, o, (300, 260))
+    assert np.array_equal(g.mcts_state()["best"]["lane"], o.mcts_state()["best"]["lane"])
 
 
 def _variant_lib(k):
@@ -104,6 +81,5 @@ def test_parity_holds_on_another_register_allocation(k):
     assert guard["flags"] == flags
     if guard["spill_stores_ahead_of_exec_restore"]:
         pytest.skip("variant %d %s is flagged by the code-generation guard itself (%d store(s)): it would never ship" % (k, flags, len(guard["spill_stores_ahead_of_exec_restore"])))
-    env = dict(os.environ, HK_LIB_PATH=lib)
-    r = subprocess.run([sys.executable, "-c", CHILD % (ROOT, ROOT, lib)], env=env, capture_output=True, text=True, timeout=1500)
-    assert r.returncode == 0 and "variant ok" in r.stdout, "variant %d %s:\n" % (k, flags) + r.stdout[-2000:] + r.stderr[-4000:]
+    r = run_child(_child_variant, lib, lib=lib, timeout=1500)
+    assert r.ok, "variant %d %s:\n" % (k, flags) + r.output

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import e2e_setups as E2E
 import oracle_lib as O
-from test_e2e_gpu import _cmp          # hk_agent_state bit for bit but the E2E slot's E2E_EXEMPT fields
+from test_e2e_gpu import _check        # every field bit for bit but the E2E slots' exempt ones
 from test_reference_logs import BANDS, LANE_DIFF_BAND
 
 pytestmark = pytest.mark.gpu
@@ -131,7 +131,7 @@ def test_e2e_setup_twin_against_the_oracle(name):
         st, br = g.get_actions()
         o.set_actions(st, br)
         o.step(1)
-        gs = _cmp(g, o, e2e, t)
+        gs = _check(g, o, e2e, t)
     assert (gs["section_index"][:, e2e] > 2).all()             # every E2E kart has passed Triggers
     m = g.mcts_state()
     assert all((m["searches"][:, i] >= 1).all() for i in e2e if s.high[i] == E2E._lib.HK_HIGH_MCTS)

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import oracle_lib as O
 import e2e_restate as R
+from parity import assert_bits_equal, assert_same_state
 import hierarchicalkarting_amd as hk
 from hierarchicalkarting_amd import _lib
 from hierarchicalkarting_amd.policy import Policy
@@ -44,22 +45,14 @@ def _twin_cfg(E, low, high, **kw):
     return _cfg(E, [RL if l == E2E else l for l in low], [FIXED if l == E2E else h for l, h in zip(low, high)], **kw)
 
 
-def _cmp(g, o, e2e, t):
-    gs, os_ = g.agent_state(), o.agent_state()
-    for name in gs.dtype.names:
-        keep = np.ones(gs.shape, bool)
-        if name in E2E_EXEMPT:
-            keep[:, e2e] = False
-        assert np.array_equal(gs[name][keep], os_[name][keep]), (t, name)
-    ge, oe = g.env_state(), o.env_state()
-    for name in ("episode_steps", "inactive_mask", "experiment_num", "episodes_done", "status", "initial_started"):
-        assert np.array_equal(ge[name], oe[name]), (t, name)
-    gr, orr = g.episode_results(), o.episode_results()
-    for name in gr.dtype.names:
-        keep = np.ones(gr.shape, bool)
-        if name in RESULT_EXEMPT:
-            keep[:, e2e] = False
-        assert np.array_equal(gr[name][keep], orr[name][keep]), (t, "result", name)
+def _check(g, o, e2e, t):
+    """every field bit for bit but the E2E slots' exempt ones; -> libhk's agent records"""
+    gs = g.agent_state()
+    slots = np.zeros(gs.shape, bool)
+    slots[:, e2e] = True
+    exempt = {"agent_state." + n: slots for n in E2E_EXEMPT}
+    exempt.update({"episode_results." + n: slots for n in RESULT_EXEMPT})
+    assert_same_state(g, o, t, results=True, exclude=exempt)
     return gs
 
 
@@ -110,21 +103,21 @@ def _actor_twin(E, low, high, track, ticks, seed, check_obs=True):
         s, b = g.get_actions()
         o.set_actions(s, b)
         o.step(1)
-        gs = _cmp(g, o, e2e, t)
+        gs = _check(g, o, e2e, t)
         if t % 20 == 0:
             states[t] = gs
         if check_obs and t % 7 == 0:
             go, oo = g.observations(), o.observations()
             for i in range(A):
                 if i not in e2e:
-                    assert np.array_equal(go[:, i].view(np.uint32), oo[:, i].view(np.uint32)), (t, i)
+                    assert_bits_equal(go[:, i], oo[:, i], (t, i))
                     continue
-                assert np.array_equal(go[:, i, oth].view(np.uint32), oo[:, i, oth].view(np.uint32)), (t, i, "others")
-                assert np.array_equal(go[:, i, rays].view(np.uint32), oo[:, i, rays].view(np.uint32)), (t, i, "rays")
+                assert_bits_equal(go[:, i, oth], oo[:, i, oth], (t, i, "others"))
+                assert_bits_equal(go[:, i, rays], oo[:, i, rays], (t, i, "rays"))
                 for env in range(E):
                     w_own, w_hz = R.observe_e2e(tr, gs[env, i], A - 1)
-                    assert np.array_equal(go[env, i, own].view(np.uint32), w_own.view(np.uint32)), (t, env, i, go[env, i, own], w_own)
-                    assert np.array_equal(go[env, i, hzn].view(np.uint32), w_hz.view(np.uint32)), (t, env, i, "horizon")
+                    assert_bits_equal(go[env, i, own], w_own, (t, env, i, "own"))
+                    assert_bits_equal(go[env, i, hzn], w_hz, (t, env, i, "horizon"))
     return g, states, e2e
 
 
@@ -149,9 +142,7 @@ def test_e2e_twin_bit_exact_against_the_oracle(low, high, track):
     g2.attach_policy(_driver(g2.obs_dim * 4, 11 + len(low)), e2e, 2)
     for t in range(20, 841, 20):
         g2.step(20)
-        s2 = g2.agent_state()
-        for name in s2.dtype.names:
-            assert np.array_equal(s2[name], states[t][name]), (t, name)
+        assert_bits_equal(g2.agent_state(), states[t], t)
 
 
 def test_e2e_plain_handle_split_halves_against_the_oracle(monkeypatch):
@@ -169,7 +160,7 @@ def test_e2e_plain_handle_split_halves_against_the_oracle(monkeypatch):
         b = r.choice([0, 1, 2, 2, 2], size=(E, 4)).astype(np.int32)
         g.set_actions(s, b); o.set_actions(s, b)
         g.step(n); o.step(n); t += n
-        _cmp(g, o, [0, 1], t)
+        _check(g, o, [0, 1], t)
     assert (g.env_state()["episodes_done"] >= 2).all()
     a = g.agent_state()
     assert (a["plan_lane"][:, :2] == 0).all() and (a["avg_lane_diff"][:, :2] == 0).all()   # quasi-MCTS off: no plan, no metric
@@ -253,7 +244,7 @@ def test_e2e_rewards_double_academy_and_unit_dividers():
                 planned_passes += int(a0["plan_lane"][s1 % tr.L] != 0)
             elif s1 != s0:
                 continue                                        # (driving back through a Trigger: not restated here)
-            assert rw[env, 0].view(np.uint32) == want.view(np.uint32), (t, env, s0, s1, rw[env, 0], want)
+            assert_bits_equal(rw[env, 0], want, (t, env, s0, s1))
             with_plan += int(a0["plan_lane"][(s0 + 1) % tr.L] != 0)
         pre, pre_steps = post, steps
     assert with_plan > 0                                         # some ticks aimed the first pass at a planned lane box

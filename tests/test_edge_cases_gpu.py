@@ -2,20 +2,12 @@
 import copy
 import numpy as np
 import pytest
-import oracle_lib as O
+import functools
 from hierarchicalkarting_amd import _lib
+from parity import assert_same_state, step_both, twin
 from hierarchicalkarting_amd.config import load_track
 
 pytestmark = pytest.mark.gpu
-
-
-def _same(g, o, t):
-    gs, os_ = g.agent_state(), o.agent_state()
-    for name in gs.dtype.names:
-        x, y = gs[name], os_[name]
-        if x.dtype.kind == "f":
-            x = x.view(np.uint32); y = y.view(np.uint32)
-        assert np.array_equal(x, y), (t, name)
 
 
 def test_zero_ticks_single_env_and_empty_batches():
@@ -38,13 +30,7 @@ def test_track_without_walls():
     tr = copy.deepcopy(load_track("oval"))
     tr["walls"] = []
     b = hk.make_config(5, 2, track=tr, jitter_seed=2)
-    g = hk.RacingEnv(b); o = O.OracleEnv(b)
-    g.reset(); o.reset()
-    for t in (100, 200, 300):
-        g.step(100); o.step(100)
-        _same(g, o, t)
-    obs = g.observations()
-    assert np.array_equal(obs, o.observations())
+    step_both(*twin(b), (100, 100, 100), check=functools.partial(assert_same_state, obs=True))
 
 
 def test_track_tables_too_large_for_lds_are_read_from_global_memory():
@@ -62,12 +48,7 @@ def test_track_tables_too_large_for_lds_are_read_from_global_memory():
         w["points"] = out
     b = hk.make_config(6, 4, track=tr, jitter_seed=5)
     assert b.cfg.num_walls * 16 > 48 * 1024                                    # the wall segments alone exceed the LDS budget
-    g = hk.RacingEnv(b); o = O.OracleEnv(b)
-    g.reset(); o.reset()
-    for t in (100, 200, 300, 400):
-        g.step(100); o.step(100)
-        _same(g, o, t)
-    assert np.array_equal(g.observations(), o.observations())
+    step_both(*twin(b), (100, 100, 100, 100), check=functools.partial(assert_same_state, obs=True))
 
 
 def test_maximum_section_count_and_many_laps():
@@ -79,11 +60,7 @@ def test_maximum_section_count_and_many_laps():
     tr["sections"] = (secs + secs + secs)[:64]          # geometry repeats: karts lap the same oval, the index space is 64 long
     b = hk.make_config(4, 2, track=tr, jitter_seed=3, laps=9, rewards=1, max_episode_steps=900)
     assert b.cfg.num_sections == 64
-    g = hk.RacingEnv(b); o = O.OracleEnv(b)
-    g.reset(); o.reset()
-    for t in (300, 600, 950):
-        g.step(t if t == 300 else (300 if t == 600 else 350)); o.step(t if t == 300 else (300 if t == 600 else 350))
-        _same(g, o, t)
+    step_both(*twin(b), (300, 300, 350))
     with pytest.raises(hk.HkError):
         tr2 = copy.deepcopy(tr); tr2["sections"] = tr["sections"] + secs[:1]       # 65 sections
         hk.RacingEnv(hk.make_config(2, 2, track=tr2))
@@ -96,16 +73,10 @@ def test_short_calls_across_resets_need_no_more_rounds_than_issued(A):
     needed one round more would raise "an env did not complete its ticks" at the next getter, a wrong state would differ from the oracle."""
     import hierarchicalkarting_amd as hk
     b = hk.make_config(96, A, jitter_seed=0x5EED0000, laps=1, max_episode_steps=100 + 7 * (A % 3))
-    g = hk.RacingEnv(b); o = O.OracleEnv(b)
-    g.reset(); o.reset()
+    g, o = twin(b)
     t = 0
     for n, reps in ((1, 130), (2, 60), (3, 45), (4, 30), (5, 25), (7, 18), (20, 7), (33, 4)):
         for _ in range(reps):
             g.step(n); o.step(n); t += n
-        gs, os_ = g.agent_state(), o.agent_state()
-        for name in gs.dtype.names:
-            x, y = gs[name], os_[name]
-            if x.dtype.kind == "f":
-                x = x.view(np.uint32); y = y.view(np.uint32)
-            assert np.array_equal(x, y), (A, t, n, name)
+        assert_same_state(g, o, (A, t, n))
     assert (g.env_state()["episodes_done"] >= 5).all()

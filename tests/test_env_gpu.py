@@ -2,33 +2,16 @@
 seeded inputs: every field of every agent record bit-identical, tick by tick."""
 import numpy as np
 import pytest
-import oracle_lib as O
+from parity import assert_bits_equal, assert_same_state, step_both, twin
 
 pytestmark = pytest.mark.gpu
 
 
-def _cmp(gs, os_, ge, oe, tick):
-    for name in gs.dtype.names:
-        if not np.array_equal(gs[name], os_[name]):
-            bad = np.argwhere(gs[name] != os_[name])
-            e, a = bad[0][0], bad[0][1]
-            raise AssertionError("tick %d field %s env %d agent %d: gpu %r oracle %r (%d mismatches)" % (
-                tick, name, e, a, gs[name][e, a], os_[name][e, a], len(bad)))
-    for name in ("episode_steps", "inactive_mask", "experiment_num", "episodes_done", "status", "initial_started"):
-        assert np.array_equal(ge[name], oe[name]), (tick, name, ge[name][:8], oe[name][:8])
-
-
 def _run(A, E, ticks, every, **kw):
     import hierarchicalkarting_amd as hk
-    b = hk.make_config(E, A, **kw)
-    g = hk.RacingEnv(b)
-    o = O.OracleEnv(b)
-    g.reset(); o.reset()
-    _cmp(g.agent_state(), o.agent_state(), g.env_state(), o.env_state(), 0)
-    t = 0
-    while t < ticks:
-        g.step(every); o.step(every); t += every
-        _cmp(g.agent_state(), o.agent_state(), g.env_state(), o.env_state(), t)
+    g, o = twin(hk.make_config(E, A, **kw))
+    assert_same_state(g, o, 0)
+    step_both(g, o, [every] * -(-ticks // every))
     return g, o
 
 
@@ -42,16 +25,14 @@ def test_four_agent_tick_by_tick():
 
 def test_four_agent_long_many_envs():
     g, o = _run(4, 256, 1500, 250, jitter_seed=0x5EED0000)
-    assert np.array_equal(g.observations(), o.observations())
+    assert_bits_equal(g.observations(), o.observations(), "observations")
 
 
 def test_full_episode_with_auto_reset_two_agents():
     """4 096 ticks: a whole 2-agent race (~3.9 k ticks), the finish, the dead tick, the auto-reset and the next start."""
     g, o = _run(2, 16, 4096, 512, jitter_seed=0x5EED0000)
-    gr, orr = g.episode_results(), o.episode_results()
-    for name in gr.dtype.names:
-        assert np.array_equal(gr[name], orr[name]), name
-    assert (gr["episode"] >= 0).any()
+    assert_bits_equal(g.episode_results(), o.episode_results(), "episode_results")
+    assert (g.episode_results()["episode"] >= 0).any()
 
 
 def _pinned_bytes(st):
@@ -79,10 +60,7 @@ def test_lq_debug_taps_and_decoded_controls(monkeypatch):
     """single-step a4 check: players, branch ids, targets, weights and u0 of every ego's game equal the oracle's"""
     monkeypatch.setenv("HK_LQ_DEBUG", "1")
     import hierarchicalkarting_amd as hk
-    b = hk.make_config(16, 4, jitter_seed=0x5EED0000)
-    g = hk.RacingEnv(b)
-    o = O.OracleEnv(b)
-    g.reset(); o.reset()
+    g, o = twin(hk.make_config(16, 4, jitter_seed=0x5EED0000))
     seen = set()
     for _ in range(60):
         g.step(8); o.step(8)
@@ -103,10 +81,7 @@ def test_rl_actions_and_partial_reset():
     """LowMode == RL agents take hk_set_actions (KA:440-478); hk_reset of a subset leaves the other envs untouched"""
     import hierarchicalkarting_amd as hk
     from hierarchicalkarting_amd import _lib
-    b = hk.make_config(6, 2, low_mode=[_lib.HK_LOW_RL, _lib.HK_LOW_LQR], jitter_seed=7)
-    g = hk.RacingEnv(b)
-    o = O.OracleEnv(b)
-    g.reset(); o.reset()
+    g, o = twin(hk.make_config(6, 2, low_mode=[_lib.HK_LOW_RL, _lib.HK_LOW_LQR], jitter_seed=7))
     rng = np.random.default_rng(0)
     for k in range(12):
         steer = rng.uniform(-1, 1, (6, 2)).astype(np.float32)
@@ -115,7 +90,7 @@ def test_rl_actions_and_partial_reset():
         g.step(20); o.step(20)
         if k == 6:
             g.reset([1, 4], experiment_num=3); o.reset([1, 4], experiment_num=3)
-        _cmp(g.agent_state(), o.agent_state(), g.env_state(), o.env_state(), k)
+        assert_same_state(g, o, k)
     assert (g.env_state()["experiment_num"][[1, 4]] == 3).all()
 
 
@@ -137,7 +112,7 @@ def test_complex_track_four_agents():
     """the 41-section Complex track (straights, large / medium / small curves, S-curves), 3 laps,
     MaxLaneChanges 4; 842 wall segments through the LDS-staged wall grid vs the oracle's brute force."""
     g, o = _run(4, 24, 1200, 150, track="complex", jitter_seed=0x5EED0000)
-    assert np.array_equal(g.observations(), o.observations())
+    assert_bits_equal(g.observations(), o.observations(), "observations")
     _run(2, 8, 600, 1, track="complex", jitter_seed=11)
 
 
@@ -146,8 +121,7 @@ def test_restored_env_words_cannot_arm_ticks_or_resume_a_phase():
     them — a record filled by hand — runs exactly the ticks of the next hk_step, as the oracle does"""
     import hierarchicalkarting_amd as hk
     b = hk.make_config(64, 4, jitter_seed=0x5EED0000)
-    g = hk.RacingEnv(b); o = O.OracleEnv(b)
-    g.reset(); o.reset()
+    g, o = twin(b)
     g.step(137); o.step(137)
     ag, es = g.agent_state(), g.env_state()
     bad = es.copy()
@@ -159,4 +133,4 @@ def test_restored_env_words_cannot_arm_ticks_or_resume_a_phase():
     assert (back["reserved"][:, 0] == 0).all() and (back["reserved"][:, 1] == 16).all()
     for n in (1, 3, 60):
         g2.step(n); o.step(n)
-        _cmp(g2.agent_state(), o.agent_state(), g2.env_state(), o.env_state(), 137 + n)
+        assert_same_state(g2, o, 137 + n)

@@ -10,156 +10,115 @@ synchronising getter:
   split handle     the slots of the parts' last launches, summed over the parts, equal the reference total (the sum does not depend on the regroup).
 And the schedule follows the meter: on a dense aligned field stepped 2, 4 or 20 ticks at a time the label leaves "sparse", and it is always meter_look's
 classification of the value hk_schedule_info reports.  Every call also keeps the agent records bit-identical to the oracle."""
-import os
-import subprocess
-import sys
 import pytest
+from parity import assert_child, assert_same_state, twin
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-CHILD = r"""
-import sys, os
-sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, "tests"))
-import numpy as np
-import oracle_lib as O
-import hierarchicalkarting_amd as hk
-CASE = %(case)r
 
-def cmp(g, o, t):
-    gs, os_ = g.agent_state(), o.agent_state()
-    for name in gs.dtype.names:
-        x, y = gs[name], os_[name]
-        if x.dtype.kind == "f":
-            x = x.view(np.uint32); y = y.view(np.uint32)
-        assert np.array_equal(x, y), (CASE, t, name, np.argwhere(x != y)[:3].tolist())
-
-def b1_launches(g):
-    return g.prof_read()["env_b1_kernel"][1]
-
-def oracle_call(o, n):
-    # the games of each solve tick of an n-tick call of a field in lock-step (0 for the solve ticks of the start hold the kernels skip: hk.h hk_prof_games)
-    tot = []
-    c = int(o.game_counts()[2:].sum())
-    for _ in range(n):
-        o.step(1)
-        steps = o.env_state()["episode_steps"]
-        assert (steps == steps[0]).all(), "the field left lock-step"
-        c1 = int(o.game_counts()[2:].sum())
-        if steps[0] %% 4 == 0:
-            tot.append(0 if 4 < steps[0] < b.cfg.start_hold_ticks else c1 - c)
-        else:
-            assert c1 == c
-        c = c1
-    return tot
-
-def decayed(seq):
+def _decayed(seq):
     m = 0
     for k in range(len(seq)):
         prev = seq[k - 1] if k > 0 else 0
         m = max(prev, m - (m >> 2))
     return m
 
-split = CASE.startswith("split")
-E = 8192 + 192 if split else 2048
-b = hk.make_config(E, 4, jitter_seed=5, laps=3, max_episode_steps=4000)
-g = hk.RacingEnv(b); o = O.OracleEnv(b)
-g.reset(); o.reset()
-g.prof_enable(True); g.prof_reset()
-seq = []                 # reference total of every B1 launch of a part (split: of both parts together, launch by launch)
-launched = 0
-t = 0
 
-def call(n):
-    global launched, t
-    before = b1_launches(g)
-    g.step(n)
-    tot = oracle_call(o, n)
-    t += n
-    L = b1_launches(g) - before
-    parts = 2 if split else 1
-    assert L %% parts == 0, (CASE, t, L)
-    L //= parts
-    assert L >= len(tot), (CASE, t, n, L, tot)
-    seq.extend(tot + [0] * (L - len(tot)))
-    launched += L
-    w = g.prof_meter()
-    if launched:
-        last = (launched - 1) %% 3
-        got = sum(w[p][last] for p in range(parts))
-        assert got == seq[-1], (CASE, t, n, "last launch", launched, w[:parts], seq[-4:])
-        if not split:
-            assert w[0][3] == decayed(seq), (CASE, t, n, "decaying maximum", w[0], decayed(seq), seq[-4:])
-    return w
+def _child_meter(case):
+    import hierarchicalkarting_amd as hk
+    split = case.startswith("split")
+    E = 8192 + 192 if split else 2048
+    b = hk.make_config(E, 4, jitter_seed=5, laps=3, max_episode_steps=4000)
+    g, o = twin(b)
+    g.prof_enable(True); g.prof_reset()
+    seq = []                 # reference total of every B1 launch of a part (split: of both parts together, launch by launch)
+    launched = 0
+    t = 0
 
-SIZES = [1] * 6 + [2] * 4 + [3] * 4 + [4] * 4 + [5] * 4 + [20] * 2 + [1, 2, 3, 4, 5, 20, 1, 7, 2]
-if not split:
-    SIZES = SIZES + [64, 512]
-for n in SIZES:                         # the race start: dense
-    call(n)
-cmp(g, o, t)
-dense_m = max(seq)
-assert dense_m > E // 8, (CASE, dense_m)
-while t < 600:                          # on to a spread field (fixed-round calls: every launch of a split handle stays split)
-    call(min(20, 600 - t) if split else min(128, 600 - t))
-cmp(g, o, t)
-for n in SIZES:                         # a spread field
-    call(n)
-cmp(g, o, t)
-print("meter ok", CASE, t, launched, dense_m, seq[-6:])
-"""
+    def oracle_call(n):
+        # the games of each solve tick of an n-tick call of a field in lock-step (0 for the solve ticks of the start hold the kernels skip: hk.h hk_prof_games)
+        tot = []
+        c = int(o.game_counts()[2:].sum())
+        for _ in range(n):
+            o.step(1)
+            steps = o.env_state()["episode_steps"]
+            assert (steps == steps[0]).all(), "the field left lock-step"
+            c1 = int(o.game_counts()[2:].sum())
+            if steps[0] % 4 == 0:
+                tot.append(0 if 4 < steps[0] < b.cfg.start_hold_ticks else c1 - c)
+            else:
+                assert c1 == c
+            c = c1
+        return tot
 
-LABEL = r"""
-import sys, os
-sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, "tests"))
-import numpy as np
-import oracle_lib as O
-import hierarchicalkarting_amd as hk
-N = %(n)d
+    def call(n):
+        nonlocal launched, t
+        before = g.prof_read()["env_b1_kernel"][1]
+        g.step(n)
+        tot = oracle_call(n)
+        t += n
+        L = g.prof_read()["env_b1_kernel"][1] - before
+        parts = 2 if split else 1
+        assert L % parts == 0, (case, t, L)
+        L //= parts
+        assert L >= len(tot), (case, t, n, L, tot)
+        seq.extend(tot + [0] * (L - len(tot)))
+        launched += L
+        w = g.prof_meter()
+        if launched:
+            last = (launched - 1) % 3
+            got = sum(w[p][last] for p in range(parts))
+            assert got == seq[-1], (case, t, n, "last launch", launched, w[:parts], seq[-4:])
+            if not split:
+                assert w[0][3] == _decayed(seq), (case, t, n, "decaying maximum", w[0], _decayed(seq), seq[-4:])
 
-E = 2048
-b = hk.make_config(E, 4, jitter_seed=5, laps=3, max_episode_steps=4000)
-g = hk.RacingEnv(b); o = O.OracleEnv(b)
-g.reset(); o.reset()
-prev_sparse = None
-labels = []
-for k in range(max(160 // N, 8)):           # the close field of the race start, stepped N ticks at a time from an aligned start
-    g.step(N); o.step(N)
-    s = g.schedule_info()
-    v, lab = s["games_meter_value"], s["games_meter"]
-    epl = E / s["streams"]
-    # meter_look (hk_api.hip): sparse up to 1 per 40 envs of a launch, or 1 per 28 if it was sparse at the last look; dense beyond 1 per 8
-    sparse = v <= epl / 40.0 or (bool(prev_sparse) and v <= epl / 28.0)
-    want = "sparse" if sparse else ("dense" if v > epl / 8.0 else "medium")
-    assert lab == want, (N, k, s)
-    prev_sparse = lab == "sparse"
-    labels.append(lab)
-gs, os_ = g.agent_state(), o.agent_state()
-for name in gs.dtype.names:
-    x, y = gs[name], os_[name]
-    if x.dtype.kind == "f":
-        x = x.view(np.uint32); y = y.view(np.uint32)
-    assert np.array_equal(x, y), name
-assert labels[-1] != "sparse", (N, labels, g.prof_meter()[0], s)
-print("label ok", N, labels[-1], s["games_meter_value"])
-"""
+    SIZES = [1] * 6 + [2] * 4 + [3] * 4 + [4] * 4 + [5] * 4 + [20] * 2 + [1, 2, 3, 4, 5, 20, 1, 7, 2]
+    if not split:
+        SIZES = SIZES + [64, 512]
+    for n in SIZES:                         # the race start: dense
+        call(n)
+    assert_same_state(g, o, (case, t))
+    dense_m = max(seq)
+    assert dense_m > E // 8, (case, dense_m)
+    while t < 600:                          # on to a spread field (fixed-round calls: every launch of a split handle stays split)
+        call(min(20, 600 - t) if split else min(128, 600 - t))
+    assert_same_state(g, o, (case, t))
+    for n in SIZES:                         # a spread field
+        call(n)
+    assert_same_state(g, o, (case, t))
+    print("meter ok", case, t, launched, dense_m, seq[-6:])
+
+
+def _child_label(N):
+    import hierarchicalkarting_amd as hk
+    E = 2048
+    g, o = twin(hk.make_config(E, 4, jitter_seed=5, laps=3, max_episode_steps=4000))
+    prev_sparse = None
+    labels = []
+    for k in range(max(160 // N, 8)):           # the close field of the race start, stepped N ticks at a time from an aligned start
+        g.step(N); o.step(N)
+        s = g.schedule_info()
+        v, lab = s["games_meter_value"], s["games_meter"]
+        epl = E / s["streams"]
+        # meter_look (hk_api.hip): sparse up to 1 per 40 envs of a launch, or 1 per 28 if it was sparse at the last look; dense beyond 1 per 8
+        sparse = v <= epl / 40.0 or (bool(prev_sparse) and v <= epl / 28.0)
+        want = "sparse" if sparse else ("dense" if v > epl / 8.0 else "medium")
+        assert lab == want, (N, k, s)
+        prev_sparse = lab == "sparse"
+        labels.append(lab)
+    assert_same_state(g, o, N)
+    assert labels[-1] != "sparse", (N, labels, g.prof_meter()[0], s)
+    print("label ok", N, labels[-1], s["games_meter_value"])
+
 
 CASES = {"unsplit": {}, "unsplit_no_optimistic": {"HK_NO_OPTIMISTIC": "1"}, "split": {}, "split_no_optimistic": {"HK_NO_OPTIMISTIC": "1"}}
 
 
-def _env(extra):
-    env = {k: v for k, v in os.environ.items() if not k.startswith("HK_") or k in ("HK_LIB_PATH",)}
-    env.update(extra)
-    return env
-
-
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_meter_equals_the_reference_per_launch_totals(case):
-    r = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT, "case": case}], env=_env(CASES[case]), capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0 and "meter ok" in r.stdout, r.stdout[-1500:] + r.stderr[-4000:]
+    assert_child(_child_meter, case, switches=CASES[case], timeout=1200)
 
 
 @pytest.mark.parametrize("n", [2, 4, 20])
 def test_schedule_follows_the_meter_on_a_dense_field(n):
-    r = subprocess.run([sys.executable, "-c", LABEL % {"root": ROOT, "n": n}], env=_env({}), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "label ok" in r.stdout, r.stdout[-1500:] + r.stderr[-4000:]
+    assert_child(_child_label, n, timeout=600)

@@ -1,10 +1,10 @@
 """MCTS planner on device (mcts_search_kernel + the request / consume hooks of the fused tick kernel, through the C ABI)
 vs the CPU oracle: planner state (pending / visible plans, beliefs, section times) and every agent field bit-identical,
 tick by tick, including time-out resets that re-plan."""
-import numpy as np
+import functools
 import pytest
-import oracle_lib as O
 from hierarchicalkarting_amd import _lib
+from parity import assert_bits_equal, assert_same_state, step_both, twin
 
 pytestmark = pytest.mark.gpu
 MC, FX = _lib.HK_HIGH_MCTS, _lib.HK_HIGH_FIXED
@@ -13,35 +13,15 @@ MC, FX = _lib.HK_HIGH_MCTS, _lib.HK_HIGH_FIXED
 def _pair(E, A, high, **kw):
     import hierarchicalkarting_amd as hk
     kw.setdefault("tree_search_depth", [8 if h == MC else 5 for h in high])
-    b = hk.make_config(E, A, high_mode=high, **kw)
-    g = hk.RacingEnv(b)
-    o = O.OracleEnv(b)
-    g.reset(); o.reset()
-    return g, o
+    return twin(hk.make_config(E, A, high_mode=high, **kw))
 
 
-def _cmp(g, o, t, full=True):
-    gm, om = g.mcts_state(), o.mcts_state()
-
-    def walk(x, y, path):
-        if x.dtype.names:
-            for n in x.dtype.names:
-                walk(x[n], y[n], path + "." + n)
-        else:
-            assert np.array_equal(x, y), (t, path, np.argwhere(x != y)[:4].tolist())
-    walk(gm, om, "mcts")
-    if full:
-        gs, os_ = g.agent_state(), o.agent_state()
-        for name in gs.dtype.names:
-            assert np.array_equal(gs[name], os_[name]), (t, name)
-        ge, oe = g.env_state(), o.env_state()
-        for name in ("episode_steps", "inactive_mask", "experiment_num", "episodes_done", "status", "initial_started"):
-            assert np.array_equal(ge[name], oe[name]), (t, name)
+_check = functools.partial(assert_same_state, mcts=True)
 
 
 def test_first_plan_matches():
     g, o = _pair(16, 2, [MC, FX], jitter_seed=3, mcts_iterations=48)
-    _cmp(g, o, 0)
+    _check(g, o, 0)
     assert (g.mcts_state()["pend"]["n_states"][:, 0] == 8).all()
 
 
@@ -49,17 +29,17 @@ def test_two_agent_mcts_vs_fixed_tick_by_tick():
     g, o = _pair(6, 2, [MC, FX], jitter_seed=5, mcts_iterations=32)
     for t in range(1, 331):
         g.step(1); o.step(1)
-        _cmp(g, o, t, full=(t % 10 == 0 or 70 < t < 80 or 140 < t < 150))
+        if t % 10 == 0 or 70 < t < 80 or 140 < t < 150:
+            _check(g, o, t)
+        else:
+            assert_bits_equal(g.mcts_state(), o.mcts_state(), (t, "mcts_state"))
 
 
 @pytest.mark.parametrize("persist_gb", ["64", "0"])
 def test_four_agents_all_mcts_odd_steps_and_timeout_resets(persist_gb, monkeypatch):
     monkeypatch.setenv("HK_MCTS_PERSIST_GB", persist_gb)
     g, o = _pair(12, 4, [MC, MC, MC, MC], jitter_seed=7, mcts_iterations=16, max_episode_steps=260)
-    t = 0
-    for n in (3, 97, 1, 45, 60, 54, 7, 100, 133, 29, 71):
-        g.step(n); o.step(n); t += n
-        _cmp(g, o, t)
+    step_both(g, o, (3, 97, 1, 45, 60, 54, 7, 100, 133, 29, 71), check=_check)
     assert (g.env_state()["episodes_done"] >= 2).all()
 
 
@@ -68,18 +48,12 @@ def test_long_calls_without_the_pause_schedule(monkeypatch):
     wait) — the schedule must not show in the results"""
     monkeypatch.setenv("HK_MCTS_NO_PAUSE", "1")
     g, o = _pair(10, 4, [MC, MC, MC, MC], jitter_seed=19, mcts_iterations=16)
-    t = 0
-    for n in (150, 90, 260):
-        g.step(n); o.step(n); t += n
-        _cmp(g, o, t)
+    step_both(g, o, (150, 90, 260), check=_check)
 
 
 def test_mixed_team_complex_track():
     g, o = _pair(8, 4, [MC, FX, MC, FX], track="complex", jitter_seed=2, mcts_iterations=20)
-    t = 0
-    for n in (100, 50, 150, 200):
-        g.step(n); o.step(n); t += n
-        _cmp(g, o, t)
+    step_both(g, o, (100, 50, 150, 200), check=_check)
 
 
 def test_create_rejects_bad_planner_budgets():
@@ -110,7 +84,7 @@ def test_root_reuse_matches_the_oracles_persistent_trees(persist_gb, monkeypatch
     t = 0
     for k in range(18):
         g.step(25); o.step(25); t += 25
-        _cmp(g, o, t)
+        _check(g, o, t)
         a = o.agent_state()
         a[:, 0] = st[:, 0]
         o.set_agent_state(a); g.set_agent_state(a)
@@ -122,32 +96,23 @@ def test_root_reuse_matches_the_oracles_persistent_trees(persist_gb, monkeypatch
 
 def test_section_window_three_reads_section_times_two_rows_back():
     g, o = _pair(8, 4, [MC, MC, MC, MC], jitter_seed=17, mcts_iterations=16, section_window=3, mcts_seed=5)
-    _cmp(g, o, 0)
+    _check(g, o, 0)
     row2 = g.agent_state()["section_index"] == 1
     assert row2.sum() == 16 and (g.mcts_state()["sec_time"][:, :, 0][row2] < 0).all()     # the second grid row got a made-up time for section 0 (REC:690)
-    t = 0
-    for n in (100, 45, 55, 100):
-        g.step(n); o.step(n); t += n
-        _cmp(g, o, t)
+    step_both(g, o, (100, 45, 55, 100), check=_check)
 
 
 def test_tick_by_tick_stepping_defers_but_never_misses_a_plan():
     """A host that steps one tick per call (Unity's FixedUpdate) or in small uneven chunks: the searches are batched over up to
     32 armed ticks, yet every plan is there when it is due — records, plans and beliefs equal the oracle's all the way."""
     import hierarchicalkarting_amd as hk
-    b = hk.make_config(6, 4, track="complex", jitter_seed=21, high_mode=_lib.HK_HIGH_MCTS, tree_search_depth=4, mcts_iterations=10,
-                       mcts_latency_ticks=41, mcts_initial_latency_ticks=41)
-    g = hk.RacingEnv(b); o = O.OracleEnv(b)
-    g.reset(); o.reset()
+    g, o = twin(hk.make_config(6, 4, track="complex", jitter_seed=21, high_mode=_lib.HK_HIGH_MCTS, tree_search_depth=4, mcts_iterations=10,
+                               mcts_latency_ticks=41, mcts_initial_latency_ticks=41))
     t = 0
     chunks = [1] * 130 + [3, 7, 31, 2, 32, 33, 1, 1, 30, 5, 64, 1] + [1] * 60
     for k, n in enumerate(chunks):
         g.step(n); o.step(n); t += n
         if k % 9 == 0 or n > 1:
-            gs, os_ = g.agent_state(), o.agent_state()
-            for name in gs.dtype.names:
-                assert np.array_equal(gs[name], os_[name]), (t, name)
-    gm, om = g.mcts_state(), o.mcts_state()
-    for name in gm.dtype.names:
-        assert np.array_equal(gm[name], om[name]), (t, name)
-    assert gm["searches"].min() >= 4
+            assert_same_state(g, o, t)
+    assert_bits_equal(g.mcts_state(), o.mcts_state(), (t, "mcts_state"))
+    assert g.mcts_state()["searches"].min() >= 4

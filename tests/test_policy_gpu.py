@@ -3,20 +3,16 @@ oracle: mu / logits bit-identical (the MFMA result is a k-ascending fmaf chain s
 oracle evaluates), sampled actions bit-identical (same Philox draws), and whole RL-driven episodes bit-identical."""
 import numpy as np
 import pytest
-import oracle_lib as O
 from hierarchicalkarting_amd import _lib
 from hierarchicalkarting_amd.policy import Policy
+from parity import assert_bits_equal, assert_same_state, step_both, twin
 
 pytestmark = pytest.mark.gpu
 
 
 def _pair(E, A, low, **kw):
     import hierarchicalkarting_amd as hk
-    b = hk.make_config(E, A, low_mode=low, **kw)
-    g = hk.RacingEnv(b)
-    o = O.OracleEnv(b)
-    g.reset(); o.reset()
-    return g, o
+    return twin(hk.make_config(E, A, low_mode=low, **kw))
 
 
 @pytest.mark.parametrize("A,stack,hidden,layers,rows,normalize", [
@@ -41,21 +37,16 @@ def test_actor_bit_exact(A, stack, hidden, layers, rows, normalize):
     obs[0, :7] = [0.0, -0.0, 1e-30, -1e30, 5.0, -5.0, 1e30]
     gm, gl = g.policy_forward(gi, obs)
     om, ol = o.policy_forward(oi, obs)
-    assert np.array_equal(gm.view(np.uint32), om.view(np.uint32)), np.abs(gm - om).max()
-    assert np.array_equal(gl.view(np.uint32), ol.view(np.uint32)), np.abs(gl - ol).max()
+    assert_bits_equal(gm, om, "mu")
+    assert_bits_equal(gl, ol, "logits")
     assert np.isfinite(gm).all() and np.abs(gm).max() > 1e-3
 
 
-def _cmp_agents(g, o, t):
-    gs, os_ = g.agent_state(), o.agent_state()
-    for name in gs.dtype.names:
-        assert np.array_equal(gs[name], os_[name]), (t, name)
-    ge, oe = g.env_state(), o.env_state()
-    for name in ("episode_steps", "inactive_mask", "experiment_num", "episodes_done", "status", "initial_started"):
-        assert np.array_equal(ge[name], oe[name]), (t, name)
-    ga, oa = g.get_actions(), o.get_actions()
-    assert np.array_equal(ga[0].view(np.uint32), oa[0].view(np.uint32)), (t, "steer")
-    assert np.array_equal(ga[1], oa[1]), (t, "branch")
+def _check(g, o, t):
+    assert_same_state(g, o, t)
+    (gs, gb), (os_, ob) = g.get_actions(), o.get_actions()
+    assert_bits_equal(gs, os_, (t, "steer"))
+    assert_bits_equal(gb, ob, (t, "branch"))
 
 
 def test_rl_vs_lq_episode_tick_by_tick():
@@ -66,7 +57,7 @@ def test_rl_vs_lq_episode_tick_by_tick():
     seen = set()
     for t in range(1, 241):
         g.step(1); o.step(1)
-        _cmp_agents(g, o, t)
+        _check(g, o, t)
         s, br = g.get_actions()
         seen.update(np.unique(s[:, 0]).tolist())
         assert (s[:, 1] == 0).all()                      # nothing latches an action for the LQ agent
@@ -83,12 +74,9 @@ def test_two_team_policies_with_timeout_resets():
     for e in (g, o):
         assert e.attach_policy(p1, [0, 1], 2) == 0
         assert e.attach_policy(p2, [2, 3], 2) == 1
-    t = 0
-    for n in (1, 3, 7, 2, 50, 101, 33, 64, 150, 75):
-        g.step(n); o.step(n); t += n
-        _cmp_agents(g, o, t)
+    step_both(g, o, (1, 3, 7, 2, 50, 101, 33, 64, 150, 75), check=_check)
     assert (g.env_state()["episodes_done"] >= 2).all()
-    assert np.array_equal(g.observations(), o.observations())
+    assert_bits_equal(g.observations(), o.observations(), "observations")
 
 
 def test_decision_period_and_explicit_reset():
@@ -97,11 +85,11 @@ def test_decision_period_and_explicit_reset():
     g.attach_policy(pol, [0, 1], 3); o.attach_policy(pol, [0, 1], 3)
     for t in range(1, 20):
         g.step(1); o.step(1)
-        _cmp_agents(g, o, t)
+        _check(g, o, t)
     g.reset([1, 3], 1); o.reset([1, 3], 1)
     for t in range(20, 40):
         g.step(1); o.step(1)
-        _cmp_agents(g, o, t)
+        _check(g, o, t)
 
 
 def test_attach_rejects_bad_requests():

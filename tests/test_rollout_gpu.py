@@ -1,23 +1,16 @@
 """Rollout recorder (hk_rollout_begin / hk_step / hk_rollout_close, include/hk.h hk_rollout_field) against the CPU oracle stepped one
 decision interval at a time: recording changes no result bit, every row holds what the actors did and what the interval paid."""
-import os
-import subprocess
-import sys
 import numpy as np
 import pytest
 import oracle_lib as O
 from hierarchicalkarting_amd import _lib
 from hierarchicalkarting_amd.policy import Policy
 from hierarchicalkarting_amd.rollout import stacked_inputs, transition_rewards
+from parity import assert_bits_equal, assert_child, assert_same_state
 from rollout_restate import logp_cont, logp_disc
 
 pytestmark = pytest.mark.gpu
 RL, P = _lib.HK_LOW_RL, 2
-ENV_FIELDS = ("episode_steps", "inactive_mask", "experiment_num", "episodes_done", "status", "initial_started")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _make(E, A=4, policies=None, **kw):
@@ -42,19 +35,8 @@ def _team_actors(D, stack2=4):
 def _same_state(x, y, what, skip_acc=False):
     """skip_acc: not the reward accumulators, and not hk_episode_result.group_reward, which is the group accumulator as the episode's end found
     it — since the last read (Agent.SendInfo), and recording reads it at every decision, as a trainer does"""
-    sx, sy = x.agent_state(), y.agent_state()
-    for n in sx.dtype.names:
-        if skip_acc and n in ("step_reward", "group_reward"):
-            continue
-        assert np.array_equal(sx[n], sy[n]), (what, n)
-    ex, ey = x.env_state(), y.env_state()
-    for n in ENV_FIELDS:
-        assert np.array_equal(ex[n], ey[n]), (what, n)
-    rx, ry = x.episode_results(), y.episode_results()
-    for n in rx.dtype.names:
-        if skip_acc and n == "group_reward":
-            continue
-        assert np.array_equal(rx[n], ry[n]), (what, n)
+    skip = np.full((x.E, x.A), skip_acc)
+    assert_same_state(x, y, what, results=True, exclude=dict.fromkeys(("agent_state.step_reward", "agent_state.group_reward", "episode_results.group_reward"), skip))
 
 
 def test_recording_changes_no_result_bit():
@@ -70,7 +52,7 @@ def test_recording_changes_no_result_bit():
         g.step(n); h.step(n); o.step(n); t += n
         _same_state(g, h, t, skip_acc=True)
         _same_state(g, o, t, skip_acc=True)
-        assert np.array_equal(_bits(g.get_actions()[0]), _bits(h.get_actions()[0]))
+        assert_bits_equal(g.get_actions()[0], h.get_actions()[0], t)
     assert g.rollout_rows() == t // P
     g.rollout_close()
     assert (g.env_state()["episodes_done"] >= 1).all()
@@ -96,11 +78,11 @@ def _rows_vs_oracle(g, o, pols, R, chunks):
         ep0 = o.env_state()["episodes_done"].copy()
         o.step(P)
         s, b = o.get_actions()
-        assert np.array_equal(_bits(ro["steer"][t][:, m]), _bits(s[:, m])), t
+        assert_bits_equal(ro["steer"][t][:, m], s[:, m], t)
         assert np.array_equal(ro["branch"][t][:, m], b[:, m]), t
         r, gr = o.rewards()
-        assert np.array_equal(_bits(ro["reward"][t][:, m]), _bits(r[:, m])), t
-        assert np.array_equal(_bits(ro["group_reward"][t][:, m]), _bits(gr[:, m])), t
+        assert_bits_equal(ro["reward"][t][:, m], r[:, m], t)
+        assert_bits_equal(ro["group_reward"][t][:, m], gr[:, m], t)
         es = o.env_state()
         d = np.where(es["episodes_done"] > ep0, np.where(es["status"] & 2, 2, 1), 0)
         assert np.array_equal(ro["done"][t], d), t
@@ -109,7 +91,7 @@ def _rows_vs_oracle(g, o, pols, R, chunks):
         if ended.any():
             n_done += int(ended.sum())
             res = o.episode_results()
-            assert np.array_equal(_bits(ro["term_group_reward"][t][ended][:, m]), _bits(res["group_reward"][ended][:, m])), t
+            assert_bits_equal(ro["term_group_reward"][t][ended][:, m], res["group_reward"][ended][:, m], t)
             if A >= 2:
                 want = (res["reward"] - cum0)[ended][:, m]
                 assert np.allclose(ro["term_reward"][t][ended][:, m], want, rtol=1e-4, atol=2e-4), t
@@ -132,9 +114,10 @@ def test_rows_against_the_oracle():
         lg, br = ro["logits"][:, :, slots, :pol.n_branch], ro["branch"][:, :, slots]
         assert np.allclose(ro["logp_cont"][:, :, slots], logp_cont(raw, mu, pol.log_sigma[0]), rtol=1e-6, atol=2e-6), k
         assert np.allclose(ro["logp_disc"][:, :, slots], logp_disc(lg, br), rtol=1e-6, atol=2e-6), k
-        assert np.array_equal(_bits(ro["steer"][:, :, slots]), _bits(np.clip(raw, np.float32(-3), np.float32(3)) / np.float32(3))), k
+        assert_bits_equal(ro["steer"][:, :, slots], np.clip(raw, np.float32(-3), np.float32(3)) / np.float32(3), k)
         if pol.deterministic:
-            assert np.array_equal(_bits(raw), _bits(mu)) and np.array_equal(br, lg.argmax(axis=-1)), k
+            assert_bits_equal(raw, mu, k)
+            assert np.array_equal(br, lg.argmax(axis=-1)), k
         else:
             assert (raw != mu).mean() > 0.9 and len(np.unique(br)) == pol.n_branch, k
 
@@ -156,8 +139,8 @@ def test_observations_and_stacks():
     for k, (pol, slots) in enumerate(pols):
         x = stacked_inputs(ro, slots, pol.stack)
         mu, lg = g.policy_forward(k, x.reshape(-1, pol.in_dim))
-        assert np.array_equal(_bits(mu), _bits(ro["mu"][:, :, slots].reshape(-1))), k
-        assert np.array_equal(_bits(lg), _bits(ro["logits"][:, :, slots, :pol.n_branch].reshape(-1, pol.n_branch))), k
+        assert_bits_equal(mu, ro["mu"][:, :, slots].reshape(-1), k)
+        assert_bits_equal(lg, ro["logits"][:, :, slots, :pol.n_branch].reshape(-1, pol.n_branch), k)
     next_obs = ro["next_obs"].copy()
     assert next_obs.any()
     # the next rollout's first decision observes exactly what close() wrote, and close() raised no reward events
@@ -165,10 +148,11 @@ def test_observations_and_stacks():
     g.step(2); o.step(2)
     g.rollout_close()
     ro2 = g.rollout()
-    assert np.array_equal(_bits(ro2["obs"][0]), _bits(next_obs))
+    assert_bits_equal(ro2["obs"][0], next_obs, "next_obs")
     r, gr = o.rewards()
-    assert np.array_equal(_bits(ro2["reward"][0]), _bits(r)) and np.array_equal(_bits(ro2["group_reward"][0]), _bits(gr))
-    assert np.array_equal(g.observations(), o.observations())
+    assert_bits_equal(ro2["reward"][0], r, "reward")
+    assert_bits_equal(ro2["group_reward"][0], gr, "group_reward")
+    assert_bits_equal(g.observations(), o.observations(), "observations")
 
 
 def test_rules():
@@ -211,7 +195,7 @@ def test_rules():
         g.step(n); twin.step(n)
         g.rollout_close()
         _same_state(g, twin, n, skip_acc=True)
-        assert np.array_equal(_bits(g.get_actions()[0]), _bits(twin.get_actions()[0]))
+        assert_bits_equal(g.get_actions()[0], twin.get_actions()[0], n)
     g.rewards()                                                                # closed: reading the accumulators is allowed again
     # destroy with an open rollout
     g.rollout_begin(2); g.step(2)
@@ -249,37 +233,32 @@ def test_instantiations_against_the_oracle(case):
     assert n_done > 0
 
 
-SCRIPT = r"""
-import torch
-torch.cuda.init()                      # torch's HIP runtime first (see RacingEnv.torch_views)
-import numpy as np
-import hierarchicalkarting_amd as hk
-from hierarchicalkarting_amd import _lib
-from hierarchicalkarting_amd.policy import Policy
-g = hk.RacingEnv(hk.make_config(32, 4, low_mode=[_lib.HK_LOW_RL] * 4, rewards=1, max_episode_steps=100, jitter_seed=2))
-g.reset()
-g.attach_policy(Policy.random(g.obs_dim * 4, 128, 2, seed=1), [0, 1, 2, 3], 2)
-g.rollout_begin(60)
-g.step(120)
-g.rollout_close()
-v = g.rollout_views()
-ro = g.rollout()
-D = g.obs_dim
-want = {"obs": (60, 32, 4, D), "logits": (60, 32, 4, 3), "done": (60, 32), "ring0": (32, 4, 3, D), "next_obs": (32, 4, D), "reward": (60, 32, 4)}
-for k, t in v.items():
-    assert t.is_cuda, k
-    assert t.dtype == (torch.int32 if k in ("first", "branch", "done") else torch.float32), k
-    assert tuple(t.shape) == ro[k].shape, k
-    if k in want:
-        assert tuple(t.shape) == want[k], k
-    assert np.array_equal(t.cpu().numpy(), ro[k]), k
-assert (ro["done"] != 0).any() and ro["obs"].any()
-print("ROLLOUT_VIEWS_OK")
-"""
+def _child_rollout_views():
+    import torch
+    torch.cuda.init()                      # torch's HIP runtime first (see RacingEnv.torch_views)
+    import numpy as np
+    import hierarchicalkarting_amd as hk
+    from hierarchicalkarting_amd import _lib
+    from hierarchicalkarting_amd.policy import Policy
+    g = hk.RacingEnv(hk.make_config(32, 4, low_mode=[_lib.HK_LOW_RL] * 4, rewards=1, max_episode_steps=100, jitter_seed=2))
+    g.reset()
+    g.attach_policy(Policy.random(g.obs_dim * 4, 128, 2, seed=1), [0, 1, 2, 3], 2)
+    g.rollout_begin(60)
+    g.step(120)
+    g.rollout_close()
+    v = g.rollout_views()
+    ro = g.rollout()
+    D = g.obs_dim
+    want = {"obs": (60, 32, 4, D), "logits": (60, 32, 4, 3), "done": (60, 32), "ring0": (32, 4, 3, D), "next_obs": (32, 4, D), "reward": (60, 32, 4)}
+    for k, t in v.items():
+        assert t.is_cuda, k
+        assert t.dtype == (torch.int32 if k in ("first", "branch", "done") else torch.float32), k
+        assert tuple(t.shape) == ro[k].shape, k
+        if k in want:
+            assert tuple(t.shape) == want[k], k
+        assert_bits_equal(t.cpu().numpy(), ro[k], k)
+    assert (ro["done"] != 0).any() and ro["obs"].any()
 
 
 def test_torch_views():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", SCRIPT], cwd=root, capture_output=True, text=True, timeout=600,
-                       env={**os.environ, "PYTHONPATH": root})
-    assert r.returncode == 0 and "ROLLOUT_VIEWS_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    assert_child(_child_rollout_views, timeout=600)
