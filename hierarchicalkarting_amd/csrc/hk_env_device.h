@@ -125,6 +125,12 @@ struct EnvParams {
     // the observation layout (env_observe_kernel), the OnActionReceived rewards and unit dividers (hk_env_reward.h), no plan at reset and the
     // bestStates copy of E2E:57-79 (hk_env_mcts.h).  0 on every handle without one.
     uint32_t e2e_mask;
+    // the forward ray's candidate lists (hk_env_params.h build_ray_lists), packed past tab_bytes in the same buffer and never staged to LDS: per
+    // (wall-grid cell, heading sector) every wall the ray can hit within RL_REACH, by ascending lower bound of the hit distance.  rl_sectors 0: none
+    // (sensor 0 not along the kart's forward), phase_assemble walks the grid samples
+    int rl_sectors;
+    float rl_scale;             // rl_sectors / 2 pi
+    int o_rloff, o_rlseg, o_rlbnd;
 };
 // ---- device buffers of the MCTS planner (hk_env_mcts.h) and of the reward shaping (hk_env_reward.h): the same for every GA
 struct MctsKartSnap { int section, lane, lane_changes, tire_age; int sec_time[HK_MCTS_SECTIME_RING]; };
@@ -180,6 +186,10 @@ constexpr float GRID_CELL = 2.0f;       // cell size (m)
 constexpr float GRID_REACH = 2.2f;      // list radius: the 2 m side rays, plus slack for float rounding of the cell index
 constexpr float NEAR_REACH = 1.3f;      // the near list: 1 m half-spacing of the long-ray samples / 1.11 m contact reach, plus slack.
                                         // On the racing line it is empty: a tick's wall-contact pass then costs two LDS reads.
+constexpr int RL_SECTORS = 16;          // heading sectors of the forward-ray lists (HK_RAY_SECTORS overrides it at hk_create, for measurements)
+constexpr float RL_REACH = 11.5f;       // the lists hold every hit up to this distance: the largest compared one, speed / 2 <= 11.25 m (hk_create)
+constexpr float RL_BOUND_UNIT = 0.05f;  // the lists' lower bounds of the hit distance, a byte each (12.75 m > RL_REACH)
+constexpr size_t RL_MAX_BYTES = 16u << 20;   // larger lists: the handle keeps the grid-sample walk
 
 // where a kernel reads the track tables from: the packed global buffer, or its per-block LDS copy
 struct TabView {
@@ -192,6 +202,11 @@ struct TabView {
     const uint2* tmask;           // [tgrid_nx * tgrid_nz] Trigger candidates per coarse cell (bit t = section t)
     const unsigned short* tmask2; // [grid_nx * grid_nz] the (at most two) Triggers a kart in this 2 m cell of the wall grid can overlap: section indices in the
                                   // low / high byte, 0xFF = none; 0xFEFE = more than two, use `tmask` (hk_env_params.h)
+    // forward-ray lists, always in global memory: [cell * rl_sectors + sector] -> entries [rl_off[i], rl_off[i + 1]) of an inline segment copy and
+    // a lower bound of its hit distance in RL_BOUND_UNIT steps
+    const unsigned* rl_off;
+    const hk_wall_seg* rl_seg;
+    const unsigned char* rl_bnd;
 };
 __host__ __device__ inline TabView tab_view(const EnvParams& P, const unsigned char* base)
 {
@@ -204,6 +219,9 @@ __host__ __device__ inline TabView tab_view(const EnvParams& P, const unsigned c
     T.cut = base + P.o_cut;
     T.tmask = reinterpret_cast<const uint2*>(base + P.o_tmask);
     T.tmask2 = reinterpret_cast<const unsigned short*>(base + P.o_tmask2);
+    T.rl_off = reinterpret_cast<const unsigned*>(P.tab + P.o_rloff);
+    T.rl_seg = reinterpret_cast<const hk_wall_seg*>(P.tab + P.o_rlseg);
+    T.rl_bnd = P.tab + P.o_rlbnd;
     return T;
 }
 // copy the packed tables into dynamic LDS (all threads of the block); TAB_LDS false: the launch passed no dynamic LDS (tables
@@ -339,6 +357,31 @@ __device__ __forceinline__ float ray_seg(float ox, float oz, float dx, float dz,
 {
     float tn, den;
     return ray_seg_hits(ox, oz, dx, dz, w, tn, den) ? tn / den : -1.0f;
+}
+
+// The forward ray (sensor 0, along the kart's forward: `heading` is its direction) through the list of the origin's cell and heading sector.
+// Returns the minimum of ray_seg over a prefix of the list: the walk stops once the next entry's lower bound is at least the minimum found (no later
+// wall can be hit closer), is beyond `hi` (nothing later changes a comparison with a distance <= hi), or once the minimum is <= `lo` (every
+// comparison with a distance >= lo is decided).  Whenever the minimum over all walls is <= hi and > lo, the result equals it bit for bit.
+__device__ __forceinline__ float ray_list_min(const EnvParams& P, const TabView& T, const float ox, const float oz, const float dx, const float dz,
+                                              const float heading, const float lo, const float hi)
+{
+    int s = (int)(heading * P.rl_scale);
+    s = s < P.rl_sectors - 1 ? s : P.rl_sectors - 1;
+    const int li = grid_cell(P, ox, oz) * P.rl_sectors + s;
+    const int w1 = (int)T.rl_off[li + 1];
+    float best = 3.0e38f;
+    // two entries per trip, their loads issued together (an odd list tests its last wall twice, which a minimum does not notice)
+    for (int w = (int)T.rl_off[li]; w < w1; w += 2) {
+        const int w2 = w + 1 < w1 ? w + 1 : w;
+        const float b = (float)T.rl_bnd[w] * RL_BOUND_UNIT;
+        const hk_wall_seg wa = T.rl_seg[w], wb = T.rl_seg[w2];
+        if (best <= b || b > hi || best <= lo) break;
+        const float ta = ray_seg(ox, oz, dx, dz, wa), tb = ray_seg(ox, oz, dx, dz, wb);
+        if (ta >= 0.0f && ta < best) best = ta;
+        if (tb >= 0.0f && tb < best) best = tb;
+    }
+    return best;
 }
 
 // ray vs another kart's capsule sliced at the ray height (stadium); origin inside -> no hit (Q10)

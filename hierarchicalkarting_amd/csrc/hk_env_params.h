@@ -29,6 +29,121 @@ inline double seg_seg_dist(double p1x, double p1z, double q1x, double q1z, doubl
     return std::min(std::min(pt_seg(p1x, p1z, p2x, p2z, q2x, q2z), pt_seg(q1x, q1z, p2x, p2z, q2x, q2z)),
                     std::min(pt_seg(p2x, p2z, p1x, p1z, q1x, q1z), pt_seg(q2x, q2z, p1x, p1z, q1x, q1z)));
 }
+
+// distance of the segment (a, b) from the convex polygon v[0..n) (counter-clockwise): 0 if they meet
+inline double seg_poly_dist(double ax, double az, double bx, double bz, const double* vx, const double* vz, int n)
+{
+    auto inside = [&](double px, double pz) {
+        for (int i = 0; i < n; i++) {
+            const int j = (i + 1) % n;
+            if ((vx[j] - vx[i]) * (pz - vz[i]) - (vz[j] - vz[i]) * (px - vx[i]) < 0.0) return false;
+        }
+        return true;
+    };
+    if (inside(ax, az) || inside(bx, bz)) return 0.0;
+    double d = 1e30;
+    for (int i = 0; i < n; i++) {
+        const int j = (i + 1) % n;
+        d = std::min(d, seg_seg_dist(ax, az, bx, bz, vx[i], vz[i], vx[j], vz[j]));
+    }
+    return d;
+}
+
+// the part of the segment (a, b) inside the convex polygon v[0..n) (counter-clockwise), as parameters [u0, u1] along it; false: none
+inline bool seg_poly_clip(double ax, double az, double bx, double bz, const double* vx, const double* vz, int n, double& u0, double& u1)
+{
+    u0 = 0.0; u1 = 1.0;
+    for (int i = 0; i < n; i++) {
+        const int j = (i + 1) % n;
+        const double ex = vx[j] - vx[i], ez = vz[j] - vz[i];
+        const double f0 = ex * (az - vz[i]) - ez * (ax - vx[i]);          // >= 0: inside this edge's half-plane
+        const double df = ex * (bz - az) - ez * (bx - ax);
+        if (df == 0.0) { if (f0 < 0.0) return false; continue; }
+        const double u = -f0 / df;
+        if (df > 0.0) u0 = std::max(u0, u); else u1 = std::min(u1, u);
+        if (u0 > u1) return false;
+    }
+    return true;
+}
+
+// convex hull (counter-clockwise, Andrew's monotone chain) of n points; returns the vertex count
+inline int convex_hull(std::vector<std::pair<double, double>> p, double* hx, double* hz)
+{
+    std::sort(p.begin(), p.end());
+    std::vector<std::pair<double, double>> h(2 * p.size());
+    auto cross = [](const std::pair<double, double>& o, const std::pair<double, double>& a, const std::pair<double, double>& b) {
+        return (a.first - o.first) * (b.second - o.second) - (a.second - o.second) * (b.first - o.first);
+    };
+    int k = 0;
+    for (size_t i = 0; i < p.size(); i++) {
+        while (k >= 2 && cross(h[k - 2], h[k - 1], p[i]) <= 0.0) k--;
+        h[k++] = p[i];
+    }
+    for (int i = (int)p.size() - 2, t = k + 1; i >= 0; i--) {
+        while (k >= t && cross(h[k - 2], h[k - 1], p[i]) <= 0.0) k--;
+        h[k++] = p[i];
+    }
+    for (int i = 0; i < k - 1; i++) { hx[i] = h[i].first; hz[i] = h[i].second; }
+    return k - 1;
+}
+
+// The forward ray's candidate lists (ray_list_min, hk_env_device.h).  For each cell of the wall grid and each of S heading sectors: every wall that
+// a ray from an origin in the cell, with a direction in the sector, meets within RL_REACH.  Conservative, in double: the cell grown by 5 cm (float
+// rounding of the cell index), the sector by 0.01 rad (rounding of the heading and of its sector index), the reach by 0.25 m, and the region those
+// rays sweep replaced by a convex superset, the cell plus the sector's wedge with its arc replaced by the two tangents at its ends.  Each entry is
+// a copy of the wall's segment and a lower bound of its hit distance: the distance from the grown cell to the part of the wall inside that
+// region, less 10 cm (float rounding of the hit distance), in RL_BOUND_UNIT steps rounded down.  Sorted by bound, then wall index.
+inline void build_ray_lists(const EnvParams& P, const std::vector<hk_wall_seg>& walls, const int S, std::vector<unsigned>& off,
+                            std::vector<hk_wall_seg>& seg, std::vector<unsigned char>& bnd)
+{
+    const double grow = 0.05, eps = 0.01, reach = (double)RL_REACH + 0.25, PI = 3.14159265358979323846;
+    const size_t ncell = (size_t)P.grid_nx * P.grid_nz;
+    off.assign(ncell * S + 1, 0u); seg.clear(); bnd.clear();
+    std::vector<double> qx((size_t)S * 4), qz((size_t)S * 4);     // the sectors' wedges about the origin: apex, arc ends, the tangents' crossing
+    for (int s = 0; s < S; s++) {
+        const double a = 2.0 * PI * s / S - eps, b = 2.0 * PI * (s + 1) / S + eps, m = 0.5 * (a + b), r = reach / std::cos(0.5 * (b - a));
+        qx[s * 4 + 0] = 0.0; qz[s * 4 + 0] = 0.0;
+        qx[s * 4 + 1] = reach * std::cos(a); qz[s * 4 + 1] = reach * std::sin(a);
+        qx[s * 4 + 2] = r * std::cos(m); qz[s * 4 + 2] = r * std::sin(m);
+        qx[s * 4 + 3] = reach * std::cos(b); qz[s * 4 + 3] = reach * std::sin(b);
+    }
+    std::vector<std::pair<unsigned, unsigned short>> ent;     // (bound, wall)
+    std::vector<int> near;
+    for (int iz = 0; iz < P.grid_nz; iz++)
+        for (int ix = 0; ix < P.grid_nx; ix++) {
+            const double cx0 = P.grid_x0 + ix * (double)GRID_CELL - grow, cz0 = P.grid_z0 + iz * (double)GRID_CELL - grow;
+            const double cx1 = cx0 + GRID_CELL + 2 * grow, cz1 = cz0 + GRID_CELL + 2 * grow;
+            const double rx[4] = {cx0, cx1, cx1, cx0}, rz[4] = {cz0, cz0, cz1, cz1};
+            near.clear();              // walls whose bounding box comes within the reach of the cell
+            for (size_t w = 0; w < walls.size(); w++) {
+                const hk_wall_seg& g = walls[w];
+                if (std::max(g.x0, g.x1) >= cx0 - reach - 1.0 && std::min(g.x0, g.x1) <= cx1 + reach + 1.0 &&
+                    std::max(g.z0, g.z1) >= cz0 - reach - 1.0 && std::min(g.z0, g.z1) <= cz1 + reach + 1.0) near.push_back((int)w);
+            }
+            for (int s = 0; s < S; s++) {
+                std::vector<std::pair<double, double>> pts;
+                for (int c = 0; c < 4; c++)
+                    for (int q = 0; q < 4; q++) pts.push_back({rx[c] + qx[s * 4 + q], rz[c] + qz[s * 4 + q]});
+                double hx[16], hz[16];
+                const int nh = convex_hull(pts, hx, hz);
+                ent.clear();
+                for (const int w : near) {
+                    const hk_wall_seg& g = walls[w];
+                    if (seg_poly_dist(g.x0, g.z0, g.x1, g.z1, hx, hz, nh) > 0.01) continue;
+                    double u0 = 0.0, u1 = 1.0;
+                    if (!seg_poly_clip(g.x0, g.z0, g.x1, g.z1, hx, hz, nh, u0, u1)) { u0 = 0.0; u1 = 1.0; }
+                    const double ax = g.x0 + u0 * (g.x1 - g.x0), az = g.z0 + u0 * (g.z1 - g.z0);
+                    const double bx = g.x0 + u1 * (g.x1 - g.x0), bz = g.z0 + u1 * (g.z1 - g.z0);
+                    const double d = seg_poly_dist(ax, az, bx, bz, rx, rz, 4) - 0.1;
+                    const double q = d <= 0.0 ? 0.0 : std::floor(d / (double)RL_BOUND_UNIT);
+                    ent.push_back({(unsigned)std::min(q, 255.0), (unsigned short)w});
+                }
+                std::sort(ent.begin(), ent.end());
+                for (const auto& e : ent) { seg.push_back(walls[e.second]); bnd.push_back((unsigned char)e.first); }
+                off[((size_t)iz * P.grid_nx + ix) * S + s + 1] = (unsigned)seg.size();
+            }
+        }
+}
 }  // namespace detail
 
 // Validates cfg, copies the track into sections / walls (cfg then points at the copies), fills P (every field but the device
@@ -353,6 +468,25 @@ inline int env_build_params(hk_config& cfg, std::vector<hk_section>& sections, s
         pk.resize((pk.size() + 15) & ~size_t(15));
         P.tab_bytes = (int)pk.size();
         P.tab_stage_bytes = P.tab_bytes;      // (env_create narrows it when the tight Trigger masks do not fit the LDS budget)
+        // the forward ray's lists, past tab_bytes: read from global memory by phase_assemble, never staged.  Only for a sensor 0 along the kart's
+        // forward (its direction is then the heading phase_assemble has); a track whose lists pass RL_MAX_BYTES keeps the grid-sample walk
+        const char* rs = std::getenv("HK_RAY_SECTORS");
+        const int S = rs ? std::atoi(rs) : RL_SECTORS;
+        P.rl_sectors = 0; P.rl_scale = 0.0f; P.o_rloff = P.o_rlseg = P.o_rlbnd = 0;
+        if (S > 0 && S <= 256 && P.sens_c[0] == 1.0f && P.sens_s[0] == 0.0f) {
+            std::vector<unsigned> roff;
+            std::vector<hk_wall_seg> rseg;
+            std::vector<unsigned char> rbnd;
+            detail::build_ray_lists(P, walls, S, roff, rseg, rbnd);
+            if (roff.size() * 4 + rseg.size() * 17 <= RL_MAX_BYTES) {
+                P.o_rloff = seg(roff.data(), roff.size() * sizeof(unsigned));
+                P.o_rlseg = seg(rseg.data(), rseg.size() * sizeof(hk_wall_seg));
+                P.o_rlbnd = seg(rbnd.data(), rbnd.size());
+                pk.resize((pk.size() + 15) & ~size_t(15));
+                P.rl_sectors = S;
+                P.rl_scale = (float)((double)S / (2.0 * 3.14159265358979323846));
+            }
+        }
     }
     return HK_OK;
 }

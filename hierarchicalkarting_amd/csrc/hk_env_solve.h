@@ -539,6 +539,7 @@ __device__ HK_ASM_ATTR int phase_assemble(const EnvParams& P, const TabView& T, 
         const float ox = k.px + SENSOR_LZ * k.fx, oz = k.pz + SENSOR_LZ * k.fz;
         HK_ST(h, 14);
 #ifndef HK_DUMMY_NO_RAYS          /* (timing / counter experiments only: tools/build_variant.py) */
+#ifndef HK_DUMMY_NO_FWD_RAY
         {
             float d0x, d0z;
             sensor_dir(P, 0, k.fx, k.fz, d0x, d0z);
@@ -547,7 +548,10 @@ __device__ HK_ASM_ATTR int phase_assemble(const EnvParams& P, const TabView& T, 
             // the largest distance this kart's ray is ever compared with (assemble_player: speed / 2, 8 m on a straight, 5 m in a curve):
             // samples up to 2 (ns - 1) >= thr - 1.25 cover every hit that can decide a comparison
             const float thr = f_max(k.speed * 0.5f, k.straight ? 8.0f : 5.0f);
-            int ns = 1 + (int)ceilf((thr - 1.25f) * 0.5f);
+            // with the (cell, heading sector) lists: one walk, stopped once both comparisons are decided (hk_env_device.h ray_list_min).  The
+            // value differs from the oracle's only where neither comparison can tell
+            if (P.rl_sectors) best = ray_list_min(P, T, ox, oz, d0x, d0z, k.heading, f_min(k.speed * 0.5f, k.straight ? 8.0f : 5.0f), thr);
+            int ns = P.rl_sectors ? 0 : 1 + (int)ceilf((thr - 1.25f) * 0.5f);
             ns = ns > 6 ? 6 : ns;
 #pragma unroll 1
             for (int sm = 0; sm < ns; sm++) {
@@ -572,6 +576,7 @@ __device__ HK_ASM_ATTR int phase_assemble(const EnvParams& P, const TabView& T, 
             }
             k.ray[0] = best;
         }
+#endif
         HK_ST(h, 15);
         {
             const int ssel[4] = {2, 4, 8, 6};
@@ -589,7 +594,9 @@ __device__ HK_ASM_ATTR int phase_assemble(const EnvParams& P, const TabView& T, 
             // (1 - 2 cm margin >> float rounding).  In one pass — test, then the rays behind an `if` — the wave ran the four ray tests for nearly every
             // listed wall, because with 64 lanes in as many places SOME lane's wall passes on almost every trip; now it runs them as often as the lane with
             // the most walls in reach needs (a minimum does not depend on the order, and the order is the list's anyway).
-            for (int base = w0; base < w1; base += 32) {
+            // A lane leaves once `side` (assemble_player) holds: a smaller value cannot change it, and no other comparison reads these four rays.
+            bool decided = false;
+            for (int base = w0; base < w1 && !decided; base += 32) {
                 const int nq = (w1 - base) < 32 ? (w1 - base) : 32;
                 uint32_t cand = 0;
                 for (int q = 0; q < nq; q += 4) {
@@ -607,7 +614,7 @@ __device__ HK_ASM_ATTR int phase_assemble(const EnvParams& P, const TabView& T, 
                         cand |= ((apart || (q + j) >= nq) ? 0u : 1u) << (q + j);
                     }
                 }
-                while (cand) {
+                while (cand && !decided) {
                     const int q = __ffs((int)cand) - 1;
                     cand &= cand - 1u;
                     HK_LP(8);
@@ -617,6 +624,7 @@ __device__ HK_ASM_ATTR int phase_assemble(const EnvParams& P, const TabView& T, 
                         const float t = ray_seg(ox, oz, ddx[r4], ddz[r4], ws);
                         if (t >= 0.0f && t < best[r4]) best[r4] = t;
                     }
+                    decided = (best[0] <= 2.0f) || (best[1] <= 1.5f) || (best[2] <= 1.5f) || (best[3] <= 2.0f);
                 }
             }
 #pragma unroll
