@@ -9,7 +9,7 @@ LIB_PATH = os.environ.get("HK_LIB_PATH") or os.path.join(_HERE, "libhk.so")   # 
 HK_MAX_AGENTS = 8
 HK_MAX_SECTIONS = 64
 HK_NUM_SENSORS = 9
-HK_ABI_VERSION = 5
+HK_ABI_VERSION = 6
 HK_PROF_STAGES = 6
 HK_METER_PARTS = 4
 PROF_STAGE_NAMES = ("env_run_kernel", "lqn_kernel<2,3,4>", "lq_batch_kernel", "policy_mlp_kernel", "observe+stack", "env_b1_kernel")
@@ -29,6 +29,11 @@ RO_FIELDS = {n: (i, dt) for i, (n, dt) in enumerate([
     ("logp_cont", "<f4"), ("logp_disc", "<f4"), ("reward", "<f4"), ("group_reward", "<f4"), ("term_reward", "<f4"),
     ("term_group_reward", "<f4"), ("done", "<i4"), ("ring0", "<f4"), ("next_obs", "<f4")])}
 HK_RO_FIELDS = len(RO_FIELDS)
+# PPO trainer (hk_ppo_field): name -> index;  stats of hk_ppo_minibatch / hk_ppo_update
+PPO_FIELDS = {n: i for i, n in enumerate(("params", "grad", "adam_m", "adam_v", "v_old", "adv", "ret", "mb_mu", "mb_logits", "mb_value", "perm"))}
+HK_PPO_FIELDS = len(PPO_FIELDS)
+HK_PPO_STATS = 6
+PPO_STAT_NAMES = ("L_pi", "L_v", "entropy", "approx_kl", "clip_fraction", "skipped")
 HK_F_ACCEL, HK_F_BRAKE, HK_F_ACTIVE, HK_F_FORWARD_COLLISION, HK_F_HAS_COLLISION, HK_F_CAN_MOVE, HK_F_ENABLED = (1 << i for i in range(7))
 
 
@@ -162,6 +167,11 @@ class PolicyDesc(C.Structure):
                 ("W_mu", _fp), ("b_mu", _fp), ("log_sigma", _fp), ("W_branch", _fp), ("b_branch", _fp)]
 
 
+class PpoConfig(C.Structure):
+    _fields_ = [("gamma", C.c_float), ("lambd", C.c_float), ("normalize_advantages", C.c_int32), ("adam_beta1", C.c_float),
+                ("adam_beta2", C.c_float), ("adam_eps", C.c_float), ("seed", C.c_uint32)]
+
+
 SYMBOLS = {
     "hk_create": (C.c_int, [C.POINTER(Config), C.POINTER(_H)]),
     "hk_destroy": (None, [_H]),
@@ -202,6 +212,14 @@ SYMBOLS = {
     "hk_rollout_rows": (C.c_int, [_H]),
     "hk_rollout_close": (C.c_int, [_H]),
     "hk_rollout_ptr": (C.c_void_p, [_H, C.c_int]),
+    "hk_ppo_create": (C.c_int, [_H, C.c_int, C.POINTER(PolicyDesc), C.POINTER(PpoConfig)]),
+    "hk_ppo_advantages": (C.c_int, [_H, C.c_int]),
+    "hk_ppo_minibatch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, _fp]),
+    "hk_ppo_adam": (C.c_int, [_H, C.c_int, C.c_float]),
+    "hk_ppo_update": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _fp]),
+    "hk_ppo_publish": (C.c_int, [_H, C.c_int]),
+    "hk_ppo_ptr": (C.c_void_p, [_H, C.c_int, C.c_int]),
+    "hk_ppo_count": (C.c_int, [_H, C.c_int, C.c_int]),
     "hk_comm_unique_id": (C.c_int, [C.c_void_p]),
     "hk_comm_init": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
     "hk_gather_results": (C.c_int, [_H, C.POINTER(EpisodeResult)]),

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -14,6 +15,7 @@
 #include "hk_env_kernels.h"
 #include "hk_policy.h"
 #include "hk_rollout.h"
+#include "hk_ppo.h"
 #include <dlfcn.h>
 
 namespace hk {
@@ -187,6 +189,8 @@ struct hk_context {
     struct Rollout {
         bool open = false;
         int R = 0;                     // rows of the current / last rollout (0: none yet)
+        int gen = 0;                   // hk_rollout_begin count (a PPO trainer's advantages belong to one rollout)
+        int npol = 0;                  // actors attached when it began (the ones it has rows of)
         int started = 0, rows = 0;     // decisions taken / intervals completed since begin
         int obs_dim = 0, nbm = 0, smax = 1;
         uint32_t driven = 0;           // agent slots an actor drives
@@ -197,6 +201,25 @@ struct hk_context {
         // row t of a [R][E][A][k] field
         template <typename T> T* row(int f, int t, size_t ea, int k = 1) const { return at<T>(f) + (size_t)t * ea * k; }
     } ro;
+    // PPO trainers (hk_ppo_*; hk_ppo.h): a master copy of the actor + critic parameters, Adam moments, the rollout's per-row values, and a
+    // workspace sized by the largest minibatch seen
+    struct Ppo {
+        int policy = -1;
+        hk::PpoNet actor, critic;
+        hk_ppo_config cfg{};
+        float* param = nullptr;        // [4][P]: PARAMS, GRAD, ADAM_M, ADAM_V
+        size_t P = 0;
+        int adam_steps = 0, epochs_done = 0;
+        int adv_gen = -1, n = 0;       // the rollout hk_ppo_advantages ran on; its rows
+        bool perm_valid = false;       // an hk_ppo_update has written PERM for the current rows
+        float* rowbuf = nullptr;       // V_OLD, ADV, RET [n], V_BOOT [E S], PERM (int) [n]
+        size_t rowbuf_n = 0;
+        void* ws = nullptr;            // minibatch workspace (ppo_workspace)
+        size_t ws_bytes = 0;
+        int cap = 0, last_m = 0;
+        float* mb_mu = nullptr; float* mb_logits = nullptr; float* mb_v = nullptr;
+    } ppo[HK_MAX_POLICIES];
+    int n_ppo = 0;
     // RCCL communicator for hk_gather_results (librccl.so loaded lazily)
     void* comm = nullptr;
     int comm_world = 0, comm_rank = 0;
@@ -365,6 +388,7 @@ void hk_destroy(hk_handle h)
     if (h->pol_scratch) (void)hipFree(h->pol_scratch);
     if (h->ro.buf) (void)hipFree(h->ro.buf);
     for (int p = 0; p < HK_MAX_POLICIES; p++) hk::policy_free(h->policy[p]);
+    for (auto& t : h->ppo) { if (t.param) (void)hipFree(t.param); if (t.rowbuf) (void)hipFree(t.rowbuf); if (t.ws) (void)hipFree(t.ws); }
     h->prof.fold();
     for (hipEvent_t e : h->prof.pool) (void)hipEventDestroy(e);
     for (hipStream_t q : h->qstream) if (q) { (void)hipStreamSynchronize(q); (void)hipStreamDestroy(q); }
@@ -1270,6 +1294,7 @@ int hk_rollout_begin(hk_handle h, int rows)
     }
     std::memcpy(ro.off, off, sizeof(off));
     ro.R = rows; ro.started = 0; ro.rows = 0; ro.obs_dim = D; ro.nbm = nbm; ro.smax = smax; ro.driven = driven;
+    ro.gen += 1; ro.npol = h->n_policies;
     HK_HIP(h, hipMemsetAsync(ro.buf, 0, total, h->stream));
     const unsigned long long decision = (unsigned long long)(h->academy_step / h->decision_period);
     for (int p = 0; p < h->n_policies; p++) {
@@ -1315,6 +1340,391 @@ void* hk_rollout_ptr(hk_handle h, int field)
     if (field < 0 || field >= HK_RO_FIELDS) { fail(h, HK_ERR_INVALID, "hk_rollout_ptr: bad field"); return nullptr; }
     if (!h->ro.buf || h->ro.R == 0) { fail(h, HK_ERR_INVALID, "hk_rollout_ptr: no rollout yet (hk_rollout_begin)"); return nullptr; }
     return h->ro.at<void>(field);
+}
+
+// ------------------------------------------------------------------ PPO trainer (hk.h; device side in hk_ppo.h)
+extern "C++" {
+namespace {
+
+// the minibatch workspace of a trainer at capacity M rows: pointers into one allocation (ppo_workspace)
+struct PpoWs {
+    int* ids; int* valid; int* n_valid;
+    float* X0;
+    float* Za[HK_POLICY_MAX_LAYERS]; float* Aa[HK_POLICY_MAX_LAYERS];
+    float* Zc[HK_POLICY_MAX_LAYERS]; float* Ac[HK_POLICY_MAX_LAYERS];
+    float *d0, *d1, *dhead, *dls, *dv, *part, *stats;
+    double *rowstat, *acc;
+    float *mb_mu, *mb_logits, *mb_v;
+};
+
+size_t ppo_ws_layout(const hk_context::Ppo& t, int M, PpoWs* w)
+{
+    size_t off = 0;
+    char* base = w ? (char*)t.ws : nullptr;
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
+    const size_t Mz = (size_t)M;
+    const int Ha = t.actor.hidden, Hc = t.critic.hidden, Hm = std::max(Ha, Hc), in = t.actor.in_dim, nb = t.actor.n_branch;
+    size_t mn = (size_t)(1 + nb) * Ha;                          // the largest weight gradient: a layer's H x K, or the heads'
+    mn = std::max(mn, (size_t)Ha * std::max(in, Ha));
+    mn = std::max(mn, (size_t)Hc * std::max(in, Hc));
+    const size_t nz = (Mz + hk::PPO_KCH - 1) / hk::PPO_KCH;
+    PpoWs d{};
+    d.ids = (int*)take(Mz * 4); d.valid = (int*)take(Mz * 4); d.n_valid = (int*)take(16);
+    d.X0 = (float*)take(Mz * in * 4);
+    for (int l = 0; l < t.actor.n_layers; l++) { d.Za[l] = (float*)take(Mz * Ha * 4); d.Aa[l] = (float*)take(Mz * Ha * 4); }
+    for (int l = 0; l < t.critic.n_layers; l++) { d.Zc[l] = (float*)take(Mz * Hc * 4); d.Ac[l] = (float*)take(Mz * Hc * 4); }
+    d.d0 = (float*)take(Mz * Hm * 4); d.d1 = (float*)take(Mz * Hm * 4);
+    d.dhead = (float*)take(Mz * hk::PM_MAX_OUT * 4); d.dls = (float*)take(Mz * 4); d.dv = (float*)take(Mz * 4);
+    d.part = (float*)take(nz * mn * 4);
+    d.stats = (float*)take(8 * 4);
+    d.rowstat = (double*)take(Mz * 6 * 8); d.acc = (double*)take(8 * 8);
+    d.mb_mu = (float*)take(Mz * 4); d.mb_logits = (float*)take(Mz * nb * 4); d.mb_v = (float*)take(Mz * 4);
+    if (w) *w = d;
+    return off;
+}
+
+int ppo_ensure_ws(hk_handle h, hk_context::Ppo& t, int M, PpoWs& w)
+{
+    if (M > t.cap) {
+        const size_t bytes = ppo_ws_layout(t, M, nullptr);
+        if (t.ws) HK_HIP(h, hipFree(t.ws));
+        t.ws = nullptr; t.cap = 0; t.ws_bytes = 0; t.last_m = 0;
+        HK_HIP(h, hipMalloc(&t.ws, bytes));
+        t.cap = M; t.ws_bytes = bytes;
+    }
+    ppo_ws_layout(t, t.cap, &w);
+    return HK_OK;
+}
+
+hk::PpoRows ppo_rows(hk_handle h, const hk_context::Ppo& t)
+{
+    const auto& ro = h->ro;
+    const hk::PolicyParams& q = h->policy[t.policy].q;
+    hk::PpoRows P{};
+    P.obs = ro.at<float>(HK_RO_OBS); P.ring0 = ro.at<float>(HK_RO_RING0); P.next_obs = ro.at<float>(HK_RO_NEXT_OBS);
+    P.raw = ro.at<float>(HK_RO_RAW); P.reward = ro.at<float>(HK_RO_REWARD); P.term_reward = ro.at<float>(HK_RO_TERM_REWARD);
+    P.logp_c = ro.at<float>(HK_RO_LOGP_CONT); P.logp_d = ro.at<float>(HK_RO_LOGP_DISC);
+    P.first = ro.at<int>(HK_RO_FIRST); P.branch = ro.at<int>(HK_RO_BRANCH); P.done = ro.at<int>(HK_RO_DONE);
+    P.mean = q.mean; P.std = q.std;
+    P.R = ro.rows; P.E = h->cfg.num_envs;        // the completed rows: a rollout may close before all R rows of hk_rollout_begin
+    P.A = h->cfg.num_agents; P.S = q.n_slots; P.D = ro.obs_dim; P.stack = q.stack; P.smax = ro.smax;
+    P.in_dim = q.in_dim; P.normalize = q.normalize;
+    for (int j = 0; j < HK_MAX_AGENTS; j++) P.slots[j] = q.slots[j];
+    return P;
+}
+
+inline unsigned nblk(size_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
+
+template <int EPI>
+void ppo_gemm(hipStream_t s, int M, int N, int K, const float* A, int sai, int sak, const float* B, int sbk, int sbj, const float* bias, float* C, int ldc,
+              float* Z, int kch)
+{
+    const int nz = (K + kch - 1) / kch;
+    const dim3 grid(nblk(N, hk::PPO_TN), nblk(M, hk::PPO_TM), nz < 1 ? 1 : nz);
+    hipLaunchKernelGGL(hk::ppo_gemm_kernel<EPI>, grid, dim3(256), 0, s, M, N, K, A, sai, sak, B, sbk, sbj, bias, C, ldc, Z, kch);
+}
+
+// a weight gradient dst = sum over rows of D(i, o) X(i, c): split into chunks of PPO_KCH rows, partial tiles combined in chunk order
+void ppo_wgrad(hipStream_t s, const PpoWs& w, int M, int N, int m, const float* D, int sdi, int sdo, const float* X, int ldx, float* out0, float* out1)
+{
+    const int nz = (m + hk::PPO_KCH - 1) / hk::PPO_KCH;
+    ppo_gemm<0>(s, M, N, m, D, sdo, sdi, X, ldx, 1, nullptr, w.part, N, nullptr, hk::PPO_KCH);
+    hipLaunchKernelGGL(hk::ppo_combine_kernel, dim3(nblk((size_t)M * N)), dim3(256), 0, s, w.part, nz, M, N, out0, out1);
+}
+
+void ppo_colsum(hipStream_t s, const float* X, int m, int ld, int ncol, float* out)
+{
+    hipLaunchKernelGGL(hk::ppo_colsum_kernel<float>, dim3(ncol), dim3(256), 0, s, X, m, ld, out);
+}
+
+// trunk forward on X0: Z[l] = W_l a_{l-1} + b_l (MFMA, k ascending), A[l] = swish(Z[l])
+void ppo_trunk_forward(hipStream_t s, const hk::PpoNet& net, const float* prm, const float* X0, int m, float* const* Z, float* const* A)
+{
+    const int H = net.hidden;
+    for (int l = 0; l < net.n_layers; l++) {
+        const int K = l == 0 ? net.in_dim : H;
+        ppo_gemm<1>(s, m, H, K, l == 0 ? X0 : A[l - 1], K, 1, prm + net.oW[l], 1, K, prm + net.ob[l], A[l], H, Z[l], K);
+    }
+}
+
+// trunk backward from dcur = dL / dZ[L - 1]: weight and bias gradients into grad, delta through W_l * swish'
+void ppo_trunk_backward(hipStream_t s, const PpoWs& w, const hk::PpoNet& net, const float* prm, float* grad, const float* X0, int m, float* const* Z,
+                        float* const* A, float* dcur, float* dnext)
+{
+    const int H = net.hidden;
+    for (int l = net.n_layers - 1; l >= 0; l--) {
+        const int K = l == 0 ? net.in_dim : H;
+        ppo_wgrad(s, w, H, K, m, dcur, H, 1, l == 0 ? X0 : A[l - 1], K, grad + net.oW[l], nullptr);
+        ppo_colsum(s, dcur, m, H, H, grad + net.ob[l]);
+        if (l > 0) {
+            ppo_gemm<2>(s, m, H, H, dcur, H, 1, prm + net.oW[l], H, 1, nullptr, dnext, H, Z[l - 1], H);
+            std::swap(dcur, dnext);
+        }
+    }
+}
+
+// one minibatch: loss, stats, gradient into GRAD (acc: the update's stats accumulator, or nullptr)
+int ppo_mb(hk_handle h, hk_context::Ppo& t, const int32_t* ids, int m, float eps, float beta, bool acc)
+{
+    PpoWs w;
+    int rc = ppo_ensure_ws(h, t, m, w);
+    if (rc) return rc;
+    hipStream_t s = h->stream;
+    const hk::PpoRows P = ppo_rows(h, t);
+    const float* prm = t.param;
+    float* grad = t.param + t.P;
+    hipLaunchKernelGGL(hk::ppo_gather_kernel, dim3(nblk((size_t)m * P.in_dim)), dim3(256), 0, s, P, ids, m, 0, w.X0, w.valid);
+    hipLaunchKernelGGL(hk::ppo_count_kernel, dim3(1), dim3(256), 0, s, w.valid, m, w.n_valid);
+    ppo_trunk_forward(s, t.actor, prm, w.X0, m, w.Za, w.Aa);
+    ppo_trunk_forward(s, t.critic, prm, w.X0, m, w.Zc, w.Ac);
+    const hk::PpoNet &na = t.actor, &nc = t.critic;
+    hk::PpoLossArgs L{};
+    L.Aa = w.Aa[na.n_layers - 1]; L.Ac = w.Ac[nc.n_layers - 1];
+    L.W_mu = prm + na.oWmu; L.b_mu = prm + na.obmu; L.log_sigma = prm + na.ols; L.W_br = prm + na.oWbr; L.b_br = prm + na.obbr;
+    L.W_v = prm + nc.oWmu; L.b_v = prm + nc.obmu;
+    L.v_old = t.rowbuf; L.adv = t.rowbuf + t.n; L.ret = t.rowbuf + 2 * (size_t)t.n;
+    L.ids = ids; L.valid = w.valid; L.n_valid = w.n_valid; L.m = m; L.n = t.n; L.Ha = na.hidden; L.Hc = nc.hidden; L.nb = na.n_branch;
+    L.eps = eps; L.beta = beta;
+    L.dhead = w.dhead; L.dls = w.dls; L.dv = w.dv; L.rowstat = w.rowstat;
+    L.mu_out = w.mb_mu; L.logit_out = w.mb_logits; L.v_out = w.mb_v;
+    hipLaunchKernelGGL(hk::ppo_loss_kernel, dim3(nblk(m)), dim3(256), 0, s, P, L);
+    hipLaunchKernelGGL(hk::ppo_stats_kernel, dim3(1), dim3(256), 0, s, w.rowstat, m, w.stats, acc ? w.acc : nullptr);
+    // actor: the heads (vector ALU), then the trunk
+    const int Ha = na.hidden, Hc = nc.hidden, nb = na.n_branch;
+    hipLaunchKernelGGL(hk::ppo_head_back_kernel, dim3(nblk((size_t)m * Ha)), dim3(256), 0, s, m, Ha, 1 + nb, w.dhead, hk::PM_MAX_OUT, prm + na.oWmu,
+                       prm + na.oWbr, w.Za[na.n_layers - 1], w.d0);
+    ppo_wgrad(s, w, 1 + nb, Ha, m, w.dhead, hk::PM_MAX_OUT, 1, w.Aa[na.n_layers - 1], Ha, grad + na.oWmu, grad + na.oWbr);
+    ppo_colsum(s, w.dhead, m, hk::PM_MAX_OUT, 1, grad + na.obmu);
+    ppo_colsum(s, w.dhead + 1, m, hk::PM_MAX_OUT, nb, grad + na.obbr);
+    ppo_colsum(s, w.dls, m, 1, 1, grad + na.ols);
+    ppo_trunk_backward(s, w, na, prm, grad, w.X0, m, w.Za, w.Aa, w.d0, w.d1);
+    // critic
+    hipLaunchKernelGGL(hk::ppo_head_back_kernel, dim3(nblk((size_t)m * Hc)), dim3(256), 0, s, m, Hc, 1, w.dv, 1, prm + nc.oWmu, nullptr,
+                       w.Zc[nc.n_layers - 1], w.d0);
+    ppo_wgrad(s, w, 1, Hc, m, w.dv, 1, 1, w.Ac[nc.n_layers - 1], Hc, grad + nc.oWmu, nullptr);
+    ppo_colsum(s, w.dv, m, 1, 1, grad + nc.obmu);
+    ppo_trunk_backward(s, w, nc, prm, grad, w.X0, m, w.Zc, w.Ac, w.d0, w.d1);
+    HK_HIP(h, hipGetLastError());
+    t.last_m = m;
+    return HK_OK;
+}
+
+int ppo_adam_step(hk_handle h, hk_context::Ppo& t, float lr)
+{
+    t.adam_steps += 1;
+    const float b1 = t.cfg.adam_beta1, b2 = t.cfg.adam_beta2;
+    const float omb1 = (float)(1.0 - (double)b1), omb2 = (float)(1.0 - (double)b2);
+    const float c1 = (float)(1.0 - std::pow((double)b1, t.adam_steps)), c2 = (float)(1.0 - std::pow((double)b2, t.adam_steps));
+    float* p = t.param;
+    hipLaunchKernelGGL(hk::ppo_adam_kernel, dim3(nblk(t.P)), dim3(256), 0, h->stream, p, p + t.P, p + 2 * t.P, p + 3 * t.P, t.P, b1, omb1, b2, omb2, c1, c2,
+                       t.cfg.adam_eps, lr);
+    HK_HIP(h, hipGetLastError());
+    return HK_OK;
+}
+
+int ppo_check(hk_handle h, int trainer, const char* fn, bool need_adv)
+{
+    if (trainer < 0 || trainer >= h->n_ppo) return fail(h, HK_ERR_INVALID, std::string(fn) + ": bad trainer index");
+    const auto& t = h->ppo[trainer];
+    if (!need_adv) return HK_OK;
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, std::string(fn) + ": refused while a rollout is open (hk_rollout_close first)");
+    if (t.adv_gen != h->ro.gen) return fail(h, HK_ERR_INVALID, std::string(fn) + ": hk_ppo_advantages has not run on the current rollout");
+    return HK_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int hk_ppo_create(hk_handle h, int policy, const hk_policy_desc* c, const hk_ppo_config* cfg)
+{
+    HK_NEED_ENV(h);
+    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, "hk_ppo_create: bad policy index");
+    if (h->n_ppo >= HK_MAX_POLICIES) return fail(h, HK_ERR_INVALID, "hk_ppo_create: HK_MAX_POLICIES trainers already exist");
+    const hk::PolicyParams& q = h->policy[policy].q;
+    if (!c) return fail(h, HK_ERR_INVALID, "hk_ppo_create: NULL critic");
+    if (c->in_dim != q.in_dim) return fail(h, HK_ERR_INVALID, "hk_ppo_create: the critic's in_dim differs from the actor's");
+    if (c->hidden < 32 || c->hidden > HK_POLICY_MAX_HIDDEN || c->hidden % 32 || c->n_layers < 1 || c->n_layers > HK_POLICY_MAX_LAYERS || c->n_branch != 0)
+        return fail(h, HK_ERR_INVALID, "hk_ppo_create: critic hidden / n_layers out of the actor's limits, or n_branch != 0");
+    for (int l = 0; l < c->n_layers; l++) if (!c->W[l] || !c->b[l]) return fail(h, HK_ERR_INVALID, "hk_ppo_create: NULL critic layer weights");
+    if (!c->W_mu || !c->b_mu) return fail(h, HK_ERR_INVALID, "hk_ppo_create: NULL critic value head");
+    hk_ppo_config d{0.99f, 0.95f, 1, 0.9f, 0.999f, 1e-8f, 0u};
+    if (cfg) d = *cfg;
+    if (!(d.adam_beta1 >= 0.0f && d.adam_beta1 < 1.0f && d.adam_beta2 >= 0.0f && d.adam_beta2 < 1.0f && d.adam_eps > 0.0f))
+        return fail(h, HK_ERR_INVALID, "hk_ppo_create: Adam constants out of range");
+    auto& t = h->ppo[h->n_ppo];
+    t = hk_context::Ppo{};
+    t.policy = policy; t.cfg = d;
+    t.actor.layout(q.in_dim, q.hidden, q.n_layers, q.n_branch, 0);
+    t.critic.layout(q.in_dim, c->hidden, c->n_layers, 0, t.actor.count);
+    t.P = t.actor.count + t.critic.count;
+    std::vector<float> host(t.critic.count);
+    for (int l = 0; l < c->n_layers; l++) {
+        const size_t nw = (size_t)c->hidden * (l == 0 ? c->in_dim : c->hidden);
+        std::memcpy(&host[t.critic.oW[l] - t.actor.count], c->W[l], nw * 4);
+        std::memcpy(&host[t.critic.ob[l] - t.actor.count], c->b[l], (size_t)c->hidden * 4);
+    }
+    std::memcpy(&host[t.critic.oWmu - t.actor.count], c->W_mu, (size_t)c->hidden * 4);
+    host[t.critic.obmu - t.actor.count] = c->b_mu[0];
+    hipError_t e = hipMalloc(&t.param, 4 * t.P * sizeof(float));
+    if (e == hipSuccess) e = hipMemsetAsync(t.param, 0, 4 * t.P * sizeof(float), h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t.param + t.actor.count, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(hk::ppo_publish_kernel<false>, dim3(nblk(t.actor.count)), dim3(256), 0, h->stream, q, t.actor, t.param);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {          // (the slot is not taken: free what was allocated)
+        if (t.param) (void)hipFree(t.param);
+        t = hk_context::Ppo{};
+        return fail(h, HK_ERR_HIP, std::string("hk_ppo_create: ") + hipGetErrorString(e));
+    }
+    return h->n_ppo++;
+}
+
+int hk_ppo_advantages(hk_handle h, int trainer)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_check(h, trainer, "hk_ppo_advantages", false);
+    if (rc) return rc;
+    auto& t = h->ppo[trainer];
+    const auto& ro = h->ro;
+    if (ro.open) return fail(h, HK_ERR_INVALID, "hk_ppo_advantages: refused while a rollout is open (hk_rollout_close first)");
+    if (ro.R == 0 || !ro.buf) return fail(h, HK_ERR_INVALID, "hk_ppo_advantages: no rollout yet (hk_rollout_begin ... hk_rollout_close)");
+    if (ro.rows < 1) return fail(h, HK_ERR_INVALID, "hk_ppo_advantages: the rollout closed with no completed row");
+    if (t.policy >= ro.npol) return fail(h, HK_ERR_INVALID, "hk_ppo_advantages: the rollout began before the trainer's actor was attached");
+    const hk::PpoRows P = ppo_rows(h, t);
+    const int n = P.R * P.E * P.S, nbt = P.E * P.S;
+    const size_t need = 3 * (size_t)n + nbt + n;
+    if (need > t.rowbuf_n) {
+        if (t.rowbuf) HK_HIP(h, hipFree(t.rowbuf));
+        t.rowbuf = nullptr; t.rowbuf_n = 0;
+        HK_HIP(h, hipMalloc(&t.rowbuf, need * sizeof(float)));
+        t.rowbuf_n = need;
+    }
+    t.n = n;
+    float *v_old = t.rowbuf, *adv = v_old + n, *ret = adv + n, *vb = ret + n;
+    PpoWs w;
+    const int chunk = std::max(t.cap, std::min(n + nbt, 16384));
+    if ((rc = ppo_ensure_ws(h, t, chunk, w))) return rc;
+    hipStream_t s = h->stream;
+    const hk::PpoNet& nc = t.critic;
+    for (int base = 0; base < n + nbt; base += chunk) {
+        const int m = std::min(chunk, n + nbt - base);
+        hipLaunchKernelGGL(hk::ppo_iota_kernel, dim3(nblk(m)), dim3(256), 0, s, w.ids, base, m);
+        hipLaunchKernelGGL(hk::ppo_gather_kernel, dim3(nblk((size_t)m * P.in_dim)), dim3(256), 0, s, P, w.ids, m, 1, w.X0, w.valid);
+        ppo_trunk_forward(s, nc, t.param, w.X0, m, w.Zc, w.Ac);
+        hipLaunchKernelGGL(hk::ppo_value_kernel, dim3(nblk(m)), dim3(256), 0, s, w.Ac[nc.n_layers - 1], m, nc.hidden, t.param + nc.oWmu, t.param + nc.obmu,
+                           w.ids, n, nbt, v_old, vb);
+    }
+    hipLaunchKernelGGL(hk::ppo_gae_kernel, dim3(nblk(nbt)), dim3(256), 0, s, P, v_old, vb, t.cfg.gamma, t.cfg.lambd, adv, ret);
+    if (t.cfg.normalize_advantages) hipLaunchKernelGGL(hk::ppo_adv_norm_kernel, dim3(1), dim3(1024), 0, s, adv, n);
+    HK_HIP(h, hipGetLastError());
+    t.adv_gen = ro.gen;
+    t.perm_valid = false;
+    return HK_OK;
+}
+
+int hk_ppo_minibatch(hk_handle h, int trainer, const int32_t* rows_dev, int m, float eps, float beta, float* stats)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_check(h, trainer, "hk_ppo_minibatch", true);
+    if (rc) return rc;
+    if (!rows_dev || m < 1) return fail(h, HK_ERR_INVALID, "hk_ppo_minibatch: NULL rows or m < 1");
+    auto& t = h->ppo[trainer];
+    if ((rc = ppo_mb(h, t, rows_dev, m, eps, beta, false))) return rc;
+    if (stats) {
+        PpoWs w;
+        ppo_ws_layout(t, t.cap, &w);
+        HK_HIP(h, hipMemcpyAsync(stats, w.stats, HK_PPO_STATS * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HK_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return HK_OK;
+}
+
+int hk_ppo_adam(hk_handle h, int trainer, float lr)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_check(h, trainer, "hk_ppo_adam", false);
+    if (rc) return rc;
+    return ppo_adam_step(h, h->ppo[trainer], lr);
+}
+
+int hk_ppo_publish(hk_handle h, int trainer)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_check(h, trainer, "hk_ppo_publish", false);
+    if (rc) return rc;
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_ppo_publish: refused while a rollout is open (hk_rollout_close first)");
+    auto& t = h->ppo[trainer];
+    hipLaunchKernelGGL(hk::ppo_publish_kernel<true>, dim3(nblk(t.actor.count)), dim3(256), 0, h->stream, h->policy[t.policy].q, t.actor, t.param);
+    HK_HIP(h, hipGetLastError());
+    return HK_OK;
+}
+
+int hk_ppo_update(hk_handle h, int trainer, int epochs, int minibatch, float lr, float eps, float beta, float* stats)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_check(h, trainer, "hk_ppo_update", true);
+    if (rc) return rc;
+    if (epochs < 1 || minibatch < 1) return fail(h, HK_ERR_INVALID, "hk_ppo_update: epochs < 1 or minibatch < 1");
+    auto& t = h->ppo[trainer];
+    const int n = t.n;
+    const int mb = std::min(minibatch, n), nmb = n / mb;
+    int* perm = (int*)(t.rowbuf + 3 * (size_t)n + (size_t)h->cfg.num_envs * h->policy[t.policy].q.n_slots);
+    PpoWs w;
+    if ((rc = ppo_ensure_ws(h, t, mb, w))) return rc;
+    for (int ep = 0; ep < epochs; ep++) {
+        const bool last = ep == epochs - 1;
+        if (last) HK_HIP(h, hipMemsetAsync(w.acc, 0, 8 * sizeof(double), h->stream));
+        hipLaunchKernelGGL(hk::ppo_perm_kernel, dim3(nblk(n)), dim3(256), 0, h->stream, perm, n, t.cfg.seed, (uint32_t)t.epochs_done);
+        t.epochs_done += 1;
+        t.perm_valid = true;
+        for (int b = 0; b < nmb; b++) {
+            if ((rc = ppo_mb(h, t, perm + (size_t)b * mb, mb, eps, beta, last))) return rc;
+            if ((rc = ppo_adam_step(h, t, lr))) return rc;
+        }
+    }
+    if ((rc = hk_ppo_publish(h, trainer))) return rc;
+    if (stats) {
+        double acc[8];
+        HK_HIP(h, hipMemcpyAsync(acc, w.acc, sizeof(acc), hipMemcpyDeviceToHost, h->stream));
+        HK_HIP(h, hipStreamSynchronize(h->stream));
+        for (int q = 0; q < HK_PPO_STATS; q++) stats[q] = (float)(acc[q] / (acc[6] > 0 ? acc[6] : 1.0));
+    }
+    return HK_OK;
+}
+
+void* hk_ppo_ptr(hk_handle h, int trainer, int field)
+{
+    if (!h) { fail(nullptr, HK_ERR_INVALID, "NULL handle"); return nullptr; }
+    if (trainer < 0 || trainer >= h->n_ppo) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: bad trainer index"); return nullptr; }
+    const auto& t = h->ppo[trainer];
+    if (field < 0 || field >= HK_PPO_FIELDS) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: bad field"); return nullptr; }
+    if (field <= HK_PPO_ADAM_V) return t.param + (size_t)field * t.P;
+    if (field <= HK_PPO_RET) {
+        if (t.adv_gen < 0) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: hk_ppo_advantages has not run"); return nullptr; }
+        return t.rowbuf + (size_t)(field - HK_PPO_V_OLD) * t.n;
+    }
+    if (field == HK_PPO_PERM) {
+        if (!t.perm_valid) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: no hk_ppo_update on the current advantages"); return nullptr; }
+        return t.rowbuf + 3 * (size_t)t.n + (size_t)h->cfg.num_envs * h->policy[t.policy].q.n_slots;
+    }
+    if (t.last_m == 0) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: no minibatch yet"); return nullptr; }
+    PpoWs w;
+    ppo_ws_layout(t, t.cap, &w);
+    return field == HK_PPO_MB_MU ? (void*)w.mb_mu : field == HK_PPO_MB_LOGITS ? (void*)w.mb_logits : (void*)w.mb_v;
+}
+
+int hk_ppo_count(hk_handle h, int trainer, int field)
+{
+    if (!h) return fail(nullptr, HK_ERR_INVALID, "NULL handle");
+    if (trainer < 0 || trainer >= h->n_ppo) return fail(h, HK_ERR_INVALID, "hk_ppo_count: bad trainer index");
+    const auto& t = h->ppo[trainer];
+    if (field < 0 || field >= HK_PPO_FIELDS) return fail(h, HK_ERR_INVALID, "hk_ppo_count: bad field");
+    if (field <= HK_PPO_ADAM_V) return (int)t.P;
+    if (field <= HK_PPO_RET) return t.adv_gen < 0 ? 0 : t.n;
+    if (field == HK_PPO_PERM) return t.perm_valid ? t.n : 0;
+    return field == HK_PPO_MB_LOGITS ? t.last_m * t.actor.n_branch : t.last_m;
 }
 
 int hk_obs_dim(hk_handle h)

@@ -72,6 +72,42 @@ struct PolicyDevice {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The pieces whose bits the PPO trainer's forward must reproduce (hk_ppo.h): one definition, used by both kernels.
+// The normaliser: clip((x - mean) / std, -5, 5)
+__device__ __forceinline__ float pm_normalise(float x, float mean, float sdev)
+{
+    x = (x - mean) / sdev;
+    return x < -5.0f ? -5.0f : (x > 5.0f ? 5.0f : x);
+}
+// A head output: bias + sum_k a[k stride] w[k] as an fmaf chain in ascending k
+__device__ __forceinline__ float pm_head(const float* a, size_t stride, const float* w, float bias, int H)
+{
+    float s = bias;
+    for (int k = 0; k < H; k++) s = __builtin_fmaf(a[(size_t)k * stride], w[k], s);
+    return s;
+}
+// The first largest logit
+__device__ __forceinline__ int pm_argmax(const float* lg, int nb)
+{
+    int best = 0;
+    for (int b = 1; b < nb; b++) if (lg[b] > lg[best]) best = b;
+    return best;
+}
+// ML-Agents' log-probabilities as the recorder writes them: the Gaussian's at the unclipped sample (sigma = hk_expf(log_sigma)), and
+// log_softmax of the logits at the pick (best = pm_argmax)
+__device__ __forceinline__ float pm_logp_cont(float raw, float mu, float sigma, float log_sigma)
+{
+    const float z = (raw - mu) / sigma;
+    return -0.5f * z * z - log_sigma - 0.918938533204672742f;      // 0.5 log(2 pi)
+}
+__device__ __forceinline__ float pm_logp_disc(const float* lg, int nb, int best, int pick)
+{
+    float tot = 0.0f;
+    for (int b = 0; b < nb; b++) tot += hk_expf(lg[b] - lg[best]);
+    return (lg[pick] - lg[best]) - hk_logf(tot);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // StackingSensor.  One wave per (env, slot), four to a block; w = ring slot that receives the newest observation.  (Round 5: a wave needs no block
 // barrier — the epoch word is read by every lane before lane 0 rewrites it, the zero fill precedes the copy in program order — and a pair moves
 // obs_dim <= 126 floats: with 128 threads and two __syncthreads per pair the kernel took 1.9 ms per decision beside the planner's searches.)
@@ -251,10 +287,7 @@ __global__ __launch_bounds__(PM_THREADS, MODE == 2 ? 2 : 4) void policy_mlp_kern
                     for (int m = 0; m < MMAX; m++) {
                         if (soff[m] < 0) continue;
                         float x = v[m];
-                        if (Q.normalize && rowok) {
-                            x = (x - mean[m]) / sdev[m];
-                            x = x < -5.0f ? -5.0f : (x > 5.0f ? 5.0f : x);
-                        }
+                        if (Q.normalize && rowok) x = pm_normalise(x, mean[m], sdev[m]);
                         At[(size_t)(lane + 64 * m) * PM_LD + r] = x;
                     }
                 }
@@ -296,9 +329,7 @@ __global__ __launch_bounds__(PM_THREADS, MODE == 2 ? 2 : 4) void policy_mlp_kern
         const int out = tid >> 6, r = tid & 63;
         if (out < 1 + Q.n_branch) {
             const float* wv = out == 0 ? Q.W_mu : Q.W_branch + (size_t)(out - 1) * H;
-            float s = out == 0 ? Q.b_mu[0] : Q.b_branch[out - 1];
-            for (int k = 0; k < H; k++) s = __builtin_fmaf(At[(size_t)k * PM_LD + r], wv[k], s);
-            head[out * PM_TILE + r] = s;
+            head[out * PM_TILE + r] = pm_head(At + r, PM_LD, wv, out == 0 ? Q.b_mu[0] : Q.b_branch[out - 1], H);
         }
     }
     __syncthreads();
@@ -323,8 +354,7 @@ __global__ __launch_bounds__(PM_THREADS, MODE == 2 ? 2 : 4) void policy_mlp_kern
             const float sigma = hk_expf(Q.log_sigma[0]);
             const float raw = mu + eps * sigma;
             const float v = raw < -3.0f ? -3.0f : (raw > 3.0f ? 3.0f : raw);
-            int best = 0;
-            for (int b = 1; b < Q.n_branch; b++) if (lg[b] > lg[best]) best = b;
+            const int best = pm_argmax(lg, Q.n_branch);
             int pick = best;
             if (!Q.deterministic) {
                 float ex[PM_MAX_OUT], tot = 0.0f;
@@ -339,16 +369,13 @@ __global__ __launch_bounds__(PM_THREADS, MODE == 2 ? 2 : 4) void policy_mlp_kern
             act_branch[ea] = pick;
             if (rec.raw) {              // (a kernel argument: wave-uniform)
                 // ML-Agents' log-probabilities: the Gaussian's at the unclipped sample, and log_softmax of the logits at the pick
-                const float z = (raw - mu) / sigma;
-                float tot = 0.0f;
-                for (int b = 0; b < Q.n_branch; b++) tot += hk_expf(lg[b] - lg[best]);
                 rec.steer[ea] = v / 3.0f;
                 rec.branch[ea] = pick;
                 rec.raw[ea] = raw;
                 rec.mu[ea] = mu;
                 for (int b = 0; b < Q.n_branch; b++) rec.logits[ea * rec.nbm + b] = lg[b];
-                rec.logp_c[ea] = -0.5f * z * z - Q.log_sigma[0] - 0.918938533204672742f;      // 0.5 log(2 pi)
-                rec.logp_d[ea] = (lg[pick] - lg[best]) - hk_logf(tot);
+                rec.logp_c[ea] = pm_logp_cont(raw, mu, sigma, Q.log_sigma[0]);
+                rec.logp_d[ea] = pm_logp_disc(lg, Q.n_branch, best, pick);
             }
         }
     }

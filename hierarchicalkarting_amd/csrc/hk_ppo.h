@@ -1,0 +1,478 @@
+// hk_ppo.h — device side of the PPO trainer (contract in include/hk.h "PPO trainer", host side in hk_api.hip).
+// Per minibatch of m rows (ids into the rollout's n = R * E * S rows):
+//   ppo_gather_kernel       the stacked input of every row rebuilt from OBS / FIRST / RING0 (NEXT_OBS for the bootstrap rows), normalised
+//                           and clipped exactly as policy_mlp_kernel's loader does: X0 [m][in_dim] (a workspace sized by the minibatch)
+//   ppo_gemm_kernel<EPI>    every matrix product, on v_mfma_f32_32x32x2_f32: the trunk forward (seeded with the bias, k ascending: the
+//                           bits of policy_mlp_kernel), the backward delta (delta W) * swish', and the weight gradients (delta^T a, K = rows,
+//                           split into fixed chunks of PPO_KCH rows whose partial tiles ppo_combine_kernel sums in chunk order)
+//   ppo_loss_kernel         the heads as fmaf chains (the bits of policy_mlp_kernel's heads), the log-probabilities as the recorder writes
+//                           them, the clipped losses and their per-row gradients; one thread per row
+//   ppo_colsum_kernel       bias / log_sigma gradients and the stats: fixed-order column sums (no float atomics anywhere)
+//   ppo_gae_kernel          one lane per (env, slot): the reverse GAE scan;  ppo_adv_norm_kernel: fp64 mean / std in one block
+//   ppo_adam_kernel, ppo_publish_kernel<TO_POLICY>              elementwise
+#pragma once
+#include "hk_policy.h"
+
+namespace hk {
+
+constexpr int PPO_KCH = 256;          // rows per split-K chunk of a weight gradient
+constexpr int PPO_TM = 64, PPO_TN = 64, PPO_TK = 32, PPO_LD = 65;
+
+// flat parameter layout of one network (torch order: W[l] [out][in], b[l], then the heads)
+struct PpoNet {
+    int in_dim = 0, hidden = 0, n_layers = 0, n_branch = 0;     // n_branch 0: the critic (one linear output)
+    size_t oW[HK_POLICY_MAX_LAYERS] = {}, ob[HK_POLICY_MAX_LAYERS] = {};
+    size_t oWmu = 0, obmu = 0, ols = 0, oWbr = 0, obbr = 0;      // critic: oWmu / obmu are the value head, ols / oWbr / obbr unused
+    size_t count = 0;
+    void layout(int in, int H, int L, int nb, size_t base)
+    {
+        in_dim = in; hidden = H; n_layers = L; n_branch = nb;
+        size_t o = base;
+        for (int l = 0; l < L; l++) {
+            oW[l] = o; o += (size_t)H * (l == 0 ? in : H);
+            ob[l] = o; o += H;
+        }
+        oWmu = o; o += H;
+        obmu = o; o += 1;
+        if (nb > 0) {
+            ols = o; o += 1;
+            oWbr = o; o += (size_t)nb * H;
+            obbr = o; o += nb;
+        }
+        count = o - base;
+    }
+};
+
+// the rollout rows a trainer reads (hk_rollout_field buffers) and its actor's input rule
+struct PpoRows {
+    const float *obs, *ring0, *next_obs, *raw, *reward, *term_reward, *logp_c, *logp_d;
+    const int *first, *branch, *done;
+    const float *mean, *std;            // the actor's normaliser (frozen); nullptr: none
+    int R, E, A, S, D, stack, smax, in_dim, normalize;
+    int slots[HK_MAX_AGENTS];
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Row ids -> X0.  id in [0, n): row (t, e, j), t = id / (E S), e = id / S % E, j = id % S.  boot && id in [n, n + E S): the bootstrap input of
+// (e, j) = id - n: the last row's stack shifted by one with NEXT_OBS pushed.  Any other id: a zero row, valid[i] = 0.
+// The stack rule of rollout.stacked_inputs: entry q (oldest first) of row t is decision u = t - (stack - 1 - q); it is present when no
+// decision in (u, t] cleared the stack (FIRST; the bootstrap's own push clears nothing) — OBS[u] for u >= 0, RING0 for u < 0 — else 0.
+__global__ __launch_bounds__(256) void ppo_gather_kernel(PpoRows P, const int* ids, int m, int boot, float* X0, int* valid)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)m * P.in_dim) return;
+    const int i = (int)(idx / P.in_dim), k = (int)(idx % P.in_dim);
+    const int n = P.R * P.E * P.S;
+    const int id = ids[i];
+    const bool is_row = id >= 0 && id < n;
+    const bool is_boot = boot && id >= n && id < n + P.E * P.S;
+    if (k == 0) valid[i] = is_row || is_boot;
+    if (!is_row && !is_boot) { X0[idx] = 0.0f; return; }
+    int t, e, j;
+    if (is_row) { t = id / (P.E * P.S); e = (id / P.S) % P.E; j = id % P.S; }
+    else { t = P.R; e = (id - n) / P.S; j = (id - n) % P.S; }
+    const int a = P.slots[j];
+    const size_t ea = (size_t)e * P.A + a, EA = (size_t)P.E * P.A;
+    const int q = k / P.D, d = k % P.D;
+    const int u = t - (P.stack - 1 - q);
+    const int last = t < P.R ? t : P.R - 1;          // the decisions whose FIRST can clear this entry: (u, last]
+    bool present = true;
+    for (int v = (u < 0 ? 0 : u + 1); v <= last; v++) if (P.first[(size_t)v * EA + ea]) { present = false; break; }
+    float x = 0.0f;
+    if (present) {
+        if (u >= P.R) x = P.next_obs[ea * P.D + d];
+        else if (u >= 0) x = P.obs[((size_t)u * EA + ea) * P.D + d];
+        else x = P.ring0[(ea * (P.smax - 1) + (P.smax - 1 + u)) * P.D + d];
+    }
+    if (P.normalize) x = pm_normalise(x, P.mean[k], P.std[k]);      // policy_mlp_kernel's loader (hk_policy.h)
+    X0[idx] = x;
+}
+
+__global__ __launch_bounds__(256) void ppo_iota_kernel(int* ids, int base, int m)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < m) ids[i] = base + i;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// C = seed + A B, A(i, k) = A[i sai + k sak] (M x K), B(k, j) = B[k sbk + j sbj] (K x N).  A workgroup of 4 waves owns a 64 x 64 tile of C,
+// one 32 x 32 block per wave; K runs through LDS in chunks of 32 (tiles stored k-major, row stride 65: the MFMA operand reads of 32
+// consecutive rows / columns are conflict-free), each chunk as MFMA 32x32x2 steps in ascending k — lane half h supplies k0 + h, the
+// pairing pm_gemm uses — so a product with K even and no split is the k-ascending fmaf chain policy_mlp_kernel computes.
+// blockIdx.z = split-K chunk of kch rows of K; chunk z writes C + z M N (row stride N) when nz > 1.
+// EPI 0: C = acc (seeded with bias[j] when bias != nullptr).  EPI 1 (trunk forward): Z = acc, C = swish(acc).  EPI 2 (backward): C = acc * swish'(Z).
+template <int EPI>
+__global__ __launch_bounds__(256) void ppo_gemm_kernel(int M, int N, int K, const float* __restrict__ A, int sai, int sak, const float* __restrict__ B,
+                                                       int sbk, int sbj, const float* __restrict__ bias, float* C, int ldc, float* Z, int kch)
+{
+    __shared__ float As[PPO_TK * PPO_LD], Bs[PPO_TK * PPO_LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i0 = blockIdx.y * PPO_TM, j0 = blockIdx.x * PPO_TN;
+    const int kbeg = blockIdx.z * kch, kend = (kbeg + kch < K) ? kbeg + kch : K;
+    const int wr = wave >> 1, wc = wave & 1, half = lane >> 5, c = lane & 31;
+    const int jcol = j0 + wc * 32 + c;
+    f32x16 acc;
+    {
+        const float s = (bias && jcol < N) ? bias[jcol] : 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[r] = s;
+    }
+    for (int kb = kbeg; kb < kend; kb += PPO_TK) {
+        const int kc = (kend - kb) < PPO_TK ? (kend - kb) : PPO_TK;
+        // A tile [kk][ii]: threads along whichever dimension is contiguous in memory
+        for (int x = tid; x < PPO_TK * PPO_TM; x += 256) {
+            int ii, kk;
+            if (sak == 1) { kk = x & 31; ii = x >> 5; } else { ii = x & 63; kk = x >> 6; }
+            const int gi = i0 + ii, gk = kb + kk;
+            As[kk * PPO_LD + ii] = (gi < M && kk < kc) ? A[(size_t)gi * sai + (size_t)gk * sak] : 0.0f;
+        }
+        for (int x = tid; x < PPO_TK * PPO_TN; x += 256) {
+            int jj, kk;
+            if (sbj == 1) { jj = x & 63; kk = x >> 6; } else { kk = x & 31; jj = x >> 5; }
+            const int gj = j0 + jj, gk = kb + kk;
+            Bs[kk * PPO_LD + jj] = (gj < N && kk < kc) ? B[(size_t)gk * sbk + (size_t)gj * sbj] : 0.0f;
+        }
+        __syncthreads();
+        const float* ap = As + half * PPO_LD + wr * 32 + c;
+        const float* bp = Bs + half * PPO_LD + wc * 32 + c;
+        const int steps = (kc + 1) >> 1;
+        for (int s = 0; s < steps; s++)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[(size_t)2 * s * PPO_LD], bp[(size_t)2 * s * PPO_LD], acc, 0, 0, 0);
+        __syncthreads();
+    }
+    if (jcol >= N) return;
+    float* Cz = C + (gridDim.z > 1 ? (size_t)blockIdx.z * M * N : 0);
+    // C/D layout: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = i0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        if (row >= M) continue;
+        const size_t o = (size_t)row * ldc + jcol;
+        if (EPI == 0) Cz[o] = acc[r];
+        else if (EPI == 1) { Z[o] = acc[r]; Cz[o] = swish(acc[r]); }
+        else {
+            const float s = Z[o];
+            const float sg = 1.0f / (1.0f + expf(-s));
+            Cz[o] = acc[r] * (sg + s * sg * (1.0f - sg));
+        }
+    }
+}
+
+// out[r][c] (row stride N; rows >= 1 go to out1 + (r - 1) N when out1) = sum over the nz chunks' partial tiles, in chunk order
+__global__ __launch_bounds__(256) void ppo_combine_kernel(const float* part, int nz, int M, int N, float* out0, float* out1)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, MN = (size_t)M * N;
+    if (idx >= MN) return;
+    float s = 0.0f;
+    for (int z = 0; z < nz; z++) s += part[(size_t)z * MN + idx];
+    const int r = (int)(idx / N);
+    if (out1 && r >= 1) out1[idx - N] = s;
+    else out0[idx] = s;
+}
+
+// out[c] = sum_i X[i ld + c] for c < ncol, one workgroup per column: fixed strided partial sums, then a fixed tree (deterministic)
+template <typename T>
+__global__ __launch_bounds__(256) void ppo_colsum_kernel(const T* X, int m, int ld, float* out)
+{
+    __shared__ double red[256];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    double s = 0.0;
+    for (int i = tid; i < m; i += 256) s += (double)X[(size_t)i * ld + c];
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) out[c] = (float)red[0];
+}
+
+// the minibatch's valid rows (one workgroup)
+__global__ __launch_bounds__(256) void ppo_count_kernel(const int* valid, int m, int* out)
+{
+    __shared__ int red[256];
+    const int tid = threadIdx.x;
+    int s = 0;
+    for (int i = tid; i < m; i += 256) s += valid[i] != 0;
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) red[tid] += red[tid + w]; __syncthreads(); }
+    if (tid == 0) out[0] = red[0];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// One thread per minibatch row: heads, log-probabilities, the losses and dL / d(head) (HK_PPO_* row stats: [0] the two clipped surrogate
+// terms summed, [1] the value term, [2] H, [3] old - new logp summed over c, d, [4] clipped columns, [5] skipped).
+struct PpoLossArgs {
+    const float *Aa, *Ac;            // the last hidden activations [m][Ha], [m][Hc]
+    const float *W_mu, *b_mu, *log_sigma, *W_br, *b_br, *W_v, *b_v;
+    const float *v_old, *adv, *ret;
+    const int* ids;
+    const int* valid;
+    const int* n_valid;              // the minibatch's valid rows (ppo_count_kernel)
+    int m, n, Ha, Hc, nb;
+    float eps, beta;
+    float *dhead;                    // [m][PM_MAX_OUT]: dmu, dlogits
+    float *dls, *dv;                 // [m]
+    double* rowstat;                 // [m][6]
+    float *mu_out, *logit_out, *v_out;   // debug taps [m], [m][nb], [m]
+};
+
+__global__ __launch_bounds__(256) void ppo_loss_kernel(PpoRows P, PpoLossArgs L)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= L.m) return;
+    double* st = L.rowstat + (size_t)i * 6;
+    float* dh = L.dhead + (size_t)i * PM_MAX_OUT;
+    const int id = L.ids[i];
+    if (!L.valid[i] || id < 0 || id >= L.n) {
+        for (int o = 0; o < PM_MAX_OUT; o++) dh[o] = 0.0f;
+        L.dls[i] = 0.0f; L.dv[i] = 0.0f;
+        for (int o = 0; o < 5; o++) st[o] = 0.0;
+        st[5] = 1.0;
+        return;
+    }
+    const float inv = 1.0f / (float)L.n_valid[0];
+    // ---- heads: policy_mlp_kernel's fmaf chains (pm_head, hk_policy.h)
+    const float* aa = L.Aa + (size_t)i * L.Ha;
+    const float mu = pm_head(aa, 1, L.W_mu, L.b_mu[0], L.Ha);
+    float lg[PM_MAX_OUT];
+    for (int b = 0; b < L.nb; b++) lg[b] = pm_head(aa, 1, L.W_br + (size_t)b * L.Ha, L.b_br[b], L.Ha);
+    const float v = pm_head(L.Ac + (size_t)i * L.Hc, 1, L.W_v, L.b_v[0], L.Hc);
+    if (L.mu_out) {
+        L.mu_out[i] = mu; L.v_out[i] = v;
+        for (int b = 0; b < L.nb; b++) L.logit_out[(size_t)i * L.nb + b] = lg[b];
+    }
+    // ---- the row
+    const int t = id / (P.E * P.S), e = (id / P.S) % P.E, j = id % P.S;
+    const size_t ea = ((size_t)t * P.E + e) * P.A + P.slots[j];
+    const float raw = P.raw[ea], old_c = P.logp_c[ea], old_d = P.logp_d[ea];
+    const int pick = P.branch[ea];
+    const float A = L.adv[id], vo = L.v_old[id], R = L.ret[id];
+    // ---- log-probabilities: the recorder's own helpers (hk_policy.h), so that unchanged parameters give rho == 1 exactly
+    const float ls = L.log_sigma[0];
+    const float sigma = hk_expf(ls);
+    const float z = (raw - mu) / sigma;
+    const float logp_c = pm_logp_cont(raw, mu, sigma, ls);
+    const int best = pm_argmax(lg, L.nb);
+    const float logp_d = pm_logp_disc(lg, L.nb, best, pick);
+    float ex[PM_MAX_OUT], tot = 0.0f;
+    for (int b = 0; b < L.nb; b++) { ex[b] = hk_expf(lg[b] - lg[best]); tot += ex[b]; }
+    const float ltot = hk_logf(tot);
+    // ---- clipped surrogate, per column (torch.min / torch.clamp gradients: a tie splits, the clamp passes inside [lo, hi])
+    const float lo = 1.0f - L.eps, hi = 1.0f + L.eps;
+    float surr = 0.0f, clipped = 0.0f, dlogp[2];
+    const float lp[2] = {logp_c, logp_d}, old[2] = {old_c, old_d};
+    for (int q = 0; q < 2; q++) {
+        const float rho = hk_expf(lp[q] - old[q]);
+        const float rc = rho < lo ? lo : (rho > hi ? hi : rho);
+        const float u = rho * A, w = rc * A;
+        const float gu = A, gw = (rho >= lo && rho <= hi) ? A : 0.0f;
+        const float g = u < w ? gu : (u > w ? gw : 0.5f * (gu + gw));
+        surr += u < w ? u : w;
+        clipped += (rho < lo || rho > hi) ? 1.0f : 0.0f;
+        dlogp[q] = -0.5f * inv * g * rho;
+    }
+    // ---- entropy
+    float Hd = 0.0f, logp_b[PM_MAX_OUT], p_b[PM_MAX_OUT];
+    for (int b = 0; b < L.nb; b++) {
+        p_b[b] = ex[b] / tot;
+        logp_b[b] = (lg[b] - lg[best]) - ltot;
+        Hd -= p_b[b] * logp_b[b];
+    }
+    const float H = 1.418938533204672742f + ls + Hd;           // 0.5 log(2 pi e) + log_sigma + categorical
+    // ---- gradients of L = L_pi + 0.5 L_v - beta mean H with respect to the heads
+    dh[0] = dlogp[0] * (z / sigma);
+    for (int b = 0; b < L.nb; b++)
+        dh[1 + b] = dlogp[1] * ((b == pick ? 1.0f : 0.0f) - p_b[b]) + L.beta * inv * p_b[b] * (logp_b[b] + Hd);
+    for (int b = 1 + L.nb; b < PM_MAX_OUT; b++) dh[b] = 0.0f;
+    L.dls[i] = dlogp[0] * (z * z - 1.0f) - L.beta * inv;
+    // ---- clipped value loss (torch.max: a tie splits)
+    const float dvv = v - vo;
+    const float dc = dvv < -L.eps ? -L.eps : (dvv > L.eps ? L.eps : dvv);
+    const float a1 = R - v, b1 = R - vo - dc;
+    const float f1 = a1 * a1, f2 = b1 * b1;
+    const float g1 = -2.0f * a1, g2 = (dvv >= -L.eps && dvv <= L.eps) ? -2.0f * b1 : 0.0f;
+    const float gv = f1 > f2 ? g1 : (f1 < f2 ? g2 : 0.5f * (g1 + g2));
+    L.dv[i] = 0.5f * inv * gv;
+    st[0] = surr; st[1] = f1 > f2 ? f1 : f2; st[2] = H; st[3] = (double)(old_c - logp_c) + (double)(old_d - logp_d); st[4] = clipped; st[5] = 0.0;
+}
+
+// the six stats of a minibatch from the row stats (one workgroup, fixed order); acc != nullptr: also added into acc[0..5], acc[6] += 1
+__global__ __launch_bounds__(256) void ppo_stats_kernel(const double* rowstat, int m, float* stats, double* acc)
+{
+    __shared__ double red[6][256];
+    const int tid = threadIdx.x;
+    double s[6] = {};
+    for (int i = tid; i < m; i += 256)
+        for (int q = 0; q < 6; q++) s[q] += rowstat[(size_t)i * 6 + q];
+    for (int q = 0; q < 6; q++) red[q][tid] = s[q];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) for (int q = 0; q < 6; q++) red[q][tid] += red[q][tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const double skipped = red[5][0], mv = (double)m - skipped;
+        const double d = mv > 0 ? mv : 1.0;
+        double o[6] = {-red[0][0] / (2.0 * d), red[1][0] / d, red[2][0] / d, red[3][0] / (2.0 * d), red[4][0] / (2.0 * d), skipped};
+        for (int q = 0; q < 6; q++) stats[q] = (float)o[q];
+        if (acc) { for (int q = 0; q < 6; q++) acc[q] += o[q]; acc[6] += 1.0; }
+    }
+}
+
+// delta_L of a trunk: dA[i][h] = (sum_o dhead[i][o] W_head[o][h]) * swish'(Z[i][h])  (vector ALU; n_out <= PM_MAX_OUT)
+__global__ __launch_bounds__(256) void ppo_head_back_kernel(int m, int H, int n_out, const float* dhead, int ldd, const float* W0, const float* W1,
+                                                            const float* Z, float* dA)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)m * H) return;
+    const int i = (int)(idx / H), h = (int)(idx % H);
+    float s = dhead[(size_t)i * ldd] * W0[h];
+    for (int o = 1; o < n_out; o++) s += dhead[(size_t)i * ldd + o] * W1[(size_t)(o - 1) * H + h];
+    const float zz = Z[idx];
+    const float sg = 1.0f / (1.0f + expf(-zz));
+    dA[idx] = s * (sg + zz * sg * (1.0f - sg));
+}
+
+// hk_ppo_advantages: the critic's value head over rows ids[0 .. m) (row ids and bootstrap ids, ppo_gather_kernel) -> v_old[id] / vb[id - n]
+__global__ __launch_bounds__(256) void ppo_value_kernel(const float* Ac, int m, int Hc, const float* W_v, const float* b_v, const int* ids, int n, int nb_boot,
+                                                        float* v_old, float* vb)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const int id = ids[i];
+    const float v = pm_head(Ac + (size_t)i * Hc, 1, W_v, b_v[0], Hc);          // the minibatch's value head, bit for bit
+    if (id >= 0 && id < n) v_old[id] = v;
+    else if (id >= n && id < n + nb_boot) vb[id - n] = v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// GAE, one lane per (e, j), t from R - 1 down (hk.h); V of row R is the bootstrap value vb[e][j]
+__global__ __launch_bounds__(256) void ppo_gae_kernel(PpoRows P, const float* v_old, const float* vb, float gamma, float lambd, float* adv, float* ret)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P.E * P.S) return;
+    const int e = p / P.S, j = p % P.S;
+    float vnext = vb[p], anext = 0.0f;
+    for (int t = P.R - 1; t >= 0; t--) {
+        const size_t r = ((size_t)t * P.E + e) * P.S + j;
+        const size_t ea = ((size_t)t * P.E + e) * P.A + P.slots[j];
+        const int d = P.done[(size_t)t * P.E + e] != 0;
+        const float rw = d ? P.term_reward[ea] : P.reward[ea];
+        const float nd = d ? 0.0f : 1.0f;
+        const float v = v_old[r];
+        const float delta = rw + gamma * nd * vnext - v;
+        const float a = delta + gamma * lambd * nd * anext;
+        adv[r] = a;
+        ret[r] = a + v;
+        vnext = v; anext = a;
+    }
+}
+
+// ADV <- (ADV - mean) / (std + 1e-10), population std, both in fp64 (one workgroup: fixed strided sums, fixed tree)
+__global__ __launch_bounds__(1024) void ppo_adv_norm_kernel(float* adv, int n)
+{
+    __shared__ double red[1024];
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    for (int i = tid; i < n; i += 1024) s += (double)adv[i];
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) { if (tid < w) red[tid] += red[tid + w]; __syncthreads(); }
+    const double mean = red[0] / n;
+    __syncthreads();
+    s = 0.0;
+    for (int i = tid; i < n; i += 1024) { const double d = (double)adv[i] - mean; s += d * d; }
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) { if (tid < w) red[tid] += red[tid + w]; __syncthreads(); }
+    const double sd = sqrt(red[0] / n) + 1e-10;
+    for (int i = tid; i < n; i += 1024) adv[i] = (float)(((double)adv[i] - mean) / sd);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The row permutation of an update's epoch: a 4-round Feistel network on 2 hb bits (2^(2 hb) >= n) keyed by (seed, count), cycle-walked
+// into [0, n).  The host twin is hierarchicalkarting_amd/ppo.py permutation().
+__host__ __device__ inline uint32_t ppo_hash(uint32_t x)
+{
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+__host__ __device__ inline uint32_t ppo_perm(uint32_t i, uint32_t n, uint32_t seed, uint32_t count)
+{
+    int bits = 2;
+    while (bits < 32 && (1u << bits) < n) bits++;
+    const int hb = (bits + 1) >> 1;
+    const uint32_t mask = (1u << hb) - 1u;
+    uint32_t key[4];
+    for (int r = 0; r < 4; r++) key[r] = ppo_hash(seed ^ ppo_hash(count * 0x9E3779B9u + (uint32_t)r * 0x85EBCA6Bu + 1u));
+    uint32_t x = i;
+    do {
+        uint32_t lft = x >> hb, rgt = x & mask;
+        for (int r = 0; r < 4; r++) {
+            const uint32_t f = ppo_hash(rgt ^ key[r]) & mask;
+            const uint32_t nr = lft ^ f;
+            lft = rgt; rgt = nr;
+        }
+        x = (lft << hb) | rgt;
+    } while (x >= n);
+    return x;
+}
+__global__ __launch_bounds__(256) void ppo_perm_kernel(int* perm, int n, uint32_t seed, uint32_t count)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) perm[i] = (int)ppo_perm((uint32_t)i, (uint32_t)n, seed, count);
+}
+
+// Adam, in the order hk.h states: m = b1 m + (1 - b1) g; v = b2 v + ((1 - b2) g) g; p = p - lr (m / c1) / (sqrt(v / c2) + eps)
+__global__ __launch_bounds__(256) void ppo_adam_kernel(float* p, const float* g, float* mm, float* vv, size_t n, float b1, float omb1, float b2, float omb2,
+                                                       float c1, float c2, float eps, float lr)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float gi = g[i];
+    const float m1 = b1 * mm[i] + omb1 * gi;
+    const float v1 = b2 * vv[i] + (omb2 * gi) * gi;
+    mm[i] = m1; vv[i] = v1;
+    const float mh = m1 / c1;
+    const float vh = v1 / c2;
+    p[i] = p[i] - lr * mh / (sqrtf(vh) + eps);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// master actor parameters (PpoNet layout) <-> the inference copies of policy_upload: Wt[k][j] = W[j][k], the group-major Wq, biases, heads.
+// One thread per element of the flat actor vector.  TO_POLICY: publish; else the master copy is read back from the attached policy.
+template <bool TO_POLICY>
+__global__ __launch_bounds__(256) void ppo_publish_kernel(PolicyParams Q, PpoNet net, float* flat)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= net.count) return;
+    const int H = Q.hidden;
+    auto mv = [&](const float* dst_c, size_t di) {
+        float* dst = const_cast<float*>(dst_c);
+        if (TO_POLICY) dst[di] = flat[idx]; else flat[idx] = dst[di];
+    };
+    for (int l = 0; l < net.n_layers; l++) {
+        const int K = l == 0 ? Q.in_dim : H;
+        if (idx >= net.oW[l] && idx < net.oW[l] + (size_t)H * K) {
+            const size_t w = idx - net.oW[l];
+            const int jj = (int)(w / K), k = (int)(w % K);
+            mv(Q.Wt[l], (size_t)k * H + jj);
+            if (TO_POLICY && k < (K / 8) * 8) {      // the group-major copy: element (g, half, col)[q4] = W[8 g + 2 q4 + half][col]
+                const int g = k >> 3, r = k & 7, q4 = r >> 1, hf = r & 1;
+                float* wq = const_cast<float*>(reinterpret_cast<const float*>(Q.Wq[l]));
+                wq[(((size_t)g * 2 + hf) * H + jj) * 4 + q4] = flat[idx];
+            }
+            return;
+        }
+        if (idx >= net.ob[l] && idx < net.ob[l] + H) { mv(Q.b[l], idx - net.ob[l]); return; }
+    }
+    if (idx >= net.oWmu && idx < net.oWmu + H) mv(Q.W_mu, idx - net.oWmu);
+    else if (idx == net.obmu) mv(Q.b_mu, 0);
+    else if (idx == net.ols) mv(Q.log_sigma, 0);
+    else if (idx >= net.oWbr && idx < net.oWbr + (size_t)net.n_branch * H) mv(Q.W_branch, idx - net.oWbr);
+    else if (idx >= net.obbr && idx < net.obbr + net.n_branch) mv(Q.b_branch, idx - net.obbr);
+}
+
+}  // namespace hk

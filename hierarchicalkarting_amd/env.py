@@ -7,6 +7,7 @@ RacingEnv  <->  RacingEnvController (+ its KartAgents / ArcadeKarts), E independ
     set_actions(steer, branch)       KartAgent.OnActionReceived (KA:440-478) for LowMode == RL agents
     attach_policy(policy, slots)     BehaviorParameters.Model: the ML-Agents actor runs on device every DecisionPeriod ticks
     rollout_begin / rollout_close    record what the attached actors did (obs, actions, log-probs, rewards) on the device
+    ppo_trainer(policy)              PPO on the recorded rows, on the device (ppo.PPOTrainer)
     agent_state() / set_agent_state  snapshot / restore of every KartAgent + ArcadeKart + Rigidbody field
     episode_results()                TelemetryViewer quantities of the last finished episode
 All arrays are numpy views of the ABI structs; all compute happens in the HIP kernels."""
@@ -281,6 +282,11 @@ class RacingEnv:
                 _lib.copy_device_to_host(a.ctypes.data, ptr, a.nbytes)
             out[name] = a
         return out
+
+    def ppo_trainer(self, policy_index, critic=None, **cfg):
+        """-> ppo.PPOTrainer of an attached policy (hk_ppo_create): it trains on this handle's closed rollouts and publishes into the policy"""
+        from .ppo import PPOTrainer
+        return PPOTrainer(self, policy_index, critic, **cfg)
 
     def observe(self):
         self._ck(self.L.hk_observe(self.h))

@@ -1,0 +1,193 @@
+"""PPO trainer of an attached actor, on the device (hk.h "PPO trainer"): consumes a closed rollout of RacingEnv's recorder
+and leaves updated weights in the attached policy, so that the next step() acts with them.
+
+    tr = PPOTrainer(env, 0)                      # policy 0; critic=None: a seeded random critic of the actor's shape
+    env.rollout_begin(R); env.step(R * P); env.rollout_close()
+    tr.advantages()                              # critic over every row + the bootstrap inputs, GAE
+    stats = tr.update(epochs=3, minibatch=512, lr=3e-4, eps=0.2, beta=5e-3)     # shuffle, minibatches, Adam; then publish
+
+Nothing is computed here: the arrays below only describe the flat parameter layout the library uses."""
+import ctypes as C
+import numpy as np
+from . import _lib
+from .policy import Policy
+
+DEFAULTS = dict(gamma=0.99, lambd=0.95, normalize_advantages=True, adam_beta1=0.9, adam_beta2=0.999, adam_eps=1e-8, seed=0)
+
+
+def param_layout(in_dim, hidden, n_layers, n_branch):
+    """-> [(name, shape)] of one network in the flat vector's order (torch layout; n_branch 0: the critic, whose value head is W_mu / b_mu)"""
+    out = []
+    for l in range(n_layers):
+        out += [("W%d" % l, (hidden, in_dim if l == 0 else hidden)), ("b%d" % l, (hidden,))]
+    out += [("W_mu", (hidden,)), ("b_mu", (1,))]
+    if n_branch:
+        out += [("log_sigma", (1,)), ("W_branch", (n_branch, hidden)), ("b_branch", (n_branch,))]
+    return out
+
+
+def split_params(flat, layout):
+    """flat vector (numpy or torch) -> dict name -> view of the given layout"""
+    out, o = {}, 0
+    for name, shape in layout:
+        k = int(np.prod(shape))
+        out[name] = flat[o:o + k].reshape(shape)
+        o += k
+    return out
+
+
+def _hash(x):
+    x &= 0xFFFFFFFF
+    x ^= x >> 16; x = (x * 0x7FEB352D) & 0xFFFFFFFF
+    x ^= x >> 15; x = (x * 0x846CA68B) & 0xFFFFFFFF
+    x ^= x >> 16
+    return x
+
+
+def permutation(n, seed, count):
+    """host twin of the device's row permutation (hk_ppo.h ppo_perm): a 4-round Feistel network keyed by (seed, count), cycle-walked into [0, n)"""
+    bits = 2
+    while bits < 32 and (1 << bits) < n:
+        bits += 1
+    hb = (bits + 1) >> 1
+    mask = (1 << hb) - 1
+    key = [_hash((seed & 0xFFFFFFFF) ^ _hash(count * 0x9E3779B9 + r * 0x85EBCA6B + 1)) for r in range(4)]
+    i = np.arange(n, dtype=np.uint64)
+    x = i.copy()
+    todo = np.ones(n, bool)
+    m64 = np.uint64(0xFFFFFFFF)
+
+    def h(v):
+        v = v & m64
+        v ^= v >> np.uint64(16); v = (v * np.uint64(0x7FEB352D)) & m64
+        v ^= v >> np.uint64(15); v = (v * np.uint64(0x846CA68B)) & m64
+        v ^= v >> np.uint64(16)
+        return v
+    while todo.any():
+        y = x[todo]
+        lft, rgt = y >> np.uint64(hb), y & np.uint64(mask)
+        for r in range(4):
+            f = h(rgt ^ np.uint64(key[r])) & np.uint64(mask)
+            lft, rgt = rgt, lft ^ f
+        y = (lft << np.uint64(hb)) | rgt
+        x[todo] = y
+        todo = x >= np.uint64(n)
+    return x.astype(np.int64)
+
+
+class PPOTrainer:
+    """One trainer of RacingEnv `env`'s attached policy `policy_index` (hk_ppo_create).  critic: a Policy with n_branch 0 semantics (its trunk and
+    W_mu / b_mu are used) or None for Policy.random-style weights of the actor's shape; cfg: DEFAULTS' keys."""
+
+    def __init__(self, env, policy_index, critic=None, **cfg):
+        bad = set(cfg) - set(DEFAULTS)
+        if bad:
+            raise TypeError("unknown PPO config keys: %s" % sorted(bad))
+        self.env, self.index = env, int(policy_index)
+        self.actor_policy = env._policies[self.index]
+        a = self.actor_policy
+        if critic is None:
+            critic = Policy.random(a.in_dim, a.hidden, len(a.W), n_branch=1, stack=a.stack, seed=0xC417 + self.index, normalize=False)
+        self.critic_policy = critic
+        c = dict(DEFAULTS, **cfg)
+        self.cfg = c
+        pc = _lib.PpoConfig(c["gamma"], c["lambd"], int(bool(c["normalize_advantages"])), c["adam_beta1"], c["adam_beta2"], c["adam_eps"],
+                            int(c["seed"]) & 0xFFFFFFFF)
+        d, _keep = critic.desc()
+        d.n_branch = 0
+        d.W_branch = d.b_branch = None
+        rc = env.L.hk_ppo_create(env.h, self.index, C.byref(d), C.byref(pc))
+        if rc < 0:
+            env._ck(rc)
+        self.t = rc
+        self.actor_layout = param_layout(a.in_dim, a.hidden, len(a.W), a.n_branch)
+        self.critic_layout = param_layout(a.in_dim, critic.hidden, len(critic.W), 0)
+        self.n_actor = sum(int(np.prod(s)) for _, s in self.actor_layout)
+
+    def _ck(self, rc):
+        self.env._ck(rc)
+
+    # ---- the entry points
+    def advantages(self):
+        self._ck(self.env.L.hk_ppo_advantages(self.env.h, self.t))
+
+    def _on_handle_stream(self, t):
+        """order the handle's stream after torch's current stream (t may still be being written there), and keep t's memory out of torch's
+        caching allocator until the handle's stream has read it"""
+        import torch
+        hs = torch.cuda.ExternalStream(self.env.L.hk_stream(self.env.h), device=t.device)
+        hs.wait_stream(torch.cuda.current_stream(t.device))
+        t.record_stream(hs)
+
+    def minibatch(self, ids, eps=0.2, beta=5e-3, stats=True):
+        """ids: a torch int32 CUDA tensor of row ids (out-of-range ids are skipped), read on the handle's stream after whatever torch's current
+        stream has queued.  -> dict of the stats (None: stats=False; the call then returns before the device has run it)"""
+        if ids.dtype.itemsize != 4 or not ids.is_cuda or not ids.is_contiguous():
+            raise TypeError("minibatch ids: a contiguous int32 CUDA tensor")
+        self._on_handle_stream(ids)
+        st = (C.c_float * _lib.HK_PPO_STATS)()
+        self._ck(self.env.L.hk_ppo_minibatch(self.env.h, self.t, C.c_void_p(ids.data_ptr()), int(ids.numel()), float(eps), float(beta),
+                                             st if stats else None))
+        return dict(zip(_lib.PPO_STAT_NAMES, list(st))) if stats else None
+
+    def adam(self, lr):
+        self._ck(self.env.L.hk_ppo_adam(self.env.h, self.t, float(lr)))
+
+    def update(self, epochs=3, minibatch=512, lr=3e-4, eps=0.2, beta=5e-3):
+        """epochs x (device shuffle, minibatches, Adam), then publish.  -> stats (mean over the last epoch's minibatches)"""
+        st = (C.c_float * _lib.HK_PPO_STATS)()
+        self._ck(self.env.L.hk_ppo_update(self.env.h, self.t, int(epochs), int(minibatch), float(lr), float(eps), float(beta), st))
+        return dict(zip(_lib.PPO_STAT_NAMES, list(st)))
+
+    def publish(self):
+        self._ck(self.env.L.hk_ppo_publish(self.env.h, self.t))
+
+    # ---- buffers
+    def _field(self, name):
+        idx = _lib.PPO_FIELDS[name]
+        n = self.env.L.hk_ppo_count(self.env.h, self.t, idx)
+        if n < 0:
+            self._ck(n)
+        ptr = self.env.L.hk_ppo_ptr(self.env.h, self.t, idx)
+        if not ptr:
+            self._ck(_lib.HK_ERR_INVALID)
+        return ptr, n
+
+    def read(self, name):
+        """-> numpy copy of an HK_PPO_* field, float32 (int32 for perm); the handle's stream is synchronised first"""
+        self.env.synchronize()
+        ptr, n = self._field(name)
+        a = np.zeros(n, np.int32 if name == "perm" else np.float32)
+        if n:
+            _lib.copy_device_to_host(a.ctypes.data, ptr, a.nbytes)
+        return a
+
+    def views(self):
+        """-> dict field -> torch CUDA tensor ALIASING the trainer's buffer, float32 (int32 for perm); rollout_views' caveats apply"""
+        import torch
+
+        class _Ext:
+            def __init__(self, ptr, n, ts):
+                self.__cuda_array_interface__ = {"shape": (n,), "typestr": ts, "data": (int(ptr), False), "version": 3, "strides": None}
+        out = {}
+        for name, idx in _lib.PPO_FIELDS.items():
+            n = self.env.L.hk_ppo_count(self.env.h, self.t, idx)
+            ptr = self.env.L.hk_ppo_ptr(self.env.h, self.t, idx) if n > 0 else None
+            if ptr:
+                out[name] = torch.as_tensor(_Ext(ptr, n, "<i4" if name == "perm" else "<f4"), device="cuda:%d" % self.env.built.cfg.device_id)
+        return out
+
+    def actor_params(self, flat=None):
+        flat = self.read("params") if flat is None else flat
+        return split_params(flat[:self.n_actor], self.actor_layout)
+
+    def critic_params(self, flat=None):
+        flat = self.read("params") if flat is None else flat
+        return split_params(flat[self.n_actor:], self.critic_layout)
+
+    def actor(self):
+        """-> host Policy of the current master actor parameters (normaliser, stack, seed and mode of the attached actor)"""
+        a, p = self.actor_policy, self.actor_params()
+        L = len(a.W)
+        return Policy([p["W%d" % l] for l in range(L)], [p["b%d" % l] for l in range(L)], p["W_mu"], p["b_mu"], p["log_sigma"], p["W_branch"],
+                      p["b_branch"], a.norm_mean, a.norm_std, a.stack, a.deterministic, a.seed)

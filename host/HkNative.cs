@@ -1,4 +1,4 @@
-// HkNative.cs — P/Invoke binding of libhk.so (include/hk.h, HK_ABI_VERSION 5) for the reference's Unity C# host.
+// HkNative.cs — P/Invoke binding of libhk.so (include/hk.h, HK_ABI_VERSION 6) for the reference's Unity C# host.
 //
 // Drop it under Assets/Karting/Scripts/AI/Native/ with libhk.so in Assets/Plugins/x86_64.  Every struct mirrors its C
 // twin field for field (tests/test_csharp_layout.py parses this file and checks field order, types, array lengths and
@@ -11,7 +11,7 @@ namespace KartGame.AI.Native
 {
     public static class HkConst
     {
-        public const int HK_ABI_VERSION = 5;
+        public const int HK_ABI_VERSION = 6;
         public const int HK_MAX_AGENTS = 8;
         public const int HK_MAX_SECTIONS = 64;
         public const int HK_NUM_SENSORS = 9;
@@ -25,6 +25,10 @@ namespace KartGame.AI.Native
         public const int HK_RO_OBS = 0, HK_RO_FIRST = 1, HK_RO_STEER = 2, HK_RO_BRANCH = 3, HK_RO_RAW = 4, HK_RO_MU = 5, HK_RO_LOGITS = 6,
                          HK_RO_LOGP_CONT = 7, HK_RO_LOGP_DISC = 8, HK_RO_REWARD = 9, HK_RO_GROUP_REWARD = 10, HK_RO_TERM_REWARD = 11,
                          HK_RO_TERM_GROUP_REWARD = 12, HK_RO_DONE = 13, HK_RO_RING0 = 14, HK_RO_NEXT_OBS = 15, HK_RO_FIELDS = 16;
+        // hk_ppo_field: the PPO trainer's buffers (hk_ppo_ptr / hk_ppo_count); HK_PPO_STATS: L_pi, L_v, entropy, approx-KL, clip fraction, skipped rows
+        public const int HK_PPO_PARAMS = 0, HK_PPO_GRAD = 1, HK_PPO_ADAM_M = 2, HK_PPO_ADAM_V = 3, HK_PPO_V_OLD = 4, HK_PPO_ADV = 5, HK_PPO_RET = 6,
+                         HK_PPO_MB_MU = 7, HK_PPO_MB_LOGITS = 8, HK_PPO_MB_VALUE = 9, HK_PPO_PERM = 10, HK_PPO_FIELDS = 11,
+                         HK_PPO_STATS = 6;
         // HierarchicalKartAgent.cs:21-33
         public const int HK_LOW_RL = 0, HK_LOW_MPC = 1, HK_LOW_LQR = 2, HK_LOW_E2E = 3;   // E2E: EndToEndKartAgent
         public const int HK_HIGH_MCTS = 0, HK_HIGH_FIXED = 1, HK_HIGH_NONE = 2;   // NONE: E2E with runQuasiMCTS off
@@ -350,6 +354,19 @@ namespace KartGame.AI.Native
         public float* b_branch;
     }
 
+    // hk_ppo_config: the trainer's constants (ML-Agents trainer_config: gamma, lambd; torch's Adam defaults)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HkPpoConfig
+    {
+        public float gamma;
+        public float lambd;
+        public int normalize_advantages;
+        public float adam_beta1;
+        public float adam_beta2;
+        public float adam_eps;
+        public uint seed;
+    }
+
     public static unsafe class Hk
     {
         const string Lib = "hk";   // libhk.so next to the player binary / in Assets/Plugins/x86_64
@@ -404,6 +421,15 @@ namespace KartGame.AI.Native
         [DllImport(Lib)] public static extern int hk_rollout_rows(IntPtr h);
         [DllImport(Lib)] public static extern int hk_rollout_close(IntPtr h);
         [DllImport(Lib)] public static extern IntPtr hk_rollout_ptr(IntPtr h, int field);
+        // PPO trainer: train an attached actor on the closed rollout, on the device (hk.h "PPO trainer")
+        [DllImport(Lib)] public static extern int hk_ppo_create(IntPtr h, int policy, HkPolicyDesc* critic, HkPpoConfig* cfg);
+        [DllImport(Lib)] public static extern int hk_ppo_advantages(IntPtr h, int trainer);
+        [DllImport(Lib)] public static extern int hk_ppo_minibatch(IntPtr h, int trainer, IntPtr rowsDev, int m, float eps, float beta, float* stats);
+        [DllImport(Lib)] public static extern int hk_ppo_adam(IntPtr h, int trainer, float lr);
+        [DllImport(Lib)] public static extern int hk_ppo_update(IntPtr h, int trainer, int epochs, int minibatch, float lr, float eps, float beta, float* stats);
+        [DllImport(Lib)] public static extern int hk_ppo_publish(IntPtr h, int trainer);
+        [DllImport(Lib)] public static extern IntPtr hk_ppo_ptr(IntPtr h, int trainer, int field);
+        [DllImport(Lib)] public static extern int hk_ppo_count(IntPtr h, int trainer, int field);
         // multi-GPU: one process per GPU, envs sharded by HkConfig.env_id_base; the only exchange is this all-gather over RCCL
         [DllImport(Lib)] public static extern int hk_comm_unique_id(byte* id128);
         [DllImport(Lib)] public static extern int hk_comm_init(IntPtr h, int worldSize, int rank, byte* id128);

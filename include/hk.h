@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define HK_ABI_VERSION 5
+#define HK_ABI_VERSION 6
 #define HK_MAX_AGENTS 8      /* the largest reference scene has 4; 5..8 agents per env is the synthetic extension of BASELINE configs[4] (start grid continued row by row) */
 #define HK_MAX_SECTIONS 64   /* Oval 24, Complex 41 */
 #define HK_NUM_SENSORS 9     /* MLAgent_Sensors.prefab */
@@ -498,6 +498,80 @@ int hk_rollout_begin(hk_handle h, int rows);
 int hk_rollout_rows(hk_handle h);               /* completed rows: decisions whose interval has fully been issued */
 int hk_rollout_close(hk_handle h);
 void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* field; NULL (hk_last_error) on a bad field or before any rollout */
+
+/* ---- PPO trainer: train an attached actor on a closed rollout, on the device ----------------------------------------------
+ * One trainer per hk_ppo_create: an attached actor (policy), a critic of its own and Adam over both; it allocates nothing before hk_ppo_create.
+ * ROWS: the trainer of policy p trains on the rows (t, e, j), t < R, e < E, j = the j-th of p's agent_slots, flattened in that order:
+ * row id = (t E + e) S + j, n = R E S, where R is the number of COMPLETED rows (hk_rollout_rows at hk_rollout_close; a rollout may close
+ * before all the rows hk_rollout_begin allotted, and the rest are never read).  The input of a row is the stacked input the actor saw there, rebuilt on the device from OBS, FIRST
+ * and RING0 by the rule of rollout.stacked_inputs (never materialised for the whole rollout); the bootstrap input of (e, j) is the last row's
+ * stack shifted by one with NEXT_OBS pushed (NEXT_OBS is the decision after the last completed row; unused where DONE[R - 1] != 0).
+ * CRITIC: n_layers x (Linear + Swish) on the actor's normalised, clipped input (the actor's normaliser), then one linear output; initial
+ * weights from an hk_policy_desc (W[], b[] the trunk, W_mu / b_mu the value head, n_branch = 0, in_dim = the actor's; hidden / n_layers
+ * within the actor's limits, other fields ignored).  It shares no weight with the actor (ML-Agents shared_critic: false).
+ * REWARD, DONE: r_t = DONE ? TERM_REWARD : REWARD (rollout.transition_rewards); every DONE != 0, the time-out (2) included, is terminal.
+ * GROUP_REWARD is not used: PPO ignores group rewards (POCA is out of scope).
+ * GAE per (e, j), backwards over t, V = V_OLD (the critic at hk_ppo_advantages), V_R = the bootstrap value, A_R = 0:
+ *   delta_t = r_t + gamma (1 - d_t) V_{t+1} - V_t;   A_t = delta_t + gamma lambd (1 - d_t) A_{t+1};   RET_t = A_t + V_t
+ * normalize_advantages: ADV = (A - mean) / (std + 1e-10) over all n rows (population std; mean and std in fp64, fixed order); RET keeps A unnormalised.
+ * LOSS over a minibatch of m valid rows, new heads mu, logits, value v; logp_c / logp_d exactly as the recorder computes LOGP_CONT of RAW and
+ * LOGP_DISC of BRANCH (so unchanged parameters give rho == 1 bit for bit):
+ *   rho_c = exp(logp_c - LOGP_CONT), rho_d = exp(logp_d - LOGP_DISC)
+ *   L_pi = -mean over rows and {c, d} of min(rho A, clip(rho, 1 - eps, 1 + eps) A)          (ML-Agents' per-column trust region)
+ *   L_v  = mean max((RET - v)^2, (RET - V_OLD - clip(v - V_OLD, -eps, eps))^2)
+ *   H    = 0.5 log(2 pi e) + log_sigma - sum softmax log_softmax
+ *   L    = L_pi + 0.5 L_v - beta mean H
+ * Gradients follow torch's conventions at ties: min / max split the gradient evenly, clip passes it inside [lo, hi] inclusive.
+ * Departure from ML-Agents: no 1e-7 inside the log-probabilities and the entropy (the recorder has none either).
+ * ADAM over the actor's and the critic's parameters (the normaliser is frozen), step s = 1, 2, ... counted per trainer, in fp32, in this order:
+ *   m = b1 m + (1 - b1) g;  v = b2 v + ((1 - b2) g) g;  p = p - lr (m / c1) / (sqrt(v / c2) + eps)
+ * with (1 - b1), (1 - b2) rounded to fp32 once, c1 = 1 - b1^s and c2 = 1 - b2^s evaluated in fp64 and rounded to fp32; every operation
+ * rounded to fp32 (no fused multiply-add), sqrt and division correctly rounded.
+ * PARAMS / GRAD / ADAM_M / ADAM_V: one flat fp32 vector, torch layout (W [out][in]): the actor's W[0], b[0], W[1], b[1], ..., W_mu [H], b_mu [1],
+ * log_sigma [1], W_branch [n_branch][H], b_branch [n_branch], then the critic's W[0], b[0], ..., W_v [Hc], b_v [1].
+ * ENTRY POINTS (HK_ERR_INVALID with hk_last_error on: a bad trainer index or field; a rollout that is open, never opened, closed with no
+ * completed row, or that began before
+ * the policy was attached; a trainer whose hk_ppo_advantages ran on an earlier rollout than the current one, for minibatch / update; a critic
+ * whose in_dim or limits do not fit; publish while a rollout is open):
+ *   hk_ppo_create      -> trainer index.  Copies the actor's parameters as attached into the master copy; cfg NULL: the defaults below.
+ *   hk_ppo_advantages  the critic over the n rows and the E S bootstrap inputs, then GAE: V_OLD, ADV, RET [n].
+ *   hk_ppo_minibatch   the loss of the rows rows_dev[0 .. m) (a device pointer) and its gradient into GRAD.  An id outside [0, n) is skipped
+ *                      (counted in the stats, never read).  stats (host, [HK_PPO_STATS], NULL: none; non-NULL synchronises):
+ *                      L_pi, L_v, mean H, approx-KL (mean over rows and {c, d} of old - new logp), clip fraction (of rows x {c, d}), skipped rows.
+ *   hk_ppo_adam        one Adam step from GRAD.
+ *   hk_ppo_update      epochs x (a permutation of the n rows generated on the device, keyed by the shuffle seed and the trainer's epoch count;
+ *                      floor(n / minibatch) minibatches (one of n rows when n < minibatch), each hk_ppo_minibatch + hk_ppo_adam), then
+ *                      hk_ppo_publish.  stats: the mean over the last epoch's minibatches.
+ *   hk_ppo_publish     re-lays the master actor parameters into the attached policy's inference copies (what hk_policy_attach builds).
+ *   hk_ppo_ptr / hk_ppo_count   device pointer / element count of an HK_PPO_* field.  MB_MU, MB_LOGITS [m][n_branch], MB_VALUE: the heads and
+ *                      the value of the last minibatch's rows (a debug tap).  PERM (int32 [n]): the row permutation of the last epoch of the last
+ *                      hk_ppo_update on the current advantages (the k-th epoch of a trainer, k = 0, 1, ..., is keyed by (seed, k)).
+ * Row ids of hk_ppo_minibatch are read on hk_stream: a caller that writes them on another stream orders the two first (PPOTrainer does).
+ * Out of scope: updating the normaliser (frozen as attached), self-play opponent swaps and ELO, POCA and group rewards, LSTM memory,
+ * gradient clipping, multi-GPU gradient all-reduce, bf16 training.  Everything is asynchronous on hk_stream. */
+#define HK_PPO_STATS 6
+typedef struct hk_ppo_config {
+    float gamma;                    /* 0.99 */
+    float lambd;                    /* 0.95 */
+    int32_t normalize_advantages;   /* 1 */
+    float adam_beta1;               /* 0.9 */
+    float adam_beta2;               /* 0.999 */
+    float adam_eps;                 /* 1e-8 */
+    uint32_t seed;                  /* shuffle seed */
+} hk_ppo_config;
+typedef enum hk_ppo_field {
+    HK_PPO_PARAMS = 0, HK_PPO_GRAD, HK_PPO_ADAM_M, HK_PPO_ADAM_V, HK_PPO_V_OLD, HK_PPO_ADV, HK_PPO_RET,
+    HK_PPO_MB_MU, HK_PPO_MB_LOGITS, HK_PPO_MB_VALUE, HK_PPO_PERM,
+    HK_PPO_FIELDS
+} hk_ppo_field;
+int hk_ppo_create(hk_handle h, int policy, const hk_policy_desc* critic, const hk_ppo_config* cfg);
+int hk_ppo_advantages(hk_handle h, int trainer);
+int hk_ppo_minibatch(hk_handle h, int trainer, const int32_t* rows_dev, int m, float eps, float beta, float* stats /*[HK_PPO_STATS]*/);
+int hk_ppo_adam(hk_handle h, int trainer, float lr);
+int hk_ppo_update(hk_handle h, int trainer, int epochs, int minibatch, float lr, float eps, float beta, float* stats /*[HK_PPO_STATS]*/);
+int hk_ppo_publish(hk_handle h, int trainer);
+void* hk_ppo_ptr(hk_handle h, int trainer, int field);
+int hk_ppo_count(hk_handle h, int trainer, int field);
 
 /* ---- multi-GPU: the path's ONE exchange step ---------------------------------------------------------------
  * Race instances are independent (one RacingEnvController owns its own Agents[] / Sections[], REC:46-52): every rank steps its

@@ -1,0 +1,76 @@
+#!/usr/bin/env python3
+"""What a PPO update costs on the RL workload (bench.py --workload rl: 2v2 Oval, every agent LowMode RL, one 312 -> 256 x 3 actor per team,
+DecisionPeriod 2, rewards on): one rollout of R rows is collected (timed), then for team 0's trainer (critic 312 -> 256 x 3):
+hk_ppo_advantages, and one-epoch hk_ppo_update calls at minibatch 512 (ML-Agents' batch_size) and at a GPU-sized minibatch; every timing
+ends in a device synchronise, medians of --repeats.  One JSON line.
+FLOP count per trained row (stated, not measured): forward + backward of actor and critic = 3 x forward, forward = 2 x (weights of the trunks
+and heads) per row: 3 x 2 x (312 x 256 + 2 x 256 x 256 + 4 x 256 + 312 x 256 + 2 x 256 x 256 + 256) = 6 x 423 168 = 2.54 MFLOP per row at this shape."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PEAK_TF = 157.3          # MI355X f32 MFMA peak (TFLOP/s)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--envs", type=int, default=16384)
+    ap.add_argument("--rows", type=int, default=64, help="R: rows (decisions) per rollout")
+    ap.add_argument("--big", type=int, default=32768, help="the GPU-sized minibatch")
+    ap.add_argument("--repeats", type=int, default=3)
+    a = ap.parse_args()
+    import numpy as np
+    import hierarchicalkarting_amd as hk
+    from hierarchicalkarting_amd import _lib
+    from hierarchicalkarting_amd.policy import Policy
+    E, A, P, R = a.envs, 4, 2, a.rows
+    env = hk.RacingEnv(hk.make_config(E, A, low_mode=[_lib.HK_LOW_RL] * A, jitter_seed=0x5EED0000, rewards=1))
+    in_dim = env.obs_dim * 4
+    env.attach_policy(Policy.random(in_dim, 256, 3, seed=101), [0, 1], P)
+    env.attach_policy(Policy.random(in_dim, 256, 3, seed=202), [2, 3], P)
+    env.reset()
+    env.step(256)
+    env.synchronize()
+    t0 = time.perf_counter()
+    env.rollout_begin(R); env.step(R * P); env.rollout_close()
+    env.synchronize()
+    collect_ms = (time.perf_counter() - t0) * 1e3
+    tr = env.ppo_trainer(0, seed=1)
+    n = R * E * 2
+
+    def timed(f):
+        out = []
+        for _ in range(a.repeats):
+            env.synchronize()
+            t = time.perf_counter()
+            f()
+            env.synchronize()
+            out.append((time.perf_counter() - t) * 1e3)
+        return statistics.median(out), out
+
+    tr.advantages()                                  # (allocates; first launches)
+    adv_ms, adv_runs = timed(tr.advantages)
+    H, K0 = 256, in_dim
+    w = K0 * H + 2 * H * H + 4 * H + K0 * H + 2 * H * H + H
+    flop_row = 3 * 2 * w
+    res = {}
+    for mb in (512, a.big):
+        tr.update(1, mb, 1e-5, 0.2, 5e-3)            # (workspace, first launches)
+        ms, runs = timed(lambda: tr.update(1, mb, 1e-5, 0.2, 5e-3))
+        rows = (n // min(mb, n)) * min(mb, n)
+        tf = rows * flop_row / (ms * 1e-3) / 1e12
+        res[str(mb)] = {"update_ms_per_epoch": ms, "runs": runs, "rows_per_s": rows / (ms * 1e-3), "tflops": tf, "peak_fraction": tf / PEAK_TF,
+                        "update_over_collection": ms / collect_ms}
+    env.close()
+    print(json.dumps({"metric": "PPO update on the RL workload (one actor + critic, one epoch)", "advantages_ms": adv_ms, "advantages_runs": adv_runs,
+                      "collect_ms": collect_ms, "minibatch": res,
+                      "config": {"envs": E, "agents": A, "rows": R, "n_rows": n, "flop_per_row": flop_row, "peak_tflops": PEAK_TF}}))
+
+
+if __name__ == "__main__":
+    main()
