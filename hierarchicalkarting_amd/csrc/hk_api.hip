@@ -126,7 +126,7 @@ struct hk_context {
     int device = 0;
     Tuning tune;
     hipStream_t stream = nullptr;
-    hipStream_t qstream[hk::SPLIT_WAYS_MAX - 1] = {};   // the other parts of a split batch run here (issue_rounds_split)
+    hipStream_t qstream[hk::SPLIT_WAYS_MAX - 1] = {};   // the other parts of a split batch run here (issue_rounds)
     bool env_ready = false;
     hk_config cfg{};
     std::vector<hk_section> sections;
@@ -153,11 +153,17 @@ struct hk_context {
     // looks (verify_optimistic): an env the plan missed kept its ticks, the belief is dropped and the laggards are finished like those of a long call.
     long long lock_tick = -1;
     bool opt_pending = false;
+    bool exact_plan = false;                 // the current fixed-round call follows the exact plan of a field in lock-step: its last round is the tick launches alone
     int exact_idx = 0, exact_total = 0;      // round counter of the current exact plan (issue_rounds is called in pieces)
+    // what else issue_rounds carries from piece to piece of a call (apply_plan / step_ticks set them; finish_ticks and the end of step_rounds clear them)
+    bool fold_split = false;                 // a folded call on the two-stream schedule: each part's last tick launch is its completion guard
+    int arm_ticks = 0;                       // > 0: a folded call; each part's next tick launch — its first of the call — adds these ticks to every env's count
+    int guard_rounds_left = 0;               // > 0: a folded call on one stream; the tick launch that brings it to 0 is the call's last, its guard
+    bool last_solve_skippable = false;       // ... of a plain handle: no env can park in that last round, so its solver launch has nothing to solve
     long long mcts_async_deadline = -1;      // short calls of planner handles: the believed episode step at which the search launch running on mcts_stream is first used (-1: none in flight)
     bool step_pending = false;
     bool split = false;            // the current call runs the batch as two halves on two streams (issue_rounds)
-    int round_half[hk::SPLIT_WAYS_MAX] = {};    // each part's own round counter (the parity picks its queue set)
+    hk::RoundPart parts[hk::SPLIT_WAYS_MAX];    // the parts of the batch, across calls: each keeps its own round and B1-launch counters
     hipEvent_t ev_fork = nullptr, ev_join[hk::SPLIT_WAYS_MAX - 1] = {};
     hipStream_t mcts_stream = nullptr;                  // the search launch of a replan runs here, beside the tick launches up to the plans' deadline (step_ticks, pause mode)
     hipEvent_t ev_mcts_go = nullptr, ev_mcts_done = nullptr;
@@ -535,118 +541,95 @@ int hk_set_actions(hk_handle h, const float* steer, const int32_t* branch)
     return HK_OK;
 }
 
-// `rounds` rounds of {fused tick kernel (up to RUN_CAP ticks per env), queued multi-player solves}
-static int issue_rounds_split(hk_handle h, int rounds);
+// `rounds` rounds of the batch as K parts (hk_env_host.h RoundPart): the whole batch on the handle's stream or, a split call, SPLIT_WAYS parts (lane groups
+// [0, E/2) and [E/2, E), each with its own pair of queue sets) on as many streams.  A round of a part is {tick launch (up to run_cap ticks per env), B1
+// launch (the fission schedule), solver launch (the queued multi-player games)} back to back.  Two parts: while one half waits for its handful of solves (one
+// solve's latency: 35 - 59 us of an otherwise idle GPU per round — a fifth of a 20-tick call) the other half's tick kernel has the whole GPU.  Nothing is
+// deferred: a queued game still costs its env one round.  The streams are joined before anything else touches the state (the guard kernel, a regroup, a getter).
 static int issue_rounds(hk_handle h, int rounds)
 {
-    if (h->split && rounds > 0) return issue_rounds_split(h, rounds);
-    hipEvent_t e = h->prof.begin(h->stream);
-    bool first = true;
-    for (int r = 0; r < rounds; r++) {
-        int rc = throttle_mark(h, r);
-        if (rc) return rc;
-        rc = hk::env_launch_run(h->dev, h->cfg, h->stream, h->err);
-        if (rc) { g_last_error = h->err; return rc; }
-        e = h->prof.chain(0, e, first, h->stream);
-        if (h->dev.exact_plan && ++h->exact_idx == h->exact_total) { h->dev.b1_due = false; h->dev.round += 1; first = false; continue; }     // (the plan's last round: no solve tick is left in the call)
-        if (h->dev.b1_due) {
-            rc = hk::env_launch_b1(h->dev, h->cfg, h->stream, h->err);
-            if (rc) { g_last_error = h->err; return rc; }
-            e = h->prof.chain(5, e, false, h->stream);
+    hk::EnvDevice& d = h->dev;
+    const int K = h->split && rounds > 0 ? SPLIT_WAYS : 1, E = h->cfg.num_envs;      // (no round: nothing to fork for)
+    hk::RoundPart* const P = h->parts;
+    if (K > 1) {
+        for (int k = 0; k < K - 1; k++) {
+            if (!h->qstream[k]) HK_HIP(h, hipStreamCreateWithFlags(&h->qstream[k], hipStreamNonBlocking));
+            if (!h->ev_join[k]) HK_HIP(h, hipEventCreateWithFlags(&h->ev_join[k], hipEventDisableTiming));
         }
-        rc = hk::env_launch_lqn(h->dev, h->cfg, h->stream, h->err);
-        if (rc) { g_last_error = h->err; return rc; }
-        if (h->dev.lqn_launched) e = h->prof.chain(1, e, false, h->stream);
-        first = false;
+        if (!h->ev_fork) HK_HIP(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+        // The periodic regroup by solve phase, several parts: counted once per piece of a call and run here, before the fork, where the streams are joined;
+        // the rounds issued below count toward the next one, so the count restarts at `rounds`.  (One part: counted round by round, below.)
+        if ((d.rounds_since_regroup += rounds) >= d.regroup_rounds) {
+            if (split_join(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)");
+            int rcg = hk::env_launch_regroup(d, h->cfg, h->stream, h->err);
+            if (rcg) { g_last_error = h->err; return rcg; }
+            d.rounds_since_regroup = rounds;
+        }
     }
-    if (first && e) h->prof.pool.push_back(e);          // no round issued: the opening event goes back
-    return HK_OK;
-}
-
-// The batch as two halves (lane groups [0, E/2) and [E/2, E), each with its own pair of queue sets) on two streams: a round of
-// one half is {tick kernel, solver kernel} back to back as before, but while one half waits for its handful of solves (one
-// solve's latency: 35 - 59 us of an otherwise idle GPU per round — a fifth of a 20-tick call) the other half's tick kernel has
-// the whole GPU.  Nothing is deferred: a queued game still costs its env one round.  Both streams are joined before anything
-// else touches the state (the guard kernel, a regroup, a getter).
-static int issue_rounds_split(hk_handle h, int rounds)
-{
-    const int K = SPLIT_WAYS;
-    for (int k = 0; k < K - 1; k++) {
-        if (!h->qstream[k]) HK_HIP(h, hipStreamCreateWithFlags(&h->qstream[k], hipStreamNonBlocking));
-        if (!h->ev_join[k]) HK_HIP(h, hipEventCreateWithFlags(&h->ev_join[k], hipEventDisableTiming));
-    }
-    if (!h->ev_fork) HK_HIP(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    const int E = h->cfg.num_envs;
-    int cut[hk::SPLIT_WAYS_MAX + 1];                       // part k: lane groups [cut[k], cut[k + 1]) (a block of the tick kernel holds 64 lane groups)
-    for (int k = 0; k <= K; k++) cut[k] = k == K ? E : (int)(((long long)E * k / K + 127) / 128 * 128);     // (whole blocks of the 512-thread form too)
-    if ((h->dev.rounds_since_regroup += rounds) >= h->dev.regroup_rounds) {  // the periodic regroup by solve phase, here where the streams are joined
-        if (split_join(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)");
-        int rcg = hk::env_launch_regroup(h->dev, h->cfg, h->stream, h->err);
-        if (rcg) { g_last_error = h->err; return rcg; }
-        h->dev.rounds_since_regroup = rounds;      // (the rounds issued below count toward the next one)
-    }
-    hipStream_t st[hk::SPLIT_WAYS_MAX];
-    hipEvent_t e[hk::SPLIT_WAYS_MAX];
-    st[0] = h->stream;
-    for (int k = 1; k < K; k++) st[k] = h->qstream[k - 1];
-    h->round_half[0] = h->dev.round;          // sets 0 / 1 are also the unsplit launches' sets: continue their parity
-    if (!h->split_open) {          // (open: the call before left its parts on these streams — this one continues them)
+    // part k: lane groups [cut(k), cut(k + 1)) — whole blocks of the tick kernel (64 lane groups; 128 in its 512-thread form).  Part 0 of an unsplit call
+    // is everything, and continues the parity of its queue sets 0 / 1 where the call before — split or not — left it.
+    auto cut = [&](int k) { return k == K ? E : (int)(((long long)E * k / K + 127) / 128 * 128); };
+    for (int k = 0; k < K; k++) { P[k].stream = k ? h->qstream[k - 1] : h->stream; P[k].index = k; P[k].slot0 = cut(k); P[k].slot1 = cut(k + 1); }
+    if (K > 1 && !h->split_open) {          // (open: the call before left its parts on these streams — this one continues them)
         HK_HIP(h, hipEventRecord(h->ev_fork, h->stream));
-        for (int k = 1; k < K; k++) HK_HIP(h, hipStreamWaitEvent(st[k], h->ev_fork, 0));
+        for (int k = 1; k < K; k++) HK_HIP(h, hipStreamWaitEvent(P[k].stream, h->ev_fork, 0));
     }
-    h->split_open = true;
-    for (int k = 0; k < K; k++) e[k] = h->prof.begin(st[k]);
+    if (K > 1) h->split_open = true;
+    hipEvent_t e[hk::SPLIT_WAYS_MAX];       // one profiler event chain per part
+    for (int k = 0; k < K; k++) e[k] = h->prof.begin(P[k].stream);
+    const bool b1 = d.fission && d.P.any_lqr != 0;      // the fission schedule: a tick launch parks its envs at their solve tick, env_b1_kernel is next on that stream
+    const int cadence = hk::solve_cadence(h->cfg);
+    // a folded call arms inside each part's first tick launch of its first piece (no env_arm_kernel in front of the fork)
+    const int arm = h->arm_ticks;
     bool first = true;
     int rc = HK_OK;
     // Round 6, from the kernel trace of the driver's 20-tick call (profiles/r06_b_short_call_trace.txt): the HOST is what the GPU waits for at the start of a
     // short call — a launch costs it 6 - 8 us, and with one part's whole round issued before the other's first launch the second stream began 93 us into a
     // 895 us call.  The launches of a round are therefore issued kind by kind: every part's tick launch, then every part's B1 launch, then the solver launches.
-    // A folded call (step_ticks: fold_split) arms inside each part's first tick launch and makes each part's last tick launch its completion guard: no
-    // env_arm_kernel in front of the fork, no env_check_kernel behind the join.
-    const int arm = h->dev.arm_ticks;
-    h->dev.arm_ticks = 0;
-    bool b1due[hk::SPLIT_WAYS_MAX] = {}, inw[hk::SPLIT_WAYS_MAX] = {};
-    auto part = [&](int k) { h->dev.slot0 = cut[k]; h->dev.slot1 = cut[k + 1]; h->dev.qbase = 2 * k; h->dev.round = h->round_half[k]; };
     for (int r = 0; r < rounds && rc == HK_OK; r++) {
         if ((rc = throttle_mark(h, r))) break;
-        const bool plan_last = h->dev.exact_plan && h->exact_idx + 1 == h->exact_total;      // (the plan's last round: the tick launches alone)
+        // the periodic regroup, one part: counted per round — it may fall between two rounds of a call
+        if (K == 1 && ++d.rounds_since_regroup >= d.regroup_rounds && (rc = hk::env_launch_regroup(d, h->cfg, h->stream, h->err))) break;
+        // The completion guard of a folded call (no env_check_kernel behind it; lazy and pause calls have none).  One part: the tick launch that ends the
+        // countdown over all the pieces of the call.  A folded split call (one piece): each part's tick launch in the last round.
+        const bool guard = K > 1 ? h->fold_split && r == rounds - 1 : h->guard_rounds_left > 0 && --h->guard_rounds_left == 0;
+        const bool plan_last = h->exact_plan && ++h->exact_idx == h->exact_total;      // (once per round, not per part)
         for (int k = 0; k < K && rc == HK_OK; k++) {
-            part(k);
-            if (r == 0) h->dev.arm_ticks = arm;
-            if (h->dev.fold_split && r == rounds - 1) h->dev.guard_rounds_left = 1;
-            rc = hk::env_launch_run_only(h->dev, h->cfg, st[k], h->err);
-            if (rc) break;
-            e[k] = h->prof.chain(0, e[k], first, st[k]);
-            b1due[k] = h->dev.b1_due; h->dev.b1_due = false;
-            if (plan_last) h->round_half[k] = h->dev.round + 1;
+            if ((rc = hk::env_launch_run(d, h->cfg, P[k], r == 0 ? arm : 0, guard, h->err))) break;
+            e[k] = h->prof.chain(0, e[k], first, P[k].stream);
         }
-        if (h->dev.exact_plan) h->exact_idx += 1;
+        h->arm_ticks = 0;
         first = false;
-        if (plan_last || rc) continue;
-        for (int k = 0; k < K && rc == HK_OK; k++) {
-            inw[k] = false;
-            if (!b1due[k]) continue;
-            part(k);
-            h->dev.b1_due = true;
-            rc = hk::env_launch_b1(h->dev, h->cfg, st[k], h->err);          // (decides whether this round's games are solved in-wave)
-            if (rc) break;
-            inw[k] = h->dev.inwave;
-            e[k] = h->prof.chain(5, e[k], false, st[k]);
+        if (rc) break;
+        if (plan_last) {            // the exact plan's last round is the tick launches alone: no solve tick is left in the call
+            for (int k = 0; k < K; k++) P[k].round += 1;
+            continue;
         }
+        // in-wave solves (hk_lq_spread.h lqs_inwave) once the field has spread — while it stands close (BULK_TICKS after a reset of every env) nearly every ego
+        // holds a game and the queues + the pair solver's 32 games per wave are several times cheaper per game  (HK_INWAVE=1, tests: in every round)
+        const bool inwave = b1 && hk::inwave_now(d);
+        for (int k = 0; b1 && k < K && rc == HK_OK; k++) {
+            if ((rc = hk::env_launch_b1(d, h->cfg, P[k], inwave, h->err))) break;
+            P[k].b1_launches += 1; P[k].meter_stale = false;          // (the launch counted into its meter slot and started stale words over)
+            e[k] = h->prof.chain(5, e[k], false, P[k].stream);
+        }
+        // The guard of a fixed-round call of a plain handle on one stream was the call's last tick launch: an env that queued a game there would be parked,
+        // i.e. the call incomplete, which the round count rules out.  The skip is verified ON THE DEVICE by that very launch: as the guard it raises status
+        // bit 2 for any env it leaves with ticks or a phase (a parked env has phase 1 or 2), and the next getter reports it.  Nothing to solve: a one-tick
+        // call is 3 launches, not 4.
+        const bool skip = guard && h->last_solve_skippable;
         for (int k = 0; k < K && rc == HK_OK; k++) {
-            part(k);
-            h->dev.inwave = inw[k];
-            rc = hk::env_launch_lqn(h->dev, h->cfg, st[k], h->err);          // (advances dev.round)
-            if (rc) break;
-            if (h->dev.lqn_launched) e[k] = h->prof.chain(1, e[k], false, st[k]);
-            h->round_half[k] = h->dev.round;
+            if ((rc = hk::env_launch_lqn(d, h->cfg, P[k], inwave, skip, h->err))) break;
+            if (!inwave) e[k] = h->prof.chain(1, e[k], false, P[k].stream);          // (a skipped launch still is a solver stage to the profiler, an in-wave round has none)
+            P[k].round += 1;
+            // a round retires at least one solve cadence; counted with part 0 only, at once: the next part's solver launch already sizes its grid by it
+            if (k == 0) d.call_ticks_issued = std::min(d.call_ticks_issued + cadence, d.call_ticks);
         }
     }
-    h->dev.inwave = false;
-    h->dev.slot0 = 0; h->dev.slot1 = 0; h->dev.qbase = 0; h->dev.round = h->round_half[0];
-    if (first) for (int k = 0; k < K; k++) if (e[k]) h->prof.pool.push_back(e[k]);
-    // a folded call (nothing follows its rounds on the handle's stream: no guard kernel, no report) leaves its parts open for the next one
-    if (!h->dev.fold_split || rc) { if (split_join(h) && !rc) rc = fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)"); }
+    if (first) for (int k = 0; k < K; k++) if (e[k]) h->prof.pool.push_back(e[k]);          // no round issued: the opening events go back
+    // a folded split call (nothing follows its rounds on the handle's stream: no guard kernel, no report) leaves its parts open for the next one; any other
+    // call, and any error, joins
+    if (K > 1 && (!h->fold_split || rc) && split_join(h) && !rc) rc = fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)");
     if (rc) g_last_error = h->err;
     return rc;
 }
@@ -666,7 +649,7 @@ static int issue_check(hk_handle h, bool lazy)
 // of which costs it a round), issue the rounds the laggard needs and look again.
 static int finish_ticks(hk_handle h)
 {
-    h->dev.last_solve_skippable = false; h->dev.guard_rounds_left = 0; h->dev.exact_plan = false; h->throttle = false;      // (the laggards' rounds are plain rounds)
+    h->last_solve_skippable = false; h->guard_rounds_left = 0; h->exact_plan = false; h->throttle = false;      // (the laggards' rounds are plain rounds)
     bool packed = false;
     for (int guard = 0; guard < 1024 && h->step_pending; guard++) {
         HK_HIP(h, hipStreamSynchronize(h->stream));
@@ -675,7 +658,7 @@ static int finish_ticks(hk_handle h)
         int rc = hk::env_launch_regroup(h->dev, h->cfg, h->stream, h->err);      // the laggards into the first lane groups
         if (rc) { g_last_error = h->err; return rc; }
         packed = true;
-        h->split = false;                // ... which all lie in the first half: the tail runs as one batch on one stream
+        h->split = false;                // ... which all lie in the first half: the tail runs as one batch on one stream (part 0: its round parity goes on)
         // Rounds for the slowest env if it met no further multi-player game (+ 1), not for the worst case (a round per cadence): the
         // batch ends with a look at the device anyway, and two thirds of the worst-case rounds used to find nothing to do (94 of 141 in
         // the headline's 3 072-tick call, ~18 us each).  An env that does park on every solve tick still gets a third of its ticks per batch.
@@ -780,12 +763,12 @@ static int throttle_mark(hk_handle h, int r)
 //   pause              long call of a planner handle without actors: stretches of rounds between search launches (step_pause)
 //   lazy               the rounds a field without multi-player games needs; the laggards are finished by the next entry point (finish_ticks)
 //   fold               the first tick launch arms and the last one is the completion guard (no env_arm_kernel, no env_check_kernel)
-//   split              two halves on two streams (issue_rounds_split); fold_split: each part's last tick launch is its guard; continue_split: a short
+//   split              two halves on two streams (issue_rounds); fold_split: each part's last tick launch is its guard; continue_split: a short
 //                      folded split call continues the parts the call before left open
 //   eager, run_cap     P.eager (the eager assembly, hk_env_run.h) and P.run_cap (ticks an env may run per launch)
 //   throttle           stay a bounded number of rounds ahead of the GPU and look at the meter (throttle_mark)
 //   rounds             rounds issued up front (pause: 0, the stretches decide); exact_plan: the optimistic plan, exactly `rounds` launches
-//   last_solve_skippable, guard_rounds_left    -> EnvDevice (hk_env_host.h); rounds_mode: hk_schedule_info's "rounds"
+//   last_solve_skippable, guard_rounds_left    -> the handle, for issue_rounds; rounds_mode: hk_schedule_info's "rounds"
 struct CallPlan {
     int n_ticks = 0, lat_min = 0, defer = 0;
     long long T0 = -1, t_req = -1;
@@ -836,7 +819,7 @@ static CallPlan plan_call(const hk_context* h, int n_ticks)
     // the eager assembly (hk_env_run.h) for plain quad handles, and in pause mode too: requests are posted on the same ticks, a round earlier at most
     // (configs[2]: 61.4 -> 63.6 M env-steps/s).  Planner / actor handles outside pause mode keep their deadline arithmetic as it was.
     p.eager = quad && (plain || p.pause);
-    // Two halves on two streams (issue_rounds_split) for every call of a plain handle of >= 8 192 envs: round 4 split the long calls (1 472 vs 1 392 M
+    // Two halves on two streams (issue_rounds) for every call of a plain handle of >= 8 192 envs: round 4 split the long calls (1 472 vs 1 392 M
     // env-steps/s in round 3's protocol window; headline 1 221 -> 1 292 M, race start 439 -> 458 M), round 6 every call, with the parts joined lazily.
     p.split = plain && p.eager && h->tune.split != 0 && cfg.num_envs >= 8192;
     p.fold_split = p.fold && p.split;
@@ -906,15 +889,15 @@ static void apply_plan(hk_handle h, const CallPlan& p)
     if (h->split != h->meter_was_split && h->dev.game_stats) {
         // the batch changes shape: the parts that stop launching (or start again after a long time) must not be read with their old words
         // (no launch for it: the parts' next B1 launches start their words over, the host reads only the parts a call ran as — meter_look)
-        h->dev.meter_fresh |= ((1u << hk::GAME_METER_PARTS) - 1u) & ~1u;
+        for (int k = 1; k < hk::SPLIT_WAYS_MAX; k++) h->parts[k].meter_stale = true;
         h->meter_was_split = h->split;
     }
     apply_meter(h);                                     // (after P.eager and the previous call's ticks)
-    h->dev.exact_plan = p.exact_plan;
-    h->exact_idx = 0; h->exact_total = p.rounds;           // (read only while dev.exact_plan is set)
-    h->dev.guard_rounds_left = p.guard_rounds_left;
-    h->dev.fold_split = p.fold_split;
-    h->dev.last_solve_skippable = p.last_solve_skippable;
+    h->exact_plan = p.exact_plan;
+    h->exact_idx = 0; h->exact_total = p.rounds;           // (read only while exact_plan is set)
+    h->guard_rounds_left = p.guard_rounds_left;
+    h->fold_split = p.fold_split;
+    h->last_solve_skippable = p.last_solve_skippable;
 }
 
 // A search launch on the side stream, behind everything issued so far on the handle's stream; the handle's stream waits for ev_mcts_done before anything
@@ -1033,12 +1016,11 @@ static int step_rounds(hk_handle h, const CallPlan& p)
     if (!p.lazy && h->dev.fission && (h->meter_ticks += p.n_ticks) >= METER_TICKS) { h->meter_ticks = 0; if ((rc = meter_copy(h, false))) return rc; }
     record_schedule(h, p);
     if (p.exact_plan) h->opt_pending = true;
-    // (an exact plan's last round is the tick launch alone and never reaches the solver launch that consumes this flag: left set, the first solver launch
-    // of the rounds that finish a missed env — verify_optimistic — would be skipped and the env would resume on stale controls; found by the fold + skew
-    // modes of tests/test_optimistic_plan_gpu.py, round 6)
-    h->dev.exact_plan = false;
-    h->dev.last_solve_skippable = false;
-    h->dev.guard_rounds_left = 0;
+    // (the call's plan ends here: the rounds that finish a missed env — verify_optimistic — are plain rounds, none of them skips its solver launch; the
+    // fold + skew modes of tests/test_optimistic_plan_gpu.py, round 6)
+    h->exact_plan = false;
+    h->last_solve_skippable = false;
+    h->guard_rounds_left = 0;
     return HK_OK;
 }
 
@@ -1059,7 +1041,7 @@ static int step_ticks(hk_handle h, int n_ticks)
         if (rc) { g_last_error = h->err; return rc; }
     }
     apply_plan(h, p);
-    if (p.fold) h->dev.arm_ticks = n_ticks;
+    if (p.fold) h->arm_ticks = n_ticks;
     else if ((rc = hk::env_launch_arm(h->dev, h->cfg, n_ticks, h->stream, h->err))) { g_last_error = h->err; return rc; }
     return p.pause ? step_pause(h, p) : step_rounds(h, p);
 }

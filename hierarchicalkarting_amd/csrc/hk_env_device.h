@@ -601,8 +601,8 @@ __device__ inline void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
 
 // The games-per-launch meter (round 6; the host's choice between in-wave solves and queues + the pair solver's launch, hk_api.hip).  Per part of the batch p
-// (issue_rounds_split; 0 for an unsplit launch) four words at game_stats[GAME_METER + 4 p]: [0 .. 2] the multi-player games (egos that hold one) the part's
-// B1 launches assembled — the part's launch k (EnvDevice::meter_launches, counted by the host; NOT dev.round, which the tick-only last round of an exact
+// (hk_env_host.h RoundPart; 0 for an unsplit launch) four words at game_stats[GAME_METER + 4 p]: [0 .. 2] the multi-player games (egos that hold one) the part's
+// B1 launches assembled — the part's launch k (RoundPart::b1_launches, counted by the host; NOT its round counter, which the tick-only last round of an exact
 // plan advances without a B1 launch) counts into slot k % 3, clears slot (k + 1) % 3 and reads the finished launch k - 1's total from slot (k + 2) % 3 —
 // and [3] a decaying maximum of those totals, m <- max(total of launch k - 1, m - (m >> 2)) (x 3/4 per launch: the handful of laggards' launches at the end
 // of a call say nothing about the field); a launch that starts the part over (the batch changed shape) sets m = 0.  hk_prof_meter reads the words;

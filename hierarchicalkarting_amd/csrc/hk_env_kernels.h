@@ -276,20 +276,12 @@ inline int env_rounds_for(const hk_config& cfg, int n_ticks, int cap = RUN_CAP, 
 // plain handles issue these, look at the device and finish the laggards: hk_api.hip finish_ticks).
 inline int env_rounds_min(int n_ticks, int cap) { return (n_ticks + cap - 1) / cap; }
 
-inline int env_launch_run(EnvDevice& d, const hk_config& cfg, hipStream_t stream, std::string& err)
-{
-    if (++d.rounds_since_regroup >= d.regroup_rounds) {
-        d.rounds_since_regroup = 0;
-        int rc = HK_GA_CALL(d, launch_regroup(d, cfg, stream, err));
-        if (rc) return rc;
-    }
-    return HK_GA_CALL(d, launch_run(d, cfg, stream, err));
-}
-// (the split batch: no periodic regroup between the halves' launches — the caller regroups where both streams are joined)
-inline int env_launch_run_only(EnvDevice& d, const hk_config& cfg, hipStream_t stream, std::string& err) { return HK_GA_CALL(d, launch_run(d, cfg, stream, err)); }
-inline int env_launch_b1(EnvDevice& d, const hk_config& cfg, hipStream_t stream, std::string& err) { return HK_GA_CALL(d, launch_b1(d, cfg, stream, err)); }
-inline int env_launch_lqn(EnvDevice& d, const hk_config& cfg, hipStream_t stream, std::string& err) { return HK_GA_CALL(d, launch_lqn(d, cfg, stream, err)); }
-// pack the envs that still have ticks to run into the first lane groups (the tail of a call; see env_regroup_count_kernel)
+// the three launches of a part's round (hk_api.hip issue_rounds; the arguments: hk_env_host.h GaOps)
+inline int env_launch_run(EnvDevice& d, const hk_config& cfg, const RoundPart& part, int arm_ticks, bool guard, std::string& err) { return HK_GA_CALL(d, launch_run(d, cfg, part, arm_ticks, guard, err)); }
+inline int env_launch_b1(EnvDevice& d, const hk_config& cfg, const RoundPart& part, bool inwave, std::string& err) { return HK_GA_CALL(d, launch_b1(d, cfg, part, inwave, err)); }
+inline int env_launch_lqn(EnvDevice& d, const hk_config& cfg, const RoundPart& part, bool inwave, bool skip, std::string& err) { return HK_GA_CALL(d, launch_lqn(d, cfg, part, inwave, skip, err)); }
+// re-assign the lane groups by solve phase (the periodic regroup), or — the tail of a call — pack the envs that still have ticks to run into the first
+// lane groups (see env_regroup_count_kernel)
 inline int env_launch_regroup(EnvDevice& d, const hk_config& cfg, hipStream_t stream, std::string& err)
 {
     d.rounds_since_regroup = 0;

@@ -97,18 +97,16 @@ inline int launch_regroup(EnvDevice& d, const hk_config& cfg, hipStream_t stream
     return HK_OK;
 }
 
-// one round, part 1: the fused tick kernel (fills queue set round & 1)
-inline int launch_run(EnvDevice& d, const hk_config& cfg, hipStream_t stream, std::string& err)
+// one round of a part, the tick launch: the fused tick kernel (fills the part's queue set round & 1)
+inline int launch_run(EnvDevice& d, const hk_config& cfg, const RoundPart& part, int arm, bool is_guard, std::string& err)
 {
-    const int s0 = d.slot1 > d.slot0 ? d.slot0 : 0, s1 = d.slot1 > d.slot0 ? d.slot1 : cfg.num_envs;
+    const int s0 = part.slot0, s1 = part.slot1, qbase = 2 * part.index, guard = is_guard ? 1 : 0;
+    const hipStream_t stream = part.stream;
     const long long threads = (long long)(s1 - s0) * GA;
-    const int arm = d.arm_ticks, guard = (d.guard_rounds_left > 0 && --d.guard_rounds_left == 0) ? 1 : 0;
-    d.arm_ticks = 0;
-    d.inwave = false;            // (launch_b1 decides for the round)
 #define HK_RUN_T(MC, RWF, TRN, TL)                                                                                            \
     hipLaunchKernelGGL((env_run_kernel<MC, RWF, TRN, TL>), dim3((unsigned)((threads + 255) / 256)), dim3(256), TL ? d.tab_lds : 0, stream, d.P, d.agents, d.hot, d.envs,   \
-                       d.results, GameSoA{d.games, (size_t)cfg.num_envs * cfg.num_agents}, d.queue_cnt, d.queue, d.round, d.act_steer, d.act_branch, d.lq_debug, d.status,     \
-                       d.mcts, d.mset, d.rw, d.perm, d.game_stats, s0, s1, d.qbase, arm, guard)
+                       d.results, GameSoA{d.games, (size_t)cfg.num_envs * cfg.num_agents}, d.queue_cnt, d.queue, part.round, d.act_steer, d.act_branch, d.lq_debug, d.status,     \
+                       d.mcts, d.mset, d.rw, d.perm, d.game_stats, s0, s1, qbase, arm, guard)
 #define HK_RUN(MC, RWF, TRN) do { if (d.tab_lds) HK_RUN_T(MC, RWF, TRN, true); else HK_RUN_T(MC, RWF, TRN, false); } while (0)
     bool train = d.P.training_reset != 0;
     for (int i = 0; i < cfg.num_agents; i++) train = train || d.P.training_agent[i] != 0;
@@ -118,12 +116,12 @@ inline int launch_run(EnvDevice& d, const hk_config& cfg, hipStream_t stream, st
         const GameSoA G{d.games, (size_t)cfg.num_envs * cfg.num_agents};
         const unsigned blocks = (unsigned)((threads + 255) / 256);
 #define HK_FIS_RUN(MC, TL) hipLaunchKernelGGL((env_run_kernel<MC, false, false, TL, true>), dim3(blocks), dim3(256), TL ? d.tab_lds : 0, stream, d.P, d.agents, d.hot, d.envs, \
-                               d.results, G, d.queue_cnt, d.queue, d.round, d.act_steer, d.act_branch, d.lq_debug, d.status, d.mcts, d.mset, d.rw, d.perm,        \
-                               d.game_stats, s0, s1, d.qbase, arm, guard)
+                               d.results, G, d.queue_cnt, d.queue, part.round, d.act_steer, d.act_branch, d.lq_debug, d.status, d.mcts, d.mset, d.rw, d.perm,        \
+                               d.game_stats, s0, s1, qbase, arm, guard)
         // (reward shaping / Training mode: phases A and C carry them, so the tick kernel has <.., HAS_RW, HAS_TRAIN, ..> twins; phase B1 knows neither)
 #define HK_FIS_RUN3(MC, RWF, TRN, TL) hipLaunchKernelGGL((env_run_kernel<MC, RWF, TRN, TL, true>), dim3(blocks), dim3(256), TL ? d.tab_lds : 0, stream, d.P, d.agents, d.hot, d.envs, \
-                               d.results, G, d.queue_cnt, d.queue, d.round, d.act_steer, d.act_branch, d.lq_debug, d.status, d.mcts, d.mset, d.rw, d.perm,        \
-                               d.game_stats, s0, s1, d.qbase, arm, guard)
+                               d.results, G, d.queue_cnt, d.queue, part.round, d.act_steer, d.act_branch, d.lq_debug, d.status, d.mcts, d.mset, d.rw, d.perm,        \
+                               d.game_stats, s0, s1, qbase, arm, guard)
         if (train) { if (d.tab_lds) HK_FIS_RUN3(true, true, true, true); else HK_FIS_RUN3(true, true, true, false); }
         else if (d.rw.sec_time) {
             if (d.mcts.st) { if (d.tab_lds) HK_FIS_RUN3(true, true, false, true); else HK_FIS_RUN3(true, true, false, false); }
@@ -133,7 +131,6 @@ inline int launch_run(EnvDevice& d, const hk_config& cfg, hipStream_t stream, st
         else { if (d.tab_lds) HK_FIS_RUN(false, true); else HK_FIS_RUN(false, false); }
 #undef HK_FIS_RUN
 #undef HK_FIS_RUN3
-        d.b1_due = d.P.any_lqr != 0;
     } else
 #endif
     if (train) HK_RUN(true, true, true);
@@ -144,24 +141,19 @@ inline int launch_run(EnvDevice& d, const hk_config& cfg, hipStream_t stream, st
     return launch_check(err, "env_run_kernel");
 }
 
-// one round, part 1b (FISSION): phase B1 of every env the tick launch parked at its solve tick
-inline int launch_b1(EnvDevice& d, const hk_config& cfg, hipStream_t stream, std::string& err)
+// one round of a part, the B1 launch (FISSION): phase B1 of every env the tick launch parked at its solve tick.  inwave: the launch solves the
+// multi-player games it assembles itself (hk_lq_spread.h lqs_inwave) instead of queueing them for the solver launch
+inline int launch_b1(EnvDevice& d, const hk_config& cfg, const RoundPart& part, bool inwave, std::string& err)
 {
 #if HK_GA == 4
-    if (!d.b1_due) return HK_OK;
-    d.b1_due = false;
-    // in-wave solves (hk_lq_spread.h lqs_inwave) once the field has spread — while it stands close (BULK_TICKS after a reset of every env) nearly every ego
-    // holds a game and the queues + the pair solver's 32 games per wave are several times cheaper per game
-    const int meter_fresh = ((d.meter_fresh >> (d.qbase >> 1)) & 1u) ? 2 : 0;
-    d.meter_fresh &= ~(1u << (d.qbase >> 1));
-    const int meter_slot = (int)(d.meter_launches[d.qbase >> 1]++ % 3u);
-    d.inwave = inwave_now(d);      // (HK_INWAVE=1, tests: in every round)
-    const int s0 = d.slot1 > d.slot0 ? d.slot0 : 0, s1 = d.slot1 > d.slot0 ? d.slot1 : cfg.num_envs;
+    const int meter_fresh = part.meter_stale ? 2 : 0, meter_slot = (int)(part.b1_launches % 3u);
+    const int s0 = part.slot0, s1 = part.slot1;
+    const hipStream_t stream = part.stream;
     const long long threads = (long long)(s1 - s0) * GA;
     const GameSoA G{d.games, (size_t)cfg.num_envs * cfg.num_agents};
     const unsigned blocks = (unsigned)((threads + 255) / 256);
 #define HK_FIS_B1(TL, MC) hipLaunchKernelGGL((env_b1_kernel<TL, MC>), dim3(blocks), dim3(256), TL ? d.P.o_tmask : 0, stream, d.P, d.agents, d.hot, d.envs, G, d.queue_cnt, d.queue, \
-                           d.round, d.lq_debug, d.status, d.mcts, d.perm, d.game_stats, s0, s1, d.qbase, d.mset, (d.inwave ? 1 : 0) | meter_fresh, meter_slot)
+                           part.round, d.lq_debug, d.status, d.mcts, d.perm, d.game_stats, s0, s1, 2 * part.index, d.mset, (inwave ? 1 : 0) | meter_fresh, meter_slot)
     // (b1_small: beside a search launch whose 4-wave workgroups hold 108.8 KB of EVERY CU's LDS, a B1 block with its 44.5 KB copy of the Complex-track tables
     // — 67 KB with the KartS staging — does not fit; the instantiation that reads the tables through L1 / L2 needs the 22.8 KB of staging only)
     if (d.mcts.st) { if (d.tab_lds && !d.b1_small) HK_FIS_B1(true, true); else HK_FIS_B1(false, true); }
@@ -169,38 +161,24 @@ inline int launch_b1(EnvDevice& d, const hk_config& cfg, hipStream_t stream, std
 #undef HK_FIS_B1
     return launch_check(err, "env_b1_kernel");
 #else
-    (void)d; (void)cfg; (void)stream; (void)err;
+    (void)d; (void)cfg; (void)part; (void)inwave; (void)err;
     return HK_OK;
 #endif
 }
 
-// one round, part 2: the Riccati solves of the queued multi-player games, binned by player count
-inline int launch_lqn(EnvDevice& d, const hk_config& cfg, hipStream_t stream, std::string& err)
+// one round of a part, the solver launch: the Riccati solves of the queued multi-player games, binned by player count.  Nothing is launched when the
+// round's B1 launch solved its games in-wave (nothing is queued), nor when the issuer knows the queues to be empty (skip: hk_api.hip issue_rounds)
+inline int launch_lqn(EnvDevice& d, const hk_config& cfg, const RoundPart& part, bool inwave, bool skip, std::string& err)
 {
     const int ngames = cfg.num_envs * cfg.num_agents;
-    const int set = d.qbase + (d.round & 1);
+    const int set = 2 * part.index + (part.round & 1);
+    const hipStream_t stream = part.stream;
+    // (the planner's periodic search launch rides on every round, also one without a solver launch)
     if (d.mcts.st && !d.mcts_defer && ++d.mcts_rounds >= MCTS_FLUSH_ROUNDS) { int rcm = flush_mcts(d, stream, err); if (rcm) return rcm; }
+    if (inwave || skip) return HK_OK;
     const int* qc = d.queue_cnt + set * 16;
     const int* qu = d.queue + (size_t)set * queue_ints_per_set((size_t)ngames);
     int rc = HK_OK;
-    d.lqn_launched = false;
-    if (d.inwave) {
-        // IN-WAVE (round 6): the B1 launch of this round solved its multi-player games itself (hk_env_run.h, hk_lq_spread.h lqs_inwave): nothing is queued
-        if (d.last_solve_skippable && d.guard_rounds_left == 0) d.last_solve_skippable = false;
-        d.round += 1;
-        if (d.qbase == 0) d.call_ticks_issued = std::min(d.call_ticks_issued + (cfg.num_agents > 2 ? 4 : 1), d.call_ticks);
-        return HK_OK;
-    }
-    d.lqn_launched = true;
-    if (d.last_solve_skippable && d.guard_rounds_left == 0) {
-        // The tick launch before this one was the call's last (its completion guard): an env that queued a game there would be parked, i.e.
-        // the call incomplete, which the round count rules out.  The skip is verified ON THE DEVICE by that very launch: as the guard it
-        // raises status bit 2 for any env it leaves with ticks or a phase (a parked env has phase 1 or 2), and the next getter reports it.  Nothing to solve: a one-tick call is 3 launches, not 4.
-        d.last_solve_skippable = false;
-        d.round += 1;
-        if (d.qbase == 0) d.call_ticks_issued = std::min(d.call_ticks_issued + (cfg.num_agents > 2 ? 4 : 1), d.call_ticks);
-        return HK_OK;
-    }
     // Bulk or sparse?  The host cannot see the queues without a sync, but it knows how long ago the field stood on the start grid:
     // for BULK_TICKS after a reset of every env most egos hold a 2-player game (their row mate), later almost none does.
     const bool bulk = cfg.num_agents == 2 || d.ticks_since_reset + d.call_ticks_issued < BULK_TICKS;
@@ -245,8 +223,6 @@ inline int launch_lqn(EnvDevice& d, const hk_config& cfg, hipStream_t stream, st
         }
 #endif
     }
-    d.round += 1;
-    if (d.qbase == 0) d.call_ticks_issued = std::min(d.call_ticks_issued + (cfg.num_agents > 2 ? 4 : 1), d.call_ticks);      // a round retires at least one solve cadence
     return HK_OK;
 }
 

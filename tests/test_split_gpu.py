@@ -1,4 +1,4 @@
-"""HK_SPLIT=1: the batch as two halves on two streams (hk_api.hip issue_rounds_split) must change nothing but the speed.
+"""HK_SPLIT=1: the batch as two halves on two streams (hk_api.hip issue_rounds over two parts) must change nothing but the speed.
 The switch is read once per process, so the comparison runs in a child process."""
 import pytest
 from parity import assert_child, step_both, twin
