@@ -224,6 +224,9 @@ struct hk_context {
         size_t ws_bytes = 0;
         int cap = 0, last_m = 0;
         float* mb_mu = nullptr; float* mb_logits = nullptr; float* mb_v = nullptr;
+        int prec = HK_PPO_PREC_F32;    // hk_ppo_set_precision
+        uint16_t* shadow = nullptr;    // HK_PPO_PREC_BF16: PARAMS rounded to bf16, the critic shadow_pad elements on (ppo_shadow_kernel)
+        size_t shadow_pad = 0;
     } ppo[HK_MAX_POLICIES];
     int n_ppo = 0;
     // RCCL communicator for hk_gather_results (librccl.so loaded lazily)
@@ -394,7 +397,7 @@ void hk_destroy(hk_handle h)
     if (h->pol_scratch) (void)hipFree(h->pol_scratch);
     if (h->ro.buf) (void)hipFree(h->ro.buf);
     for (int p = 0; p < HK_MAX_POLICIES; p++) hk::policy_free(h->policy[p]);
-    for (auto& t : h->ppo) { if (t.param) (void)hipFree(t.param); if (t.rowbuf) (void)hipFree(t.rowbuf); if (t.ws) (void)hipFree(t.ws); }
+    for (auto& t : h->ppo) { if (t.param) (void)hipFree(t.param); if (t.rowbuf) (void)hipFree(t.rowbuf); if (t.ws) (void)hipFree(t.ws); if (t.shadow) (void)hipFree(t.shadow); }
     h->prof.fold();
     for (hipEvent_t e : h->prof.pool) (void)hipEventDestroy(e);
     for (hipStream_t q : h->qstream) if (q) { (void)hipStreamSynchronize(q); (void)hipStreamDestroy(q); }
@@ -1337,6 +1340,10 @@ struct PpoWs {
     float *d0, *d1, *dhead, *dls, *dv, *part, *stats;
     double *rowstat, *acc;
     float *mb_mu, *mb_logits, *mb_v;
+    // HK_PPO_PREC_BF16: the input, the post-activations below the last layer and the deltas are bf16 (X0, those Aa / Ac, d0, d1 are then null)
+    uint16_t* X0b;
+    uint16_t* Aab[HK_POLICY_MAX_LAYERS]; uint16_t* Acb[HK_POLICY_MAX_LAYERS];
+    uint16_t *d0b, *d1b;
 };
 
 size_t ppo_ws_layout(const hk_context::Ppo& t, int M, PpoWs* w)
@@ -1352,10 +1359,23 @@ size_t ppo_ws_layout(const hk_context::Ppo& t, int M, PpoWs* w)
     const size_t nz = (Mz + hk::PPO_KCH - 1) / hk::PPO_KCH;
     PpoWs d{};
     d.ids = (int*)take(Mz * 4); d.valid = (int*)take(Mz * 4); d.n_valid = (int*)take(16);
-    d.X0 = (float*)take(Mz * in * 4);
-    for (int l = 0; l < t.actor.n_layers; l++) { d.Za[l] = (float*)take(Mz * Ha * 4); d.Aa[l] = (float*)take(Mz * Ha * 4); }
-    for (int l = 0; l < t.critic.n_layers; l++) { d.Zc[l] = (float*)take(Mz * Hc * 4); d.Ac[l] = (float*)take(Mz * Hc * 4); }
-    d.d0 = (float*)take(Mz * Hm * 4); d.d1 = (float*)take(Mz * Hm * 4);
+    if (t.prec == HK_PPO_PREC_BF16) {
+        d.X0b = (uint16_t*)take(Mz * in * 2);
+        for (int l = 0; l < t.actor.n_layers; l++) {
+            d.Za[l] = (float*)take(Mz * Ha * 4);
+            if (l == t.actor.n_layers - 1) d.Aa[l] = (float*)take(Mz * Ha * 4); else d.Aab[l] = (uint16_t*)take(Mz * Ha * 2);
+        }
+        for (int l = 0; l < t.critic.n_layers; l++) {
+            d.Zc[l] = (float*)take(Mz * Hc * 4);
+            if (l == t.critic.n_layers - 1) d.Ac[l] = (float*)take(Mz * Hc * 4); else d.Acb[l] = (uint16_t*)take(Mz * Hc * 2);
+        }
+        d.d0b = (uint16_t*)take(Mz * Hm * 2); d.d1b = (uint16_t*)take(Mz * Hm * 2);
+    } else {
+        d.X0 = (float*)take(Mz * in * 4);
+        for (int l = 0; l < t.actor.n_layers; l++) { d.Za[l] = (float*)take(Mz * Ha * 4); d.Aa[l] = (float*)take(Mz * Ha * 4); }
+        for (int l = 0; l < t.critic.n_layers; l++) { d.Zc[l] = (float*)take(Mz * Hc * 4); d.Ac[l] = (float*)take(Mz * Hc * 4); }
+        d.d0 = (float*)take(Mz * Hm * 4); d.d1 = (float*)take(Mz * Hm * 4);
+    }
     d.dhead = (float*)take(Mz * hk::PM_MAX_OUT * 4); d.dls = (float*)take(Mz * 4); d.dv = (float*)take(Mz * 4);
     d.part = (float*)take(nz * mn * 4);
     d.stats = (float*)take(8 * 4);
@@ -1419,6 +1439,64 @@ void ppo_colsum(hipStream_t s, const float* X, int m, int ld, int ncol, float* o
     hipLaunchKernelGGL(hk::ppo_colsum_kernel<float>, dim3(ncol), dim3(256), 0, s, X, m, ld, out);
 }
 
+// ---- HK_PPO_PREC_BF16: the same products on ppo_gemm_bf16_kernel (hk_ppo.h)
+template <int EPI>
+void ppo_gemm_bf16(hipStream_t s, int M, int N, int K, const uint16_t* A, int lda, bool a_kc, const uint16_t* B, int ldb, bool b_kc, const float* bias, float* C,
+                   uint16_t* Cb, int ldc, float* Z, int kch)
+{
+    const int nz = (K + kch - 1) / kch;
+    const dim3 grid(nblk(N, hk::PB_TN), nblk(M, hk::PB_TM), nz < 1 ? 1 : nz);
+    hipLaunchKernelGGL(hk::ppo_gemm_bf16_kernel<EPI>, grid, dim3(256), 0, s, M, N, K, A, lda, (int)a_kc, B, ldb, (int)b_kc, bias, C, Cb, ldc, Z, kch);
+}
+
+// dst [M][N] = sum over the m rows of D[i][o] X[i][c] (both bf16, row-major): fixed chunks of PPO_KCH rows, combined in chunk order
+void ppo_wgrad_bf16(hipStream_t s, float* part, int M, int N, int m, const uint16_t* D, int ldd, const uint16_t* X, int ldx, float* out)
+{
+    const int nz = (m + hk::PPO_KCH - 1) / hk::PPO_KCH;
+    ppo_gemm_bf16<0>(s, M, N, m, D, ldd, false, X, ldx, false, nullptr, part, nullptr, N, nullptr, hk::PPO_KCH);
+    hipLaunchKernelGGL(hk::ppo_combine_kernel, dim3(nblk((size_t)M * N)), dim3(256), 0, s, part, nz, M, N, out, (float*)nullptr);
+}
+
+// the shadow's view of a network's layer l ([out][in], as PARAMS)
+const uint16_t* ppo_shadow_w(const hk_context::Ppo& t, const hk::PpoNet& net, int l)
+{
+    return t.shadow + net.oW[l] + (&net == &t.critic ? t.shadow_pad : 0);
+}
+
+void ppo_shadow_refresh(hipStream_t s, const hk_context::Ppo& t)
+{
+    hipLaunchKernelGGL(hk::ppo_shadow_kernel, dim3(nblk(t.P)), dim3(256), 0, s, t.param, t.shadow, t.P, t.actor.count, t.shadow_pad);
+}
+
+// trunk forward: Z[l] fp32; the post-activation rounded to bf16 (Ab[l]) below the last layer, fp32 (A[L - 1]) at it, where the heads read it
+void ppo_trunk_forward_bf16(hipStream_t s, const hk_context::Ppo& t, const hk::PpoNet& net, const uint16_t* X0b, int m, float* const* Z, float* const* A,
+                            uint16_t* const* Ab)
+{
+    const int H = net.hidden;
+    for (int l = 0; l < net.n_layers; l++) {
+        const int K = l == 0 ? net.in_dim : H;
+        const bool last = l == net.n_layers - 1;
+        ppo_gemm_bf16<1>(s, m, H, K, l == 0 ? X0b : Ab[l - 1], K, true, ppo_shadow_w(t, net, l), K, true, t.param + net.ob[l], last ? A[l] : nullptr,
+                         last ? nullptr : Ab[l], H, Z[l], K);
+    }
+}
+
+// trunk backward from dcur = dL / dZ[L - 1] (bf16): weight and bias gradients into grad, delta through W_l * swish' (rounded by the epilogue)
+void ppo_trunk_backward_bf16(hipStream_t s, const PpoWs& w, const hk_context::Ppo& t, const hk::PpoNet& net, float* grad, int m, float* const* Z,
+                             uint16_t* const* Ab, uint16_t* dcur, uint16_t* dnext)
+{
+    const int H = net.hidden;
+    for (int l = net.n_layers - 1; l >= 0; l--) {
+        const int K = l == 0 ? net.in_dim : H;
+        ppo_wgrad_bf16(s, w.part, H, K, m, dcur, H, l == 0 ? w.X0b : Ab[l - 1], K, grad + net.oW[l]);
+        hipLaunchKernelGGL(hk::ppo_colsum_kernel<hk::ppo_bf16>, dim3(H), dim3(256), 0, s, reinterpret_cast<const hk::ppo_bf16*>(dcur), m, H, grad + net.ob[l]);
+        if (l > 0) {
+            ppo_gemm_bf16<2>(s, m, H, H, dcur, H, true, ppo_shadow_w(t, net, l), H, false, nullptr, nullptr, dnext, H, Z[l - 1], H);
+            std::swap(dcur, dnext);
+        }
+    }
+}
+
 // trunk forward on X0: Z[l] = W_l a_{l-1} + b_l (MFMA, k ascending), A[l] = swish(Z[l])
 void ppo_trunk_forward(hipStream_t s, const hk::PpoNet& net, const float* prm, const float* X0, int m, float* const* Z, float* const* A)
 {
@@ -1455,10 +1533,17 @@ int ppo_mb(hk_handle h, hk_context::Ppo& t, const int32_t* ids, int m, float eps
     const hk::PpoRows P = ppo_rows(h, t);
     const float* prm = t.param;
     float* grad = t.param + t.P;
-    hipLaunchKernelGGL(hk::ppo_gather_kernel, dim3(nblk((size_t)m * P.in_dim)), dim3(256), 0, s, P, ids, m, 0, w.X0, w.valid);
+    const bool bf = t.prec == HK_PPO_PREC_BF16;
+    if (bf) hipLaunchKernelGGL(hk::ppo_gather_kernel<uint16_t>, dim3(nblk((size_t)m * P.in_dim)), dim3(256), 0, s, P, ids, m, 0, w.X0b, w.valid);
+    else hipLaunchKernelGGL(hk::ppo_gather_kernel<float>, dim3(nblk((size_t)m * P.in_dim)), dim3(256), 0, s, P, ids, m, 0, w.X0, w.valid);
     hipLaunchKernelGGL(hk::ppo_count_kernel, dim3(1), dim3(256), 0, s, w.valid, m, w.n_valid);
-    ppo_trunk_forward(s, t.actor, prm, w.X0, m, w.Za, w.Aa);
-    ppo_trunk_forward(s, t.critic, prm, w.X0, m, w.Zc, w.Ac);
+    if (bf) {
+        ppo_trunk_forward_bf16(s, t, t.actor, w.X0b, m, w.Za, w.Aa, w.Aab);
+        ppo_trunk_forward_bf16(s, t, t.critic, w.X0b, m, w.Zc, w.Ac, w.Acb);
+    } else {
+        ppo_trunk_forward(s, t.actor, prm, w.X0, m, w.Za, w.Aa);
+        ppo_trunk_forward(s, t.critic, prm, w.X0, m, w.Zc, w.Ac);
+    }
     const hk::PpoNet &na = t.actor, &nc = t.critic;
     hk::PpoLossArgs L{};
     L.Aa = w.Aa[na.n_layers - 1]; L.Ac = w.Ac[nc.n_layers - 1];
@@ -1473,19 +1558,25 @@ int ppo_mb(hk_handle h, hk_context::Ppo& t, const int32_t* ids, int m, float eps
     hipLaunchKernelGGL(hk::ppo_stats_kernel, dim3(1), dim3(256), 0, s, w.rowstat, m, w.stats, acc ? w.acc : nullptr);
     // actor: the heads (vector ALU), then the trunk
     const int Ha = na.hidden, Hc = nc.hidden, nb = na.n_branch;
-    hipLaunchKernelGGL(hk::ppo_head_back_kernel, dim3(nblk((size_t)m * Ha)), dim3(256), 0, s, m, Ha, 1 + nb, w.dhead, hk::PM_MAX_OUT, prm + na.oWmu,
+    if (bf) hipLaunchKernelGGL(hk::ppo_head_back_bf16_kernel, dim3(nblk((size_t)m * Ha)), dim3(256), 0, s, m, Ha, 1 + nb, w.dhead, hk::PM_MAX_OUT,
+                               prm + na.oWmu, prm + na.oWbr, w.Za[na.n_layers - 1], w.d0b);
+    else hipLaunchKernelGGL(hk::ppo_head_back_kernel, dim3(nblk((size_t)m * Ha)), dim3(256), 0, s, m, Ha, 1 + nb, w.dhead, hk::PM_MAX_OUT, prm + na.oWmu,
                        prm + na.oWbr, w.Za[na.n_layers - 1], w.d0);
     ppo_wgrad(s, w, 1 + nb, Ha, m, w.dhead, hk::PM_MAX_OUT, 1, w.Aa[na.n_layers - 1], Ha, grad + na.oWmu, grad + na.oWbr);
     ppo_colsum(s, w.dhead, m, hk::PM_MAX_OUT, 1, grad + na.obmu);
     ppo_colsum(s, w.dhead + 1, m, hk::PM_MAX_OUT, nb, grad + na.obbr);
     ppo_colsum(s, w.dls, m, 1, 1, grad + na.ols);
-    ppo_trunk_backward(s, w, na, prm, grad, w.X0, m, w.Za, w.Aa, w.d0, w.d1);
+    if (bf) ppo_trunk_backward_bf16(s, w, t, na, grad, m, w.Za, w.Aab, w.d0b, w.d1b);
+    else ppo_trunk_backward(s, w, na, prm, grad, w.X0, m, w.Za, w.Aa, w.d0, w.d1);
     // critic
-    hipLaunchKernelGGL(hk::ppo_head_back_kernel, dim3(nblk((size_t)m * Hc)), dim3(256), 0, s, m, Hc, 1, w.dv, 1, prm + nc.oWmu, nullptr,
+    if (bf) hipLaunchKernelGGL(hk::ppo_head_back_bf16_kernel, dim3(nblk((size_t)m * Hc)), dim3(256), 0, s, m, Hc, 1, w.dv, 1, prm + nc.oWmu,
+                               (const float*)nullptr, w.Zc[nc.n_layers - 1], w.d0b);
+    else hipLaunchKernelGGL(hk::ppo_head_back_kernel, dim3(nblk((size_t)m * Hc)), dim3(256), 0, s, m, Hc, 1, w.dv, 1, prm + nc.oWmu, nullptr,
                        w.Zc[nc.n_layers - 1], w.d0);
     ppo_wgrad(s, w, 1, Hc, m, w.dv, 1, 1, w.Ac[nc.n_layers - 1], Hc, grad + nc.oWmu, nullptr);
     ppo_colsum(s, w.dv, m, 1, 1, grad + nc.obmu);
-    ppo_trunk_backward(s, w, nc, prm, grad, w.X0, m, w.Zc, w.Ac, w.d0, w.d1);
+    if (bf) ppo_trunk_backward_bf16(s, w, t, nc, grad, m, w.Zc, w.Acb, w.d0b, w.d1b);
+    else ppo_trunk_backward(s, w, nc, prm, grad, w.X0, m, w.Zc, w.Ac, w.d0, w.d1);
     HK_HIP(h, hipGetLastError());
     t.last_m = m;
     return HK_OK;
@@ -1500,6 +1591,7 @@ int ppo_adam_step(hk_handle h, hk_context::Ppo& t, float lr)
     float* p = t.param;
     hipLaunchKernelGGL(hk::ppo_adam_kernel, dim3(nblk(t.P)), dim3(256), 0, h->stream, p, p + t.P, p + 2 * t.P, p + 3 * t.P, t.P, b1, omb1, b2, omb2, c1, c2,
                        t.cfg.adam_eps, lr);
+    if (t.prec == HK_PPO_PREC_BF16) ppo_shadow_refresh(h->stream, t);
     HK_HIP(h, hipGetLastError());
     return HK_OK;
 }
@@ -1590,11 +1682,17 @@ int hk_ppo_advantages(hk_handle h, int trainer)
     if ((rc = ppo_ensure_ws(h, t, chunk, w))) return rc;
     hipStream_t s = h->stream;
     const hk::PpoNet& nc = t.critic;
+    if (t.prec == HK_PPO_PREC_BF16) ppo_shadow_refresh(s, t);      // PARAMS is writable through hk_ppo_ptr
     for (int base = 0; base < n + nbt; base += chunk) {
         const int m = std::min(chunk, n + nbt - base);
         hipLaunchKernelGGL(hk::ppo_iota_kernel, dim3(nblk(m)), dim3(256), 0, s, w.ids, base, m);
-        hipLaunchKernelGGL(hk::ppo_gather_kernel, dim3(nblk((size_t)m * P.in_dim)), dim3(256), 0, s, P, w.ids, m, 1, w.X0, w.valid);
-        ppo_trunk_forward(s, nc, t.param, w.X0, m, w.Zc, w.Ac);
+        if (t.prec == HK_PPO_PREC_BF16) {
+            hipLaunchKernelGGL(hk::ppo_gather_kernel<uint16_t>, dim3(nblk((size_t)m * P.in_dim)), dim3(256), 0, s, P, w.ids, m, 1, w.X0b, w.valid);
+            ppo_trunk_forward_bf16(s, t, nc, w.X0b, m, w.Zc, w.Ac, w.Acb);
+        } else {
+            hipLaunchKernelGGL(hk::ppo_gather_kernel<float>, dim3(nblk((size_t)m * P.in_dim)), dim3(256), 0, s, P, w.ids, m, 1, w.X0, w.valid);
+            ppo_trunk_forward(s, nc, t.param, w.X0, m, w.Zc, w.Ac);
+        }
         hipLaunchKernelGGL(hk::ppo_value_kernel, dim3(nblk(m)), dim3(256), 0, s, w.Ac[nc.n_layers - 1], m, nc.hidden, t.param + nc.oWmu, t.param + nc.obmu,
                            w.ids, n, nbt, v_old, vb);
     }
@@ -1613,6 +1711,7 @@ int hk_ppo_minibatch(hk_handle h, int trainer, const int32_t* rows_dev, int m, f
     if (rc) return rc;
     if (!rows_dev || m < 1) return fail(h, HK_ERR_INVALID, "hk_ppo_minibatch: NULL rows or m < 1");
     auto& t = h->ppo[trainer];
+    if (t.prec == HK_PPO_PREC_BF16) ppo_shadow_refresh(h->stream, t);      // PARAMS is writable through hk_ppo_ptr
     if ((rc = ppo_mb(h, t, rows_dev, m, eps, beta, false))) return rc;
     if (stats) {
         PpoWs w;
@@ -1655,6 +1754,7 @@ int hk_ppo_update(hk_handle h, int trainer, int epochs, int minibatch, float lr,
     int* perm = (int*)(t.rowbuf + 3 * (size_t)n + (size_t)h->cfg.num_envs * h->policy[t.policy].q.n_slots);
     PpoWs w;
     if ((rc = ppo_ensure_ws(h, t, mb, w))) return rc;
+    if (t.prec == HK_PPO_PREC_BF16) ppo_shadow_refresh(h->stream, t);      // PARAMS is writable through hk_ppo_ptr
     for (int ep = 0; ep < epochs; ep++) {
         const bool last = ep == epochs - 1;
         if (last) HK_HIP(h, hipMemsetAsync(w.acc, 0, 8 * sizeof(double), h->stream));
@@ -1676,6 +1776,63 @@ int hk_ppo_update(hk_handle h, int trainer, int epochs, int minibatch, float lr,
     return HK_OK;
 }
 
+int hk_ppo_set_precision(hk_handle h, int trainer, int precision)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_check(h, trainer, "hk_ppo_set_precision", false);
+    if (rc) return rc;
+    if (precision != HK_PPO_PREC_F32 && precision != HK_PPO_PREC_BF16) return fail(h, HK_ERR_INVALID, "hk_ppo_set_precision: unknown precision");
+    auto& t = h->ppo[trainer];
+    if (precision == t.prec) return HK_OK;
+    // the workspace is laid out per precision: drop it once the stream is done with it (the next minibatch allocates the other layout)
+    HK_HIP(h, hipStreamSynchronize(h->stream));
+    if (t.ws) HK_HIP(h, hipFree(t.ws));
+    t.ws = nullptr; t.cap = 0; t.ws_bytes = 0; t.last_m = 0;
+    if (precision == HK_PPO_PREC_BF16) {
+        if (!t.shadow) {
+            t.shadow_pad = (8 - t.actor.count % 8) % 8;
+            HK_HIP(h, hipMalloc(&t.shadow, (t.P + t.shadow_pad) * sizeof(uint16_t)));
+            HK_HIP(h, hipMemsetAsync(t.shadow, 0, (t.P + t.shadow_pad) * sizeof(uint16_t), h->stream));
+        }
+        ppo_shadow_refresh(h->stream, t);
+        HK_HIP(h, hipGetLastError());
+    }
+    t.prec = precision;
+    return HK_OK;
+}
+
+int hk_ppo_get_precision(hk_handle h, int trainer)
+{
+    if (!h) return fail(nullptr, HK_ERR_INVALID, "NULL handle");
+    if (trainer < 0 || trainer >= h->n_ppo) return fail(h, HK_ERR_INVALID, "hk_ppo_get_precision: bad trainer index");
+    return h->ppo[trainer].prec;
+}
+
+int hk_ppo_gemm_bf16(hk_handle h, int epi, int M, int N, int K, const void* A_dev, const void* B_dev, const float* bias_dev, const float* aux_dev, float* C_dev)
+{
+    HK_NEED_ENV(h);
+    if (epi < 0 || epi > 2) return fail(h, HK_ERR_INVALID, "hk_ppo_gemm_bf16: unknown epi");
+    if (M < 1 || N < 1 || K < 1) return fail(h, HK_ERR_INVALID, "hk_ppo_gemm_bf16: M, N, K must be positive");
+    if (!A_dev || !B_dev || !C_dev || (epi == 2 && !aux_dev)) return fail(h, HK_ERR_INVALID, "hk_ppo_gemm_bf16: NULL operand");
+    const uint16_t *A = (const uint16_t*)A_dev, *B = (const uint16_t*)B_dev;
+    hipStream_t s = h->stream;
+    if (epi == 0) {
+        float* part = nullptr;
+        const size_t nz = ((size_t)K + hk::PPO_KCH - 1) / hk::PPO_KCH;
+        HK_HIP(h, hipMalloc(&part, nz * M * N * sizeof(float)));
+        ppo_wgrad_bf16(s, part, M, N, K, A, M, B, N, C_dev);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        (void)hipFree(part);
+        HK_HIP(h, e);
+        return HK_OK;
+    }
+    if (epi == 1) ppo_gemm_bf16<1>(s, M, N, K, A, K, true, B, K, true, bias_dev, C_dev, nullptr, N, nullptr, K);
+    else ppo_gemm_bf16<2>(s, M, N, K, A, K, true, B, N, false, nullptr, C_dev, nullptr, N, const_cast<float*>(aux_dev), K);
+    HK_HIP(h, hipGetLastError());
+    return HK_OK;
+}
+
 void* hk_ppo_ptr(hk_handle h, int trainer, int field)
 {
     if (!h) { fail(nullptr, HK_ERR_INVALID, "NULL handle"); return nullptr; }
@@ -1690,6 +1847,10 @@ void* hk_ppo_ptr(hk_handle h, int trainer, int field)
     if (field == HK_PPO_PERM) {
         if (!t.perm_valid) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: no hk_ppo_update on the current advantages"); return nullptr; }
         return t.rowbuf + 3 * (size_t)t.n + (size_t)h->cfg.num_envs * h->policy[t.policy].q.n_slots;
+    }
+    if (field == HK_PPO_SHADOW) {
+        if (!t.shadow) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: the trainer has never been in HK_PPO_PREC_BF16"); return nullptr; }
+        return t.shadow;
     }
     if (t.last_m == 0) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: no minibatch yet"); return nullptr; }
     PpoWs w;
@@ -1706,6 +1867,7 @@ int hk_ppo_count(hk_handle h, int trainer, int field)
     if (field <= HK_PPO_ADAM_V) return (int)t.P;
     if (field <= HK_PPO_RET) return t.adv_gen < 0 ? 0 : t.n;
     if (field == HK_PPO_PERM) return t.perm_valid ? t.n : 0;
+    if (field == HK_PPO_SHADOW) return t.shadow ? (int)(t.P + t.shadow_pad) : 0;
     return field == HK_PPO_MB_LOGITS ? t.last_m * t.actor.n_branch : t.last_m;
 }
 

@@ -10,6 +10,9 @@
 //   ppo_colsum_kernel       bias / log_sigma gradients and the stats: fixed-order column sums (no float atomics anywhere)
 //   ppo_gae_kernel          one lane per (env, slot): the reverse GAE scan;  ppo_adv_norm_kernel: fp64 mean / std in one block
 //   ppo_adam_kernel, ppo_publish_kernel<TO_POLICY>              elementwise
+// HK_PPO_PREC_BF16 (hk.h "PRECISION"): the trunk products run on ppo_gemm_bf16_kernel<EPI> (v_mfma_f32_32x32x16_bf16, fp32 accumulation) over
+// operands their producers rounded once — ppo_shadow_kernel (the weights, after Adam), ppo_gather_kernel<uint16_t>, ppo_head_back_bf16_kernel and
+// the product's own epilogues; everything else above is shared with the fp32 mode.
 #pragma once
 #include "hk_policy.h"
 
@@ -52,12 +55,27 @@ struct PpoRows {
     int slots[HK_MAX_AGENTS];
 };
 
+// fp32 -> bf16, to nearest even; Inf stays Inf, every NaN becomes the quiet NaN 0x7FC0 (torch's conversion; host twin ppo.bf16_round)
+__device__ __forceinline__ uint16_t ppo_bf16_rne(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)0x7FC0u;
+    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+__device__ __forceinline__ float ppo_bf16_f32(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
+struct ppo_bf16 { uint16_t v; __device__ operator double() const { return (double)ppo_bf16_f32(v); } };      // an element type for ppo_colsum_kernel
+// a producer's store: as it is, or rounded once to bf16
+__device__ __forceinline__ void ppo_put(float* p, size_t i, float v) { p[i] = v; }
+__device__ __forceinline__ void ppo_put(uint16_t* p, size_t i, float v) { p[i] = ppo_bf16_rne(v); }
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Row ids -> X0.  id in [0, n): row (t, e, j), t = id / (E S), e = id / S % E, j = id % S.  boot && id in [n, n + E S): the bootstrap input of
 // (e, j) = id - n: the last row's stack shifted by one with NEXT_OBS pushed.  Any other id: a zero row, valid[i] = 0.
 // The stack rule of rollout.stacked_inputs: entry q (oldest first) of row t is decision u = t - (stack - 1 - q); it is present when no
 // decision in (u, t] cleared the stack (FIRST; the bootstrap's own push clears nothing) — OBS[u] for u >= 0, RING0 for u < 0 — else 0.
-__global__ __launch_bounds__(256) void ppo_gather_kernel(PpoRows P, const int* ids, int m, int boot, float* X0, int* valid)
+// T: float, or uint16_t (HK_PPO_PREC_BF16: rounded once to bf16 as it is written, ppo_put)
+template <typename T>
+__global__ __launch_bounds__(256) void ppo_gather_kernel(PpoRows P, const int* ids, int m, int boot, T* X0, int* valid)
 {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)m * P.in_dim) return;
@@ -67,7 +85,7 @@ __global__ __launch_bounds__(256) void ppo_gather_kernel(PpoRows P, const int* i
     const bool is_row = id >= 0 && id < n;
     const bool is_boot = boot && id >= n && id < n + P.E * P.S;
     if (k == 0) valid[i] = is_row || is_boot;
-    if (!is_row && !is_boot) { X0[idx] = 0.0f; return; }
+    if (!is_row && !is_boot) { ppo_put(X0, idx, 0.0f); return; }
     int t, e, j;
     if (is_row) { t = id / (P.E * P.S); e = (id / P.S) % P.E; j = id % P.S; }
     else { t = P.R; e = (id - n) / P.S; j = (id - n) % P.S; }
@@ -85,7 +103,7 @@ __global__ __launch_bounds__(256) void ppo_gather_kernel(PpoRows P, const int* i
         else x = P.ring0[(ea * (P.smax - 1) + (P.smax - 1 + u)) * P.D + d];
     }
     if (P.normalize) x = pm_normalise(x, P.mean[k], P.std[k]);      // policy_mlp_kernel's loader (hk_policy.h)
-    X0[idx] = x;
+    ppo_put(X0, idx, x);
 }
 
 __global__ __launch_bounds__(256) void ppo_iota_kernel(int* ids, int base, int m)
@@ -156,6 +174,137 @@ __global__ __launch_bounds__(256) void ppo_gemm_kernel(int M, int N, int K, cons
             Cz[o] = acc[r] * (sg + s * sg * (1.0f - sg));
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// HK_PPO_PREC_BF16: C = seed + A B over bf16 operands (raw bits) on v_mfma_f32_32x32x16_bf16, fp32 accumulation.  The tile, the wave blocks, the
+// split-K rule and the three epilogues are ppo_gemm_kernel's.  An operand is stored either with k contiguous (a_kc: A is [M][K], b_kc: B is
+// [N][K]; leading dimension lda / ldb) or with k as its row index ([K][M], [K][N]: the weight-gradient operands and W of the backward delta).
+// K runs through LDS in chunks of 64 (4 MFMAs per wave), every tile kept [row][k] with a row stride of 72 elements (144 B: the 16-byte
+// operand reads of 16 consecutive rows cover the 64 banks once), so an MFMA operand is one ds_read_b128.  The loader moves 8 elements
+// (16 bytes) per load along whichever dimension is contiguous — element by element where the leading dimension or the base is not a
+// multiple of 16 bytes, or the piece crosses an edge — holds the next chunk in registers while the MFMAs of the current one run, and stores
+// it into the other LDS buffer: one barrier per chunk.  A k-as-row operand is transposed by that store (eight 2-byte stores per piece,
+// consecutive lanes on consecutive k: conflict-free); there is no transposed copy in memory and no transposing LDS read.  Whatever lies
+// past M, N or the chunk's K is staged as +0.0, which changes no fp32 sum.
+// EPI 0: C = acc (fp32; the split-K partial tile of chunk blockIdx.z).  EPI 1: Z = acc (when Z), swish(acc) to C (fp32) and / or Cb (rounded to
+// bf16).  EPI 2: acc * swish'(Z) to C and / or Cb.
+constexpr int PB_TM = 64, PB_TN = 64, PB_TK = 64, PB_LD = 72;
+typedef __bf16 ppo_bf16x8 __attribute__((ext_vector_type(8)));
+
+// this thread's two pieces of the 64 x 64 tile (rows r0 .. of the operand, limit rlim; k from kb, limit kend), zero outside
+__device__ __forceinline__ void pb_fetch(uint4 (&v)[2], const uint16_t* __restrict__ P, int ld, bool kc, bool vec, int r0, int rlim, int kb, int kend, int tid)
+{
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const int x = tid + 256 * q;
+        int f, flim, c, clim;                      // f: the index on the strided dimension, c: the first of 8 on the contiguous one
+        if (kc) { f = r0 + (x >> 3); flim = rlim; c = kb + (x & 7) * 8; clim = kend; }
+        else { f = kb + (x & 63); flim = kend; c = r0 + (x >> 6) * 8; clim = rlim; }
+        uint4 w = make_uint4(0u, 0u, 0u, 0u);
+        if (f < flim && c < clim) {
+            const uint16_t* p = P + (size_t)f * ld + c;
+            if (vec && c + 8 <= clim) w = *reinterpret_cast<const uint4*>(p);
+            else {
+                uint32_t e[8];
+#pragma unroll
+                for (int j = 0; j < 8; j++) e[j] = (c + j < clim) ? (uint32_t)p[j] : 0u;
+                w = make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
+            }
+        }
+        v[q] = w;
+    }
+}
+// ... into the LDS tile T [64][PB_LD] (k contiguous)
+__device__ __forceinline__ void pb_stage(uint16_t* T, const uint4 (&v)[2], bool kc, int tid)
+{
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const int x = tid + 256 * q;
+        if (kc) *reinterpret_cast<uint4*>(T + (x >> 3) * PB_LD + (x & 7) * 8) = v[q];
+        else {
+            uint16_t* t = T + ((x >> 6) * 8) * PB_LD + (x & 63);
+            const uint32_t w[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
+#pragma unroll
+            for (int j = 0; j < 8; j++) t[j * PB_LD] = (uint16_t)(w[j >> 1] >> (16 * (j & 1)));
+        }
+    }
+}
+
+template <int EPI>
+__global__ __launch_bounds__(256) void ppo_gemm_bf16_kernel(int M, int N, int K, const uint16_t* __restrict__ A, int lda, int a_kc,
+                                                            const uint16_t* __restrict__ B, int ldb, int b_kc, const float* __restrict__ bias, float* C,
+                                                            uint16_t* Cb, int ldc, float* Z, int kch)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t As[2][PB_TM * PB_LD], Bs[2][PB_TN * PB_LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i0 = blockIdx.y * PB_TM, j0 = blockIdx.x * PB_TN;
+    const int kbeg = blockIdx.z * kch, kend = (kbeg + kch < K) ? kbeg + kch : K;
+    const int wr = wave >> 1, wc = wave & 1, half = lane >> 5, c = lane & 31;
+    const int jcol = j0 + wc * 32 + c;
+    const bool avec = (lda & 7) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0;
+    const bool bvec = (ldb & 7) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0;
+    f32x16 acc;
+    {
+        const float s = (bias && jcol < N) ? bias[jcol] : 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[r] = s;
+    }
+    const int nch = (kend - kbeg + PB_TK - 1) / PB_TK;
+    uint4 va[2], vb[2];
+    pb_fetch(va, A, lda, a_kc != 0, avec, i0, M, kbeg, kend, tid);
+    pb_fetch(vb, B, ldb, b_kc != 0, bvec, j0, N, kbeg, kend, tid);
+    pb_stage(As[0], va, a_kc != 0, tid);
+    pb_stage(Bs[0], vb, b_kc != 0, tid);
+    __syncthreads();
+    for (int n = 0; n < nch; n++) {
+        const int cur = n & 1;
+        const bool more = n + 1 < nch;
+        if (more) {                              // the next chunk's loads are in flight while this one's MFMAs run
+            pb_fetch(va, A, lda, a_kc != 0, avec, i0, M, kbeg + (n + 1) * PB_TK, kend, tid);
+            pb_fetch(vb, B, ldb, b_kc != 0, bvec, j0, N, kbeg + (n + 1) * PB_TK, kend, tid);
+        }
+        // operand maps of 32x32x16: lane (r = lane & 31, h = lane >> 5) holds A[r][8 h + j] and B[8 h + j][r], j = 0 .. 7
+        const uint16_t* ap = As[cur] + (wr * 32 + c) * PB_LD + half * 8;
+        const uint16_t* bp = Bs[cur] + (wc * 32 + c) * PB_LD + half * 8;
+#pragma unroll
+        for (int s = 0; s < PB_TK / 16; s++) {
+            const ppo_bf16x8 a = *reinterpret_cast<const ppo_bf16x8*>(ap + s * 16);
+            const ppo_bf16x8 b = *reinterpret_cast<const ppo_bf16x8*>(bp + s * 16);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+        }
+        if (more) {                              // the other buffer: every wave finished reading it before the last barrier
+            pb_stage(As[cur ^ 1], va, a_kc != 0, tid);
+            pb_stage(Bs[cur ^ 1], vb, b_kc != 0, tid);
+        }
+        __syncthreads();
+    }
+    if (jcol >= N) return;
+    const size_t zo = gridDim.z > 1 ? (size_t)blockIdx.z * M * N : 0;
+    // C/D layout: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = i0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        if (row >= M) continue;
+        const size_t o = (size_t)row * ldc + jcol;
+        float v;
+        if (EPI == 0) v = acc[r];
+        else if (EPI == 1) { if (Z) Z[o] = acc[r]; v = swish(acc[r]); }
+        else {
+            const float s = Z[o];
+            const float sg = 1.0f / (1.0f + expf(-s));
+            v = acc[r] * (sg + s * sg * (1.0f - sg));
+        }
+        if (C) C[zo + o] = v;
+        if (Cb) Cb[o] = ppo_bf16_rne(v);
+    }
+}
+
+// the bf16 shadow of PARAMS: element i of the actor at i, of the critic at i + pad (the critic's matrices then start on 16 bytes as the actor's do)
+__global__ __launch_bounds__(256) void ppo_shadow_kernel(const float* p, uint16_t* shadow, size_t n, size_t n_actor, size_t pad)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) shadow[i + (i >= n_actor ? pad : 0)] = ppo_bf16_rne(p[i]);
 }
 
 // out[r][c] (row stride N; rows >= 1 go to out1 + (r - 1) N when out1) = sum over the nz chunks' partial tiles, in chunk order
@@ -322,8 +471,8 @@ __global__ __launch_bounds__(256) void ppo_stats_kernel(const double* rowstat, i
 }
 
 // delta_L of a trunk: dA[i][h] = (sum_o dhead[i][o] W_head[o][h]) * swish'(Z[i][h])  (vector ALU; n_out <= PM_MAX_OUT)
-__global__ __launch_bounds__(256) void ppo_head_back_kernel(int m, int H, int n_out, const float* dhead, int ldd, const float* W0, const float* W1,
-                                                            const float* Z, float* dA)
+template <typename T>
+__device__ __forceinline__ void ppo_head_back_row(int m, int H, int n_out, const float* dhead, int ldd, const float* W0, const float* W1, const float* Z, T* dA)
 {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)m * H) return;
@@ -332,7 +481,17 @@ __global__ __launch_bounds__(256) void ppo_head_back_kernel(int m, int H, int n_
     for (int o = 1; o < n_out; o++) s += dhead[(size_t)i * ldd + o] * W1[(size_t)(o - 1) * H + h];
     const float zz = Z[idx];
     const float sg = 1.0f / (1.0f + expf(-zz));
-    dA[idx] = s * (sg + zz * sg * (1.0f - sg));
+    ppo_put(dA, idx, s * (sg + zz * sg * (1.0f - sg)));
+}
+__global__ __launch_bounds__(256) void ppo_head_back_kernel(int m, int H, int n_out, const float* dhead, int ldd, const float* W0, const float* W1,
+                                                            const float* Z, float* dA)
+{
+    ppo_head_back_row(m, H, n_out, dhead, ldd, W0, W1, Z, dA);
+}
+__global__ __launch_bounds__(256) void ppo_head_back_bf16_kernel(int m, int H, int n_out, const float* dhead, int ldd, const float* W0, const float* W1,
+                                                                 const float* Z, uint16_t* dA)
+{
+    ppo_head_back_row(m, H, n_out, dhead, ldd, W0, W1, Z, dA);
 }
 
 // hk_ppo_advantages: the critic's value head over rows ids[0 .. m) (row ids and bootstrap ids, ppo_gather_kernel) -> v_old[id] / vb[id - n]

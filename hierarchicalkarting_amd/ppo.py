@@ -5,6 +5,7 @@ and leaves updated weights in the attached policy, so that the next step() acts 
     env.rollout_begin(R); env.step(R * P); env.rollout_close()
     tr.advantages()                              # critic over every row + the bootstrap inputs, GAE
     stats = tr.update(epochs=3, minibatch=512, lr=3e-4, eps=0.2, beta=5e-3)     # shuffle, minibatches, Adam; then publish
+    tr.set_precision("bf16")                     # trunk products on the bf16 matrix cores, fp32 master weights (hk.h "PRECISION")
 
 Nothing is computed here: the arrays below only describe the flat parameter layout the library uses."""
 import ctypes as C
@@ -13,6 +14,44 @@ from . import _lib
 from .policy import Policy
 
 DEFAULTS = dict(gamma=0.99, lambd=0.95, normalize_advantages=True, adam_beta1=0.9, adam_beta2=0.999, adam_eps=1e-8, seed=0)
+PRECISIONS = {"f32": _lib.HK_PPO_PREC_F32, "bf16": _lib.HK_PPO_PREC_BF16}
+_DTYPES = {"perm": np.int32, "shadow": np.uint16}       # every other HK_PPO_* field is float32
+
+
+def bf16_round(x):
+    """host twin of the device's fp32 -> bf16 rounding (hk_ppo.h ppo_bf16_rne): to nearest even, Inf kept, every NaN -> 0x7FC0.  -> uint16 bits"""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    r = ((u.astype(np.uint64) + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+    return np.where((u & 0x7FFFFFFF) > 0x7F800000, np.uint16(0x7FC0), r)
+
+
+def bf16_value(bits):
+    """bf16 bit patterns (uint16) -> the float32 values they stand for"""
+    return (np.ascontiguousarray(bits, np.uint16).astype(np.uint32) << 16).view(np.float32)
+
+
+def gemm_bf16(env, epi, A, B, bias=None, aux=None):
+    """One product of the trainer's bf16 kernel (hk_ppo_gemm_bf16, a debug tap) on uint16 bf16 bit patterns -> float32 [M, N].
+    epi 1: swish(bias + A B^T), A [M, K], B [N, K];  epi 2: (A B) * swish'(aux), A [M, K], B [K, N], aux [M, N];  epi 0: A^T B, A [K, M], B [K, N]"""
+    import torch
+    A, B = np.ascontiguousarray(A, np.uint16), np.ascontiguousarray(B, np.uint16)
+    if epi == 0:
+        (K, M), N = A.shape, B.shape[1]
+    else:
+        (M, K), N = A.shape, (B.shape[0] if epi == 1 else B.shape[1])
+    if B.shape != ((N, K) if epi == 1 else (K, N)):
+        raise ValueError("gemm_bf16: the operands' shapes do not fit epi %d" % epi)
+    dev = "cuda:%d" % env.built.cfg.device_id
+    up = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dt).view(np.int16 if dt == np.uint16 else dt)).to(dev)
+    a, b, bi, ax = up(A, np.uint16), up(B, np.uint16), up(bias, np.float32), up(aux, np.float32)
+    if (bi is not None and bi.numel() != N) or (ax is not None and tuple(ax.shape) != (M, N)):
+        raise ValueError("gemm_bf16: bias is [N], aux is [M, N]")
+    c = torch.empty((M, N), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    env._ck(env.L.hk_ppo_gemm_bf16(env.h, int(epi), M, N, K, ptr(a), ptr(b), ptr(bi), ptr(ax), ptr(c)))
+    env.synchronize()
+    return c.cpu().numpy()
 
 
 def param_layout(in_dim, hidden, n_layers, n_branch):
@@ -77,9 +116,11 @@ def permutation(n, seed, count):
 
 class PPOTrainer:
     """One trainer of RacingEnv `env`'s attached policy `policy_index` (hk_ppo_create).  critic: a Policy with n_branch 0 semantics (its trunk and
-    W_mu / b_mu are used) or None for Policy.random-style weights of the actor's shape; cfg: DEFAULTS' keys."""
+    W_mu / b_mu are used) or None for Policy.random-style weights of the actor's shape; precision: "f32" | "bf16" (set_precision); cfg: DEFAULTS' keys."""
 
-    def __init__(self, env, policy_index, critic=None, **cfg):
+    def __init__(self, env, policy_index, critic=None, precision="f32", **cfg):
+        if precision not in PRECISIONS:
+            raise ValueError("precision: one of %s" % sorted(PRECISIONS))
         bad = set(cfg) - set(DEFAULTS)
         if bad:
             raise TypeError("unknown PPO config keys: %s" % sorted(bad))
@@ -103,11 +144,31 @@ class PPOTrainer:
         self.actor_layout = param_layout(a.in_dim, a.hidden, len(a.W), a.n_branch)
         self.critic_layout = param_layout(a.in_dim, critic.hidden, len(critic.W), 0)
         self.n_actor = sum(int(np.prod(s)) for _, s in self.actor_layout)
+        self.set_precision(precision)
 
     def _ck(self, rc):
         self.env._ck(rc)
 
     # ---- the entry points
+    def set_precision(self, precision):
+        """ "f32" (the default: exact) or "bf16" (trunk products on the bf16 matrix cores, fp32 masters); between calls, never inside one"""
+        if precision not in PRECISIONS:
+            raise ValueError("precision: one of %s" % sorted(PRECISIONS))
+        self._ck(self.env.L.hk_ppo_set_precision(self.env.h, self.t, PRECISIONS[precision]))
+
+    @property
+    def precision(self):
+        rc = self.env.L.hk_ppo_get_precision(self.env.h, self.t)
+        if rc < 0:
+            self._ck(rc)
+        return {v: k for k, v in PRECISIONS.items()}[rc]
+
+    def shadow(self):
+        """-> the bf16 shadow of PARAMS as uint16 bit patterns in PARAMS' order (the critic's alignment gap removed)"""
+        s = self.read("shadow")
+        pad = s.size - self.read("params").size
+        return np.concatenate([s[:self.n_actor], s[self.n_actor + pad:]])
+
     def advantages(self):
         self._ck(self.env.L.hk_ppo_advantages(self.env.h, self.t))
 
@@ -154,16 +215,16 @@ class PPOTrainer:
         return ptr, n
 
     def read(self, name):
-        """-> numpy copy of an HK_PPO_* field, float32 (int32 for perm); the handle's stream is synchronised first"""
+        """-> numpy copy of an HK_PPO_* field, float32 (int32 for perm, uint16 for shadow); the handle's stream is synchronised first"""
         self.env.synchronize()
         ptr, n = self._field(name)
-        a = np.zeros(n, np.int32 if name == "perm" else np.float32)
+        a = np.zeros(n, _DTYPES.get(name, np.float32))
         if n:
             _lib.copy_device_to_host(a.ctypes.data, ptr, a.nbytes)
         return a
 
     def views(self):
-        """-> dict field -> torch CUDA tensor ALIASING the trainer's buffer, float32 (int32 for perm); rollout_views' caveats apply"""
+        """-> dict field -> torch CUDA tensor ALIASING the trainer's buffer, float32 (int32 for perm, int16 bits for shadow); rollout_views' caveats apply"""
         import torch
 
         class _Ext:
@@ -174,7 +235,7 @@ class PPOTrainer:
             n = self.env.L.hk_ppo_count(self.env.h, self.t, idx)
             ptr = self.env.L.hk_ppo_ptr(self.env.h, self.t, idx) if n > 0 else None
             if ptr:
-                out[name] = torch.as_tensor(_Ext(ptr, n, "<i4" if name == "perm" else "<f4"), device="cuda:%d" % self.env.built.cfg.device_id)
+                out[name] = torch.as_tensor(_Ext(ptr, n, {"perm": "<i4", "shadow": "<i2"}.get(name, "<f4")), device="cuda:%d" % self.env.built.cfg.device_id)
         return out
 
     def actor_params(self, flat=None):

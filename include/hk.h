@@ -547,8 +547,28 @@ void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* 
  *                      the value of the last minibatch's rows (a debug tap).  PERM (int32 [n]): the row permutation of the last epoch of the last
  *                      hk_ppo_update on the current advantages (the k-th epoch of a trainer, k = 0, 1, ..., is keyed by (seed, k)).
  * Row ids of hk_ppo_minibatch are read on hk_stream: a caller that writes them on another stream orders the two first (PPOTrainer does).
+ * PRECISION (hk_ppo_set_precision; HK_PPO_PREC_F32 is the default and is everything above, bit for bit).  HK_PPO_PREC_BF16 is mixed precision
+ * with fp32 master weights: both operands of every TRUNK matrix product of the actor and the critic — the forward a_l = swish(W_l a_{l-1} + b_l),
+ * the backward delta (delta W_l) * swish' and the weight gradient delta^T a_{l-1}, in hk_ppo_advantages as in a minibatch — are bf16, multiplied
+ * on the bf16 matrix cores and accumulated in fp32 (the forward accumulator seeded with the fp32 bias).  Each operand is rounded ONCE, where it is
+ * made, to nearest even (Inf kept, a NaN becomes the quiet NaN 0x7FC0): the trunk weights into a bf16 shadow of PARAMS (HK_PPO_SHADOW) after
+ * every Adam step, when the mode is switched on and at the entry of hk_ppo_advantages / hk_ppo_minibatch / hk_ppo_update (PARAMS is writable); the normalised,
+ * clipped input by the gather; the post-activations below the last layer and every delta by the kernel that makes them (so a bias gradient is
+ * the fp64 column sum of the rounded deltas).  Everything else stays fp32 and is computed as above: PARAMS, GRAD, the Adam moments, V_OLD / ADV /
+ * RET, the pre-activations swish' reads, the last layer's post-activation and the heads, log-probabilities, losses and per-row gradients on
+ * it, the head weight gradients, the column sums (fp64), the split-K combine (chunks of 256 rows, in chunk order) and hk_ppo_publish, which
+ * copies the fp32 masters; inference never sees the shadow.  No float atomics: the same call on the same state gives the same bits.
+ * What is no longer exact: the training forward is not the inference chain, and the rollout's LOGP_* come from the fp32 inference chain, so
+ * at unchanged parameters rho != 1, approx-KL and the clip fraction are small non-zero numbers and MB_MU / MB_LOGITS differ from MU / LOGITS
+ * by the bf16 rounding of the trunk.  Switching back to HK_PPO_PREC_F32 restores the exact path.  The precision is set between calls (a call
+ * waits for hk_stream and releases the minibatch workspace, which is laid out per precision: MB_* are unavailable until the next minibatch);
+ * an unknown value or a bad trainer index is refused with HK_ERR_INVALID.
+ * hk_ppo_gemm_bf16 (a debug tap in the spirit of hk_policy_forward) runs ONE product of the bf16 kernel on the caller's device buffers, bf16
+ * operands as raw 16-bit patterns, C fp32 [M][N], on hk_stream: epi 1 (forward) C = swish(bias + A B^T), A [M][K], B [N][K], bias [N] or NULL;
+ * epi 2 (backward delta) C = (A B) * swish'(aux), A [M][K], B [K][N], aux fp32 [M][N]; epi 0 (weight gradient) C = A^T B, A [K][M], B [K][N],
+ * split over K in chunks of 256 and combined in chunk order (synchronises).  A NULL operand, a non-positive M / N / K or another epi is refused.
  * Out of scope: updating the normaliser (frozen as attached), self-play opponent swaps and ELO, POCA and group rewards, LSTM memory,
- * gradient clipping, multi-GPU gradient all-reduce, bf16 training.  Everything is asynchronous on hk_stream. */
+ * gradient clipping, multi-GPU gradient all-reduce, bf16 inference and bf16 optimiser state.  Everything is asynchronous on hk_stream. */
 #define HK_PPO_STATS 6
 typedef struct hk_ppo_config {
     float gamma;                    /* 0.99 */
@@ -562,8 +582,11 @@ typedef struct hk_ppo_config {
 typedef enum hk_ppo_field {
     HK_PPO_PARAMS = 0, HK_PPO_GRAD, HK_PPO_ADAM_M, HK_PPO_ADAM_V, HK_PPO_V_OLD, HK_PPO_ADV, HK_PPO_RET,
     HK_PPO_MB_MU, HK_PPO_MB_LOGITS, HK_PPO_MB_VALUE, HK_PPO_PERM,
+    HK_PPO_SHADOW,      /* uint16 [P + pad]: PARAMS as bf16; the actor's element i at i, the critic's at i + pad, pad = (8 - n_actor % 8) % 8; once
+                           the trainer has been in HK_PPO_PREC_BF16 */
     HK_PPO_FIELDS
 } hk_ppo_field;
+typedef enum { HK_PPO_PREC_F32 = 0, HK_PPO_PREC_BF16 = 1 } hk_ppo_precision;
 int hk_ppo_create(hk_handle h, int policy, const hk_policy_desc* critic, const hk_ppo_config* cfg);
 int hk_ppo_advantages(hk_handle h, int trainer);
 int hk_ppo_minibatch(hk_handle h, int trainer, const int32_t* rows_dev, int m, float eps, float beta, float* stats /*[HK_PPO_STATS]*/);
@@ -572,6 +595,10 @@ int hk_ppo_update(hk_handle h, int trainer, int epochs, int minibatch, float lr,
 int hk_ppo_publish(hk_handle h, int trainer);
 void* hk_ppo_ptr(hk_handle h, int trainer, int field);
 int hk_ppo_count(hk_handle h, int trainer, int field);
+int hk_ppo_set_precision(hk_handle h, int trainer, int precision);
+int hk_ppo_get_precision(hk_handle h, int trainer);
+int hk_ppo_gemm_bf16(hk_handle h, int epi, int M, int N, int K, const void* A_dev, const void* B_dev, const float* bias_dev, const float* aux_dev,
+                     float* C_dev);
 
 /* ---- multi-GPU: the path's ONE exchange step ---------------------------------------------------------------
  * Race instances are independent (one RacingEnvController owns its own Agents[] / Sections[], REC:46-52): every rank steps its

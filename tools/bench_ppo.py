@@ -2,7 +2,8 @@
 """What a PPO update costs on the RL workload (bench.py --workload rl: 2v2 Oval, every agent LowMode RL, one 312 -> 256 x 3 actor per team,
 DecisionPeriod 2, rewards on): one rollout of R rows is collected (timed), then for team 0's trainer (critic 312 -> 256 x 3):
 hk_ppo_advantages, and one-epoch hk_ppo_update calls at minibatch 512 (ML-Agents' batch_size) and at a GPU-sized minibatch; every timing
-ends in a device synchronise, medians of --repeats.  One JSON line.
+ends in a device synchronise, medians of --repeats.  One JSON line per --precision; with several, the precisions alternate round by round
+(after a switch: advantages and one untimed update at the large minibatch, which allocate the workspace of that precision).
 FLOP count per trained row (stated, not measured): forward + backward of actor and critic = 3 x forward, forward = 2 x (weights of the trunks
 and heads) per row: 3 x 2 x (312 x 256 + 2 x 256 x 256 + 4 x 256 + 312 x 256 + 2 x 256 x 256 + 256) = 6 x 423 168 = 2.54 MFLOP per row at this shape."""
 import argparse
@@ -14,7 +15,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-PEAK_TF = 157.3          # MI355X f32 MFMA peak (TFLOP/s)
+PEAK_TF = {"f32": 157.3, "bf16": 16 * 157.3}          # MI355X MFMA peaks (TFLOP/s): f32 in / f32 acc, and bf16 at 16 x that rate
 
 
 def main():
@@ -23,6 +24,7 @@ def main():
     ap.add_argument("--rows", type=int, default=64, help="R: rows (decisions) per rollout")
     ap.add_argument("--big", type=int, default=32768, help="the GPU-sized minibatch")
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--precision", nargs="+", choices=("f32", "bf16"), default=["f32"], help="hk_ppo_set_precision; several: alternated")
     a = ap.parse_args()
     import numpy as np
     import hierarchicalkarting_amd as hk
@@ -43,33 +45,40 @@ def main():
     tr = env.ppo_trainer(0, seed=1)
     n = R * E * 2
 
-    def timed(f):
-        out = []
-        for _ in range(a.repeats):
-            env.synchronize()
-            t = time.perf_counter()
-            f()
-            env.synchronize()
-            out.append((time.perf_counter() - t) * 1e3)
-        return statistics.median(out), out
-
-    tr.advantages()                                  # (allocates; first launches)
-    adv_ms, adv_runs = timed(tr.advantages)
     H, K0 = 256, in_dim
     w = K0 * H + 2 * H * H + 4 * H + K0 * H + 2 * H * H + H
     flop_row = 3 * 2 * w
-    res = {}
-    for mb in (512, a.big):
-        tr.update(1, mb, 1e-5, 0.2, 5e-3)            # (workspace, first launches)
-        ms, runs = timed(lambda: tr.update(1, mb, 1e-5, 0.2, 5e-3))
-        rows = (n // min(mb, n)) * min(mb, n)
-        tf = rows * flop_row / (ms * 1e-3) / 1e12
-        res[str(mb)] = {"update_ms_per_epoch": ms, "runs": runs, "rows_per_s": rows / (ms * 1e-3), "tflops": tf, "peak_fraction": tf / PEAK_TF,
-                        "update_over_collection": ms / collect_ms}
+    sizes = (a.big, 512)
+    runs = {p: {"adv": [], **{mb: [] for mb in sizes}} for p in a.precision}
+
+    def timed(f):
+        env.synchronize()
+        t = time.perf_counter()
+        f()
+        env.synchronize()
+        return (time.perf_counter() - t) * 1e3
+
+    for _ in range(a.repeats):
+        for prec in a.precision:
+            tr.set_precision(prec)
+            tr.advantages()                              # (allocates; first launches)
+            tr.update(1, a.big, 1e-5, 0.2, 5e-3)
+            runs[prec]["adv"].append(timed(tr.advantages))
+            for mb in sizes:
+                runs[prec][mb].append(timed(lambda: tr.update(1, mb, 1e-5, 0.2, 5e-3)))
     env.close()
-    print(json.dumps({"metric": "PPO update on the RL workload (one actor + critic, one epoch)", "advantages_ms": adv_ms, "advantages_runs": adv_runs,
-                      "collect_ms": collect_ms, "minibatch": res,
-                      "config": {"envs": E, "agents": A, "rows": R, "n_rows": n, "flop_per_row": flop_row, "peak_tflops": PEAK_TF}}))
+    for prec in a.precision:
+        res = {}
+        for mb in sorted(sizes):
+            ms = statistics.median(runs[prec][mb])
+            rows = (n // min(mb, n)) * min(mb, n)
+            tf = rows * flop_row / (ms * 1e-3) / 1e12
+            res[str(mb)] = {"update_ms_per_epoch": ms, "runs": runs[prec][mb], "rows_per_s": rows / (ms * 1e-3), "tflops": tf,
+                            "peak_fraction": tf / PEAK_TF[prec], "update_over_collection": ms / collect_ms}
+        print(json.dumps({"metric": "PPO update on the RL workload (one actor + critic, one epoch)", "precision": prec,
+                          "advantages_ms": statistics.median(runs[prec]["adv"]), "advantages_runs": runs[prec]["adv"], "collect_ms": collect_ms,
+                          "minibatch": res, "config": {"envs": E, "agents": A, "rows": R, "n_rows": n, "flop_per_row": flop_row,
+                                                       "peak_tflops": PEAK_TF[prec]}}))
 
 
 if __name__ == "__main__":
