@@ -220,10 +220,8 @@ struct hk_context {
         bool perm_valid = false;       // an hk_ppo_update has written PERM for the current rows
         float* rowbuf = nullptr;       // V_OLD, ADV, RET [n], V_BOOT [E S], PERM (int) [n]
         size_t rowbuf_n = 0;
-        void* ws = nullptr;            // minibatch workspace (ppo_workspace)
-        size_t ws_bytes = 0;
+        void* ws = nullptr;            // minibatch workspace of cap rows (PpoWs, ppo_ws_layout); last_m: the rows of the last minibatch
         int cap = 0, last_m = 0;
-        float* mb_mu = nullptr; float* mb_logits = nullptr; float* mb_v = nullptr;
         int prec = HK_PPO_PREC_F32;    // hk_ppo_set_precision
         uint16_t* shadow = nullptr;    // HK_PPO_PREC_BF16: PARAMS rounded to bf16, the critic shadow_pad elements on (ppo_shadow_kernel)
         size_t shadow_pad = 0;
@@ -1331,19 +1329,29 @@ void* hk_rollout_ptr(hk_handle h, int field)
 extern "C++" {
 namespace {
 
-// the minibatch workspace of a trainer at capacity M rows: pointers into one allocation (ppo_workspace)
+// The two precisions (hk.h "PRECISION") share every line from the gather to Adam: a trunk matrix is a PpoMat, and ppo_gather, ppo_product
+// (ppo_wgrad goes through it), ppo_colsum, ppo_head_back and ppo_weights are the only places that look at which kind it is.
+
+// a matrix in the trainer's trunk precision: fp32 (f) or bf16 bit patterns (b), exactly one of them set
+struct PpoMat {
+    float* f = nullptr;
+    uint16_t* b = nullptr;
+    PpoMat() = default;
+    PpoMat(float* p) : f(p) {}
+    PpoMat(uint16_t* p) : b(p) {}
+};
+
+// the minibatch workspace of a trainer at capacity M rows: pointers into one allocation (Ppo::ws)
 struct PpoWs {
     int* ids; int* valid; int* n_valid;
-    float* X0;
-    float* Za[HK_POLICY_MAX_LAYERS]; float* Aa[HK_POLICY_MAX_LAYERS];
-    float* Zc[HK_POLICY_MAX_LAYERS]; float* Ac[HK_POLICY_MAX_LAYERS];
-    float *d0, *d1, *dhead, *dls, *dv, *part, *stats;
+    // HK_PPO_PREC_BF16: the input, the post-activations below the last layer and the deltas are bf16; the last layer's stays fp32 (the heads read it)
+    PpoMat X0;
+    float* Za[HK_POLICY_MAX_LAYERS]; PpoMat Aa[HK_POLICY_MAX_LAYERS];
+    float* Zc[HK_POLICY_MAX_LAYERS]; PpoMat Ac[HK_POLICY_MAX_LAYERS];
+    PpoMat d0, d1;
+    float *dhead, *dls, *dv, *part, *stats;
     double *rowstat, *acc;
     float *mb_mu, *mb_logits, *mb_v;
-    // HK_PPO_PREC_BF16: the input, the post-activations below the last layer and the deltas are bf16 (X0, those Aa / Ac, d0, d1 are then null)
-    uint16_t* X0b;
-    uint16_t* Aab[HK_POLICY_MAX_LAYERS]; uint16_t* Acb[HK_POLICY_MAX_LAYERS];
-    uint16_t *d0b, *d1b;
 };
 
 size_t ppo_ws_layout(const hk_context::Ppo& t, int M, PpoWs* w)
@@ -1351,6 +1359,8 @@ size_t ppo_ws_layout(const hk_context::Ppo& t, int M, PpoWs* w)
     size_t off = 0;
     char* base = w ? (char*)t.ws : nullptr;
     auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
+    const bool bf = t.prec == HK_PPO_PREC_BF16;
+    auto mat = [&](size_t count, bool bits) { char* p = take(count * (bits ? 2 : 4)); return bits ? PpoMat((uint16_t*)p) : PpoMat((float*)p); };
     const size_t Mz = (size_t)M;
     const int Ha = t.actor.hidden, Hc = t.critic.hidden, Hm = std::max(Ha, Hc), in = t.actor.in_dim, nb = t.actor.n_branch;
     size_t mn = (size_t)(1 + nb) * Ha;                          // the largest weight gradient: a layer's H x K, or the heads'
@@ -1359,23 +1369,10 @@ size_t ppo_ws_layout(const hk_context::Ppo& t, int M, PpoWs* w)
     const size_t nz = (Mz + hk::PPO_KCH - 1) / hk::PPO_KCH;
     PpoWs d{};
     d.ids = (int*)take(Mz * 4); d.valid = (int*)take(Mz * 4); d.n_valid = (int*)take(16);
-    if (t.prec == HK_PPO_PREC_BF16) {
-        d.X0b = (uint16_t*)take(Mz * in * 2);
-        for (int l = 0; l < t.actor.n_layers; l++) {
-            d.Za[l] = (float*)take(Mz * Ha * 4);
-            if (l == t.actor.n_layers - 1) d.Aa[l] = (float*)take(Mz * Ha * 4); else d.Aab[l] = (uint16_t*)take(Mz * Ha * 2);
-        }
-        for (int l = 0; l < t.critic.n_layers; l++) {
-            d.Zc[l] = (float*)take(Mz * Hc * 4);
-            if (l == t.critic.n_layers - 1) d.Ac[l] = (float*)take(Mz * Hc * 4); else d.Acb[l] = (uint16_t*)take(Mz * Hc * 2);
-        }
-        d.d0b = (uint16_t*)take(Mz * Hm * 2); d.d1b = (uint16_t*)take(Mz * Hm * 2);
-    } else {
-        d.X0 = (float*)take(Mz * in * 4);
-        for (int l = 0; l < t.actor.n_layers; l++) { d.Za[l] = (float*)take(Mz * Ha * 4); d.Aa[l] = (float*)take(Mz * Ha * 4); }
-        for (int l = 0; l < t.critic.n_layers; l++) { d.Zc[l] = (float*)take(Mz * Hc * 4); d.Ac[l] = (float*)take(Mz * Hc * 4); }
-        d.d0 = (float*)take(Mz * Hm * 4); d.d1 = (float*)take(Mz * Hm * 4);
-    }
+    d.X0 = mat(Mz * in, bf);
+    for (int l = 0; l < t.actor.n_layers; l++) { d.Za[l] = (float*)take(Mz * Ha * 4); d.Aa[l] = mat(Mz * Ha, bf && l < t.actor.n_layers - 1); }
+    for (int l = 0; l < t.critic.n_layers; l++) { d.Zc[l] = (float*)take(Mz * Hc * 4); d.Ac[l] = mat(Mz * Hc, bf && l < t.critic.n_layers - 1); }
+    d.d0 = mat(Mz * Hm, bf); d.d1 = mat(Mz * Hm, bf);
     d.dhead = (float*)take(Mz * hk::PM_MAX_OUT * 4); d.dls = (float*)take(Mz * 4); d.dv = (float*)take(Mz * 4);
     d.part = (float*)take(nz * mn * 4);
     d.stats = (float*)take(8 * 4);
@@ -1385,17 +1382,32 @@ size_t ppo_ws_layout(const hk_context::Ppo& t, int M, PpoWs* w)
     return off;
 }
 
+int ppo_drop_ws(hk_handle h, hk_context::Ppo& t)
+{
+    if (t.ws) HK_HIP(h, hipFree(t.ws));
+    t.ws = nullptr; t.cap = 0; t.last_m = 0;
+    return HK_OK;
+}
+
 int ppo_ensure_ws(hk_handle h, hk_context::Ppo& t, int M, PpoWs& w)
 {
     if (M > t.cap) {
-        const size_t bytes = ppo_ws_layout(t, M, nullptr);
-        if (t.ws) HK_HIP(h, hipFree(t.ws));
-        t.ws = nullptr; t.cap = 0; t.ws_bytes = 0; t.last_m = 0;
-        HK_HIP(h, hipMalloc(&t.ws, bytes));
-        t.cap = M; t.ws_bytes = bytes;
+        int rc = ppo_drop_ws(h, t);
+        if (rc) return rc;
+        HK_HIP(h, hipMalloc(&t.ws, ppo_ws_layout(t, M, nullptr)));
+        t.cap = M;
     }
     ppo_ws_layout(t, t.cap, &w);
     return HK_OK;
+}
+
+// the rows' buffer of a trainer (Ppo::rowbuf) after hk_ppo_advantages set t.n: V_OLD, ADV, RET [n], V_BOOT [E S], PERM [n]
+struct PpoRowBuf { float *v_old, *adv, *ret, *v_boot; int* perm; };
+PpoRowBuf ppo_rowbuf(hk_handle h, const hk_context::Ppo& t)
+{
+    const size_t n = (size_t)t.n, nbt = (size_t)h->cfg.num_envs * h->policy[t.policy].q.n_slots;
+    float* p = t.rowbuf;
+    return PpoRowBuf{p, p + n, p + 2 * n, p + 3 * n, (int*)(p + 3 * n + nbt)};
 }
 
 hk::PpoRows ppo_rows(hk_handle h, const hk_context::Ppo& t)
@@ -1417,107 +1429,87 @@ hk::PpoRows ppo_rows(hk_handle h, const hk_context::Ppo& t)
 
 inline unsigned nblk(size_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
 
+void ppo_gather(hipStream_t s, const hk::PpoRows& P, const int* ids, int m, int boot, PpoMat X0, int* valid)
+{
+    const dim3 grid(nblk((size_t)m * P.in_dim));
+    if (X0.b) hipLaunchKernelGGL(hk::ppo_gather_kernel<uint16_t>, grid, dim3(256), 0, s, P, ids, m, boot, X0.b, valid);
+    else hipLaunchKernelGGL(hk::ppo_gather_kernel<float>, grid, dim3(256), 0, s, P, ids, m, boot, X0.f, valid);
+}
+
+// C [M][N] = epilogue EPI of the product of A and B over K, in chunks of kch (hk_ppo.h).  An operand is given as its leading dimension and
+// whether k is its contiguous index — the bf16 kernel's form, which the fp32 kernel's two strides per operand follow from
 template <int EPI>
-void ppo_gemm(hipStream_t s, int M, int N, int K, const float* A, int sai, int sak, const float* B, int sbk, int sbj, const float* bias, float* C, int ldc,
-              float* Z, int kch)
+void ppo_product(hipStream_t s, int M, int N, int K, PpoMat A, int lda, bool a_kc, PpoMat B, int ldb, bool b_kc, const float* bias, PpoMat C, int ldc, float* Z,
+                 int kch)
 {
     const int nz = (K + kch - 1) / kch;
-    const dim3 grid(nblk(N, hk::PPO_TN), nblk(M, hk::PPO_TM), nz < 1 ? 1 : nz);
-    hipLaunchKernelGGL(hk::ppo_gemm_kernel<EPI>, grid, dim3(256), 0, s, M, N, K, A, sai, sak, B, sbk, sbj, bias, C, ldc, Z, kch);
+    const unsigned gz = nz < 1 ? 1 : nz;
+    if (A.b)
+        hipLaunchKernelGGL(hk::ppo_gemm_bf16_kernel<EPI>, dim3(nblk(N, hk::PB_TN), nblk(M, hk::PB_TM), gz), dim3(256), 0, s, M, N, K, A.b, lda, (int)a_kc, B.b,
+                           ldb, (int)b_kc, bias, C.f, C.b, ldc, Z, kch);
+    else
+        hipLaunchKernelGGL(hk::ppo_gemm_kernel<EPI>, dim3(nblk(N, hk::PPO_TN), nblk(M, hk::PPO_TM), gz), dim3(256), 0, s, M, N, K, A.f, a_kc ? lda : 1,
+                           a_kc ? 1 : lda, B.f, b_kc ? 1 : ldb, b_kc ? ldb : 1, bias, C.f, ldc, Z, kch);
 }
 
-// a weight gradient dst = sum over rows of D(i, o) X(i, c): split into chunks of PPO_KCH rows, partial tiles combined in chunk order
-void ppo_wgrad(hipStream_t s, const PpoWs& w, int M, int N, int m, const float* D, int sdi, int sdo, const float* X, int ldx, float* out0, float* out1)
+// a weight gradient out [M][N] = sum over the m rows of D[i][o] X[i][c] (both row-major, of one kind): fixed chunks of PPO_KCH rows into part,
+// the partial tiles combined in chunk order (out1: the rows from the second on go there, the heads' W_branch)
+void ppo_wgrad(hipStream_t s, float* part, int M, int N, int m, PpoMat D, int ldd, PpoMat X, int ldx, float* out0, float* out1)
 {
     const int nz = (m + hk::PPO_KCH - 1) / hk::PPO_KCH;
-    ppo_gemm<0>(s, M, N, m, D, sdo, sdi, X, ldx, 1, nullptr, w.part, N, nullptr, hk::PPO_KCH);
-    hipLaunchKernelGGL(hk::ppo_combine_kernel, dim3(nblk((size_t)M * N)), dim3(256), 0, s, w.part, nz, M, N, out0, out1);
+    ppo_product<0>(s, M, N, m, D, ldd, false, X, ldx, false, nullptr, part, N, nullptr, hk::PPO_KCH);
+    hipLaunchKernelGGL(hk::ppo_combine_kernel, dim3(nblk((size_t)M * N)), dim3(256), 0, s, part, nz, M, N, out0, out1);
 }
 
-void ppo_colsum(hipStream_t s, const float* X, int m, int ld, int ncol, float* out)
+void ppo_colsum(hipStream_t s, PpoMat X, int m, int ld, int ncol, float* out)
 {
-    hipLaunchKernelGGL(hk::ppo_colsum_kernel<float>, dim3(ncol), dim3(256), 0, s, X, m, ld, out);
+    if (X.b) hipLaunchKernelGGL(hk::ppo_colsum_kernel<hk::ppo_bf16>, dim3(ncol), dim3(256), 0, s, reinterpret_cast<const hk::ppo_bf16*>(X.b), m, ld, out);
+    else hipLaunchKernelGGL(hk::ppo_colsum_kernel<float>, dim3(ncol), dim3(256), 0, s, X.f, m, ld, out);
 }
 
-// ---- HK_PPO_PREC_BF16: the same products on ppo_gemm_bf16_kernel (hk_ppo.h)
-template <int EPI>
-void ppo_gemm_bf16(hipStream_t s, int M, int N, int K, const uint16_t* A, int lda, bool a_kc, const uint16_t* B, int ldb, bool b_kc, const float* bias, float* C,
-                   uint16_t* Cb, int ldc, float* Z, int kch)
+// the last trunk layer's delta dA = (dhead [W0; W1]) * swish'(Z), through the heads' weights on the vector ALU
+void ppo_head_back(hipStream_t s, int m, int H, int n_out, const float* dhead, int ldd, const float* W0, const float* W1, const float* Z, PpoMat dA)
 {
-    const int nz = (K + kch - 1) / kch;
-    const dim3 grid(nblk(N, hk::PB_TN), nblk(M, hk::PB_TM), nz < 1 ? 1 : nz);
-    hipLaunchKernelGGL(hk::ppo_gemm_bf16_kernel<EPI>, grid, dim3(256), 0, s, M, N, K, A, lda, (int)a_kc, B, ldb, (int)b_kc, bias, C, Cb, ldc, Z, kch);
+    const dim3 grid(nblk((size_t)m * H));
+    if (dA.b) hipLaunchKernelGGL(hk::ppo_head_back_bf16_kernel, grid, dim3(256), 0, s, m, H, n_out, dhead, ldd, W0, W1, Z, dA.b);
+    else hipLaunchKernelGGL(hk::ppo_head_back_kernel, grid, dim3(256), 0, s, m, H, n_out, dhead, ldd, W0, W1, Z, dA.f);
 }
 
-// dst [M][N] = sum over the m rows of D[i][o] X[i][c] (both bf16, row-major): fixed chunks of PPO_KCH rows, combined in chunk order
-void ppo_wgrad_bf16(hipStream_t s, float* part, int M, int N, int m, const uint16_t* D, int ldd, const uint16_t* X, int ldx, float* out)
+// a network's layer l as the trunk products read it ([out][in]): PARAMS, or their bf16 shadow (the critic's shadow_pad elements on)
+PpoMat ppo_weights(const hk_context::Ppo& t, const hk::PpoNet& net, int l)
 {
-    const int nz = (m + hk::PPO_KCH - 1) / hk::PPO_KCH;
-    ppo_gemm_bf16<0>(s, M, N, m, D, ldd, false, X, ldx, false, nullptr, part, nullptr, N, nullptr, hk::PPO_KCH);
-    hipLaunchKernelGGL(hk::ppo_combine_kernel, dim3(nblk((size_t)M * N)), dim3(256), 0, s, part, nz, M, N, out, (float*)nullptr);
-}
-
-// the shadow's view of a network's layer l ([out][in], as PARAMS)
-const uint16_t* ppo_shadow_w(const hk_context::Ppo& t, const hk::PpoNet& net, int l)
-{
+    if (t.prec != HK_PPO_PREC_BF16) return t.param + net.oW[l];
     return t.shadow + net.oW[l] + (&net == &t.critic ? t.shadow_pad : 0);
 }
 
+// HK_PPO_PREC_BF16: PARAMS rounded into the shadow — after Adam, and at every entry point, since PARAMS is writable through hk_ppo_ptr
 void ppo_shadow_refresh(hipStream_t s, const hk_context::Ppo& t)
 {
+    if (t.prec != HK_PPO_PREC_BF16) return;
     hipLaunchKernelGGL(hk::ppo_shadow_kernel, dim3(nblk(t.P)), dim3(256), 0, s, t.param, t.shadow, t.P, t.actor.count, t.shadow_pad);
 }
 
-// trunk forward: Z[l] fp32; the post-activation rounded to bf16 (Ab[l]) below the last layer, fp32 (A[L - 1]) at it, where the heads read it
-void ppo_trunk_forward_bf16(hipStream_t s, const hk_context::Ppo& t, const hk::PpoNet& net, const uint16_t* X0b, int m, float* const* Z, float* const* A,
-                            uint16_t* const* Ab)
+// trunk forward on X0: Z[l] = W_l a_{l-1} + b_l (MFMA, k ascending; fp32), A[l] = swish(Z[l]) in the kind the workspace gave it
+void ppo_trunk_forward(hipStream_t s, const hk_context::Ppo& t, const hk::PpoNet& net, PpoMat X0, int m, float* const* Z, const PpoMat* A)
 {
     const int H = net.hidden;
     for (int l = 0; l < net.n_layers; l++) {
         const int K = l == 0 ? net.in_dim : H;
-        const bool last = l == net.n_layers - 1;
-        ppo_gemm_bf16<1>(s, m, H, K, l == 0 ? X0b : Ab[l - 1], K, true, ppo_shadow_w(t, net, l), K, true, t.param + net.ob[l], last ? A[l] : nullptr,
-                         last ? nullptr : Ab[l], H, Z[l], K);
+        ppo_product<1>(s, m, H, K, l == 0 ? X0 : A[l - 1], K, true, ppo_weights(t, net, l), K, true, t.param + net.ob[l], A[l], H, Z[l], K);
     }
 }
 
-// trunk backward from dcur = dL / dZ[L - 1] (bf16): weight and bias gradients into grad, delta through W_l * swish' (rounded by the epilogue)
-void ppo_trunk_backward_bf16(hipStream_t s, const PpoWs& w, const hk_context::Ppo& t, const hk::PpoNet& net, float* grad, int m, float* const* Z,
-                             uint16_t* const* Ab, uint16_t* dcur, uint16_t* dnext)
+// trunk backward from dcur = dL / dZ[L - 1]: weight and bias gradients into grad, delta through W_l * swish' (dnext: the other delta buffer)
+void ppo_trunk_backward(hipStream_t s, const PpoWs& w, const hk_context::Ppo& t, const hk::PpoNet& net, float* grad, int m, float* const* Z, const PpoMat* A,
+                        PpoMat dcur, PpoMat dnext)
 {
     const int H = net.hidden;
     for (int l = net.n_layers - 1; l >= 0; l--) {
         const int K = l == 0 ? net.in_dim : H;
-        ppo_wgrad_bf16(s, w.part, H, K, m, dcur, H, l == 0 ? w.X0b : Ab[l - 1], K, grad + net.oW[l]);
-        hipLaunchKernelGGL(hk::ppo_colsum_kernel<hk::ppo_bf16>, dim3(H), dim3(256), 0, s, reinterpret_cast<const hk::ppo_bf16*>(dcur), m, H, grad + net.ob[l]);
-        if (l > 0) {
-            ppo_gemm_bf16<2>(s, m, H, H, dcur, H, true, ppo_shadow_w(t, net, l), H, false, nullptr, nullptr, dnext, H, Z[l - 1], H);
-            std::swap(dcur, dnext);
-        }
-    }
-}
-
-// trunk forward on X0: Z[l] = W_l a_{l-1} + b_l (MFMA, k ascending), A[l] = swish(Z[l])
-void ppo_trunk_forward(hipStream_t s, const hk::PpoNet& net, const float* prm, const float* X0, int m, float* const* Z, float* const* A)
-{
-    const int H = net.hidden;
-    for (int l = 0; l < net.n_layers; l++) {
-        const int K = l == 0 ? net.in_dim : H;
-        ppo_gemm<1>(s, m, H, K, l == 0 ? X0 : A[l - 1], K, 1, prm + net.oW[l], 1, K, prm + net.ob[l], A[l], H, Z[l], K);
-    }
-}
-
-// trunk backward from dcur = dL / dZ[L - 1]: weight and bias gradients into grad, delta through W_l * swish'
-void ppo_trunk_backward(hipStream_t s, const PpoWs& w, const hk::PpoNet& net, const float* prm, float* grad, const float* X0, int m, float* const* Z,
-                        float* const* A, float* dcur, float* dnext)
-{
-    const int H = net.hidden;
-    for (int l = net.n_layers - 1; l >= 0; l--) {
-        const int K = l == 0 ? net.in_dim : H;
-        ppo_wgrad(s, w, H, K, m, dcur, H, 1, l == 0 ? X0 : A[l - 1], K, grad + net.oW[l], nullptr);
+        ppo_wgrad(s, w.part, H, K, m, dcur, H, l == 0 ? w.X0 : A[l - 1], K, grad + net.oW[l], nullptr);
         ppo_colsum(s, dcur, m, H, H, grad + net.ob[l]);
         if (l > 0) {
-            ppo_gemm<2>(s, m, H, H, dcur, H, 1, prm + net.oW[l], H, 1, nullptr, dnext, H, Z[l - 1], H);
+            ppo_product<2>(s, m, H, H, dcur, H, true, ppo_weights(t, net, l), H, false, nullptr, dnext, H, Z[l - 1], H);
             std::swap(dcur, dnext);
         }
     }
@@ -1531,52 +1523,38 @@ int ppo_mb(hk_handle h, hk_context::Ppo& t, const int32_t* ids, int m, float eps
     if (rc) return rc;
     hipStream_t s = h->stream;
     const hk::PpoRows P = ppo_rows(h, t);
+    const PpoRowBuf rows = ppo_rowbuf(h, t);
     const float* prm = t.param;
     float* grad = t.param + t.P;
-    const bool bf = t.prec == HK_PPO_PREC_BF16;
-    if (bf) hipLaunchKernelGGL(hk::ppo_gather_kernel<uint16_t>, dim3(nblk((size_t)m * P.in_dim)), dim3(256), 0, s, P, ids, m, 0, w.X0b, w.valid);
-    else hipLaunchKernelGGL(hk::ppo_gather_kernel<float>, dim3(nblk((size_t)m * P.in_dim)), dim3(256), 0, s, P, ids, m, 0, w.X0, w.valid);
-    hipLaunchKernelGGL(hk::ppo_count_kernel, dim3(1), dim3(256), 0, s, w.valid, m, w.n_valid);
-    if (bf) {
-        ppo_trunk_forward_bf16(s, t, t.actor, w.X0b, m, w.Za, w.Aa, w.Aab);
-        ppo_trunk_forward_bf16(s, t, t.critic, w.X0b, m, w.Zc, w.Ac, w.Acb);
-    } else {
-        ppo_trunk_forward(s, t.actor, prm, w.X0, m, w.Za, w.Aa);
-        ppo_trunk_forward(s, t.critic, prm, w.X0, m, w.Zc, w.Ac);
-    }
     const hk::PpoNet &na = t.actor, &nc = t.critic;
+    const int Ha = na.hidden, Hc = nc.hidden, nb = na.n_branch, La = na.n_layers - 1, Lc = nc.n_layers - 1;      // La, Lc: the last trunk layers
+    ppo_gather(s, P, ids, m, 0, w.X0, w.valid);
+    hipLaunchKernelGGL(hk::ppo_count_kernel, dim3(1), dim3(256), 0, s, w.valid, m, w.n_valid);
+    ppo_trunk_forward(s, t, na, w.X0, m, w.Za, w.Aa);
+    ppo_trunk_forward(s, t, nc, w.X0, m, w.Zc, w.Ac);
     hk::PpoLossArgs L{};
-    L.Aa = w.Aa[na.n_layers - 1]; L.Ac = w.Ac[nc.n_layers - 1];
+    L.Aa = w.Aa[La].f; L.Ac = w.Ac[Lc].f;
     L.W_mu = prm + na.oWmu; L.b_mu = prm + na.obmu; L.log_sigma = prm + na.ols; L.W_br = prm + na.oWbr; L.b_br = prm + na.obbr;
     L.W_v = prm + nc.oWmu; L.b_v = prm + nc.obmu;
-    L.v_old = t.rowbuf; L.adv = t.rowbuf + t.n; L.ret = t.rowbuf + 2 * (size_t)t.n;
-    L.ids = ids; L.valid = w.valid; L.n_valid = w.n_valid; L.m = m; L.n = t.n; L.Ha = na.hidden; L.Hc = nc.hidden; L.nb = na.n_branch;
+    L.v_old = rows.v_old; L.adv = rows.adv; L.ret = rows.ret;
+    L.ids = ids; L.valid = w.valid; L.n_valid = w.n_valid; L.m = m; L.n = t.n; L.Ha = Ha; L.Hc = Hc; L.nb = nb;
     L.eps = eps; L.beta = beta;
     L.dhead = w.dhead; L.dls = w.dls; L.dv = w.dv; L.rowstat = w.rowstat;
     L.mu_out = w.mb_mu; L.logit_out = w.mb_logits; L.v_out = w.mb_v;
     hipLaunchKernelGGL(hk::ppo_loss_kernel, dim3(nblk(m)), dim3(256), 0, s, P, L);
     hipLaunchKernelGGL(hk::ppo_stats_kernel, dim3(1), dim3(256), 0, s, w.rowstat, m, w.stats, acc ? w.acc : nullptr);
-    // actor: the heads (vector ALU), then the trunk
-    const int Ha = na.hidden, Hc = nc.hidden, nb = na.n_branch;
-    if (bf) hipLaunchKernelGGL(hk::ppo_head_back_bf16_kernel, dim3(nblk((size_t)m * Ha)), dim3(256), 0, s, m, Ha, 1 + nb, w.dhead, hk::PM_MAX_OUT,
-                               prm + na.oWmu, prm + na.oWbr, w.Za[na.n_layers - 1], w.d0b);
-    else hipLaunchKernelGGL(hk::ppo_head_back_kernel, dim3(nblk((size_t)m * Ha)), dim3(256), 0, s, m, Ha, 1 + nb, w.dhead, hk::PM_MAX_OUT, prm + na.oWmu,
-                       prm + na.oWbr, w.Za[na.n_layers - 1], w.d0);
-    ppo_wgrad(s, w, 1 + nb, Ha, m, w.dhead, hk::PM_MAX_OUT, 1, w.Aa[na.n_layers - 1], Ha, grad + na.oWmu, grad + na.oWbr);
+    // actor: the heads (vector ALU; their gradients fp32 in both precisions), then the trunk
+    ppo_head_back(s, m, Ha, 1 + nb, w.dhead, hk::PM_MAX_OUT, prm + na.oWmu, prm + na.oWbr, w.Za[La], w.d0);
+    ppo_wgrad(s, w.part, 1 + nb, Ha, m, w.dhead, hk::PM_MAX_OUT, w.Aa[La], Ha, grad + na.oWmu, grad + na.oWbr);
     ppo_colsum(s, w.dhead, m, hk::PM_MAX_OUT, 1, grad + na.obmu);
     ppo_colsum(s, w.dhead + 1, m, hk::PM_MAX_OUT, nb, grad + na.obbr);
     ppo_colsum(s, w.dls, m, 1, 1, grad + na.ols);
-    if (bf) ppo_trunk_backward_bf16(s, w, t, na, grad, m, w.Za, w.Aab, w.d0b, w.d1b);
-    else ppo_trunk_backward(s, w, na, prm, grad, w.X0, m, w.Za, w.Aa, w.d0, w.d1);
+    ppo_trunk_backward(s, w, t, na, grad, m, w.Za, w.Aa, w.d0, w.d1);
     // critic
-    if (bf) hipLaunchKernelGGL(hk::ppo_head_back_bf16_kernel, dim3(nblk((size_t)m * Hc)), dim3(256), 0, s, m, Hc, 1, w.dv, 1, prm + nc.oWmu,
-                               (const float*)nullptr, w.Zc[nc.n_layers - 1], w.d0b);
-    else hipLaunchKernelGGL(hk::ppo_head_back_kernel, dim3(nblk((size_t)m * Hc)), dim3(256), 0, s, m, Hc, 1, w.dv, 1, prm + nc.oWmu, nullptr,
-                       w.Zc[nc.n_layers - 1], w.d0);
-    ppo_wgrad(s, w, 1, Hc, m, w.dv, 1, 1, w.Ac[nc.n_layers - 1], Hc, grad + nc.oWmu, nullptr);
+    ppo_head_back(s, m, Hc, 1, w.dv, 1, prm + nc.oWmu, nullptr, w.Zc[Lc], w.d0);
+    ppo_wgrad(s, w.part, 1, Hc, m, w.dv, 1, w.Ac[Lc], Hc, grad + nc.oWmu, nullptr);
     ppo_colsum(s, w.dv, m, 1, 1, grad + nc.obmu);
-    if (bf) ppo_trunk_backward_bf16(s, w, t, nc, grad, m, w.Zc, w.Acb, w.d0b, w.d1b);
-    else ppo_trunk_backward(s, w, nc, prm, grad, w.X0, m, w.Zc, w.Ac, w.d0, w.d1);
+    ppo_trunk_backward(s, w, t, nc, grad, m, w.Zc, w.Ac, w.d0, w.d1);
     HK_HIP(h, hipGetLastError());
     t.last_m = m;
     return HK_OK;
@@ -1591,7 +1569,7 @@ int ppo_adam_step(hk_handle h, hk_context::Ppo& t, float lr)
     float* p = t.param;
     hipLaunchKernelGGL(hk::ppo_adam_kernel, dim3(nblk(t.P)), dim3(256), 0, h->stream, p, p + t.P, p + 2 * t.P, p + 3 * t.P, t.P, b1, omb1, b2, omb2, c1, c2,
                        t.cfg.adam_eps, lr);
-    if (t.prec == HK_PPO_PREC_BF16) ppo_shadow_refresh(h->stream, t);
+    ppo_shadow_refresh(h->stream, t);
     HK_HIP(h, hipGetLastError());
     return HK_OK;
 }
@@ -1676,28 +1654,23 @@ int hk_ppo_advantages(hk_handle h, int trainer)
         t.rowbuf_n = need;
     }
     t.n = n;
-    float *v_old = t.rowbuf, *adv = v_old + n, *ret = adv + n, *vb = ret + n;
+    const PpoRowBuf rows = ppo_rowbuf(h, t);
     PpoWs w;
     const int chunk = std::max(t.cap, std::min(n + nbt, 16384));
     if ((rc = ppo_ensure_ws(h, t, chunk, w))) return rc;
     hipStream_t s = h->stream;
     const hk::PpoNet& nc = t.critic;
-    if (t.prec == HK_PPO_PREC_BF16) ppo_shadow_refresh(s, t);      // PARAMS is writable through hk_ppo_ptr
+    ppo_shadow_refresh(s, t);
     for (int base = 0; base < n + nbt; base += chunk) {
         const int m = std::min(chunk, n + nbt - base);
         hipLaunchKernelGGL(hk::ppo_iota_kernel, dim3(nblk(m)), dim3(256), 0, s, w.ids, base, m);
-        if (t.prec == HK_PPO_PREC_BF16) {
-            hipLaunchKernelGGL(hk::ppo_gather_kernel<uint16_t>, dim3(nblk((size_t)m * P.in_dim)), dim3(256), 0, s, P, w.ids, m, 1, w.X0b, w.valid);
-            ppo_trunk_forward_bf16(s, t, nc, w.X0b, m, w.Zc, w.Ac, w.Acb);
-        } else {
-            hipLaunchKernelGGL(hk::ppo_gather_kernel<float>, dim3(nblk((size_t)m * P.in_dim)), dim3(256), 0, s, P, w.ids, m, 1, w.X0, w.valid);
-            ppo_trunk_forward(s, nc, t.param, w.X0, m, w.Zc, w.Ac);
-        }
-        hipLaunchKernelGGL(hk::ppo_value_kernel, dim3(nblk(m)), dim3(256), 0, s, w.Ac[nc.n_layers - 1], m, nc.hidden, t.param + nc.oWmu, t.param + nc.obmu,
-                           w.ids, n, nbt, v_old, vb);
+        ppo_gather(s, P, w.ids, m, 1, w.X0, w.valid);
+        ppo_trunk_forward(s, t, nc, w.X0, m, w.Zc, w.Ac);
+        hipLaunchKernelGGL(hk::ppo_value_kernel, dim3(nblk(m)), dim3(256), 0, s, w.Ac[nc.n_layers - 1].f, m, nc.hidden, t.param + nc.oWmu, t.param + nc.obmu,
+                           w.ids, n, nbt, rows.v_old, rows.v_boot);
     }
-    hipLaunchKernelGGL(hk::ppo_gae_kernel, dim3(nblk(nbt)), dim3(256), 0, s, P, v_old, vb, t.cfg.gamma, t.cfg.lambd, adv, ret);
-    if (t.cfg.normalize_advantages) hipLaunchKernelGGL(hk::ppo_adv_norm_kernel, dim3(1), dim3(1024), 0, s, adv, n);
+    hipLaunchKernelGGL(hk::ppo_gae_kernel, dim3(nblk(nbt)), dim3(256), 0, s, P, rows.v_old, rows.v_boot, t.cfg.gamma, t.cfg.lambd, rows.adv, rows.ret);
+    if (t.cfg.normalize_advantages) hipLaunchKernelGGL(hk::ppo_adv_norm_kernel, dim3(1), dim3(1024), 0, s, rows.adv, n);
     HK_HIP(h, hipGetLastError());
     t.adv_gen = ro.gen;
     t.perm_valid = false;
@@ -1711,7 +1684,7 @@ int hk_ppo_minibatch(hk_handle h, int trainer, const int32_t* rows_dev, int m, f
     if (rc) return rc;
     if (!rows_dev || m < 1) return fail(h, HK_ERR_INVALID, "hk_ppo_minibatch: NULL rows or m < 1");
     auto& t = h->ppo[trainer];
-    if (t.prec == HK_PPO_PREC_BF16) ppo_shadow_refresh(h->stream, t);      // PARAMS is writable through hk_ppo_ptr
+    ppo_shadow_refresh(h->stream, t);
     if ((rc = ppo_mb(h, t, rows_dev, m, eps, beta, false))) return rc;
     if (stats) {
         PpoWs w;
@@ -1751,10 +1724,10 @@ int hk_ppo_update(hk_handle h, int trainer, int epochs, int minibatch, float lr,
     auto& t = h->ppo[trainer];
     const int n = t.n;
     const int mb = std::min(minibatch, n), nmb = n / mb;
-    int* perm = (int*)(t.rowbuf + 3 * (size_t)n + (size_t)h->cfg.num_envs * h->policy[t.policy].q.n_slots);
+    int* perm = ppo_rowbuf(h, t).perm;
     PpoWs w;
     if ((rc = ppo_ensure_ws(h, t, mb, w))) return rc;
-    if (t.prec == HK_PPO_PREC_BF16) ppo_shadow_refresh(h->stream, t);      // PARAMS is writable through hk_ppo_ptr
+    ppo_shadow_refresh(h->stream, t);
     for (int ep = 0; ep < epochs; ep++) {
         const bool last = ep == epochs - 1;
         if (last) HK_HIP(h, hipMemsetAsync(w.acc, 0, 8 * sizeof(double), h->stream));
@@ -1786,18 +1759,15 @@ int hk_ppo_set_precision(hk_handle h, int trainer, int precision)
     if (precision == t.prec) return HK_OK;
     // the workspace is laid out per precision: drop it once the stream is done with it (the next minibatch allocates the other layout)
     HK_HIP(h, hipStreamSynchronize(h->stream));
-    if (t.ws) HK_HIP(h, hipFree(t.ws));
-    t.ws = nullptr; t.cap = 0; t.ws_bytes = 0; t.last_m = 0;
-    if (precision == HK_PPO_PREC_BF16) {
-        if (!t.shadow) {
-            t.shadow_pad = (8 - t.actor.count % 8) % 8;
-            HK_HIP(h, hipMalloc(&t.shadow, (t.P + t.shadow_pad) * sizeof(uint16_t)));
-            HK_HIP(h, hipMemsetAsync(t.shadow, 0, (t.P + t.shadow_pad) * sizeof(uint16_t), h->stream));
-        }
-        ppo_shadow_refresh(h->stream, t);
-        HK_HIP(h, hipGetLastError());
+    if ((rc = ppo_drop_ws(h, t))) return rc;
+    if (precision == HK_PPO_PREC_BF16 && !t.shadow) {
+        t.shadow_pad = (8 - t.actor.count % 8) % 8;
+        HK_HIP(h, hipMalloc(&t.shadow, (t.P + t.shadow_pad) * sizeof(uint16_t)));
+        HK_HIP(h, hipMemsetAsync(t.shadow, 0, (t.P + t.shadow_pad) * sizeof(uint16_t), h->stream));
     }
-    t.prec = precision;
+    t.prec = precision;          // (before the refresh, which looks at it)
+    ppo_shadow_refresh(h->stream, t);
+    HK_HIP(h, hipGetLastError());
     return HK_OK;
 }
 
@@ -1814,21 +1784,21 @@ int hk_ppo_gemm_bf16(hk_handle h, int epi, int M, int N, int K, const void* A_de
     if (epi < 0 || epi > 2) return fail(h, HK_ERR_INVALID, "hk_ppo_gemm_bf16: unknown epi");
     if (M < 1 || N < 1 || K < 1) return fail(h, HK_ERR_INVALID, "hk_ppo_gemm_bf16: M, N, K must be positive");
     if (!A_dev || !B_dev || !C_dev || (epi == 2 && !aux_dev)) return fail(h, HK_ERR_INVALID, "hk_ppo_gemm_bf16: NULL operand");
-    const uint16_t *A = (const uint16_t*)A_dev, *B = (const uint16_t*)B_dev;
+    const PpoMat A((uint16_t*)A_dev), B((uint16_t*)B_dev);          // (read only)
     hipStream_t s = h->stream;
     if (epi == 0) {
         float* part = nullptr;
         const size_t nz = ((size_t)K + hk::PPO_KCH - 1) / hk::PPO_KCH;
         HK_HIP(h, hipMalloc(&part, nz * M * N * sizeof(float)));
-        ppo_wgrad_bf16(s, part, M, N, K, A, M, B, N, C_dev);
+        ppo_wgrad(s, part, M, N, K, A, M, B, N, C_dev, nullptr);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         (void)hipFree(part);
         HK_HIP(h, e);
         return HK_OK;
     }
-    if (epi == 1) ppo_gemm_bf16<1>(s, M, N, K, A, K, true, B, K, true, bias_dev, C_dev, nullptr, N, nullptr, K);
-    else ppo_gemm_bf16<2>(s, M, N, K, A, K, true, B, N, false, nullptr, C_dev, nullptr, N, const_cast<float*>(aux_dev), K);
+    if (epi == 1) ppo_product<1>(s, M, N, K, A, K, true, B, K, true, bias_dev, C_dev, N, nullptr, K);
+    else ppo_product<2>(s, M, N, K, A, K, true, B, N, false, nullptr, C_dev, N, const_cast<float*>(aux_dev), K);
     HK_HIP(h, hipGetLastError());
     return HK_OK;
 }
@@ -1842,11 +1812,12 @@ void* hk_ppo_ptr(hk_handle h, int trainer, int field)
     if (field <= HK_PPO_ADAM_V) return t.param + (size_t)field * t.P;
     if (field <= HK_PPO_RET) {
         if (t.adv_gen < 0) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: hk_ppo_advantages has not run"); return nullptr; }
-        return t.rowbuf + (size_t)(field - HK_PPO_V_OLD) * t.n;
+        const PpoRowBuf rows = ppo_rowbuf(h, t);
+        return field == HK_PPO_V_OLD ? rows.v_old : field == HK_PPO_ADV ? rows.adv : rows.ret;
     }
     if (field == HK_PPO_PERM) {
         if (!t.perm_valid) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: no hk_ppo_update on the current advantages"); return nullptr; }
-        return t.rowbuf + 3 * (size_t)t.n + (size_t)h->cfg.num_envs * h->policy[t.policy].q.n_slots;
+        return ppo_rowbuf(h, t).perm;
     }
     if (field == HK_PPO_SHADOW) {
         if (!t.shadow) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: the trainer has never been in HK_PPO_PREC_BF16"); return nullptr; }

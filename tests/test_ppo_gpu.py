@@ -272,6 +272,35 @@ def test_short_rollout_trains_on_its_completed_rows():
     assert g.L.hk_ppo_advantages(g.h, tr.t) == _lib.HK_ERR_INVALID
 
 
+def test_critic_chunks_do_not_change_the_advantages():
+    """hk_ppo_advantages runs the critic in chunks of max(cap, min(n + E S, 16 384)) rows.  96 envs: n = 17 280, n + E S = 17 472 — two chunks
+    (16 384 + 1 088) on a dropped workspace, one chunk once a minibatch of 17 472 ids has raised cap.  Bit equality, in both precisions: an output
+    row of either product kernel is a fixed-order chain over k whatever tile or chunk the row falls in, the value head is per row, and GAE and
+    the normalisation are fixed-order functions of V_OLD."""
+    import hierarchicalkarting_amd as hk
+    torch = _torch()
+    E, S = 96, 2
+    g = hk.RacingEnv(hk.make_config(E, 4, **KW))
+    g.reset()
+    for pol, slots in _actors(g.obs_dim):
+        g.attach_policy(pol, slots, P)
+    g.rollout_begin(R); g.step(R * P); g.rollout_close()
+    n = R * E * S
+    assert n == 17280 and 16384 < n + E * S < 2 * 16384
+    ids = _ids(torch, np.concatenate([np.arange(n), np.full(E * S, n)]))
+    tr = g.ppo_trainer(0)
+    for prec in ("f32", "bf16"):
+        tr.set_precision(prec)                  # (drops the workspace: cap 0)
+        tr.advantages()
+        two = {k: tr.read(k) for k in ("v_old", "adv", "ret")}
+        assert two["v_old"].size == n
+        st = tr.minibatch(ids, 0.2, 5e-3)       # the ids equal to n are out of range for a minibatch
+        assert st["skipped"] == float(E * S), st
+        tr.advantages()
+        for k, a in two.items():
+            assert_bits_equal(tr.read(k), a, "%s %s: one chunk against two" % (prec, k))
+
+
 def test_update_optimises():
     g, pols = _env()
     # the value fit: eps 1e3, since the value clip around the fixed V_OLD would hold L_v near its start by design (PPO's clipped value loss)
