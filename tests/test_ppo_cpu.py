@@ -60,6 +60,110 @@ def test_restatement_gradients_match_central_differences():
     assert checked > 40
 
 
+def _off_tie_problem(seed=3, m=600, s=0.25, eps=0.2):
+    """_small_problem's networks with a rollout recorded at them (RAW, BRANCH sampled from the heads, the old log-probabilities and V_OLD
+    theirs), then every parameter perturbed to p (1 + s xi) (+ 0.1 s xi' on the vectors): rho != 1 and v != v_old.
+    -> (ap, cp, rows, La, Lc, eps, classes) over the decided rows only"""
+    ap, cp, rows, La, Lc = _small_problem(seed, m)
+    r = np.random.default_rng(seed + 100)
+    t = {k: torch.tensor(v) for k, v in rows.items()}
+    with torch.no_grad():
+        a0, c0 = PR.tensors(ap), PR.tensors(cp)
+        h = PR.trunk(t["x"], a0, La)
+        mu = (h @ a0["W_mu"] + a0["b_mu"][0]).numpy()
+        p = torch.softmax(h @ a0["W_branch"].T + a0["b_branch"], -1).numpy()
+        v0 = PR.critic_values(t["x"], c0, Lc).numpy()
+    rows["raw"] = mu + r.standard_normal(m) * np.exp(ap["log_sigma"][0])
+    rows["branch"] = np.array([r.choice(p.shape[1], p=q) for q in p])
+    rows["old_c"], rows["old_d"] = np.zeros(m), np.zeros(m)
+    t0 = _terms(ap, cp, rows, La, Lc, eps)
+    rows["old_c"], rows["old_d"] = np.log(t0["rho"][:, 0]), np.log(t0["rho"][:, 1])      # rho == 1 at the recording parameters
+    rows["v_old"] = v0
+    rows["ret"] = v0 + r.standard_normal(m)
+    for d in (ap, cp):
+        for name, a in d.items():
+            a *= 1.0 + s * r.standard_normal(a.shape)
+            if a.ndim == 1:
+                a += 0.1 * s * r.standard_normal(a.shape)
+    cl = PR.classify(_terms(ap, cp, rows, La, Lc, eps), rows["adv"], eps, 1e-3)
+    keep = cl["decided"]
+    rows = {k: v[keep] for k, v in rows.items()}
+    return ap, cp, rows, La, Lc, eps, {k: v[keep] for k, v in cl.items()}
+
+
+def _terms(ap, cp, rows, La, Lc, eps):
+    t = {k: torch.tensor(v) for k, v in rows.items()}
+    return PR.row_terms(PR.tensors(ap), PR.tensors(cp), La, Lc, t["x"], t["raw"], t["branch"].long(), t["old_c"], t["old_d"], t["adv"], t["v_old"],
+                        t["ret"], eps, 0.0)
+
+
+def test_restatement_gradients_match_central_differences_off_the_tie_point():
+    """perturbed parameters: rows in each of the 5 classes of both policy columns and in each of the 3 value classes (classify), none of them
+    within 1e-3 of a branch boundary, so that a central difference of width 1e-6 never crosses one"""
+    ap0, cp0, rows, La, Lc, eps, cl = _off_tie_problem()
+    for q in (0, 1):
+        assert np.bincount(cl["policy"][:, q], minlength=5).min() >= 5, np.bincount(cl["policy"][:, q], minlength=5)
+    assert np.bincount(cl["value"], minlength=3).min() >= 5 and cl["decided"].all()
+    ap, cp = PR.tensors(ap0, True), PR.tensors(cp0, True)
+    _L(ap, cp, rows, La, Lc, eps).backward()
+    h = 1e-6
+    checked = 0
+    for params, grads in ((ap0, ap), (cp0, cp)):
+        for name, arr in params.items():
+            g = grads[name].grad.numpy()
+            flat = arr.reshape(-1)
+            for k in range(0, flat.size, max(1, flat.size // 7)):
+                save = flat[k]
+                flat[k] = save + h
+                lp = _L(PR.tensors(ap0), PR.tensors(cp0), rows, La, Lc, eps).item()
+                flat[k] = save - h
+                lm = _L(PR.tensors(ap0), PR.tensors(cp0), rows, La, Lc, eps).item()
+                flat[k] = save
+                fd = (lp - lm) / (2 * h)
+                assert abs(fd - g.reshape(-1)[k]) <= 1e-6 + 1e-5 * abs(fd), (name, k, fd, g.reshape(-1)[k])
+                checked += 1
+    assert checked > 40
+
+
+def test_dead_rows_hand_worked_case():
+    """four rows whose rho and value terms are set by hand (eps 0.2, beta 0): rho_c = rho_d = 0.5 with A = -2 and rho_c = rho_d = 1.5 with
+    A = +3 are dead in both columns — min picks clip(rho) A, a constant: L_pi = -(2 * 0.8 * -2 + 2 * 1.2 * 3) / 4 = -1 — and v = v_old + 0.5,
+    ret = v + 1 is value-dead: f1 = 1 < f2 = (1 + 0.3)^2 = 1.69, so L_v = 1.69.  autograd gives exact zeros for the actor and for the critic.
+    The live twins (A's signs flipped; ret = v - 1: f1 = 1 > f2 = 0.49) do not."""
+    ap0, cp0, rows, La, Lc = _small_problem(1, 4)
+    eps = 0.2
+    rows["old_c"], rows["old_d"] = np.zeros(4), np.zeros(4)
+    t0 = _terms(ap0, cp0, rows, La, Lc, eps)
+    target = np.array([0.5, 1.5, 0.5, 1.5])
+    rows["old_c"], rows["old_d"] = np.log(t0["rho"][:, 0] / target), np.log(t0["rho"][:, 1] / target)
+    rows["adv"] = np.array([-2.0, 3.0, -2.0, 3.0])
+    rows["v_old"] = t0["v"] - 0.5
+    rows["ret"] = t0["v"] + 1.0
+    tm = _terms(ap0, cp0, rows, La, Lc, eps)
+    assert np.allclose(tm["rho"], target[:, None], rtol=1e-12) and np.allclose(tm["f1"], 1.0) and np.allclose(tm["f2"], 1.69)
+    cl = PR.classify(tm, rows["adv"], eps, 1e-3)
+    assert cl["decided"].all() and (cl["value"] == PR.V_DEAD).all()
+    assert np.array_equal(cl["policy"][:, 0], [PR.BELOW_DEAD, PR.ABOVE_DEAD] * 2) and np.array_equal(cl["policy"], cl["policy"][:, :1].repeat(2, 1))
+    ap, cp = PR.tensors(ap0, True), PR.tensors(cp0, True)
+    t = {k: torch.tensor(v) for k, v in rows.items()}
+    L, st, _ = PR.loss(ap, cp, La, Lc, t["x"], t["raw"], t["branch"].long(), t["old_c"], t["old_d"], t["adv"], t["v_old"], t["ret"], eps, 0.0)
+    L.backward()
+    assert abs(st["L_pi"] + 1.0) < 1e-12 and abs(st["L_v"] - 1.69) < 1e-12 and st["clip_fraction"] == 1.0
+    for d in (ap, cp):
+        for name, p in d.items():
+            assert not p.grad.numpy().any(), name
+    # the live twins
+    rows["adv"] = -rows["adv"]
+    rows["ret"] = t0["v"] - 1.0
+    tm = _terms(ap0, cp0, rows, La, Lc, eps)
+    cl = PR.classify(tm, rows["adv"], eps, 1e-3)
+    assert np.array_equal(cl["policy"][:, 0], [PR.BELOW_LIVE, PR.ABOVE_LIVE] * 2) and (cl["value"] == PR.V_LIVE).all() and np.allclose(tm["f2"], 0.49)
+    ap, cp = PR.tensors(ap0, True), PR.tensors(cp0, True)
+    _L(ap, cp, rows, La, Lc, eps, 0.0).backward()
+    for d in (ap, cp):
+        assert all(p.grad.numpy().any() for p in d.values())
+
+
 def test_gae_hand_worked_case():
     """one (e, j), R = 4: DONE = 1 at t = 1, DONE = 2 (time-out) at t = 3 -> the bootstrap is unused; and again with no done at the end"""
     g, lam = 0.5, 0.5
