@@ -34,6 +34,7 @@ PPO_FIELDS = {n: i for i, n in enumerate(("params", "grad", "adam_m", "adam_v", 
 HK_PPO_FIELDS = len(PPO_FIELDS)
 HK_PPO_STATS = 6
 HK_PPO_PREC_F32, HK_PPO_PREC_BF16 = 0, 1
+HK_POLICY_PREC_F32, HK_POLICY_PREC_BF16 = 0, 1
 PPO_STAT_NAMES = ("L_pi", "L_v", "entropy", "approx_kl", "clip_fraction", "skipped")
 HK_F_ACCEL, HK_F_BRAKE, HK_F_ACTIVE, HK_F_FORWARD_COLLISION, HK_F_HAS_COLLISION, HK_F_CAN_MOVE, HK_F_ENABLED = (1 << i for i in range(7))
 
@@ -207,6 +208,8 @@ SYMBOLS = {
     "hk_build_info": (C.c_char_p, []),
     "hk_schedule_info": (C.c_char_p, [_H]),
     "hk_policy_attach": (C.c_int, [_H, C.POINTER(PolicyDesc), C.POINTER(C.c_int32), C.c_int, C.c_int]),
+    "hk_policy_set_precision": (C.c_int, [_H, C.c_int, C.c_int]),
+    "hk_policy_get_precision": (C.c_int, [_H, C.c_int]),
     "hk_policy_forward": (C.c_int, [_H, C.c_int, C.c_int, _fp, _fp, _fp]),
     "hk_get_actions": (C.c_int, [_H, _fp, C.POINTER(C.c_int32)]),
     "hk_rollout_begin": (C.c_int, [_H, C.c_int]),

@@ -1232,6 +1232,38 @@ int hk_policy_forward(hk_handle h, int policy, int rows, const float* obs, float
     return HK_OK;
 }
 
+int hk_policy_set_precision(hk_handle h, int policy, int precision)
+{
+    HK_NEED_ENV(h);
+    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, "hk_policy_set_precision: bad policy index");
+    if (precision != HK_POLICY_PREC_F32 && precision != HK_POLICY_PREC_BF16) return fail(h, HK_ERR_INVALID, "hk_policy_set_precision: unknown precision");
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_policy_set_precision: refused while a rollout is open (hk_rollout_close first)");
+    hk::PolicyDevice& pd = h->policy[policy];
+    if (precision == HK_POLICY_PREC_BF16 && !pd.wbf) {
+        // the second allocation: every layer's fragment-major bf16 copy, built on the stream from the CURRENT fp32 copies (so after a publish too)
+        size_t off[HK_POLICY_MAX_LAYERS + 1] = {};
+        for (int l = 0; l < pd.q.n_layers; l++) off[l + 1] = off[l] + hk::policy_bf16_layer_elems(pd.q, l);
+        HK_HIP(h, hipMalloc(&pd.wbf, off[pd.q.n_layers] * sizeof(uint16_t)));
+        for (int l = 0; l < pd.q.n_layers; l++) pd.bq.Wf[l] = pd.wbf + off[l];
+        const hipError_t e = hk::policy_bf16_refresh(pd.q, pd.bq, h->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(pd.wbf);
+            pd.wbf = nullptr;
+            pd.bq = hk::PolicyBf16{};
+            HK_HIP(h, e);
+        }
+    }
+    pd.prec = precision;
+    return HK_OK;
+}
+
+int hk_policy_get_precision(hk_handle h, int policy)
+{
+    if (!h) return fail(nullptr, HK_ERR_INVALID, "NULL handle");
+    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, "hk_policy_get_precision: bad policy index");
+    return h->policy[policy].prec;
+}
+
 int hk_get_actions(hk_handle h, float* steer, int32_t* branch)
 {
     HK_NEED_ENV(h);
@@ -1712,6 +1744,9 @@ int hk_ppo_publish(hk_handle h, int trainer)
     auto& t = h->ppo[trainer];
     hipLaunchKernelGGL(hk::ppo_publish_kernel<true>, dim3(nblk(t.actor.count)), dim3(256), 0, h->stream, h->policy[t.policy].q, t.actor, t.param);
     HK_HIP(h, hipGetLastError());
+    // the bf16 inference copies, when the policy has them: rebuilt from the fp32 copies just written (each an exact copy of its master, so every
+    // weight is the master rounded once by ppo_bf16_rne: HK_PPO_SHADOW's element), whichever precision the policy is in now
+    if (h->policy[t.policy].wbf) HK_HIP(h, hk::policy_bf16_refresh(h->policy[t.policy].q, h->policy[t.policy].bq, h->stream));
     return HK_OK;
 }
 

@@ -4,6 +4,8 @@
 //   policy_stack_kernel     StackingSensor: push the newest observation into the agent's ring, zero the ring first when
 //                           the episode changed since the last decision
 //   policy_mlp_kernel       normalise -> n x (Linear + Swish) -> {mu, logits} -> sample -> latch steer / branch
+//                           (HK_POLICY_PREC_BF16, opt-in per policy: policy_mlp_bf16_kernel, hk_policy_bf16.h — the same decision with the
+//                           trunk on the bf16 matrix cores; everything said of arithmetic below is the default precision's)
 //
 // policy_mlp_kernel: one workgroup (8 waves) per tile of 64 rows (row = one agent's stacked observation).  The tile's
 // activations live TRANSPOSED in LDS (At[k][row], row stride 65 floats: conflict-free for the column writes of the loader
@@ -23,6 +25,7 @@
 #include "../../include/hk.h"
 #include "../../include/hk_detmath.h"
 #include "hk_swish.h"      // Sigmoid then Mul in the exported graph
+#include "hk_bf16.h"
 #include "hk_env_device.h"
 
 namespace hk {
@@ -63,9 +66,18 @@ struct PolicyRec {
     int nbm;                                 // logits per agent in the row (the largest n_branch of the handle's actors)
 };
 
+// HK_POLICY_PREC_BF16 (hk_policy_bf16.h): the bf16 copies of the trunk weights, an argument of the bf16 kernels alone (PolicyParams, which every
+// kernel of the actor takes, is as it was)
+struct PolicyBf16 {
+    const uint16_t* Wf[HK_POLICY_MAX_LAYERS];   // fragment-major [column block][k step][lane][8]; nullptr until the first switch
+};
+
 struct PolicyDevice {
     PolicyParams q{};
+    PolicyBf16 bq{};
     float* weights = nullptr;                // one allocation behind every const float* above
+    uint16_t* wbf = nullptr;                 // the second allocation, behind bq.Wf: made by the first switch to HK_POLICY_PREC_BF16
+    int prec = HK_POLICY_PREC_F32;           // hk_policy_set_precision: which chain policy_launch_mlp runs
     bool used = false;
 };
 
@@ -217,6 +229,70 @@ __device__ __forceinline__ void pm_gemm(f32x16& acc0, f32x16& acc1, const float*
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The tail of a decision, from the heads to the recorder's stores, as a function: policy_mlp_bf16_kernel's (hk_policy_bf16.h).  It is
+// policy_mlp_kernel's tail word for word; that kernel keeps its own inline copy (see there).  At: the last layer's fp32 post-activations
+// [k][PM_LD] in LDS, complete (a barrier precedes the call); head: PM_MAX_OUT x PM_TILE floats of LDS beside it; tid = threadIdx.x, H = hidden.
+__device__ __forceinline__ void pm_tail(const PolicyParams& Q, const float* At, float* head, int rows, int row0, unsigned long long decision,
+                                        int env_id_base, int A, float* mu_out, float* logit_out, float* act_steer, int* act_branch, const PolicyRec& rec, int tid, int H)
+{
+    // ---- heads: out 0 = mu, 1.. = branch logits; thread -> (out = tid / 64, row = tid % 64)
+    {
+        const int out = tid >> 6, r = tid & 63;
+        if (out < 1 + Q.n_branch) {
+            const float* wv = out == 0 ? Q.W_mu : Q.W_branch + (size_t)(out - 1) * H;
+            head[out * PM_TILE + r] = pm_head(At + r, PM_LD, wv, out == 0 ? Q.b_mu[0] : Q.b_branch[out - 1], H);
+        }
+    }
+    __syncthreads();
+    if (tid < PM_TILE && row0 + tid < rows) {
+        const int row = row0 + tid;
+        const float mu = head[tid];
+        float lg[PM_MAX_OUT];
+        for (int b = 0; b < Q.n_branch; b++) lg[b] = head[(1 + b) * PM_TILE + tid];
+        if (mu_out) mu_out[row] = mu;
+        if (logit_out) for (int b = 0; b < Q.n_branch; b++) logit_out[(size_t)row * Q.n_branch + b] = lg[b];
+        if (act_steer) {
+            const int env = row / Q.n_slots, agent = Q.slots[row % Q.n_slots];
+            const uint32_t grow = (uint32_t)(env_id_base + env) * (uint32_t)A + (uint32_t)agent;
+            uint32_t rnd[4];
+            philox4x32((uint32_t)decision, (uint32_t)(decision >> 32), grow, 0x504F4C49u, Q.seed, (uint32_t)Q.index, rnd);
+            float eps = 0.0f;
+            if (!Q.deterministic) {
+                const float u1 = (float)((rnd[0] >> 8) + 1u) * (1.0f / 16777216.0f);
+                const float u2 = u01(rnd[1]);
+                eps = sqrtf(-2.0f * hk_logf(u1)) * hk_cosf((2.0f * HK_PI_F) * u2);
+            }
+            const float sigma = hk_expf(Q.log_sigma[0]);
+            const float raw = mu + eps * sigma;
+            const float v = raw < -3.0f ? -3.0f : (raw > 3.0f ? 3.0f : raw);
+            const int best = pm_argmax(lg, Q.n_branch);
+            int pick = best;
+            if (!Q.deterministic) {
+                float ex[PM_MAX_OUT], tot = 0.0f;
+                for (int b = 0; b < Q.n_branch; b++) { ex[b] = hk_expf(lg[b] - lg[best]); tot += ex[b]; }
+                const float thr = u01(rnd[2]) * tot;
+                float cum = 0.0f;
+                pick = Q.n_branch - 1;
+                for (int b = 0; b < Q.n_branch; b++) { cum += ex[b]; if (thr < cum) { pick = b; break; } }
+            }
+            const size_t ea = (size_t)env * A + agent;
+            act_steer[ea] = v / 3.0f;
+            act_branch[ea] = pick;
+            if (rec.raw) {              // (a kernel argument: wave-uniform)
+                // ML-Agents' log-probabilities: the Gaussian's at the unclipped sample, and log_softmax of the logits at the pick
+                rec.steer[ea] = v / 3.0f;
+                rec.branch[ea] = pick;
+                rec.raw[ea] = raw;
+                rec.mu[ea] = mu;
+                for (int b = 0; b < Q.n_branch; b++) rec.logits[ea * rec.nbm + b] = lg[b];
+                rec.logp_c[ea] = pm_logp_cont(raw, mu, sigma, Q.log_sigma[0]);
+                rec.logp_d[ea] = pm_logp_disc(lg, Q.n_branch, best, pick);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // src: [rows][in_dim]; logical element k of a row lives at ((w + 1 + k / obs_dim) % stack) * obs_dim + k % obs_dim
 // (w = stack - 1 for plain oldest-first rows).  Outputs: mu_out / logit_out when non-null; act_steer / act_branch
 // (indexed [env][agent], row = env * n_slots + j) when non-null, and then the rollout row `rec` when rec.raw is non-null.
@@ -324,6 +400,8 @@ __global__ __launch_bounds__(PM_THREADS, MODE == 2 ? 2 : 4) void policy_mlp_kern
         __syncthreads();
     }
 
+    // (the tail below is pm_tail's text: calling pm_tail here took one VGPR off every MODE of this kernel, whose resource rows are held
+    // fixed, so it keeps its own copy — change both together)
     // ---- heads: out 0 = mu, 1.. = branch logits; thread -> (out = tid / 64, row = tid % 64)
     {
         const int out = tid >> 6, r = tid & 63;
@@ -476,9 +554,14 @@ inline int policy_upload(PolicyDevice& pd, const hk_policy_desc* d, int index, i
     return HK_OK;
 }
 
+}  // namespace hk
+#include "hk_policy_bf16.h"      // policy_mlp_bf16_kernel: the same decision on the bf16 matrix cores (HK_POLICY_PREC_BF16)
+namespace hk {
+
 inline void policy_free(PolicyDevice& pd)
 {
     if (pd.weights) (void)hipFree(pd.weights);
+    if (pd.wbf) (void)hipFree(pd.wbf);
     if (pd.q.ring) (void)hipFree(pd.q.ring);
     if (pd.q.epoch) (void)hipFree(pd.q.epoch);
     pd = PolicyDevice{};
@@ -489,7 +572,9 @@ inline int policy_launch_mlp(const PolicyDevice& pd, int rows, const float* src,
                              const PolicyRec& rec, hipStream_t stream, std::string& err)
 {
     if (rows <= 0) return HK_OK;
-    const size_t lds = policy_lds_bytes(pd.q);
+    const bool bf = pd.prec == HK_POLICY_PREC_BF16;
+    if (bf && !pd.wbf) { err = "policy_mlp_bf16_kernel: the policy has no bf16 weights"; return HK_ERR_INVALID; }
+    const size_t lds = bf ? policy_bf16_lds_bytes(pd.q) : policy_lds_bytes(pd.q);
     // the kernels use ~68 KB of dynamic LDS, above the 64 KB default: raise the limit once per DEVICE (the attribute belongs to
     // the device's code object; a second handle on another device needs it too).  Guarded by a mutex: handles of different
     // devices may be driven from different host threads.
@@ -503,18 +588,24 @@ inline int policy_launch_mlp(const PolicyDevice& pd, int rows, const float* src,
             (void)hipFuncSetAttribute((const void*)policy_mlp_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             (void)hipFuncSetAttribute((const void*)policy_mlp_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             (void)hipFuncSetAttribute((const void*)policy_mlp_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute((const void*)policy_mlp_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute((const void*)policy_mlp_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (dev >= 0 && dev < 64) done_mask |= 1ull << dev;
         }
     }
     const dim3 grid((rows + PM_TILE - 1) / PM_TILE), block(PM_THREADS);
-    if (pd.q.hidden <= 128)
+    if (bf && pd.q.hidden <= 128)
+        hipLaunchKernelGGL(policy_mlp_bf16_kernel<false>, grid, block, lds, stream, pd.q, pd.bq, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
+    else if (bf)
+        hipLaunchKernelGGL(policy_mlp_bf16_kernel<true>, grid, block, lds, stream, pd.q, pd.bq, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
+    else if (pd.q.hidden <= 128)
         hipLaunchKernelGGL(policy_mlp_kernel<0>, grid, block, lds, stream, pd.q, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
     else if (pd.q.hidden == 256)
         hipLaunchKernelGGL(policy_mlp_kernel<1>, grid, block, lds, stream, pd.q, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
     else
         hipLaunchKernelGGL(policy_mlp_kernel<2>, grid, block, lds, stream, pd.q, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { err = std::string("policy_mlp_kernel: ") + hipGetErrorString(e); return HK_ERR_HIP; }
+    if (e != hipSuccess) { err = std::string(bf ? "policy_mlp_bf16_kernel: " : "policy_mlp_kernel: ") + hipGetErrorString(e); return HK_ERR_HIP; }
     return HK_OK;
 }
 

@@ -55,14 +55,7 @@ struct PpoRows {
     int slots[HK_MAX_AGENTS];
 };
 
-// fp32 -> bf16, to nearest even; Inf stays Inf, every NaN becomes the quiet NaN 0x7FC0 (torch's conversion; host twin ppo.bf16_round)
-__device__ __forceinline__ uint16_t ppo_bf16_rne(float f)
-{
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)0x7FC0u;
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ float ppo_bf16_f32(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
+// (ppo_bf16_rne / ppo_bf16_f32, the fp32 <-> bf16 conversions: hk_bf16.h, shared with the bf16 inference chain)
 struct ppo_bf16 { uint16_t v; __device__ operator double() const { return (double)ppo_bf16_f32(v); } };      // an element type for ppo_colsum_kernel
 // a producer's store: as it is, or rounded once to bf16
 __device__ __forceinline__ void ppo_put(float* p, size_t i, float v) { p[i] = v; }

@@ -118,16 +118,36 @@ class RacingEnv:
         return s, b
 
     # ---- RL low-level policy on device
-    def attach_policy(self, policy, agent_slots, decision_period=2):
+    POLICY_PRECISIONS = {"f32": _lib.HK_POLICY_PREC_F32, "bf16": _lib.HK_POLICY_PREC_BF16}
+
+    def attach_policy(self, policy, agent_slots, decision_period=2, precision="f32"):
         """policy: hierarchicalkarting_amd.policy.Policy (e.g. Policy.from_onnx(path)); agent_slots: LowMode RL or E2E
-        agents it drives; decision_period: DecisionRequester.DecisionPeriod (2 in the reference scenes).  -> policy index"""
+        agents it drives; decision_period: DecisionRequester.DecisionPeriod (2 in the reference scenes); precision: policy_set_precision
+        of the new policy.  -> policy index"""
+        if precision not in self.POLICY_PRECISIONS:
+            raise ValueError("precision: one of %s" % sorted(self.POLICY_PRECISIONS))
         d, _keep = policy.desc()
         slots = np.ascontiguousarray(agent_slots, np.int32)
         rc = self.L.hk_policy_attach(self.h, C.byref(d), slots.ctypes.data_as(C.POINTER(C.c_int32)), len(slots), int(decision_period))
         if rc < 0:
             self._ck(rc)
         self._policies = getattr(self, "_policies", []) + [policy]
+        if precision != "f32":
+            self.policy_set_precision(rc, precision)
         return rc
+
+    def policy_set_precision(self, index, precision):
+        """ "f32" (the default: the oracle's chain, bit for bit) or "bf16" (the trunk on the bf16 matrix cores, the bf16 trainer's forward bit
+        for bit; hk.h beside hk_policy_attach); per policy, between calls, never while a rollout is open"""
+        if precision not in self.POLICY_PRECISIONS:
+            raise ValueError("precision: one of %s" % sorted(self.POLICY_PRECISIONS))
+        self._ck(self.L.hk_policy_set_precision(self.h, int(index), self.POLICY_PRECISIONS[precision]))
+
+    def policy_precision(self, index):
+        rc = self.L.hk_policy_get_precision(self.h, int(index))
+        if rc < 0:
+            self._ck(rc)
+        return {v: k for k, v in self.POLICY_PRECISIONS.items()}[rc]
 
     def policy_forward(self, index, obs):
         """the actor alone on stacked observations [rows, in_dim] -> (mu [rows], logits [rows, n_branch])"""

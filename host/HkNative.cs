@@ -29,6 +29,7 @@ namespace KartGame.AI.Native
         public const int HK_PPO_PARAMS = 0, HK_PPO_GRAD = 1, HK_PPO_ADAM_M = 2, HK_PPO_ADAM_V = 3, HK_PPO_V_OLD = 4, HK_PPO_ADV = 5, HK_PPO_RET = 6,
                          HK_PPO_MB_MU = 7, HK_PPO_MB_LOGITS = 8, HK_PPO_MB_VALUE = 9, HK_PPO_PERM = 10, HK_PPO_SHADOW = 11, HK_PPO_FIELDS = 12,
                          HK_PPO_PREC_F32 = 0, HK_PPO_PREC_BF16 = 1,
+                         HK_POLICY_PREC_F32 = 0, HK_POLICY_PREC_BF16 = 1,      // hk_policy_precision
                          HK_PPO_STATS = 6;
         // HierarchicalKartAgent.cs:21-33
         public const int HK_LOW_RL = 0, HK_LOW_MPC = 1, HK_LOW_LQR = 2, HK_LOW_E2E = 3;   // E2E: EndToEndKartAgent
@@ -415,6 +416,8 @@ namespace KartGame.AI.Native
         [DllImport(Lib)] public static extern IntPtr hk_schedule_info(IntPtr h);     // const char* (JSON), owned by the handle
         // LowMode == RL: the actor runs on device every DecisionPeriod ticks instead of Barracuda (KA:440, HKA:1371-1379)
         [DllImport(Lib)] public static extern int hk_policy_attach(IntPtr h, HkPolicyDesc* desc, int* agentSlots, int nSlots, int decisionPeriod);
+        [DllImport(Lib)] public static extern int hk_policy_set_precision(IntPtr h, int policy, int precision);
+        [DllImport(Lib)] public static extern int hk_policy_get_precision(IntPtr h, int policy);
         [DllImport(Lib)] public static extern int hk_policy_forward(IntPtr h, int policy, int rows, float* obs, float* mu, float* logits);
         [DllImport(Lib)] public static extern int hk_get_actions(IntPtr h, float* steer, int* branch);
         // rollout recorder: every decision of the attached actors writes a row of device buffers (fields: hk.h hk_rollout_field)

@@ -453,7 +453,29 @@ typedef struct hk_policy_desc {
  * in_dim).  Returns the policy index (>= 0) or a negative hk_status.  decision_period (DecisionRequester) is per handle:
  * a second attach with a different period is refused with HK_ERR_INVALID. */
 int hk_policy_attach(hk_handle h, const hk_policy_desc* desc, const int32_t* agent_slots, int n_slots, int decision_period);
-/* The MLP alone on caller-supplied stacked observations (host pointers): mu[rows], logits[rows][n_branch]. */
+/* PRECISION of an attached policy (hk_policy_set_precision; HK_POLICY_PREC_F32 is the default and is everything above, bit for bit with the
+ * CPU oracle).  HK_POLICY_PREC_BF16 runs the policy's trunk on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16), operand for operand the
+ * bf16 PPO trainer's forward (below, "PPO trainer" PRECISION): the input is normalised and clipped in fp32, then rounded once to bf16 (to
+ * nearest even, Inf kept, a NaN becomes 0x7FC0); every trunk weight is rounded once from its fp32 value; each layer's fp32 accumulator is
+ * seeded with the fp32 bias and stepped in ascending k over K zero-padded to a multiple of 64; the post-activations below the last layer are
+ * rounded once to bf16, the last layer's stays fp32.  The heads, the arg-max, the sampling, both log-probabilities and the recorder's rows
+ * are the fp32 tail of the default precision, unchanged, on that last activation.
+ * What is given up: in HK_POLICY_PREC_BF16 the policy no longer agrees with the CPU oracle — mu / logits differ from it by the bf16 rounding
+ * of the trunk, so actions, and therefore races, differ.  What is regained: with the trainer in HK_PPO_PREC_BF16 too, the training forward IS
+ * the inference chain again, bit for bit, so at unchanged parameters rho == 1 and approx-KL and the clip fraction are exactly 0.  Mixed
+ * settings (an fp32 trainer on a bf16 policy, or the reverse) are allowed and have the small non-zero statistics described there.
+ * The precision is per policy and is set between calls; only hk_stream's order is implied.  The first switch to bf16 gives the policy a second
+ * device allocation, the bf16 copies of its trunk weights in the matrix instruction's operand order, built on hk_stream from the CURRENT fp32
+ * inference copies (so a switch after hk_ppo_publish is correct); hk_ppo_publish rebuilds them in the same call once they exist, each the
+ * master weight rounded once (HK_PPO_SHADOW's element).  The fp32 copies are kept current in both modes: switching back to
+ * HK_POLICY_PREC_F32 is the oracle's chain again, bit for bit.  Every consumer (hk_step's decisions of RL / MCTS-RL / E2E agents,
+ * hk_policy_forward) follows the switch.  Refused with HK_ERR_INVALID and a message: a bad policy index, an unknown precision, and any switch
+ * while a rollout is open (the rows of one rollout come from one chain); a refused call leaves the precision as it was.
+ * hk_policy_get_precision: >= 0 the precision, < 0 an hk_status. */
+typedef enum { HK_POLICY_PREC_F32 = 0, HK_POLICY_PREC_BF16 = 1 } hk_policy_precision;
+int hk_policy_set_precision(hk_handle h, int policy, int precision);
+int hk_policy_get_precision(hk_handle h, int policy);
+/* The MLP alone on caller-supplied stacked observations (host pointers): mu[rows], logits[rows][n_branch]; in the policy's precision. */
 int hk_policy_forward(hk_handle h, int policy, int rows, const float* obs /*[rows][in_dim]*/, float* mu, float* logits);
 /* The actions currently latched for every agent (what the policies / hk_set_actions wrote): steer[E][A], branch[E][A] */
 int hk_get_actions(hk_handle h, float* steer, int32_t* branch);
@@ -557,8 +579,9 @@ void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* 
  * the fp64 column sum of the rounded deltas).  Everything else stays fp32 and is computed as above: PARAMS, GRAD, the Adam moments, V_OLD / ADV /
  * RET, the pre-activations swish' reads, the last layer's post-activation and the heads, log-probabilities, losses and per-row gradients on
  * it, the head weight gradients, the column sums (fp64), the split-K combine (chunks of 256 rows, in chunk order) and hk_ppo_publish, which
- * copies the fp32 masters; inference never sees the shadow.  No float atomics: the same call on the same state gives the same bits.
- * What is no longer exact: the training forward is not the inference chain, and the rollout's LOGP_* come from the fp32 inference chain, so
+ * copies the fp32 masters (and rebuilds a bf16 policy's weight copies from them, equal to the shadow element for element).  No float atomics: the same call on the same state gives the same bits.
+ * What is no longer exact while the POLICY stays in HK_POLICY_PREC_F32 (in HK_POLICY_PREC_BF16 the two chains are one again, see there): the
+ * training forward is not the inference chain, and the rollout's LOGP_* come from the fp32 inference chain, so
  * at unchanged parameters rho != 1, approx-KL and the clip fraction are small non-zero numbers and MB_MU / MB_LOGITS differ from MU / LOGITS
  * by the bf16 rounding of the trunk.  Switching back to HK_PPO_PREC_F32 restores the exact path.  The precision is set between calls (a call
  * waits for hk_stream and releases the minibatch workspace, which is laid out per precision: MB_* are unavailable until the next minibatch);
@@ -568,7 +591,7 @@ void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* 
  * epi 2 (backward delta) C = (A B) * swish'(aux), A [M][K], B [K][N], aux fp32 [M][N]; epi 0 (weight gradient) C = A^T B, A [K][M], B [K][N],
  * split over K in chunks of 256 and combined in chunk order (synchronises).  A NULL operand, a non-positive M / N / K or another epi is refused.
  * Out of scope: updating the normaliser (frozen as attached), self-play opponent swaps and ELO, POCA and group rewards, LSTM memory,
- * gradient clipping, multi-GPU gradient all-reduce, bf16 inference and bf16 optimiser state.  Everything is asynchronous on hk_stream. */
+ * gradient clipping, multi-GPU gradient all-reduce and bf16 optimiser state.  Everything is asynchronous on hk_stream. */
 #define HK_PPO_STATS 6
 typedef struct hk_ppo_config {
     float gamma;                    /* 0.99 */

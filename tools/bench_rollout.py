@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=7, help="windows per mode (>= 5)")
     ap.add_argument("--warmup", type=int, default=256, help="untimed ticks before the first window")
     ap.add_argument("--no-host-loop", action="store_true")
+    ap.add_argument("--policy-precision", nargs="+", choices=("f32", "bf16"), default=["f32"],
+                    help="hk_policy_set_precision of both actors; several: alternated window by window, reported per precision")
     a = ap.parse_args()
     import hierarchicalkarting_amd as hk
     from hierarchicalkarting_amd import _lib
@@ -51,17 +53,35 @@ def main():
         env.synchronize()
         return E * ticks / (time.perf_counter() - t0)
 
-    rates = {"off": [], "on": []}
+    precs = list(dict.fromkeys(a.policy_precision))
+    by_prec = {p: {"off": [], "on": []} for p in precs}
+
+    def set_precision(p):
+        for k in (0, 1):
+            env.policy_set_precision(k, p)
+
+    if precs != ["f32"]:
+        for p in precs[1:] + precs[:1]:       # (the bf16 copies and every kernel's first launch, outside the windows)
+            set_precision(p)
+            env.step(4 * P)
     for _ in range(a.repeats):
-        rates["off"].append(window(False))
-        rates["on"].append(window(True))
+        for p in precs:
+            if len(precs) > 1 or p != "f32":
+                set_precision(p)
+            by_prec[p]["off"].append(window(False))
+            by_prec[p]["on"].append(window(True))
     env.close()
+    rates = by_prec[precs[0]]
     stat = lambda v: {"median": statistics.median(v), "min": min(v), "max": max(v), "runs": v}
     out = {"metric": "env-steps/s, rollout recording off / on (RL workload, rewards on)", "unit": "env-steps/s",
            "off": stat(rates["off"]), "on": stat(rates["on"]),
            "overhead": 1.0 - statistics.median(rates["on"]) / statistics.median(rates["off"]),
            "config": {"envs": E, "agents": A, "decision_period": P, "rows": R, "rollouts_per_window": K, "ticks_per_window": ticks,
-                      "repeats": a.repeats, "row_bytes_per_env_step": A * (env.obs_dim + 9 + 3 + 2) * 4 / P}}
+                      "repeats": a.repeats, "policy_precision": precs[0], "row_bytes_per_env_step": A * (env.obs_dim + 9 + 3 + 2) * 4 / P}}
+    if len(precs) > 1:
+        out["by_policy_precision"] = {p: {"off": stat(r["off"]), "on": stat(r["on"])} for p, r in by_prec.items()}
+        if "f32" in by_prec and "bf16" in by_prec:
+            out["bf16_over_f32_env_steps"] = {m: statistics.median(by_prec["bf16"][m]) / statistics.median(by_prec["f32"][m]) for m in ("off", "on")}
     if not a.no_host_loop:
         h = hk.RacingEnv(hk.make_config(E, A, **kw))
         h.reset()
