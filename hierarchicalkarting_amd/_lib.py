@@ -30,7 +30,8 @@ RO_FIELDS = {n: (i, dt) for i, (n, dt) in enumerate([
     ("term_group_reward", "<f4"), ("done", "<i4"), ("ring0", "<f4"), ("next_obs", "<f4")])}
 HK_RO_FIELDS = len(RO_FIELDS)
 # PPO trainer (hk_ppo_field): name -> index;  stats of hk_ppo_minibatch / hk_ppo_update
-PPO_FIELDS = {n: i for i, n in enumerate(("params", "grad", "adam_m", "adam_v", "v_old", "adv", "ret", "mb_mu", "mb_logits", "mb_value", "perm", "shadow"))}
+PPO_FIELDS = {n: i for i, n in enumerate(("params", "grad", "adam_m", "adam_v", "v_old", "adv", "ret", "mb_mu", "mb_logits", "mb_value", "perm", "shadow",
+                                               "norm_mean", "norm_std"))}
 HK_PPO_FIELDS = len(PPO_FIELDS)
 HK_PPO_STATS = 6
 HK_PPO_PREC_F32, HK_PPO_PREC_BF16 = 0, 1
@@ -227,6 +228,10 @@ SYMBOLS = {
     "hk_ppo_set_precision": (C.c_int, [_H, C.c_int, C.c_int]),
     "hk_ppo_get_precision": (C.c_int, [_H, C.c_int]),
     "hk_ppo_gemm_bf16": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hk_ppo_normalizer_init": (C.c_int, [_H, C.c_int, C.c_int64]),
+    "hk_ppo_normalizer_update": (C.c_int, [_H, C.c_int]),
+    "hk_ppo_normalizer_get": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
+    "hk_ppo_normalizer_set": (C.c_int, [_H, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "hk_comm_unique_id": (C.c_int, [C.c_void_p]),
     "hk_comm_init": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
     "hk_gather_results": (C.c_int, [_H, C.POINTER(EpisodeResult)]),

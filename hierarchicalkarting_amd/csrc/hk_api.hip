@@ -225,6 +225,12 @@ struct hk_context {
         int prec = HK_PPO_PREC_F32;    // hk_ppo_set_precision
         uint16_t* shadow = nullptr;    // HK_PPO_PREC_BF16: PARAMS rounded to bf16, the critic shadow_pad elements on (ppo_shadow_kernel)
         size_t shadow_pad = 0;
+        // the running normaliser (hk_ppo_normalizer_*; nothing before init / set): norm_steps 0 = no state
+        int64_t norm_steps = 0;        // N
+        double* norm = nullptr;        // m [in_dim], M2 [in_dim], then the combined sums [2 in_dim + stack] of an update
+        double* norm_part = nullptr;   // an update's per-workgroup partials [norm_part_wg][2 in_dim + stack]
+        int norm_part_wg = 0;
+        bool adv_stale = false;        // the policy's statistics changed after hk_ppo_advantages: V_OLD is the critic on other inputs
     } ppo[HK_MAX_POLICIES];
     int n_ppo = 0;
     // RCCL communicator for hk_gather_results (librccl.so loaded lazily)
@@ -395,7 +401,7 @@ void hk_destroy(hk_handle h)
     if (h->pol_scratch) (void)hipFree(h->pol_scratch);
     if (h->ro.buf) (void)hipFree(h->ro.buf);
     for (int p = 0; p < HK_MAX_POLICIES; p++) hk::policy_free(h->policy[p]);
-    for (auto& t : h->ppo) { if (t.param) (void)hipFree(t.param); if (t.rowbuf) (void)hipFree(t.rowbuf); if (t.ws) (void)hipFree(t.ws); if (t.shadow) (void)hipFree(t.shadow); }
+    for (auto& t : h->ppo) { if (t.param) (void)hipFree(t.param); if (t.rowbuf) (void)hipFree(t.rowbuf); if (t.ws) (void)hipFree(t.ws); if (t.shadow) (void)hipFree(t.shadow); if (t.norm) (void)hipFree(t.norm); if (t.norm_part) (void)hipFree(t.norm_part); }
     h->prof.fold();
     for (hipEvent_t e : h->prof.pool) (void)hipEventDestroy(e);
     for (hipStream_t q : h->qstream) if (q) { (void)hipStreamSynchronize(q); (void)hipStreamDestroy(q); }
@@ -1613,7 +1619,64 @@ int ppo_check(hk_handle h, int trainer, const char* fn, bool need_adv)
     if (!need_adv) return HK_OK;
     if (h->ro.open) return fail(h, HK_ERR_INVALID, std::string(fn) + ": refused while a rollout is open (hk_rollout_close first)");
     if (t.adv_gen != h->ro.gen) return fail(h, HK_ERR_INVALID, std::string(fn) + ": hk_ppo_advantages has not run on the current rollout");
+    if (t.adv_stale) return fail(h, HK_ERR_INVALID, std::string(fn) + ": the actor's normaliser changed after hk_ppo_advantages (run it again)");
     return HK_OK;
+}
+
+// the preconditions of everything that reads the closed rollout's rows of a trainer (hk_ppo_advantages, hk_ppo_normalizer_update)
+int ppo_check_rows(hk_handle h, const hk_context::Ppo& t, const char* fn)
+{
+    const auto& ro = h->ro;
+    const std::string f(fn);
+    if (ro.open) return fail(h, HK_ERR_INVALID, f + ": refused while a rollout is open (hk_rollout_close first)");
+    if (ro.R == 0 || !ro.buf) return fail(h, HK_ERR_INVALID, f + ": no rollout yet (hk_rollout_begin ... hk_rollout_close)");
+    if (ro.rows < 1) return fail(h, HK_ERR_INVALID, f + ": the rollout closed with no completed row");
+    if (t.policy >= ro.npol) return fail(h, HK_ERR_INVALID, f + ": the rollout began before the trainer's actor was attached");
+    return HK_OK;
+}
+
+// hk_ppo_normalizer_*: the trainer, and what every one of them refuses
+int ppo_norm_check(hk_handle h, int trainer, const char* fn, bool need_state)
+{
+    int rc = ppo_check(h, trainer, fn, false);
+    if (rc) return rc;
+    const auto& t = h->ppo[trainer];
+    const std::string f(fn);
+    if (!h->policy[t.policy].q.normalize) return fail(h, HK_ERR_INVALID, f + ": the policy was attached with normalize == 0 (it has no statistics)");
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, f + ": refused while a rollout is open (hk_rollout_close first)");
+    if (need_state && t.norm_steps < 1) return fail(h, HK_ERR_INVALID, f + ": no normaliser state (hk_ppo_normalizer_init or hk_ppo_normalizer_set first)");
+    return HK_OK;
+}
+
+// a normaliser state as init / set accept it; what names the first offender
+int ppo_norm_valid(hk_handle h, const char* fn, int64_t steps, const double* mean, const double* spread, int in_dim, const char* spread_name)
+{
+    const std::string f(fn);
+    if (steps < 1) return fail(h, HK_ERR_INVALID, f + ": steps < 1");
+    for (int k = 0; k < in_dim; k++) {
+        if (!std::isfinite(mean[k])) return fail(h, HK_ERR_INVALID, f + ": mean[" + std::to_string(k) + "] is not finite");
+        if (!(std::isfinite(spread[k]) && spread[k] > 0.0)) return fail(h, HK_ERR_INVALID, f + ": " + spread_name + "[" + std::to_string(k) + "] is not finite and > 0");
+    }
+    return HK_OK;
+}
+
+// the state's buffer, and the state (steps, m, M2) uploaded into it
+int ppo_norm_store(hk_handle h, hk_context::Ppo& t, int64_t steps, const double* m, const double* m2)
+{
+    const hk::PolicyParams& q = h->policy[t.policy].q;
+    const size_t K = (size_t)q.in_dim;
+    if (!t.norm) HK_HIP(h, hipMalloc(&t.norm, (4 * K + q.stack) * sizeof(double)));
+    HK_HIP(h, hipMemcpyAsync(t.norm, m, K * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HK_HIP(h, hipMemcpyAsync(t.norm + K, m2, K * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HK_HIP(h, hipStreamSynchronize(h->stream));          // (the host arrays are the caller's)
+    t.norm_steps = steps;
+    return HK_OK;
+}
+
+// the statistics of policy p changed: the advantages of its trainers are those of other inputs
+void ppo_norm_stale(hk_handle h, int policy)
+{
+    for (int i = 0; i < h->n_ppo; i++) if (h->ppo[i].policy == policy) h->ppo[i].adv_stale = true;
 }
 
 }  // namespace
@@ -1672,10 +1735,7 @@ int hk_ppo_advantages(hk_handle h, int trainer)
     if (rc) return rc;
     auto& t = h->ppo[trainer];
     const auto& ro = h->ro;
-    if (ro.open) return fail(h, HK_ERR_INVALID, "hk_ppo_advantages: refused while a rollout is open (hk_rollout_close first)");
-    if (ro.R == 0 || !ro.buf) return fail(h, HK_ERR_INVALID, "hk_ppo_advantages: no rollout yet (hk_rollout_begin ... hk_rollout_close)");
-    if (ro.rows < 1) return fail(h, HK_ERR_INVALID, "hk_ppo_advantages: the rollout closed with no completed row");
-    if (t.policy >= ro.npol) return fail(h, HK_ERR_INVALID, "hk_ppo_advantages: the rollout began before the trainer's actor was attached");
+    if ((rc = ppo_check_rows(h, t, "hk_ppo_advantages"))) return rc;
     const hk::PpoRows P = ppo_rows(h, t);
     const int n = P.R * P.E * P.S, nbt = P.E * P.S;
     const size_t need = 3 * (size_t)n + nbt + n;
@@ -1706,6 +1766,7 @@ int hk_ppo_advantages(hk_handle h, int trainer)
     HK_HIP(h, hipGetLastError());
     t.adv_gen = ro.gen;
     t.perm_valid = false;
+    t.adv_stale = false;
     return HK_OK;
 }
 
@@ -1784,6 +1845,93 @@ int hk_ppo_update(hk_handle h, int trainer, int epochs, int minibatch, float lr,
     return HK_OK;
 }
 
+int hk_ppo_normalizer_init(hk_handle h, int trainer, int64_t steps)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_norm_check(h, trainer, "hk_ppo_normalizer_init", false);
+    if (rc) return rc;
+    auto& t = h->ppo[trainer];
+    const hk::PolicyParams& q = h->policy[t.policy].q;
+    const int K = q.in_dim;
+    std::vector<float> mean(K), sdev(K);
+    HK_HIP(h, hipMemcpyAsync(mean.data(), q.mean, K * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HK_HIP(h, hipMemcpyAsync(sdev.data(), q.std, K * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HK_HIP(h, hipStreamSynchronize(h->stream));
+    std::vector<double> m(mean.begin(), mean.end()), sd(sdev.begin(), sdev.end()), m2(K);
+    if ((rc = ppo_norm_valid(h, "hk_ppo_normalizer_init", steps, m.data(), sd.data(), K, "std"))) return rc;
+    for (int k = 0; k < K; k++) m2[k] = sd[k] * sd[k] * (double)steps;
+    return ppo_norm_store(h, t, steps, m.data(), m2.data());          // (the published values stay as they are)
+}
+
+int hk_ppo_normalizer_set(hk_handle h, int trainer, int64_t steps, const double* mean, const double* m2)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_norm_check(h, trainer, "hk_ppo_normalizer_set", false);
+    if (rc) return rc;
+    if (!mean || !m2) return fail(h, HK_ERR_INVALID, "hk_ppo_normalizer_set: NULL mean or m2");
+    auto& t = h->ppo[trainer];
+    const hk::PolicyParams& q = h->policy[t.policy].q;
+    if ((rc = ppo_norm_valid(h, "hk_ppo_normalizer_set", steps, mean, m2, q.in_dim, "m2"))) return rc;
+    if ((rc = ppo_norm_store(h, t, steps, mean, m2))) return rc;
+    hipLaunchKernelGGL(hk::ppo_norm_publish_kernel, dim3(nblk(q.in_dim)), dim3(256), 0, h->stream, t.norm, const_cast<float*>(q.mean), const_cast<float*>(q.std),
+                       q.in_dim, (double)steps);
+    HK_HIP(h, hipGetLastError());
+    ppo_norm_stale(h, t.policy);
+    return HK_OK;
+}
+
+int hk_ppo_normalizer_get(hk_handle h, int trainer, int64_t* steps, double* mean, double* m2)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_norm_check(h, trainer, "hk_ppo_normalizer_get", true);
+    if (rc) return rc;
+    const auto& t = h->ppo[trainer];
+    const size_t K = (size_t)h->policy[t.policy].q.in_dim;
+    if (mean) HK_HIP(h, hipMemcpyAsync(mean, t.norm, K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (m2) HK_HIP(h, hipMemcpyAsync(m2, t.norm + K, K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HK_HIP(h, hipStreamSynchronize(h->stream));
+    if (steps) *steps = t.norm_steps;
+    return HK_OK;
+}
+
+int hk_ppo_normalizer_update(hk_handle h, int trainer)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_norm_check(h, trainer, "hk_ppo_normalizer_update", true);
+    if (rc) return rc;
+    auto& t = h->ppo[trainer];
+    if ((rc = ppo_check_rows(h, t, "hk_ppo_normalizer_update"))) return rc;
+    const hk::PpoRows P = ppo_rows(h, t);
+    const hk::PolicyParams& q = h->policy[t.policy].q;
+    const int K = P.in_dim, W = 2 * K + P.stack;
+    const long long n = (long long)P.R * P.E * P.S;
+    // the fixed partition: the items (u, e, j) in order, cut into at most PPO_NORM_MAXWG runs of whole trips
+    const int DL = std::min(P.D, 256), trip = (256 / DL) * hk::PPO_NORM_U;
+    const long long items = (long long)(P.R + P.stack - 1) * P.E * P.S;
+    long long ipw = (items + hk::PPO_NORM_MAXWG - 1) / hk::PPO_NORM_MAXWG;
+    ipw = (ipw + trip - 1) / trip * trip;
+    if (items + ipw > 0x7FFFFFFFLL) return fail(h, HK_ERR_UNSUPPORTED, "hk_ppo_normalizer_update: more than 2^31 recorded observations");
+    const int nwg = (int)((items + ipw - 1) / ipw);
+    if (nwg > t.norm_part_wg) {
+        if (t.norm_part) HK_HIP(h, hipFree(t.norm_part));
+        t.norm_part = nullptr; t.norm_part_wg = 0;
+        HK_HIP(h, hipMalloc(&t.norm_part, (size_t)nwg * W * sizeof(double)));
+        t.norm_part_wg = nwg;
+    }
+    hipStream_t s = h->stream;
+    double* sums = t.norm + 2 * (size_t)K;
+    const dim3 grid(nwg, (P.stack + hk::PPO_NORM_Q - 1) / hk::PPO_NORM_Q, (P.D + 255) / 256);
+    hipLaunchKernelGGL(hk::ppo_norm_partial_kernel, grid, dim3(256), 0, s, P, t.norm, (int)ipw, t.norm_part);
+    hipLaunchKernelGGL(hk::ppo_norm_combine_kernel, dim3(nblk(W, 256 / hk::PPO_NORM_SEG)), dim3(256), 0, s, t.norm_part, nwg, W, sums);
+    const int64_t N1 = t.norm_steps + n;
+    hipLaunchKernelGGL(hk::ppo_norm_finalise_kernel, dim3(nblk(K)), dim3(256), 0, s, sums, t.norm, const_cast<float*>(q.mean), const_cast<float*>(q.std), K,
+                       P.D, (double)n, (double)N1);
+    HK_HIP(h, hipGetLastError());
+    t.norm_steps = N1;
+    ppo_norm_stale(h, t.policy);
+    return HK_OK;
+}
+
 int hk_ppo_set_precision(hk_handle h, int trainer, int precision)
 {
     HK_NEED_ENV(h);
@@ -1854,6 +2002,11 @@ void* hk_ppo_ptr(hk_handle h, int trainer, int field)
         if (!t.perm_valid) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: no hk_ppo_update on the current advantages"); return nullptr; }
         return ppo_rowbuf(h, t).perm;
     }
+    if (field == HK_PPO_NORM_MEAN || field == HK_PPO_NORM_STD) {
+        const hk::PolicyParams& q = h->policy[t.policy].q;
+        if (!q.normalize) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: the policy was attached with normalize == 0"); return nullptr; }
+        return const_cast<float*>(field == HK_PPO_NORM_MEAN ? q.mean : q.std);
+    }
     if (field == HK_PPO_SHADOW) {
         if (!t.shadow) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: the trainer has never been in HK_PPO_PREC_BF16"); return nullptr; }
         return t.shadow;
@@ -1874,6 +2027,7 @@ int hk_ppo_count(hk_handle h, int trainer, int field)
     if (field <= HK_PPO_RET) return t.adv_gen < 0 ? 0 : t.n;
     if (field == HK_PPO_PERM) return t.perm_valid ? t.n : 0;
     if (field == HK_PPO_SHADOW) return t.shadow ? (int)(t.P + t.shadow_pad) : 0;
+    if (field == HK_PPO_NORM_MEAN || field == HK_PPO_NORM_STD) return h->policy[t.policy].q.normalize ? h->policy[t.policy].q.in_dim : 0;
     return field == HK_PPO_MB_LOGITS ? t.last_m * t.actor.n_branch : t.last_m;
 }
 

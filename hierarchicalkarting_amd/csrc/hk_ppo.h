@@ -10,6 +10,8 @@
 //   ppo_colsum_kernel       bias / log_sigma gradients and the stats: fixed-order column sums (no float atomics anywhere)
 //   ppo_gae_kernel          one lane per (env, slot): the reverse GAE scan;  ppo_adv_norm_kernel: fp64 mean / std in one block
 //   ppo_adam_kernel, ppo_publish_kernel<TO_POLICY>              elementwise
+//   ppo_norm_partial / combine / finalise / publish_kernel      the running normaliser (hk.h "NORMALISER"): fp64 sums over OBS / FIRST / RING0 read
+//                           once, per-workgroup partials combined in partition order, the new state and the policy's fp32 mean / std
 // HK_PPO_PREC_BF16 (hk.h "PRECISION"): the trunk products run on ppo_gemm_bf16_kernel<EPI> (v_mfma_f32_32x32x16_bf16, fp32 accumulation) over
 // operands their producers rounded once — ppo_shadow_kernel (the weights, after Adam), ppo_gather_kernel<uint16_t>, ppo_head_back_bf16_kernel and
 // the product's own epilogues; everything else above is shared with the fp32 mode.
@@ -50,7 +52,7 @@ struct PpoNet {
 struct PpoRows {
     const float *obs, *ring0, *next_obs, *raw, *reward, *term_reward, *logp_c, *logp_d;
     const int *first, *branch, *done;
-    const float *mean, *std;            // the actor's normaliser (frozen); nullptr: none
+    const float *mean, *std;            // the actor's normaliser, read in place (hk_ppo_normalizer_* publish into it); nullptr: none
     int R, E, A, S, D, stack, smax, in_dim, normalize;
     int slots[HK_MAX_AGENTS];
 };
@@ -625,6 +627,149 @@ __global__ __launch_bounds__(256) void ppo_publish_kernel(PolicyParams Q, PpoNet
     else if (idx == net.ols) mv(Q.log_sigma, 0);
     else if (idx >= net.oWbr && idx < net.oWbr + (size_t)net.n_branch * H) mv(Q.W_branch, idx - net.oWbr);
     else if (idx >= net.obbr && idx < net.obbr + net.n_branch) mv(Q.b_branch, idx - net.obbr);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Running normaliser (hk.h "PPO trainer" NORMALISER): sum_i c_ik and sum_i c_ik^2, c_ik = x_ik - m_k, over the n rows' stacked inputs, which
+// are never built.  An ITEM is one recorded observation (u, e, j), u in [-(stack - 1), R): OBS[u] for u >= 0, the RING0 entry for u < 0.  It is
+// entry q = stack - 1 - s of row t = u + s for every s in [0, stack) with 0 <= t < R and no FIRST in (u, t] (ppo_gather_kernel's rule, read
+// from the entry's side), so one read of the item feeds every stack position: s ascending, the FIRST words of (e, j) ORed as it goes.  What
+// is absent is not visited: the finalise kernel adds (n - present_q) (-m_k) and (n - present_q) m_k^2 from the counts.
+// Threads: lane d of a group of DL = min(D, 256) lanes owns observation column d (coalesced along the observation; blockIdx.z: further
+// blocks of 256 columns), the 256 / DL groups of a workgroup take consecutive items, PPO_NORM_U of them per trip with their loads issued
+// together.  blockIdx.y: PPO_NORM_Q stack positions per pass (one pass up to stack 8; a taller stack reads its items once per 8 positions).
+// Workgroup x owns the items [x ipw, (x + 1) ipw) — a partition fixed by the shapes — and writes its fp64 partials to part[x][W],
+// W = 2 in_dim + stack: sum c [in_dim], sum c^2 [in_dim], present [stack]; every sum in a fixed order, no atomics.
+constexpr int PPO_NORM_Q = 8, PPO_NORM_U = 4, PPO_NORM_MAXWG = 2048, PPO_NORM_SEG = 16;
+
+__global__ __launch_bounds__(256) void ppo_norm_partial_kernel(PpoRows P, const double* __restrict__ state, int ipw, double* __restrict__ part)
+{
+    __shared__ double red[PPO_NORM_Q][256];
+    const int tid = threadIdx.x;
+    const int D = P.D, stack = P.stack, R = P.R, ES = P.E * P.S;
+    const int DL = D < 256 ? D : 256, G = 256 / DL;
+    const int g = tid / DL, d = blockIdx.z * 256 + tid % DL;
+    const bool lane_ok = g < G && d < D;
+    const int q_hi = stack - blockIdx.y * PPO_NORM_Q;                 // this pass: positions [q_hi - nq, q_hi), acc[r] <-> q = q_hi - 1 - r, s = s0 + r
+    const int nq = q_hi < PPO_NORM_Q ? q_hi : PPO_NORM_Q;
+    const int s0 = stack - q_hi;
+    const int items = (R + stack - 1) * ES;
+    const int lo = blockIdx.x * ipw, hi = (lo + ipw < items) ? lo + ipw : items;
+    const size_t EA = (size_t)P.E * P.A;
+    double m[PPO_NORM_Q], s1[PPO_NORM_Q], s2[PPO_NORM_Q];
+    unsigned cnt[PPO_NORM_Q];
+#pragma unroll
+    for (int r = 0; r < PPO_NORM_Q; r++) {
+        m[r] = (lane_ok && r < nq) ? state[(size_t)(q_hi - 1 - r) * D + d] : 0.0;
+        s1[r] = 0.0; s2[r] = 0.0; cnt[r] = 0u;
+    }
+    for (int base = lo; base < hi; base += G * PPO_NORM_U) {
+        float x[PPO_NORM_U];
+        int uu[PPO_NORM_U];
+        size_t eaa[PPO_NORM_U];
+        bool ok[PPO_NORM_U];
+#pragma unroll
+        for (int v = 0; v < PPO_NORM_U; v++) {
+            const int it = base + v * G + g;
+            ok[v] = lane_ok && it < hi;
+            const int itc = ok[v] ? it : lo;
+            const int ue = itc / ES, rem = itc - ue * ES, e = rem / P.S;
+            const int u = ue - (stack - 1), a = P.slots[rem - e * P.S];
+            const size_t ea = (size_t)e * P.A + a;
+            uu[v] = u; eaa[v] = ea;
+            x[v] = 0.0f;
+            if (ok[v]) x[v] = u >= 0 ? P.obs[((size_t)u * EA + ea) * D + d] : P.ring0[(ea * (P.smax - 1) + (P.smax - 1 + u)) * D + d];
+        }
+#pragma unroll
+        for (int v = 0; v < PPO_NORM_U; v++) {
+            const int u = uu[v];
+            const int* fr = P.first + eaa[v];
+            bool dead = !ok[v];
+            for (int s = 1; s < s0; s++) {                            // (a stack above PPO_NORM_Q: the positions of the passes before this one)
+                const int t = u + s;
+                if (t >= 0 && t < R && fr[(size_t)t * EA]) dead = true;
+            }
+            const double xd = (double)x[v];
+#pragma unroll
+            for (int r = 0; r < PPO_NORM_Q; r++) {
+                const int s = s0 + r, t = u + s;
+                const bool row = r < nq && t >= 0 && t < R;
+                if (row && s >= 1 && fr[(size_t)t * EA]) dead = true;
+                if (row && !dead) {
+                    const double c = xd - m[r];
+                    s1[r] += c; s2[r] += c * c; cnt[r] += 1u;
+                }
+            }
+        }
+    }
+    // the groups' sums, group 0 first (fixed order); one LDS buffer, used for sum c, then sum c^2, then the counts
+    const int in_dim = P.in_dim;
+    double* out = part + (size_t)blockIdx.x * (2 * in_dim + stack);
+    const bool writer = lane_ok && g == 0;
+    for (int pass = 0; pass < 3; pass++) {
+#pragma unroll
+        for (int r = 0; r < PPO_NORM_Q; r++) red[r][tid] = pass == 0 ? s1[r] : (pass == 1 ? s2[r] : (double)cnt[r]);
+        __syncthreads();
+        if (writer && (pass < 2 || d == 0)) {
+#pragma unroll
+            for (int r = 0; r < PPO_NORM_Q; r++) {
+                if (r >= nq) continue;
+                double a = red[r][tid];
+                for (int gg = 1; gg < G; gg++) a += red[r][gg * DL + tid];
+                const int q = q_hi - 1 - r;
+                if (pass < 2) out[(size_t)pass * in_dim + (size_t)q * D + d] = a;
+                else out[2 * in_dim + q] = a;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// sums[c] = the nwg partials of column c in partition order: PPO_NORM_SEG consecutive runs summed side by side, then the runs in order
+__global__ __launch_bounds__(256) void ppo_norm_combine_kernel(const double* __restrict__ part, int nwg, int W, double* __restrict__ sums)
+{
+    __shared__ double red[PPO_NORM_SEG][256 / PPO_NORM_SEG];
+    constexpr int NC = 256 / PPO_NORM_SEG;
+    const int tid = threadIdx.x, cl = tid % NC, seg = tid / NC;
+    const int c = blockIdx.x * NC + cl;
+    const int per = (nwg + PPO_NORM_SEG - 1) / PPO_NORM_SEG;
+    const int x0 = seg * per, x1 = (x0 + per < nwg) ? x0 + per : nwg;
+    double s = 0.0;
+    if (c < W) for (int x = x0; x < x1; x++) s += part[(size_t)x * W + c];
+    red[seg][cl] = s;
+    __syncthreads();
+    if (seg != 0 || c >= W) return;
+    for (int k = 1; k < PPO_NORM_SEG; k++) s += red[k][cl];
+    sums[c] = s;
+}
+
+// the published form of a state: mean = fp32(m), std = fp32(sqrt(M2 / N)), division and square root in fp64 (IEEE: no fast-math in this build)
+__device__ __forceinline__ void ppo_norm_put(double m, double M2, double N, float* mean, float* sdev, int k)
+{
+    mean[k] = (float)m;
+    sdev[k] = (float)sqrt(M2 / N);
+}
+
+// one thread per stacked input k: the batch update of hk.h from the combined sums (n rows, N1 = N + n), the new state and its published form
+__global__ __launch_bounds__(256) void ppo_norm_finalise_kernel(const double* __restrict__ sums, double* state, float* mean, float* sdev, int in_dim, int D,
+                                                                double n, double N1)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= in_dim) return;
+    const double absent = n - sums[2 * in_dim + k / D];
+    const double m = state[k];
+    const double delta = sums[k] - absent * m;
+    const double c2 = sums[in_dim + k] + absent * (m * m);
+    const double m1 = m + delta / N1;
+    const double M2 = state[in_dim + k] + (c2 - (delta * delta) / N1);
+    state[k] = m1; state[in_dim + k] = M2;
+    ppo_norm_put(m1, M2, N1, mean, sdev, k);
+}
+
+__global__ __launch_bounds__(256) void ppo_norm_publish_kernel(const double* __restrict__ state, float* mean, float* sdev, int in_dim, double N)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < in_dim) ppo_norm_put(state[k], state[in_dim + k], N, mean, sdev, k);
 }
 
 }  // namespace hk

@@ -6,6 +6,7 @@ and leaves updated weights in the attached policy, so that the next step() acts 
     tr.advantages()                              # critic over every row + the bootstrap inputs, GAE
     stats = tr.update(epochs=3, minibatch=512, lr=3e-4, eps=0.2, beta=5e-3)     # shuffle, minibatches, Adam; then publish
     tr.set_precision("bf16")                     # trunk products on the bf16 matrix cores, fp32 master weights (hk.h "PRECISION")
+    tr.normalizer_init(); ...; tr.normalizer_update()     # the running input normaliser, folded from the closed rollout (hk.h "NORMALISER")
 
 Nothing is computed here: the arrays below only describe the flat parameter layout the library uses."""
 import ctypes as C
@@ -112,6 +113,43 @@ def permutation(n, seed, count):
         x[todo] = y
         todo = x >= np.uint64(n)
     return x.astype(np.int64)
+
+
+def _normalizer_check(steps, mean, m2, in_dim=None):
+    """the validity rules of hk_ppo_normalizer_set on the host -> (int steps, float64 mean, float64 m2); ValueError names the offender"""
+    mean, m2 = np.asarray(mean, np.float64), np.asarray(m2, np.float64)
+    if int(steps) != steps or int(steps) < 1:
+        raise ValueError("normaliser: steps must be an integer >= 1")
+    if mean.ndim != 1 or mean.shape != m2.shape or (in_dim is not None and mean.size != in_dim):
+        raise ValueError("normaliser: mean and m2 are [in_dim]%s" % ("" if in_dim is None else " = [%d]" % in_dim))
+    if not np.isfinite(mean).all():
+        raise ValueError("normaliser: a mean is not finite")
+    if not (np.isfinite(m2) & (m2 > 0.0)).all():
+        raise ValueError("normaliser: an m2 is not finite and > 0")
+    return int(steps), np.ascontiguousarray(mean), np.ascontiguousarray(m2)
+
+
+def normalizer_merge(steps, mean, m2, X):
+    """host twin of hk_ppo_normalizer_update in float64 (ML-Agents' batch update; hk.h "NORMALISER"): folds the rows X [n, in_dim] — the
+    UN-normalised stacked inputs, zero padding included — into the state.  -> (steps', mean', m2').  With c = x - mean:
+        N' = N + n;  delta = sum c;  mean' = mean + delta / N';  m2' = m2 + sum (x - mean')(x - mean)
+    The result does not depend, algebraically, on how the rows are split into successive calls."""
+    steps, mean, m2 = _normalizer_check(steps, mean, m2)
+    X = np.asarray(X, np.float64)
+    if X.ndim != 2 or X.shape[1] != mean.size:
+        raise ValueError("normalizer_merge: X is [n, %d]" % mean.size)
+    n = X.shape[0]
+    if n == 0:
+        return steps, mean.copy(), m2.copy()
+    N1 = steps + n
+    c = X - mean
+    mean1 = mean + c.sum(axis=0) / N1
+    return N1, mean1, m2 + ((X - mean1) * c).sum(axis=0)
+
+
+def normalizer_published(steps, mean, m2):
+    """-> (norm_mean, norm_std) float32: the published form of a state, as the device rounds it"""
+    return np.float32(np.asarray(mean, np.float64)), np.float32(np.sqrt(np.asarray(m2, np.float64) / np.float64(steps)))
 
 
 class PPOTrainer:
@@ -246,9 +284,34 @@ class PPOTrainer:
         flat = self.read("params") if flat is None else flat
         return split_params(flat[self.n_actor:], self.critic_layout)
 
+    # ---- the running normaliser (hk.h "NORMALISER")
+    def normalizer_init(self, steps=1):
+        """state from the policy's current published statistics: N = steps, m = mean, M2 = std^2 steps (steps = 1 on mean 0, std 1: ML-Agents' start)"""
+        self._ck(self.env.L.hk_ppo_normalizer_init(self.env.h, self.t, int(steps)))
+
+    def normalizer_update(self):
+        """fold the closed rollout's rows of this trainer into the state and publish; advantages() must run (again) before minibatch() / update()"""
+        self._ck(self.env.L.hk_ppo_normalizer_update(self.env.h, self.t))
+
+    def normalizer_state(self):
+        """-> (steps, mean float64 [in_dim], m2 float64 [in_dim]); with normalizer_load, the normaliser's checkpoint"""
+        k = self.actor_policy.in_dim
+        steps, mean, m2 = C.c_int64(0), np.zeros(k, np.float64), np.zeros(k, np.float64)
+        self._ck(self.env.L.hk_ppo_normalizer_get(self.env.h, self.t, C.byref(steps), C.c_void_p(mean.ctypes.data), C.c_void_p(m2.ctypes.data)))
+        return int(steps.value), mean, m2
+
+    def normalizer_load(self, steps, mean, m2):
+        """load a state and publish it (validated here first: ValueError; the library applies the same rules)"""
+        steps, mean, m2 = _normalizer_check(steps, mean, m2, self.actor_policy.in_dim)
+        self._ck(self.env.L.hk_ppo_normalizer_set(self.env.h, self.t, steps, C.c_void_p(mean.ctypes.data), C.c_void_p(m2.ctypes.data)))
+
     def actor(self):
-        """-> host Policy of the current master actor parameters (normaliser, stack, seed and mode of the attached actor)"""
+        """-> host Policy of the current master actor parameters (stack, seed and mode of the attached actor) with the policy's CURRENT published
+        normaliser, read from the device: the attached actor's arrays bit for bit until a normalizer_update / normalizer_load publishes others"""
         a, p = self.actor_policy, self.actor_params()
         L = len(a.W)
+        mean, std = a.norm_mean, a.norm_std
+        if mean is not None:
+            mean, std = self.read("norm_mean"), self.read("norm_std")
         return Policy([p["W%d" % l] for l in range(L)], [p["b%d" % l] for l in range(L)], p["W_mu"], p["b_mu"], p["log_sigma"], p["W_branch"],
-                      p["b_branch"], a.norm_mean, a.norm_std, a.stack, a.deterministic, a.seed)
+                      p["b_branch"], mean, std, a.stack, a.deterministic, a.seed)

@@ -27,7 +27,7 @@ namespace KartGame.AI.Native
                          HK_RO_TERM_GROUP_REWARD = 12, HK_RO_DONE = 13, HK_RO_RING0 = 14, HK_RO_NEXT_OBS = 15, HK_RO_FIELDS = 16;
         // hk_ppo_field: the PPO trainer's buffers (hk_ppo_ptr / hk_ppo_count); HK_PPO_STATS: L_pi, L_v, entropy, approx-KL, clip fraction, skipped rows
         public const int HK_PPO_PARAMS = 0, HK_PPO_GRAD = 1, HK_PPO_ADAM_M = 2, HK_PPO_ADAM_V = 3, HK_PPO_V_OLD = 4, HK_PPO_ADV = 5, HK_PPO_RET = 6,
-                         HK_PPO_MB_MU = 7, HK_PPO_MB_LOGITS = 8, HK_PPO_MB_VALUE = 9, HK_PPO_PERM = 10, HK_PPO_SHADOW = 11, HK_PPO_FIELDS = 12,
+                         HK_PPO_MB_MU = 7, HK_PPO_MB_LOGITS = 8, HK_PPO_MB_VALUE = 9, HK_PPO_PERM = 10, HK_PPO_SHADOW = 11, HK_PPO_NORM_MEAN = 12, HK_PPO_NORM_STD = 13, HK_PPO_FIELDS = 14,
                          HK_PPO_PREC_F32 = 0, HK_PPO_PREC_BF16 = 1,
                          HK_POLICY_PREC_F32 = 0, HK_POLICY_PREC_BF16 = 1,      // hk_policy_precision
                          HK_PPO_STATS = 6;
@@ -437,6 +437,11 @@ namespace KartGame.AI.Native
         [DllImport(Lib)] public static extern int hk_ppo_set_precision(IntPtr h, int trainer, int precision);
         [DllImport(Lib)] public static extern int hk_ppo_get_precision(IntPtr h, int trainer);
         [DllImport(Lib)] public static extern int hk_ppo_gemm_bf16(IntPtr h, int epi, int M, int N, int K, IntPtr aDev, IntPtr bDev, float* biasDev, float* auxDev, float* cDev);
+        // the running normaliser of a trainer's actor (hk.h "PPO trainer" NORMALISER): fp64 state per trainer, published into the attached policy
+        [DllImport(Lib)] public static extern int hk_ppo_normalizer_init(IntPtr h, int trainer, long steps);
+        [DllImport(Lib)] public static extern int hk_ppo_normalizer_update(IntPtr h, int trainer);
+        [DllImport(Lib)] public static extern int hk_ppo_normalizer_get(IntPtr h, int trainer, long* steps, double* mean, double* m2);
+        [DllImport(Lib)] public static extern int hk_ppo_normalizer_set(IntPtr h, int trainer, long steps, double* mean, double* m2);
         // multi-GPU: one process per GPU, envs sharded by HkConfig.env_id_base; the only exchange is this all-gather over RCCL
         [DllImport(Lib)] public static extern int hk_comm_unique_id(byte* id128);
         [DllImport(Lib)] public static extern int hk_comm_init(IntPtr h, int worldSize, int rank, byte* id128);

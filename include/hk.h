@@ -545,7 +545,7 @@ void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* 
  *   L    = L_pi + 0.5 L_v - beta mean H
  * Gradients follow torch's conventions at ties: min / max split the gradient evenly, clip passes it inside [lo, hi] inclusive.
  * Departure from ML-Agents: no 1e-7 inside the log-probabilities and the entropy (the recorder has none either).
- * ADAM over the actor's and the critic's parameters (the normaliser is frozen), step s = 1, 2, ... counted per trainer, in fp32, in this order:
+ * ADAM over the actor's and the critic's parameters (never the normaliser: NORMALISER below), step s = 1, 2, ... counted per trainer, in fp32, in this order:
  *   m = b1 m + (1 - b1) g;  v = b2 v + ((1 - b2) g) g;  p = p - lr (m / c1) / (sqrt(v / c2) + eps)
  * with (1 - b1), (1 - b2) rounded to fp32 once, c1 = 1 - b1^s and c2 = 1 - b2^s evaluated in fp64 and rounded to fp32; every operation
  * rounded to fp32 (no fused multiply-add), sqrt and division correctly rounded.
@@ -590,8 +590,36 @@ void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* 
  * operands as raw 16-bit patterns, C fp32 [M][N], on hk_stream: epi 1 (forward) C = swish(bias + A B^T), A [M][K], B [N][K], bias [N] or NULL;
  * epi 2 (backward delta) C = (A B) * swish'(aux), A [M][K], B [K][N], aux fp32 [M][N]; epi 0 (weight gradient) C = A^T B, A [K][M], B [K][N],
  * split over K in chunks of 256 and combined in chunk order (synchronises).  A NULL operand, a non-positive M / N / K or another epi is refused.
- * Out of scope: updating the normaliser (frozen as attached), self-play opponent swaps and ELO, POCA and group rewards, LSTM memory,
- * gradient clipping, multi-GPU gradient all-reduce and bf16 optimiser state.  Everything is asynchronous on hk_stream. */
+ * NORMALISER (hk_ppo_normalizer_*; opt-in: a trainer that never calls them leaves the statistics frozen as attached, and every entry point above
+ * computes what it computed, bit for bit).  STATE per trainer, once initialised: a step count N (int64) and, per stacked input k < in_dim, an
+ * fp64 mean m_k and an fp64 sum of squared deviations M2_k — ML-Agents' normalization_steps, running_mean and running_variance, kept in fp64.
+ * The attached policy's fp32 statistics are the PUBLISHED form, mean_k = fp32(m_k), std_k = fp32(sqrt(M2_k / N)) with the division and the square
+ * root in fp64 (correctly rounded): hk_policy_desc.norm_std's exported divisor.  They live where hk_policy_attach put them and are read in place by
+ * both inference chains (fp32 and bf16) and by the trainer's gather, so every consumer follows a publication; clip((x - mean) / std, -5, 5) is untouched.
+ *   hk_ppo_normalizer_init    N = steps (>= 1), m_k = mean_k, M2_k = (double)std_k^2 * steps from the policy's CURRENT device values (synchronises;
+ *                             publishes nothing).  A fresh actor attached with mean 0, std 1 and steps = 1 is ML-Agents' initial normaliser.
+ *   hk_ppo_normalizer_update  folds the trainer's n = R E S rows of the closed rollout (its COMPLETED rows; the preconditions of hk_ppo_advantages)
+ *                             into the state and publishes.  x_ik is the UN-normalised stacked input of row i, rebuilt by the rule of ROWS above
+ *                             (an absent entry is 0 and counts, as ML-Agents' zero-padded stack does; the bootstrap rows are excluded).  With
+ *                             c_ik = x_ik - m_k:  N' = N + n;  delta_k = sum_i c_ik;  m'_k = m_k + delta_k / N';
+ *                             M2'_k = M2_k + sum_i (x_ik - m'_k)(x_ik - m_k), evaluated in one pass as sum_i c_ik^2 - delta_k^2 / N' — ML-Agents'
+ *                             batch update, algebraically independent of how the rows are split into batches.  All sums are fp64 over a partition
+ *                             of the recorded observations fixed by the shapes, combined in partition order; no float atomics: the same call on
+ *                             the same state gives the same bits.  Asynchronous.
+ *   hk_ppo_normalizer_get     steps, mean [in_dim], m2 [in_dim] to host pointers (any may be NULL); synchronises.
+ *   hk_ppo_normalizer_set     loads a state (host pointers) and publishes it; with get, the normaliser's checkpoint.  Synchronises.
+ * Refused with HK_ERR_INVALID (state and published values as they were): every one of the four on a policy attached with normalize == 0 (it has
+ * no buffers) or while a rollout is open (the rows of one rollout come from one chain); init / set on steps < 1, a non-finite mean, a std (init)
+ * or m2 (set) that is not finite and > 0, set on a NULL array; update / get before init or set; update on whatever hk_ppo_advantages refuses.
+ * After update or set the advantages of EVERY trainer of that policy are stale (V_OLD is the critic on inputs it will not be trained on):
+ * hk_ppo_minibatch / hk_ppo_update are refused until hk_ppo_advantages has run again, exactly as after a new rollout.
+ * ORDER (neither is enforced).  ML-Agents' order, normalizer_update -> advantages -> update: the rollout's LOGP_* were recorded under the old
+ * statistics, so rho != 1 at unchanged parameters.  The exact order, advantages -> update -> normalizer_update: the new statistics act from the
+ * next rollout on, rho == 1 and the bit-equal training forward hold as above, in both precisions.  A dimension that never varies keeps M2_k at its
+ * initial value, so its std shrinks as 1 / sqrt(N): ML-Agents' behaviour, not guarded.
+ * HK_PPO_NORM_MEAN / HK_PPO_NORM_STD (hk_ppo_ptr): the policy's published fp32 statistics themselves, [in_dim]; count 0 on normalize == 0.
+ * Out of scope: self-play opponent swaps and ELO, POCA and group rewards, LSTM memory, a normaliser for policies attached with normalize == 0,
+ * gradient clipping, multi-GPU gradient all-reduce and bf16 optimiser state.  Everything is asynchronous on hk_stream unless noted. */
 #define HK_PPO_STATS 6
 typedef struct hk_ppo_config {
     float gamma;                    /* 0.99 */
@@ -607,6 +635,7 @@ typedef enum hk_ppo_field {
     HK_PPO_MB_MU, HK_PPO_MB_LOGITS, HK_PPO_MB_VALUE, HK_PPO_PERM,
     HK_PPO_SHADOW,      /* uint16 [P + pad]: PARAMS as bf16; the actor's element i at i, the critic's at i + pad, pad = (8 - n_actor % 8) % 8; once
                            the trainer has been in HK_PPO_PREC_BF16 */
+    HK_PPO_NORM_MEAN, HK_PPO_NORM_STD,      /* fp32 [in_dim]: the attached policy's published statistics (NORMALISER) */
     HK_PPO_FIELDS
 } hk_ppo_field;
 typedef enum { HK_PPO_PREC_F32 = 0, HK_PPO_PREC_BF16 = 1 } hk_ppo_precision;
@@ -622,6 +651,10 @@ int hk_ppo_set_precision(hk_handle h, int trainer, int precision);
 int hk_ppo_get_precision(hk_handle h, int trainer);
 int hk_ppo_gemm_bf16(hk_handle h, int epi, int M, int N, int K, const void* A_dev, const void* B_dev, const float* bias_dev, const float* aux_dev,
                      float* C_dev);
+int hk_ppo_normalizer_init(hk_handle h, int trainer, int64_t steps);
+int hk_ppo_normalizer_update(hk_handle h, int trainer);
+int hk_ppo_normalizer_get(hk_handle h, int trainer, int64_t* steps, double* mean /*[in_dim]*/, double* m2 /*[in_dim]*/);
+int hk_ppo_normalizer_set(hk_handle h, int trainer, int64_t steps, const double* mean /*[in_dim]*/, const double* m2 /*[in_dim]*/);
 
 /* ---- multi-GPU: the path's ONE exchange step ---------------------------------------------------------------
  * Race instances are independent (one RacingEnvController owns its own Agents[] / Sections[], REC:46-52): every rank steps its

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """What a PPO update costs on the RL workload (bench.py --workload rl: 2v2 Oval, every agent LowMode RL, one 312 -> 256 x 3 actor per team,
 DecisionPeriod 2, rewards on): one rollout of R rows is collected (timed), then for team 0's trainer (critic 312 -> 256 x 3):
-hk_ppo_advantages, and one-epoch hk_ppo_update calls at minibatch 512 (ML-Agents' batch_size) and at a GPU-sized minibatch; every timing
-ends in a device synchronise, medians of --repeats.  One JSON line per --precision; with several, the precisions alternate round by round
+hk_ppo_advantages, one-epoch hk_ppo_update calls at minibatch 512 (ML-Agents' batch_size) and at a GPU-sized minibatch, and
+hk_ppo_normalizer_update (normalizer_ms; the state is put back after every call, which republishes the attached statistics bit for bit, so
+the other timings run on what they always ran on); every timing ends in a device synchronise, medians of --repeats.  One JSON line per --precision; with several, the precisions alternate round by round
 (after a switch: advantages and one untimed update at the large minibatch, which allocate the workspace of that precision).
 FLOP count per trained row (stated, not measured): forward + backward of actor and critic = 3 x forward, forward = 2 x (weights of the trunks
 and heads) per row: 3 x 2 x (312 x 256 + 2 x 256 x 256 + 4 x 256 + 312 x 256 + 2 x 256 x 256 + 256) = 6 x 423 168 = 2.54 MFLOP per row at this shape."""
@@ -16,6 +17,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 PEAK_TF = {"f32": 157.3, "bf16": 16 * 157.3}          # MI355X MFMA peaks (TFLOP/s): f32 in / f32 acc, and bf16 at 16 x that rate
+PEAK_HBM_TB = 8.0                                     # MI355X HBM3E peak (TB/s)
 
 
 def main():
@@ -49,7 +51,14 @@ def main():
     w = K0 * H + 2 * H * H + 4 * H + K0 * H + 2 * H * H + H
     flop_row = 3 * 2 * w
     sizes = (a.big, 512)
-    runs = {p: {"adv": [], **{mb: [] for mb in sizes}} for p in a.precision}
+    runs = {p: {"adv": [], "norm": [], **{mb: [] for mb in sizes}} for p in a.precision}
+    # what hk_ppo_normalizer_update reads, once each: the trainer's slots of OBS [R][E][S][D] and FIRST [R][E][S], RING0 [E][S][stack - 1][D]
+    D, S, stack = env.obs_dim, 2, 4
+    norm_bytes = 4 * (R * E * S * D + R * E * S + E * S * (stack - 1) * D)
+    tr.normalizer_init(1)
+    norm_state = tr.normalizer_state()
+    tr.normalizer_update()                               # (allocates the partials; first launches)
+    tr.normalizer_load(*norm_state)
 
     def timed(f):
         env.synchronize()
@@ -66,6 +75,8 @@ def main():
             runs[prec]["adv"].append(timed(tr.advantages))
             for mb in sizes:
                 runs[prec][mb].append(timed(lambda: tr.update(1, mb, 1e-5, 0.2, 5e-3)))
+            runs[prec]["norm"].append(timed(tr.normalizer_update))
+            tr.normalizer_load(*norm_state)
     env.close()
     for prec in a.precision:
         res = {}
@@ -77,6 +88,8 @@ def main():
                             "peak_fraction": tf / PEAK_TF[prec], "update_over_collection": ms / collect_ms}
         print(json.dumps({"metric": "PPO update on the RL workload (one actor + critic, one epoch)", "precision": prec,
                           "advantages_ms": statistics.median(runs[prec]["adv"]), "advantages_runs": runs[prec]["adv"], "collect_ms": collect_ms,
+                          "normalizer_ms": statistics.median(runs[prec]["norm"]), "normalizer_runs": runs[prec]["norm"], "normalizer_bytes": norm_bytes,
+                          "normalizer_hbm_fraction": norm_bytes / (statistics.median(runs[prec]["norm"]) * 1e-3) / (PEAK_HBM_TB * 1e12),
                           "minibatch": res, "config": {"envs": E, "agents": A, "rows": R, "n_rows": n, "flop_per_row": flop_row,
                                                        "peak_tflops": PEAK_TF[prec]}}))
 
