@@ -18,6 +18,8 @@ HK_MAX_POLICIES = 4
 HK_POLICY_MAX_LAYERS = 4
 HK_POLICY_MAX_IN = 1280
 HK_POLICY_MAX_HIDDEN = 256
+HK_MAX_POOLS = 8
+HK_POOL_MAX_SLOTS = 64
 
 HK_OK, HK_ERR_INVALID, HK_ERR_NO_DEVICE, HK_ERR_HIP, HK_ERR_UNSUPPORTED, HK_ERR_SINGULAR = 0, -1, -2, -3, -4, -5
 HK_LOW_RL, HK_LOW_MPC, HK_LOW_LQR, HK_LOW_E2E = 0, 1, 2, 3
@@ -175,6 +177,11 @@ class PpoConfig(C.Structure):
                 ("adam_beta2", C.c_float), ("adam_eps", C.c_float), ("seed", C.c_uint32)]
 
 
+class EpisodeStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("episodes", "partial", "wins", "draws", "losses", "timeouts", "len_sum")] + [
+        (n, C.c_double) for n in ("ret_sum", "ret_sumsq", "ret_min", "ret_max", "gret_sum", "gret_sumsq")]
+
+
 SYMBOLS = {
     "hk_create": (C.c_int, [C.POINTER(Config), C.POINTER(_H)]),
     "hk_destroy": (None, [_H]),
@@ -232,6 +239,13 @@ SYMBOLS = {
     "hk_ppo_normalizer_update": (C.c_int, [_H, C.c_int]),
     "hk_ppo_normalizer_get": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
     "hk_ppo_normalizer_set": (C.c_int, [_H, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "hk_policy_pool_create": (C.c_int, [_H, C.c_int, C.c_int]),
+    "hk_policy_pool_save": (C.c_int, [_H, C.c_int, C.c_int, C.c_int]),
+    "hk_policy_pool_load": (C.c_int, [_H, C.c_int, C.c_int, C.c_int]),
+    "hk_policy_pool_put": (C.c_int, [_H, C.c_int, C.c_int, _fp]),
+    "hk_policy_pool_get": (C.c_int, [_H, C.c_int, C.c_int, _fp]),
+    "hk_policy_pool_count": (C.c_int, [_H, C.c_int]),
+    "hk_rollout_episode_stats": (C.c_int, [_H, C.c_int, C.POINTER(EpisodeStats)]),
     "hk_comm_unique_id": (C.c_int, [C.c_void_p]),
     "hk_comm_init": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
     "hk_gather_results": (C.c_int, [_H, C.POINTER(EpisodeResult)]),

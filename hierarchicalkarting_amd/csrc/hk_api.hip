@@ -16,6 +16,7 @@
 #include "hk_policy.h"
 #include "hk_rollout.h"
 #include "hk_ppo.h"
+#include "hk_selfplay.h"
 #include <dlfcn.h>
 
 namespace hk {
@@ -233,6 +234,26 @@ struct hk_context {
         bool adv_stale = false;        // the policy's statistics changed after hk_ppo_advantages: V_OLD is the critic on other inputs
     } ppo[HK_MAX_POLICIES];
     int n_ppo = 0;
+    // self-play (hk.h "SELF-PLAY"; hk_selfplay.h); nothing is allocated before the first hk_policy_pool_create / hk_rollout_episode_stats
+    struct Pool {
+        int in_dim = 0, stack = 0, hidden = 0, n_layers = 0, n_branch = 0, normalize = 0;    // the SHAPE
+        hk::PpoNet net;                // the flat actor layout (base 0); a slot is net.count floats, then mean, std [in_dim] when normalize
+        int slots = 0;
+        size_t count = 0;              // floats per slot
+        float* buf = nullptr;          // [slots][count]
+        uint64_t filled = 0;           // bit s: slot s has been written
+    } pool[HK_MAX_POOLS];
+    int n_pools = 0;
+    struct Episodes {
+        void* buf = nullptr;           // one allocation: the two carries (ret, gret, len, whole: [E][A] each), the lanes' records [E A], the result [1]
+        hk::EpisodeCarry carry[2] = {};
+        int in = 0;                    // carry[in] is the current rollout's carry-in, carry[in ^ 1] what the statistics write
+        hk_episode_stats* part = nullptr;
+        hk_episode_stats* out = nullptr;
+        bool moved = true;             // an hk_step / hk_reset / hk_set_*_state / hk_policy_attach ran since the last hk_rollout_close
+        int stats_gen[HK_MAX_POLICIES] = {};      // the rollout (Rollout::gen) whose statistics were last computed for the policy
+        bool carry_ok[HK_MAX_POLICIES] = {};      // the open / last rollout began with a carry-in adopted for the policy
+    } ep;
     // RCCL communicator for hk_gather_results (librccl.so loaded lazily)
     void* comm = nullptr;
     int comm_world = 0, comm_rank = 0;
@@ -402,6 +423,8 @@ void hk_destroy(hk_handle h)
     if (h->ro.buf) (void)hipFree(h->ro.buf);
     for (int p = 0; p < HK_MAX_POLICIES; p++) hk::policy_free(h->policy[p]);
     for (auto& t : h->ppo) { if (t.param) (void)hipFree(t.param); if (t.rowbuf) (void)hipFree(t.rowbuf); if (t.ws) (void)hipFree(t.ws); if (t.shadow) (void)hipFree(t.shadow); if (t.norm) (void)hipFree(t.norm); if (t.norm_part) (void)hipFree(t.norm_part); }
+    for (auto& pl : h->pool) if (pl.buf) (void)hipFree(pl.buf);
+    if (h->ep.buf) (void)hipFree(h->ep.buf);
     h->prof.fold();
     for (hipEvent_t e : h->prof.pool) (void)hipEventDestroy(e);
     for (hipStream_t q : h->qstream) if (q) { (void)hipStreamSynchronize(q); (void)hipStreamDestroy(q); }
@@ -523,6 +546,7 @@ int hk_reset(hk_handle h, const int32_t* env_ids, int n, int experiment_num)
 {
     HK_NEED_ENV(h);
     if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_reset: refused while a rollout is open (hk_rollout_close first)");
+    h->ep.moved = true;                         // (the episode statistics' carry ends here: hk.h "SELF-PLAY" CARRY)
     int rc = hk::env_reset(h->dev, h->cfg, env_ids, n, experiment_num, h->stream, h->err);
     if (rc) { g_last_error = h->err; return rc; }
     h->lock_tick = env_ids ? -1 : 0;            // every env stands on episode step 0 again / some do: the field is no longer known to be in lock-step
@@ -1144,6 +1168,7 @@ int hk_step(hk_handle h, int n_ticks)
     HK_NEED_ENV_STEP(h);
     if (n_ticks < 0) return fail(h, HK_ERR_INVALID, "hk_step: n_ticks < 0");
     if (n_ticks == 0) return HK_OK;
+    h->ep.moved = true;                         // (cleared by hk_rollout_close: a step after it ends the episode statistics' carry)
     if (h->n_policies == 0) {
         h->academy_step += n_ticks;
         return step_ticks(h, n_ticks);
@@ -1201,6 +1226,7 @@ int hk_policy_attach(hk_handle h, const hk_policy_desc* desc, const int32_t* age
     }
     if (h->n_policies > 0 && decision_period != h->decision_period)
         return fail(h, HK_ERR_INVALID, "hk_policy_attach: decision_period differs from the policies already attached (DecisionRequester is per handle)");
+    h->ep.moved = true;
     const int idx = h->n_policies;
     rc = hk::policy_upload(h->policy[idx], desc, idx, hk_obs_dim(h), agent_slots, n_slots, h->cfg.num_envs, h->stream, h->err);
     if (rc) { hk::policy_free(h->policy[idx]); g_last_error = h->err; return rc; }
@@ -1315,6 +1341,15 @@ int hk_rollout_begin(hk_handle h, int rows)
     }
     std::memcpy(ro.off, off, sizeof(off));
     ro.R = rows; ro.started = 0; ro.rows = 0; ro.obs_dim = D; ro.nbm = nbm; ro.smax = smax; ro.driven = driven;
+    {   // the episode statistics' carry (hk.h "SELF-PLAY" CARRY): what the statistics of the rollout just closed wrote becomes this one's carry-in
+        auto& ep = h->ep;
+        bool any = false;
+        for (int p = 0; p < HK_MAX_POLICIES; p++) {
+            ep.carry_ok[p] = ep.buf && !ep.moved && ro.gen > 0 && p < ro.npol && ep.stats_gen[p] == ro.gen;
+            any = any || ep.carry_ok[p];
+        }
+        if (any) ep.in ^= 1;
+    }
     ro.gen += 1; ro.npol = h->n_policies;
     HK_HIP(h, hipMemsetAsync(ro.buf, 0, total, h->stream));
     const unsigned long long decision = (unsigned long long)(h->academy_step / h->decision_period);
@@ -1348,6 +1383,7 @@ int hk_rollout_close(hk_handle h)
     int rc = hk::env_launch_observe_quiet(h->dev, h->cfg, ro.driven, ro.at<float>(HK_RO_NEXT_OBS), h->stream, h->err);
     if (rc) { g_last_error = h->err; return rc; }
     ro.open = false;
+    h->ep.moved = false;
     int bad = 0;
     HK_HIP(h, hipMemcpyAsync(&bad, ro.at<int>(HK_RO_FIELDS + 1), sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipStreamSynchronize(h->stream));
@@ -2031,6 +2067,171 @@ int hk_ppo_count(hk_handle h, int trainer, int field)
     return field == HK_PPO_MB_LOGITS ? t.last_m * t.actor.n_branch : t.last_m;
 }
 
+// ------------------------------------------------------------------ self-play (hk.h "SELF-PLAY"; device side of the statistics in hk_selfplay.h)
+extern "C++" {
+namespace {
+
+// pool / slot / policy indices and the policy's shape against the pool's; policy < 0: not checked
+int pool_check(hk_handle h, const char* fn, int pool, int slot, int policy)
+{
+    const std::string f(fn);
+    if (pool < 0 || pool >= h->n_pools) return fail(h, HK_ERR_INVALID, f + ": bad pool index");
+    const auto& pl = h->pool[pool];
+    if (slot < 0 || slot >= pl.slots) return fail(h, HK_ERR_INVALID, f + ": bad slot index");
+    if (policy == -1) return HK_OK;
+    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, f + ": bad policy index");
+    const hk::PolicyParams& q = h->policy[policy].q;
+    if (q.in_dim != pl.in_dim || q.stack != pl.stack || q.hidden != pl.hidden || q.n_layers != pl.n_layers || q.n_branch != pl.n_branch ||
+        (q.normalize != 0) != (pl.normalize != 0))
+        return fail(h, HK_ERR_INVALID, f + ": the policy's shape (in_dim, stack, hidden, n_layers, n_branch, normalize) differs from the pool's");
+    return HK_OK;
+}
+
+inline float* pool_slot(const hk_context::Pool& pl, int slot) { return pl.buf + (size_t)slot * pl.count; }
+
+}  // namespace
+}  // extern "C++"
+
+int hk_policy_pool_create(hk_handle h, int policy, int slots)
+{
+    HK_NEED_ENV(h);
+    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, "hk_policy_pool_create: bad policy index");
+    if (slots < 1 || slots > HK_POOL_MAX_SLOTS) return fail(h, HK_ERR_INVALID, "hk_policy_pool_create: slots outside [1, HK_POOL_MAX_SLOTS]");
+    if (h->n_pools >= HK_MAX_POOLS) return fail(h, HK_ERR_INVALID, "hk_policy_pool_create: HK_MAX_POOLS pools already exist");
+    const hk::PolicyParams& q = h->policy[policy].q;
+    hk_context::Pool pl;
+    pl.in_dim = q.in_dim; pl.stack = q.stack; pl.hidden = q.hidden; pl.n_layers = q.n_layers; pl.n_branch = q.n_branch; pl.normalize = q.normalize != 0;
+    pl.net.layout(q.in_dim, q.hidden, q.n_layers, q.n_branch, 0);
+    pl.slots = slots;
+    pl.count = pl.net.count + (pl.normalize ? 2 * (size_t)q.in_dim : 0);
+    HK_HIP(h, hipMalloc(&pl.buf, (size_t)slots * pl.count * sizeof(float)));
+    h->pool[h->n_pools] = pl;
+    return h->n_pools++;
+}
+
+int hk_policy_pool_count(hk_handle h, int pool)
+{
+    if (!h) return fail(nullptr, HK_ERR_INVALID, "NULL handle");
+    if (pool < 0 || pool >= h->n_pools) return fail(h, HK_ERR_INVALID, "hk_policy_pool_count: bad pool index");
+    return (int)h->pool[pool].count;
+}
+
+int hk_policy_pool_save(hk_handle h, int pool, int slot, int policy)
+{
+    HK_NEED_ENV(h);
+    if (policy == -1) policy = -2;
+    int rc = pool_check(h, "hk_policy_pool_save", pool, slot, policy);
+    if (rc) return rc;
+    auto& pl = h->pool[pool];
+    const hk::PolicyParams& q = h->policy[policy].q;
+    float* dst = pool_slot(pl, slot);
+    hipLaunchKernelGGL(hk::ppo_publish_kernel<false>, dim3(nblk(pl.net.count)), dim3(256), 0, h->stream, q, pl.net, dst);
+    HK_HIP(h, hipGetLastError());
+    if (pl.normalize) {
+        const size_t nb = (size_t)pl.in_dim * sizeof(float);
+        HK_HIP(h, hipMemcpyAsync(dst + pl.net.count, q.mean, nb, hipMemcpyDeviceToDevice, h->stream));
+        HK_HIP(h, hipMemcpyAsync(dst + pl.net.count + pl.in_dim, q.std, nb, hipMemcpyDeviceToDevice, h->stream));
+    }
+    pl.filled |= 1ull << slot;
+    return HK_OK;
+}
+
+int hk_policy_pool_load(hk_handle h, int pool, int slot, int policy)
+{
+    HK_NEED_ENV(h);
+    if (policy == -1) policy = -2;
+    int rc = pool_check(h, "hk_policy_pool_load", pool, slot, policy);
+    if (rc) return rc;
+    const auto& pl = h->pool[pool];
+    if (!((pl.filled >> slot) & 1ull)) return fail(h, HK_ERR_INVALID, "hk_policy_pool_load: the slot has never been written (hk_policy_pool_save / hk_policy_pool_put)");
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_policy_pool_load: refused while a rollout is open (hk_rollout_close first)");
+    for (int i = 0; i < h->n_ppo; i++)
+        if (h->ppo[i].policy == policy)
+            return fail(h, HK_ERR_INVALID, "hk_policy_pool_load: the policy has a PPO trainer (its master weights would disagree with what plays)");
+    hk::PolicyDevice& pd = h->policy[policy];
+    float* src = pool_slot(pl, slot);
+    hipLaunchKernelGGL(hk::ppo_publish_kernel<true>, dim3(nblk(pl.net.count)), dim3(256), 0, h->stream, pd.q, pl.net, src);
+    HK_HIP(h, hipGetLastError());
+    if (pl.normalize) {
+        const size_t nb = (size_t)pl.in_dim * sizeof(float);
+        HK_HIP(h, hipMemcpyAsync(const_cast<float*>(pd.q.mean), src + pl.net.count, nb, hipMemcpyDeviceToDevice, h->stream));
+        HK_HIP(h, hipMemcpyAsync(const_cast<float*>(pd.q.std), src + pl.net.count + pl.in_dim, nb, hipMemcpyDeviceToDevice, h->stream));
+    }
+    // the bf16 inference copies, when the policy has them: rebuilt from the fp32 copies just written, whichever precision the policy is in now
+    if (pd.wbf) HK_HIP(h, hk::policy_bf16_refresh(pd.q, pd.bq, h->stream));
+    return HK_OK;
+}
+
+int hk_policy_pool_put(hk_handle h, int pool, int slot, const float* flat)
+{
+    HK_NEED_ENV(h);
+    int rc = pool_check(h, "hk_policy_pool_put", pool, slot, -1);
+    if (rc) return rc;
+    if (!flat) return fail(h, HK_ERR_INVALID, "hk_policy_pool_put: NULL pointer");
+    auto& pl = h->pool[pool];
+    HK_HIP(h, hipMemcpyAsync(pool_slot(pl, slot), flat, pl.count * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HK_HIP(h, hipStreamSynchronize(h->stream));          // (the host array is the caller's)
+    pl.filled |= 1ull << slot;
+    return HK_OK;
+}
+
+int hk_policy_pool_get(hk_handle h, int pool, int slot, float* flat)
+{
+    HK_NEED_ENV(h);
+    int rc = pool_check(h, "hk_policy_pool_get", pool, slot, -1);
+    if (rc) return rc;
+    if (!flat) return fail(h, HK_ERR_INVALID, "hk_policy_pool_get: NULL pointer");
+    const auto& pl = h->pool[pool];
+    if (!((pl.filled >> slot) & 1ull)) return fail(h, HK_ERR_INVALID, "hk_policy_pool_get: the slot has never been written");
+    HK_HIP(h, hipMemcpyAsync(flat, pool_slot(pl, slot), pl.count * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HK_HIP(h, hipStreamSynchronize(h->stream));
+    return HK_OK;
+}
+
+int hk_rollout_episode_stats(hk_handle h, int policy, hk_episode_stats* out)
+{
+    HK_NEED_ENV(h);
+    const auto& ro = h->ro;
+    const char* fn = "hk_rollout_episode_stats";
+    if (!out) return fail(h, HK_ERR_INVALID, std::string(fn) + ": NULL pointer");
+    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, std::string(fn) + ": bad policy index");
+    if (!h->cfg.rewards) return fail(h, HK_ERR_INVALID, std::string(fn) + ": hk_config.rewards == 0 (the rows carry no rewards)");
+    if (ro.open) return fail(h, HK_ERR_INVALID, std::string(fn) + ": refused while a rollout is open (hk_rollout_close first)");
+    if (ro.R == 0 || !ro.buf) return fail(h, HK_ERR_INVALID, std::string(fn) + ": no rollout yet (hk_rollout_begin ... hk_rollout_close)");
+    if (ro.rows < 1) return fail(h, HK_ERR_INVALID, std::string(fn) + ": the rollout closed with no completed row");
+    if (policy >= ro.npol) return fail(h, HK_ERR_INVALID, std::string(fn) + ": the rollout began before the policy was attached");
+    auto& ep = h->ep;
+    const int E = h->cfg.num_envs, A = h->cfg.num_agents;
+    const size_t ea = (size_t)E * A;
+    if (!ep.buf) {
+        const size_t carry_bytes = (4 * ea * 4 + 255) & ~(size_t)255;
+        const size_t total = 2 * carry_bytes + (ea + 1) * sizeof(hk_episode_stats);
+        HK_HIP(h, hipMalloc(&ep.buf, total));
+        HK_HIP(h, hipMemsetAsync(ep.buf, 0, total, h->stream));
+        for (int k = 0; k < 2; k++) {
+            float* f = (float*)((char*)ep.buf + k * carry_bytes);
+            ep.carry[k] = hk::EpisodeCarry{f, f + ea, (int*)(f + 2 * ea), (int*)(f + 3 * ea)};
+        }
+        ep.part = (hk_episode_stats*)((char*)ep.buf + 2 * carry_bytes);
+        ep.out = ep.part + ea;
+    }
+    const hk::PolicyParams& q = h->policy[policy].q;
+    hk::EpisodeRows P{};
+    P.reward = ro.at<float>(HK_RO_REWARD); P.group_reward = ro.at<float>(HK_RO_GROUP_REWARD);
+    P.term_reward = ro.at<float>(HK_RO_TERM_REWARD); P.term_group = ro.at<float>(HK_RO_TERM_GROUP_REWARD);
+    P.done = ro.at<int>(HK_RO_DONE);
+    P.R = ro.rows; P.E = E; P.A = A; P.S = q.n_slots;
+    for (int j = 0; j < HK_MAX_AGENTS; j++) P.slots[j] = q.slots[j];
+    const int lanes = E * q.n_slots;
+    hipLaunchKernelGGL(hk::episode_scan_kernel, dim3(nblk(lanes)), dim3(256), 0, h->stream, P, ep.carry[ep.in], ep.carry_ok[policy] ? 1 : 0, ep.carry[ep.in ^ 1], ep.part);
+    hipLaunchKernelGGL(hk::episode_combine_kernel, dim3(1), dim3(hk::EPISODE_COMBINE_THREADS), 0, h->stream, ep.part, lanes, ep.out);
+    HK_HIP(h, hipGetLastError());
+    HK_HIP(h, hipMemcpyAsync(out, ep.out, sizeof(hk_episode_stats), hipMemcpyDeviceToHost, h->stream));
+    HK_HIP(h, hipStreamSynchronize(h->stream));
+    ep.stats_gen[policy] = ro.gen;
+    return HK_OK;
+}
+
 int hk_obs_dim(hk_handle h)
 {
     if (!h || !h->env_ready) return HK_ERR_INVALID;
@@ -2094,6 +2295,7 @@ int hk_set_agent_state(hk_handle h, const hk_agent_state* in)
                 return fail(h, HK_ERR_INVALID, "hk_set_agent_state: section_index / init_checkpoint_index out of range (negative, or beyond 2^32 / num_sections)");
     }
     h->dev.P.hold_dedupe = 0;          // the host moves karts by hand: a held kart is no longer guaranteed to be where its last solve saw it
+    h->ep.moved = true;
     HK_HIP(h, hipMemcpyAsync(h->dev.agents, in, cnt * sizeof(hk_agent_state), hipMemcpyHostToDevice, h->stream));
     { int rc = hk::ga_ops(h->dev).launch_hot_scatter(h->dev, h->cfg, h->stream, h->err); if (rc) { g_last_error = h->err; return rc; } }
     { int rc = hk::env_mcts_invalidate(h->dev, h->cfg, h->stream, h->err); if (rc) { g_last_error = h->err; return rc; } }   // plans were rewritten
@@ -2119,6 +2321,7 @@ int hk_set_env_state(hk_handle h, const hk_env_state* in)
     if (!in) return fail(h, HK_ERR_INVALID, "NULL pointer");
     h->dev.P.hold_dedupe = 0;          // (as hk_set_agent_state: episode_steps may be rewound into a hold whose solves were skipped)
     h->lock_tick = -1;                 // (the host wrote episode steps)
+    h->ep.moved = true;
     HK_HIP(h, hipMemcpyAsync(h->dev.envs_stage, in, (size_t)h->cfg.num_envs * sizeof(hk_env_state), hipMemcpyHostToDevice, h->stream));
     { int rc = hk::ga_ops(h->dev).launch_envs_scatter(h->dev, h->cfg, h->stream, h->err); if (rc) { g_last_error = h->err; return rc; } }   // (progress words sanitized on the way)
     HK_HIP(h, hipStreamSynchronize(h->stream));

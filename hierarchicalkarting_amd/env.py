@@ -7,6 +7,8 @@ RacingEnv  <->  RacingEnvController (+ its KartAgents / ArcadeKarts), E independ
     set_actions(steer, branch)       KartAgent.OnActionReceived (KA:440-478) for LowMode == RL agents
     attach_policy(policy, slots)     BehaviorParameters.Model: the ML-Agents actor runs on device every DecisionPeriod ticks
     rollout_begin / rollout_close    record what the attached actors did (obs, actions, log-probs, rewards) on the device
+    episode_stats(policy)            returns, lengths, wins / draws / losses of the closed rollout's episodes, reduced on the device
+    snapshot_pool(policy, slots)     device slots of saved actors; load one into an attached policy (self-play opponent swaps)
     ppo_trainer(policy)              PPO on the recorded rows, on the device (ppo.PPOTrainer)
     agent_state() / set_agent_state  snapshot / restore of every KartAgent + ArcadeKart + Rigidbody field
     episode_results()                TelemetryViewer quantities of the last finished episode
@@ -132,6 +134,8 @@ class RacingEnv:
         if rc < 0:
             self._ck(rc)
         self._policies = getattr(self, "_policies", []) + [policy]
+        self._policy_slots = getattr(self, "_policy_slots", []) + [[int(a) for a in slots]]
+        self._decision_period = int(decision_period)
         if precision != "f32":
             self.policy_set_precision(rc, precision)
         return rc
@@ -302,6 +306,18 @@ class RacingEnv:
                 _lib.copy_device_to_host(a.ctypes.data, ptr, a.nbytes)
             out[name] = a
         return out
+
+    def episode_stats(self, policy_index):
+        """-> dict of hk_episode_stats: episodes, partial, wins, draws, losses, timeouts, len_sum (ints), ret_sum, ret_sumsq, ret_min, ret_max,
+        gret_sum, gret_sumsq (floats) of the closed rollout's completed rows, over the agent slots of the policy (hk.h "SELF-PLAY")"""
+        st = _lib.EpisodeStats()
+        self._ck(self.L.hk_rollout_episode_stats(self.h, int(policy_index), C.byref(st)))
+        return {n: getattr(st, n) for n, _ in _lib.EpisodeStats._fields_}
+
+    def snapshot_pool(self, policy_index, slots):
+        """-> selfplay.SnapshotPool of the policy's shape (hk_policy_pool_create)"""
+        from .selfplay import SnapshotPool
+        return SnapshotPool(self, policy_index, slots)
 
     def ppo_trainer(self, policy_index, critic=None, **cfg):
         """-> ppo.PPOTrainer of an attached policy (hk_ppo_create): it trains on this handle's closed rollouts and publishes into the policy"""

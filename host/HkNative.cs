@@ -21,6 +21,7 @@ namespace KartGame.AI.Native
         public const int HK_COMM_ID_BYTES = 128;
         public const int HK_PROF_STAGES = 6;
         public const int HK_METER_PARTS = 4;
+        public const int HK_MAX_POOLS = 8, HK_POOL_MAX_SLOTS = 64;
         // hk_rollout_field: the buffers of the rollout recorder (hk_rollout_ptr)
         public const int HK_RO_OBS = 0, HK_RO_FIRST = 1, HK_RO_STEER = 2, HK_RO_BRANCH = 3, HK_RO_RAW = 4, HK_RO_MU = 5, HK_RO_LOGITS = 6,
                          HK_RO_LOGP_CONT = 7, HK_RO_LOGP_DISC = 8, HK_RO_REWARD = 9, HK_RO_GROUP_REWARD = 10, HK_RO_TERM_REWARD = 11,
@@ -369,6 +370,25 @@ namespace KartGame.AI.Native
         public uint seed;
     }
 
+    // hk_episode_stats: returns, lengths and outcomes of the closed rollout's episodes (hk.h "SELF-PLAY")
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HkEpisodeStats
+    {
+        public long episodes;
+        public long partial;
+        public long wins;
+        public long draws;
+        public long losses;
+        public long timeouts;
+        public long len_sum;
+        public double ret_sum;
+        public double ret_sumsq;
+        public double ret_min;
+        public double ret_max;
+        public double gret_sum;
+        public double gret_sumsq;
+    }
+
     public static unsafe class Hk
     {
         const string Lib = "hk";   // libhk.so next to the player binary / in Assets/Plugins/x86_64
@@ -442,6 +462,14 @@ namespace KartGame.AI.Native
         [DllImport(Lib)] public static extern int hk_ppo_normalizer_update(IntPtr h, int trainer);
         [DllImport(Lib)] public static extern int hk_ppo_normalizer_get(IntPtr h, int trainer, long* steps, double* mean, double* m2);
         [DllImport(Lib)] public static extern int hk_ppo_normalizer_set(IntPtr h, int trainer, long steps, double* mean, double* m2);
+        // self-play (hk.h "SELF-PLAY"): device slots of saved actors, loaded into an attached opponent; episode statistics of the closed rollout
+        [DllImport(Lib)] public static extern int hk_policy_pool_create(IntPtr h, int policy, int slots);
+        [DllImport(Lib)] public static extern int hk_policy_pool_save(IntPtr h, int pool, int slot, int policy);
+        [DllImport(Lib)] public static extern int hk_policy_pool_load(IntPtr h, int pool, int slot, int policy);
+        [DllImport(Lib)] public static extern int hk_policy_pool_put(IntPtr h, int pool, int slot, float* flat);
+        [DllImport(Lib)] public static extern int hk_policy_pool_get(IntPtr h, int pool, int slot, float* flat);
+        [DllImport(Lib)] public static extern int hk_policy_pool_count(IntPtr h, int pool);
+        [DllImport(Lib)] public static extern int hk_rollout_episode_stats(IntPtr h, int policy, HkEpisodeStats* stats);
         // multi-GPU: one process per GPU, envs sharded by HkConfig.env_id_base; the only exchange is this all-gather over RCCL
         [DllImport(Lib)] public static extern int hk_comm_unique_id(byte* id128);
         [DllImport(Lib)] public static extern int hk_comm_init(IntPtr h, int worldSize, int rank, byte* id128);

@@ -618,7 +618,7 @@ void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* 
  * next rollout on, rho == 1 and the bit-equal training forward hold as above, in both precisions.  A dimension that never varies keeps M2_k at its
  * initial value, so its std shrinks as 1 / sqrt(N): ML-Agents' behaviour, not guarded.
  * HK_PPO_NORM_MEAN / HK_PPO_NORM_STD (hk_ppo_ptr): the policy's published fp32 statistics themselves, [in_dim]; count 0 on normalize == 0.
- * Out of scope: self-play opponent swaps and ELO, POCA and group rewards, LSTM memory, a normaliser for policies attached with normalize == 0,
+ * Out of scope (self-play opponent swaps, episode statistics and ELO: "SELF-PLAY" below): POCA and group rewards, LSTM memory, a normaliser for policies attached with normalize == 0,
  * gradient clipping, multi-GPU gradient all-reduce and bf16 optimiser state.  Everything is asynchronous on hk_stream unless noted. */
 #define HK_PPO_STATS 6
 typedef struct hk_ppo_config {
@@ -655,6 +655,64 @@ int hk_ppo_normalizer_init(hk_handle h, int trainer, int64_t steps);
 int hk_ppo_normalizer_update(hk_handle h, int trainer);
 int hk_ppo_normalizer_get(hk_handle h, int trainer, int64_t* steps, double* mean /*[in_dim]*/, double* m2 /*[in_dim]*/);
 int hk_ppo_normalizer_set(hk_handle h, int trainer, int64_t steps, const double* mean /*[in_dim]*/, const double* m2 /*[in_dim]*/);
+
+/* ---- SELF-PLAY: snapshot pool, opponent swaps, episode statistics of a closed rollout -------------------------------------
+ * What ML-Agents' `self_play:` block needs of the library; the driver (window, save_steps / swap_steps, ELO, the linear schedules) is host
+ * code: hierarchicalkarting_amd/selfplay.py.  Everything here is opt-in: a handle that never calls these entry points computes what it
+ * computed, bit for bit, and allocates nothing.
+ * SNAPSHOT POOL.  A pool is `slots` device slots of one SHAPE — in_dim, stack, hidden, n_layers, n_branch and normalize of the policy it was
+ * created from.  A slot holds one actor: its flat fp32 parameters in the trainer's torch layout (the actor part of HK_PPO_PARAMS: W[0], b[0],
+ * ..., W_mu, b_mu, log_sigma, W_branch, b_branch), followed for a normalize == 1 shape by mean [in_dim] and std [in_dim], the published fp32
+ * statistics: hk_policy_pool_count floats.  seed, deterministic, the agent slots, the observation ring and the precision belong to the
+ * attached policy and are never touched by a load.
+ *   hk_policy_pool_create   -> pool index (up to HK_MAX_POOLS per handle); 1 <= slots <= HK_POOL_MAX_SLOTS
+ *   hk_policy_pool_save     the policy's CURRENT fp32 inference copies and published statistics -> slot; asynchronous on hk_stream
+ *   hk_policy_pool_load     slot -> the policy's inference copies (the transposed weights, the group-major copy, biases, heads), its mean / std,
+ *                           and its bf16 copies if they exist (rebuilt from the fp32 copies just written, as hk_ppo_publish does); asynchronous.
+ *                           Every consumer follows: hk_step's decisions, hk_policy_forward, both precisions.
+ *   hk_policy_pool_put / _get   a slot from / to a host array of hk_policy_pool_count floats (both synchronise)
+ * Refused with HK_ERR_INVALID and a message, state as it was: a bad pool, slot or policy index; a policy whose shape differs from the pool's;
+ * a load or get of a slot never written; a load while a rollout is open (the rows of one rollout come from one chain); a load into a policy
+ * that has a PPO trainer (its master weights would silently disagree with what plays: train the learner, swap the opponent); a NULL host pointer.
+ * EPISODE STATISTICS (hk_rollout_episode_stats; synchronises) of the COMPLETED rows of the closed rollout, over the agent slots (e, j) of
+ * `policy`.  Per (e, j), t ascending, every operation one fp32 operation (no fused multiply-add), so a numpy fp32 loop restates it bit for bit:
+ *   acc = carry_ret; gacc = carry_gret; len = carry_len           (0 where there is no valid carry)
+ *   row t, DONE == 0:  acc += REWARD; gacc += GROUP_REWARD; len += 1
+ *   row t, DONE != 0:  acc += TERM_REWARD; gacc += TERM_GROUP_REWARD; len += 1;  EMIT(acc, gacc, len, DONE, f);
+ *                      acc = REWARD; gacc = GROUP_REWARD; len = 0   (the part after the reset belongs to the new episode)
+ *   f = TERM_REWARD + TERM_GROUP_REWARD of that row (one fp32 add): f > 0 a win, f < 0 a loss, anything else a draw (+0, -0, an exact
+ *   cancellation and a NaN are draws).  DONE == 2 (the time-out) is an episode end like any other and is also tallied in timeouts.
+ * This is the outcome rule of ML-Agents 2.0.1's ghost trainer as the maintainers read it (the last step's reward plus group reward; every episode
+ * end of the reference is EndGroupEpisode, never an interruption).  mlagents was not available to compare against: the rules written here are the contract.
+ * An emitted episode whose beginning lies before the rollout with no valid carry is counted in `partial` and nowhere else.  len_sum is in
+ * decisions; ret_* (acc) and gret_* (gacc) are over the emitted, non-partial episodes, summed across episodes in fp64: each lane keeps its own
+ * partial record, one workgroup combines the records in (e, j) order — no float atomics, the same call gives the same bits.  ret_min / ret_max
+ * are +inf / -inf when episodes == 0.
+ * CARRY.  The call is idempotent: it reads a carry-in and writes a carry-out (acc, gacc, len per [E][A], and whether that episode began inside
+ * the chain).  hk_rollout_begin adopts the carry-out as the new rollout's carry-in for a policy only if the previous rollout's statistics were
+ * computed for that policy and no hk_step, hk_reset, hk_set_agent_state, hk_set_env_state or hk_policy_attach ran between that close and this
+ * begin; otherwise the carry is cleared.  The adoption is host code.  A carried episode that began before the first rollout of such a chain
+ * stays partial when it ends, in whichever rollout that is.
+ * Refused with HK_ERR_INVALID: no closed rollout with a completed row, a rollout open, a bad policy index (or one attached after the rollout
+ * began), out == NULL, hk_config.rewards == 0.
+ * ELO (host code, selfplay.elo_apply): ML-Agents applies each finished episode's own result in arrival order.  Thousands of episodes end together
+ * here and have no order, so a rollout's W wins, D draws and L losses are applied as n = W + D + L sequential steps of the MEAN result
+ * s = (W + D / 2) / n: change = k (s - 1 / (1 + 10^((r_opp - r_learner) / 400))), r_learner += change, r_opp -= change.  Order-free, equal to
+ * ML-Agents' sequence when all results agree, and self-limiting where a one-shot change of n (s - e) would move ratings by thousands of points.
+ * Out of scope: team_change (a trainer is bound to one policy), per-env opponents, POCA and LSTM. */
+#define HK_MAX_POOLS 8
+#define HK_POOL_MAX_SLOTS 64
+int hk_policy_pool_create(hk_handle h, int policy, int slots);
+int hk_policy_pool_save(hk_handle h, int pool, int slot, int policy);
+int hk_policy_pool_load(hk_handle h, int pool, int slot, int policy);
+int hk_policy_pool_put(hk_handle h, int pool, int slot, const float* flat /*host [hk_policy_pool_count]*/);
+int hk_policy_pool_get(hk_handle h, int pool, int slot, float* flat /*host [hk_policy_pool_count]*/);
+int hk_policy_pool_count(hk_handle h, int pool);       /* floats per slot (>= 0), or a negative hk_status */
+typedef struct hk_episode_stats {
+    int64_t episodes, partial, wins, draws, losses, timeouts, len_sum;
+    double ret_sum, ret_sumsq, ret_min, ret_max, gret_sum, gret_sumsq;
+} hk_episode_stats;
+int hk_rollout_episode_stats(hk_handle h, int policy, hk_episode_stats* out);
 
 /* ---- multi-GPU: the path's ONE exchange step ---------------------------------------------------------------
  * Race instances are independent (one RacingEnvController owns its own Agents[] / Sections[], REC:46-52): every rank steps its

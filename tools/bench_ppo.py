@@ -3,7 +3,9 @@
 DecisionPeriod 2, rewards on): one rollout of R rows is collected (timed), then for team 0's trainer (critic 312 -> 256 x 3):
 hk_ppo_advantages, one-epoch hk_ppo_update calls at minibatch 512 (ML-Agents' batch_size) and at a GPU-sized minibatch, and
 hk_ppo_normalizer_update (normalizer_ms; the state is put back after every call, which republishes the attached statistics bit for bit, so
-the other timings run on what they always ran on); every timing ends in a device synchronise, medians of --repeats.  One JSON line per --precision; with several, the precisions alternate round by round
+the other timings run on what they always ran on), and the self-play facilities on the same rollout: hk_rollout_episode_stats of team 0
+(episode_stats_ms), hk_policy_pool_save of team 0's actor into a pool slot and hk_policy_pool_load of that slot into team 1's actor, which has
+no trainer (pool_save_ms, pool_load_ms; the load runs last, after every other timing); every timing ends in a device synchronise, medians of --repeats.  One JSON line per --precision; with several, the precisions alternate round by round
 (after a switch: advantages and one untimed update at the large minibatch, which allocate the workspace of that precision).
 FLOP count per trained row (stated, not measured): forward + backward of actor and critic = 3 x forward, forward = 2 x (weights of the trunks
 and heads) per row: 3 x 2 x (312 x 256 + 2 x 256 x 256 + 4 x 256 + 312 x 256 + 2 x 256 x 256 + 256) = 6 x 423 168 = 2.54 MFLOP per row at this shape."""
@@ -67,6 +69,16 @@ def main():
         env.synchronize()
         return (time.perf_counter() - t) * 1e3
 
+    # what hk_rollout_episode_stats reads, once each: REWARD, GROUP_REWARD, TERM_REWARD, TERM_GROUP_REWARD of the policy's slots [R][E][S], DONE [R][E]
+    stats_bytes = 4 * (4 * R * E * S + R * E)
+    pool = env.snapshot_pool(0, 2)
+    pool_bytes = 4 * pool.count
+    env.episode_stats(0)                                 # (allocates; first launches)
+    pool.save(0)
+    sp_runs = {"stats": [], "save": []}
+    for _ in range(a.repeats):
+        sp_runs["stats"].append(timed(lambda: env.episode_stats(0)))
+        sp_runs["save"].append(timed(lambda: pool.save(0)))
     for _ in range(a.repeats):
         for prec in a.precision:
             tr.set_precision(prec)
@@ -77,7 +89,12 @@ def main():
                 runs[prec][mb].append(timed(lambda: tr.update(1, mb, 1e-5, 0.2, 5e-3)))
             runs[prec]["norm"].append(timed(tr.normalizer_update))
             tr.normalizer_load(*norm_state)
+    sp_runs["load"] = [timed(lambda: pool.load(0, 1)) for _ in range(a.repeats + 1)][1:]       # (the first call is the warm-up)
     env.close()
+    selfplay = {"episode_stats_ms": statistics.median(sp_runs["stats"]), "episode_stats_runs": sp_runs["stats"], "episode_stats_bytes": stats_bytes,
+                "episode_stats_hbm_fraction": stats_bytes / (statistics.median(sp_runs["stats"]) * 1e-3) / (PEAK_HBM_TB * 1e12),
+                "pool_save_ms": statistics.median(sp_runs["save"]), "pool_save_runs": sp_runs["save"],
+                "pool_load_ms": statistics.median(sp_runs["load"]), "pool_load_runs": sp_runs["load"], "pool_slot_bytes": pool_bytes}
     for prec in a.precision:
         res = {}
         for mb in sorted(sizes):
@@ -90,7 +107,7 @@ def main():
                           "advantages_ms": statistics.median(runs[prec]["adv"]), "advantages_runs": runs[prec]["adv"], "collect_ms": collect_ms,
                           "normalizer_ms": statistics.median(runs[prec]["norm"]), "normalizer_runs": runs[prec]["norm"], "normalizer_bytes": norm_bytes,
                           "normalizer_hbm_fraction": norm_bytes / (statistics.median(runs[prec]["norm"]) * 1e-3) / (PEAK_HBM_TB * 1e12),
-                          "minibatch": res, "config": {"envs": E, "agents": A, "rows": R, "n_rows": n, "flop_per_row": flop_row,
+                          **selfplay, "minibatch": res, "config": {"envs": E, "agents": A, "rows": R, "n_rows": n, "flop_per_row": flop_row,
                                                        "peak_tflops": PEAK_TF[prec]}}))
 
 
