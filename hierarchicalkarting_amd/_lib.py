@@ -33,12 +33,13 @@ RO_FIELDS = {n: (i, dt) for i, (n, dt) in enumerate([
 HK_RO_FIELDS = len(RO_FIELDS)
 # PPO trainer (hk_ppo_field): name -> index;  stats of hk_ppo_minibatch / hk_ppo_update
 PPO_FIELDS = {n: i for i, n in enumerate(("params", "grad", "adam_m", "adam_v", "v_old", "adv", "ret", "mb_mu", "mb_logits", "mb_value", "perm", "shadow",
-                                               "norm_mean", "norm_std"))}
+                                               "norm_mean", "norm_std", "clip"))}
 HK_PPO_FIELDS = len(PPO_FIELDS)
 HK_PPO_STATS = 6
 HK_PPO_PREC_F32, HK_PPO_PREC_BF16 = 0, 1
 HK_POLICY_PREC_F32, HK_POLICY_PREC_BF16 = 0, 1
 PPO_STAT_NAMES = ("L_pi", "L_v", "entropy", "approx_kl", "clip_fraction", "skipped")
+PPO_CLIP_NAMES = ("norm", "coef", "steps", "clipped", "nonfinite", "norm_sum", "norm_max", "reserved")      # the HK_PPO_CLIP words (hk.h "LONG RUNS")
 HK_F_ACCEL, HK_F_BRAKE, HK_F_ACTIVE, HK_F_FORWARD_COLLISION, HK_F_HAS_COLLISION, HK_F_CAN_MOVE, HK_F_ENABLED = (1 << i for i in range(7))
 
 
@@ -177,6 +178,16 @@ class PpoConfig(C.Structure):
                 ("adam_beta2", C.c_float), ("adam_eps", C.c_float), ("seed", C.c_uint32)]
 
 
+class PpoUpdateOpts(C.Structure):
+    _fields_ = [("epochs", C.c_int32), ("minibatch", C.c_int32), ("lr", C.c_float), ("eps", C.c_float), ("beta", C.c_float),
+                ("max_grad_norm", C.c_float), ("target_kl", C.c_float), ("reserved", C.c_int32)]
+
+
+class PpoUpdateReport(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("epochs_run", "minibatches_run", "stopped_by_kl", "clipped_steps", "nonfinite_steps", "reserved")] + [
+        (n, C.c_double) for n in ("last_epoch_kl", "grad_norm_mean", "grad_norm_max")]
+
+
 class EpisodeStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("episodes", "partial", "wins", "draws", "losses", "timeouts", "len_sum")] + [
         (n, C.c_double) for n in ("ret_sum", "ret_sumsq", "ret_min", "ret_max", "gret_sum", "gret_sumsq")]
@@ -239,6 +250,10 @@ SYMBOLS = {
     "hk_ppo_normalizer_update": (C.c_int, [_H, C.c_int]),
     "hk_ppo_normalizer_get": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
     "hk_ppo_normalizer_set": (C.c_int, [_H, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "hk_ppo_update_opt": (C.c_int, [_H, C.c_int, C.POINTER(PpoUpdateOpts), _fp, C.POINTER(PpoUpdateReport)]),
+    "hk_ppo_adam_clipped": (C.c_int, [_H, C.c_int, C.c_float, C.c_float]),
+    "hk_ppo_get_counters": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "hk_ppo_set_counters": (C.c_int, [_H, C.c_int, C.c_int64, C.c_int64]),
     "hk_policy_pool_create": (C.c_int, [_H, C.c_int, C.c_int]),
     "hk_policy_pool_save": (C.c_int, [_H, C.c_int, C.c_int, C.c_int]),
     "hk_policy_pool_load": (C.c_int, [_H, C.c_int, C.c_int, C.c_int]),
@@ -298,3 +313,12 @@ def copy_device_to_host(dst, src, nbytes):
     rc = f(C.c_void_p(dst), C.c_void_p(src), C.c_size_t(nbytes), 2)      # hipMemcpyDeviceToHost
     if rc != 0:
         raise RuntimeError("hipMemcpy (device -> host) failed: hipError_t %d" % rc)
+
+
+def copy_host_to_device(dst, src, nbytes):
+    """hipMemcpy host -> device, through the same runtime as copy_device_to_host"""
+    f = load().hipMemcpy
+    f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    rc = f(C.c_void_p(dst), C.c_void_p(src), C.c_size_t(nbytes), 1)      # hipMemcpyHostToDevice
+    if rc != 0:
+        raise RuntimeError("hipMemcpy (host -> device) failed: hipError_t %d" % rc)

@@ -232,6 +232,8 @@ struct hk_context {
         double* norm_part = nullptr;   // an update's per-workgroup partials [norm_part_wg][2 in_dim + stack]
         int norm_part_wg = 0;
         bool adv_stale = false;        // the policy's statistics changed after hk_ppo_advantages: V_OLD is the critic on other inputs
+        double* clip = nullptr;        // hk.h "LONG RUNS" (nothing before the first clip-aware step): the HK_PPO_CLIP words [8], then the norm's partials [clip_parts]
+        int clip_parts = 0;
     } ppo[HK_MAX_POLICIES];
     int n_ppo = 0;
     // self-play (hk.h "SELF-PLAY"; hk_selfplay.h); nothing is allocated before the first hk_policy_pool_create / hk_rollout_episode_stats
@@ -422,7 +424,7 @@ void hk_destroy(hk_handle h)
     if (h->pol_scratch) (void)hipFree(h->pol_scratch);
     if (h->ro.buf) (void)hipFree(h->ro.buf);
     for (int p = 0; p < HK_MAX_POLICIES; p++) hk::policy_free(h->policy[p]);
-    for (auto& t : h->ppo) { if (t.param) (void)hipFree(t.param); if (t.rowbuf) (void)hipFree(t.rowbuf); if (t.ws) (void)hipFree(t.ws); if (t.shadow) (void)hipFree(t.shadow); if (t.norm) (void)hipFree(t.norm); if (t.norm_part) (void)hipFree(t.norm_part); }
+    for (auto& t : h->ppo) { if (t.param) (void)hipFree(t.param); if (t.rowbuf) (void)hipFree(t.rowbuf); if (t.ws) (void)hipFree(t.ws); if (t.shadow) (void)hipFree(t.shadow); if (t.norm) (void)hipFree(t.norm); if (t.norm_part) (void)hipFree(t.norm_part); if (t.clip) (void)hipFree(t.clip); }
     for (auto& pl : h->pool) if (pl.buf) (void)hipFree(pl.buf);
     if (h->ep.buf) (void)hipFree(h->ep.buf);
     h->prof.fold();
@@ -1634,15 +1636,35 @@ int ppo_mb(hk_handle h, hk_context::Ppo& t, const int32_t* ids, int m, float eps
     return HK_OK;
 }
 
-int ppo_adam_step(hk_handle h, hk_context::Ppo& t, float lr)
+// the HK_PPO_CLIP words and the partials of the norm, allocated (and zeroed) by the first clip-aware step
+int ppo_ensure_clip(hk_handle h, hk_context::Ppo& t)
 {
+    if (t.clip) return HK_OK;
+    const int parts = (int)((t.P + hk::PPO_GN_RUN - 1) / hk::PPO_GN_RUN);
+    HK_HIP(h, hipMalloc(&t.clip, (size_t)(8 + parts) * sizeof(double)));
+    t.clip_parts = parts;
+    HK_HIP(h, hipMemsetAsync(t.clip, 0, (size_t)(8 + parts) * sizeof(double), h->stream));
+    return HK_OK;
+}
+
+// one Adam step from GRAD; max_norm > 0: the clip-aware step of hk.h "LONG RUNS" (the norm's partials, then norm, coef and the step in one kernel)
+int ppo_adam_step(hk_handle h, hk_context::Ppo& t, float lr, float max_norm = 0.0f)
+{
+    if (max_norm > 0.0f) { int rc = ppo_ensure_clip(h, t); if (rc) return rc; }
     t.adam_steps += 1;
     const float b1 = t.cfg.adam_beta1, b2 = t.cfg.adam_beta2;
     const float omb1 = (float)(1.0 - (double)b1), omb2 = (float)(1.0 - (double)b2);
     const float c1 = (float)(1.0 - std::pow((double)b1, t.adam_steps)), c2 = (float)(1.0 - std::pow((double)b2, t.adam_steps));
     float* p = t.param;
-    hipLaunchKernelGGL(hk::ppo_adam_kernel, dim3(nblk(t.P)), dim3(256), 0, h->stream, p, p + t.P, p + 2 * t.P, p + 3 * t.P, t.P, b1, omb1, b2, omb2, c1, c2,
-                       t.cfg.adam_eps, lr);
+    if (max_norm > 0.0f) {
+        double* part = t.clip + 8;
+        hipLaunchKernelGGL(hk::ppo_gradnorm_partial_kernel, dim3(t.clip_parts), dim3(256), 0, h->stream, p + t.P, t.P, part);
+        hipLaunchKernelGGL(hk::ppo_adam_clip_kernel, dim3(nblk(t.P)), dim3(256), 0, h->stream, p, p + t.P, p + 2 * t.P, p + 3 * t.P, t.P, b1, omb1, b2, omb2,
+                           c1, c2, t.cfg.adam_eps, lr, part, t.clip_parts, max_norm, t.clip);
+    } else {
+        hipLaunchKernelGGL(hk::ppo_adam_kernel, dim3(nblk(t.P)), dim3(256), 0, h->stream, p, p + t.P, p + 2 * t.P, p + 3 * t.P, t.P, b1, omb1, b2, omb2, c1, c2,
+                           t.cfg.adam_eps, lr);
+    }
     ppo_shadow_refresh(h->stream, t);
     HK_HIP(h, hipGetLastError());
     return HK_OK;
@@ -1847,37 +1869,133 @@ int hk_ppo_publish(hk_handle h, int trainer)
     return HK_OK;
 }
 
+extern "C++" {
+namespace {
+
+// hk_ppo_update and hk_ppo_update_opt: epochs x (shuffle, minibatches, Adam), then publish.  max_norm 0 and target_kl 0 issue exactly the plain
+// update's launches.  target_kl > 0: the stats accumulator is zeroed at the start of every epoch and read after it (one 64-byte copy and a
+// synchronise per epoch); an epoch whose mean approx-KL exceeds target_kl is the last.  opt: the call is hk_ppo_update_opt.
+int ppo_update_run(hk_handle h, int trainer, bool opt, int epochs, int minibatch, float lr, float eps, float beta, float max_norm,
+                   float target_kl, float* stats, hk_ppo_update_report* report)
+{
+    auto& t = h->ppo[trainer];
+    const int n = t.n;
+    const int mb = std::min(minibatch, n), nmb = n / mb;
+    const bool kl_stop = target_kl > 0.0f;
+    int* perm = ppo_rowbuf(h, t).perm;
+    PpoWs w;
+    int rc;
+    if ((rc = ppo_ensure_ws(h, t, mb, w))) return rc;
+    if (max_norm > 0.0f && (rc = ppo_ensure_clip(h, t))) return rc;
+    if (opt && t.clip) HK_HIP(h, hipMemsetAsync(t.clip + 2, 0, 5 * sizeof(double), h->stream));       // the accumulating words [2 .. 6]
+    ppo_shadow_refresh(h->stream, t);
+    double acc[8] = {};
+    bool have_acc = false;
+    int run = 0, stopped = 0;
+    for (int ep = 0; ep < epochs; ep++) {
+        const bool last = ep == epochs - 1;
+        if (last || kl_stop) HK_HIP(h, hipMemsetAsync(w.acc, 0, 8 * sizeof(double), h->stream));
+        hipLaunchKernelGGL(hk::ppo_perm_kernel, dim3(nblk(n)), dim3(256), 0, h->stream, perm, n, t.cfg.seed, (uint32_t)t.epochs_done);
+        t.epochs_done += 1;
+        t.perm_valid = true;
+        for (int b = 0; b < nmb; b++) {
+            if ((rc = ppo_mb(h, t, perm + (size_t)b * mb, mb, eps, beta, last || kl_stop))) return rc;
+            if ((rc = ppo_adam_step(h, t, lr, max_norm))) return rc;
+        }
+        run += 1;
+        if (kl_stop) {
+            HK_HIP(h, hipMemcpyAsync(acc, w.acc, sizeof(acc), hipMemcpyDeviceToHost, h->stream));
+            HK_HIP(h, hipStreamSynchronize(h->stream));
+            have_acc = true;
+            if (!last && acc[3] / (acc[6] > 0 ? acc[6] : 1.0) > (double)target_kl) { stopped = 1; break; }
+        }
+    }
+    if ((rc = hk_ppo_publish(h, trainer))) return rc;
+    if (stats || report) {
+        double words[8] = {};
+        if (!have_acc) HK_HIP(h, hipMemcpyAsync(acc, w.acc, sizeof(acc), hipMemcpyDeviceToHost, h->stream));
+        if (report && max_norm > 0.0f) HK_HIP(h, hipMemcpyAsync(words, t.clip, sizeof(words), hipMemcpyDeviceToHost, h->stream));
+        HK_HIP(h, hipStreamSynchronize(h->stream));
+        const double d = acc[6] > 0 ? acc[6] : 1.0;
+        if (stats) for (int q = 0; q < HK_PPO_STATS; q++) stats[q] = (float)(acc[q] / d);
+        if (report) {
+            hk_ppo_update_report r{};
+            r.epochs_run = run; r.minibatches_run = run * nmb; r.stopped_by_kl = stopped;
+            r.clipped_steps = (int32_t)words[3]; r.nonfinite_steps = (int32_t)words[4];
+            r.last_epoch_kl = acc[3] / d;
+            const double fin = words[2] - words[4];
+            r.grad_norm_mean = fin > 0 ? words[5] / fin : 0.0;
+            r.grad_norm_max = words[6];
+            *report = r;
+        }
+    }
+    return HK_OK;
+}
+
+// max_grad_norm / target_kl as hk_ppo_update_opts states them: 0 off, > 0 on (+inf allowed for the norm), < 0 or NaN refused
+int ppo_opt_range(hk_handle h, const char* fn, const char* name, float v, bool inf_ok)
+{
+    if (v >= 0.0f && (inf_ok || std::isfinite(v))) return HK_OK;
+    return fail(h, HK_ERR_INVALID, std::string(fn) + ": " + name + " is negative, NaN" + (inf_ok ? "" : " or infinite") + " (0: off)");
+}
+
+}  // namespace
+}  // extern "C++"
+
 int hk_ppo_update(hk_handle h, int trainer, int epochs, int minibatch, float lr, float eps, float beta, float* stats)
 {
     HK_NEED_ENV(h);
     int rc = ppo_check(h, trainer, "hk_ppo_update", true);
     if (rc) return rc;
     if (epochs < 1 || minibatch < 1) return fail(h, HK_ERR_INVALID, "hk_ppo_update: epochs < 1 or minibatch < 1");
+    return ppo_update_run(h, trainer, false, epochs, minibatch, lr, eps, beta, 0.0f, 0.0f, stats, nullptr);
+}
+
+int hk_ppo_update_opt(hk_handle h, int trainer, const hk_ppo_update_opts* o, float* stats, hk_ppo_update_report* report)
+{
+    HK_NEED_ENV(h);
+    const char* fn = "hk_ppo_update_opt";
+    int rc = ppo_check(h, trainer, fn, true);
+    if (rc) return rc;
+    if (!o) return fail(h, HK_ERR_INVALID, "hk_ppo_update_opt: NULL opts");
+    if (o->epochs < 1) return fail(h, HK_ERR_INVALID, "hk_ppo_update_opt: epochs < 1");
+    if (o->minibatch < 1) return fail(h, HK_ERR_INVALID, "hk_ppo_update_opt: minibatch < 1");
+    if ((rc = ppo_opt_range(h, fn, "max_grad_norm", o->max_grad_norm, true))) return rc;
+    if ((rc = ppo_opt_range(h, fn, "target_kl", o->target_kl, false))) return rc;
+    if (o->reserved != 0) return fail(h, HK_ERR_INVALID, "hk_ppo_update_opt: reserved != 0");
+    return ppo_update_run(h, trainer, true, o->epochs, o->minibatch, o->lr, o->eps, o->beta, o->max_grad_norm, o->target_kl, stats, report);
+}
+
+int hk_ppo_adam_clipped(hk_handle h, int trainer, float lr, float max_grad_norm)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_check(h, trainer, "hk_ppo_adam_clipped", false);
+    if (rc) return rc;
+    if (!(max_grad_norm > 0.0f)) return fail(h, HK_ERR_INVALID, "hk_ppo_adam_clipped: max_grad_norm is not > 0 (NaN included; +inf measures only)");
+    return ppo_adam_step(h, h->ppo[trainer], lr, max_grad_norm);
+}
+
+int hk_ppo_get_counters(hk_handle h, int trainer, int64_t* adam_steps, int64_t* epochs_done)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_check(h, trainer, "hk_ppo_get_counters", false);
+    if (rc) return rc;
+    const auto& t = h->ppo[trainer];
+    if (adam_steps) *adam_steps = t.adam_steps;
+    if (epochs_done) *epochs_done = t.epochs_done;
+    return HK_OK;
+}
+
+int hk_ppo_set_counters(hk_handle h, int trainer, int64_t adam_steps, int64_t epochs_done)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_check(h, trainer, "hk_ppo_set_counters", false);
+    if (rc) return rc;
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_ppo_set_counters: refused while a rollout is open (hk_rollout_close first)");
+    if (adam_steps < 0 || adam_steps > INT32_MAX) return fail(h, HK_ERR_INVALID, "hk_ppo_set_counters: adam_steps outside [0, INT32_MAX]");
+    if (epochs_done < 0 || epochs_done > INT32_MAX) return fail(h, HK_ERR_INVALID, "hk_ppo_set_counters: epochs_done outside [0, INT32_MAX]");
     auto& t = h->ppo[trainer];
-    const int n = t.n;
-    const int mb = std::min(minibatch, n), nmb = n / mb;
-    int* perm = ppo_rowbuf(h, t).perm;
-    PpoWs w;
-    if ((rc = ppo_ensure_ws(h, t, mb, w))) return rc;
-    ppo_shadow_refresh(h->stream, t);
-    for (int ep = 0; ep < epochs; ep++) {
-        const bool last = ep == epochs - 1;
-        if (last) HK_HIP(h, hipMemsetAsync(w.acc, 0, 8 * sizeof(double), h->stream));
-        hipLaunchKernelGGL(hk::ppo_perm_kernel, dim3(nblk(n)), dim3(256), 0, h->stream, perm, n, t.cfg.seed, (uint32_t)t.epochs_done);
-        t.epochs_done += 1;
-        t.perm_valid = true;
-        for (int b = 0; b < nmb; b++) {
-            if ((rc = ppo_mb(h, t, perm + (size_t)b * mb, mb, eps, beta, last))) return rc;
-            if ((rc = ppo_adam_step(h, t, lr))) return rc;
-        }
-    }
-    if ((rc = hk_ppo_publish(h, trainer))) return rc;
-    if (stats) {
-        double acc[8];
-        HK_HIP(h, hipMemcpyAsync(acc, w.acc, sizeof(acc), hipMemcpyDeviceToHost, h->stream));
-        HK_HIP(h, hipStreamSynchronize(h->stream));
-        for (int q = 0; q < HK_PPO_STATS; q++) stats[q] = (float)(acc[q] / (acc[6] > 0 ? acc[6] : 1.0));
-    }
+    t.adam_steps = (int)adam_steps; t.epochs_done = (int)epochs_done;
     return HK_OK;
 }
 
@@ -2047,6 +2165,10 @@ void* hk_ppo_ptr(hk_handle h, int trainer, int field)
         if (!t.shadow) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: the trainer has never been in HK_PPO_PREC_BF16"); return nullptr; }
         return t.shadow;
     }
+    if (field == HK_PPO_CLIP) {
+        if (!t.clip) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: no clip-aware step yet"); return nullptr; }
+        return t.clip;
+    }
     if (t.last_m == 0) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: no minibatch yet"); return nullptr; }
     PpoWs w;
     ppo_ws_layout(t, t.cap, &w);
@@ -2063,6 +2185,7 @@ int hk_ppo_count(hk_handle h, int trainer, int field)
     if (field <= HK_PPO_RET) return t.adv_gen < 0 ? 0 : t.n;
     if (field == HK_PPO_PERM) return t.perm_valid ? t.n : 0;
     if (field == HK_PPO_SHADOW) return t.shadow ? (int)(t.P + t.shadow_pad) : 0;
+    if (field == HK_PPO_CLIP) return t.clip ? 8 : 0;
     if (field == HK_PPO_NORM_MEAN || field == HK_PPO_NORM_STD) return h->policy[t.policy].q.normalize ? h->policy[t.policy].q.in_dim : 0;
     return field == HK_PPO_MB_LOGITS ? t.last_m * t.actor.n_branch : t.last_m;
 }

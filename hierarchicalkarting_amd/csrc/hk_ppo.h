@@ -10,6 +10,8 @@
 //   ppo_colsum_kernel       bias / log_sigma gradients and the stats: fixed-order column sums (no float atomics anywhere)
 //   ppo_gae_kernel          one lane per (env, slot): the reverse GAE scan;  ppo_adv_norm_kernel: fp64 mean / std in one block
 //   ppo_adam_kernel, ppo_publish_kernel<TO_POLICY>              elementwise
+//   ppo_gradnorm_partial_kernel, ppo_adam_clip_kernel           the clip-aware Adam step (hk.h "LONG RUNS"): fp64 partials of |GRAD|^2 over fixed
+//                           runs, then norm, coef and ppo_adam_kernel's step on g coef in one launch
 //   ppo_norm_partial / combine / finalise / publish_kernel      the running normaliser (hk.h "NORMALISER"): fp64 sums over OBS / FIRST / RING0 read
 //                           once, per-workgroup partials combined in partition order, the new state and the policy's fp32 mean / std
 // HK_PPO_PREC_BF16 (hk.h "PRECISION"): the trunk products run on ppo_gemm_bf16_kernel<EPI> (v_mfma_f32_32x32x16_bf16, fp32 accumulation) over
@@ -586,6 +588,92 @@ __global__ __launch_bounds__(256) void ppo_adam_kernel(float* p, const float* g,
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float gi = g[i];
+    const float m1 = b1 * mm[i] + omb1 * gi;
+    const float v1 = b2 * vv[i] + (omb2 * gi) * gi;
+    mm[i] = m1; vv[i] = v1;
+    const float mh = m1 / c1;
+    const float vh = v1 / c2;
+    p[i] = p[i] - lr * mh / (sqrtf(vh) + eps);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Clip by the global L2 norm (hk.h "LONG RUNS"): two launches per step.
+//   ppo_gradnorm_partial_kernel   workgroup x owns the run [x PPO_GN_RUN, (x + 1) PPO_GN_RUN) of GRAD and writes part[x] = sum (double)g (double)g
+//                                 (a square of an fp32 value is exact in fp64).  GRAD starts P floats into the allocation, so its runs are
+//                                 16-byte aligned only when P % 4 == 0: the run is peeled to alignment (head < 4 elements, lanes 0 .. head - 1),
+//                                 read as float4 v = tid, tid + 256, ... (coalesced), and closed by a tail of < 4 elements.  A lane adds its
+//                                 elements in ascending index order, then a fixed LDS tree: the partition and the order depend on P alone.
+//   ppo_adam_clip_kernel          every workgroup sums the partials in index order (lane 0; <= a few hundred cached loads), derives the same
+//                                 norm and coef, and does ppo_adam_kernel's step, operation for operation, on g' = g coef.  A norm2 that is not
+//                                 finite: nothing is written.  Workgroup 0 keeps the HK_PPO_CLIP words.
+constexpr int PPO_GN_RUN = 4096;
+
+__global__ __launch_bounds__(256) void ppo_gradnorm_partial_kernel(const float* __restrict__ g, size_t n, double* __restrict__ part)
+{
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    const size_t lo = (size_t)blockIdx.x * PPO_GN_RUN;
+    const int len = (int)((n - lo < (size_t)PPO_GN_RUN) ? n - lo : (size_t)PPO_GN_RUN);
+    const float* run = g + lo;
+    int head = (int)((4u - (unsigned)(((uintptr_t)run >> 2) & 3u)) & 3u);
+    if (head > len) head = len;
+    const int nv = (len - head) >> 2, tail0 = head + 4 * nv;
+    const float4* body = reinterpret_cast<const float4*>(run + head);
+    double s = 0.0;
+    if (tid < head) { const double x = (double)run[tid]; s += x * x; }
+    float4 x[PPO_GN_RUN / 1024];
+#pragma unroll
+    for (int j = 0; j < PPO_GN_RUN / 1024; j++) {
+        const int v = tid + 256 * j;
+        x[j] = v < nv ? body[v] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+#pragma unroll
+    for (int j = 0; j < PPO_GN_RUN / 1024; j++) {
+        if (tid + 256 * j < nv) {
+            const double a = (double)x[j].x, b = (double)x[j].y, c = (double)x[j].z, d = (double)x[j].w;
+            s += a * a; s += b * b; s += c * c; s += d * d;
+        }
+    }
+    if (tail0 + tid < len) { const double y = (double)run[tail0 + tid]; s += y * y; }
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) part[blockIdx.x] = red[0];
+}
+
+// words: HK_PPO_CLIP [8] — norm, coef, steps, steps with coef < 1, non-finite steps, sum and max of norm over the finite steps, 0
+__global__ __launch_bounds__(256) void ppo_adam_clip_kernel(float* p, const float* g, float* mm, float* vv, size_t n, float b1, float omb1, float b2, float omb2,
+                                                            float c1, float c2, float eps, float lr, const double* __restrict__ part, int npart,
+                                                            float max_norm, double* words)
+{
+    __shared__ float s_coef;
+    __shared__ int s_finite;
+    if (threadIdx.x == 0) {
+        double norm2 = 0.0;
+        for (int x = 0; x < npart; x++) norm2 += part[x];
+        const bool finite = isfinite(norm2);
+        const double norm = sqrt(norm2);
+        const double r = (double)max_norm / (norm + 1e-6);
+        const float coef = finite ? (float)(r < 1.0 ? r : 1.0) : 0.0f;
+        s_coef = coef; s_finite = finite ? 1 : 0;
+        if (blockIdx.x == 0) {
+            words[0] = norm; words[1] = (double)coef; words[2] += 1.0; words[7] = 0.0;
+            if (finite) {
+                if (coef < 1.0f) words[3] += 1.0;
+                words[5] += norm;
+                if (norm > words[6]) words[6] = norm;
+            } else {
+                words[4] += 1.0;
+            }
+        }
+    }
+    __syncthreads();
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !s_finite) return;
+    const float gi = g[i] * s_coef;
     const float m1 = b1 * mm[i] + omb1 * gi;
     const float v1 = b2 * vv[i] + (omb2 * gi) * gi;
     mm[i] = m1; vv[i] = v1;

@@ -7,16 +7,20 @@ and leaves updated weights in the attached policy, so that the next step() acts 
     stats = tr.update(epochs=3, minibatch=512, lr=3e-4, eps=0.2, beta=5e-3)     # shuffle, minibatches, Adam; then publish
     tr.set_precision("bf16")                     # trunk products on the bf16 matrix cores, fp32 master weights (hk.h "PRECISION")
     tr.normalizer_init(); ...; tr.normalizer_update()     # the running input normaliser, folded from the closed rollout (hk.h "NORMALISER")
+    tr.update(3, 512, 3e-4, max_grad_norm=0.5, target_kl=0.02); tr.last_report      # clip by the global norm, KL stop (hk.h "LONG RUNS")
+    tr.save(path); ...; tr2.load(path)           # exact resume: masters, Adam moments, the two counters, precision, normaliser
 
 Nothing is computed here: the arrays below only describe the flat parameter layout the library uses."""
 import ctypes as C
+import math
 import numpy as np
 from . import _lib
 from .policy import Policy
 
 DEFAULTS = dict(gamma=0.99, lambd=0.95, normalize_advantages=True, adam_beta1=0.9, adam_beta2=0.999, adam_eps=1e-8, seed=0)
 PRECISIONS = {"f32": _lib.HK_PPO_PREC_F32, "bf16": _lib.HK_PPO_PREC_BF16}
-_DTYPES = {"perm": np.int32, "shadow": np.uint16}       # every other HK_PPO_* field is float32
+_DTYPES = {"perm": np.int32, "shadow": np.uint16, "clip": np.float64}       # every other HK_PPO_* field is float32
+CHECKPOINT_FORMAT = 1
 
 
 def bf16_round(x):
@@ -152,6 +156,78 @@ def normalizer_published(steps, mean, m2):
     return np.float32(np.asarray(mean, np.float64)), np.float32(np.sqrt(np.asarray(m2, np.float64) / np.float64(steps)))
 
 
+def grad_norm(g):
+    """host twin of the device's global gradient norm (hk.h "LONG RUNS"): sqrt of the exactly rounded sum (math.fsum) of the squares, which are
+    exact in float64 for a float32 g.  -> float64; not finite when g holds a NaN or an Inf"""
+    x = np.asarray(g, np.float64).reshape(-1)
+    sq = x * x
+    if not np.isfinite(sq).all():
+        return np.float64(np.nan if np.isnan(sq).any() else np.inf)
+    return np.float64(math.sqrt(math.fsum(sq.tolist())))
+
+
+def clip_coefficient(norm, max_norm, dtype=np.float32):
+    """host twin of the clip-aware step's coefficient: (float) min(1.0, (double)max_norm / (norm + 1e-6)) — torch's clip_coef, clamped — with
+    max_norm taken as the float32 the C ABI receives.  -> np.float32, the device's value; dtype=np.float64: the expression before that one rounding"""
+    return dtype(min(1.0, float(np.float32(max_norm)) / (float(norm) + 1e-6)))
+
+
+def _flatten(d, prefix=""):
+    out = {}
+    for k, v in d.items():
+        if "/" in str(k):
+            raise ValueError("checkpoint: a key may not contain '/': %r" % (k,))
+        if isinstance(v, dict):
+            out.update(_flatten(v, prefix + str(k) + "/"))
+        else:
+            a = np.asarray(v)
+            if a.dtype == object:
+                raise ValueError("checkpoint: %s%s is not an array, a number or a string" % (prefix, k))
+            out[prefix + str(k)] = a
+    return out
+
+
+def checkpoint_write(path, d):
+    """one .npz of a (nested) dict of numpy arrays, numbers and strings; nested dicts are flattened with '/'.  No pickle.  "format" is added when absent"""
+    flat = _flatten(dict({"format": CHECKPOINT_FORMAT}, **d))
+    with open(path, "wb") as f:
+        np.savez(f, **flat)
+
+
+def checkpoint_read(path):
+    """-> the dict checkpoint_write was given: arrays bit for bit with their dtypes, 0-d entries as Python scalars.  ValueError: no or an unknown "format" """
+    out = {}
+    with np.load(path, allow_pickle=False) as z:
+        for key in z.files:
+            a = z[key]
+            node = out
+            parts = key.split("/")
+            for part in parts[:-1]:
+                node = node.setdefault(part, {})
+            node[parts[-1]] = a.item() if a.ndim == 0 else a
+    if "format" not in out:
+        raise ValueError("checkpoint: no 'format' entry")
+    if out["format"] != CHECKPOINT_FORMAT:
+        raise ValueError("checkpoint: format %r is not the format %d this version reads" % (out["format"], CHECKPOINT_FORMAT))
+    return out
+
+
+def _need(d, key, what="state"):
+    if key not in d:
+        raise ValueError("%s: missing key %r" % (what, key))
+    return d[key]
+
+
+def _option(name, v, inf_ok):
+    """an update option as hk_ppo_update_opts takes it: None -> 0 (off); negative, NaN (or infinite) -> ValueError"""
+    if v is None:
+        return 0.0
+    v = float(v)
+    if not v >= 0.0 or (math.isinf(v) and not inf_ok):
+        raise ValueError("%s: >= 0%s (0 or None: off)" % (name, ", +inf allowed" if inf_ok else " and finite"))
+    return v
+
+
 class PPOTrainer:
     """One trainer of RacingEnv `env`'s attached policy `policy_index` (hk_ppo_create).  critic: a Policy with n_branch 0 semantics (its trunk and
     W_mu / b_mu are used) or None for Policy.random-style weights of the actor's shape; precision: "f32" | "bf16" (set_precision); cfg: DEFAULTS' keys."""
@@ -182,6 +258,7 @@ class PPOTrainer:
         self.actor_layout = param_layout(a.in_dim, a.hidden, len(a.W), a.n_branch)
         self.critic_layout = param_layout(a.in_dim, critic.hidden, len(critic.W), 0)
         self.n_actor = sum(int(np.prod(s)) for _, s in self.actor_layout)
+        self.last_report = None           # of the last update(): a dict when it was given an option, else None
         self.set_precision(precision)
 
     def _ck(self, rc):
@@ -229,14 +306,47 @@ class PPOTrainer:
                                              st if stats else None))
         return dict(zip(_lib.PPO_STAT_NAMES, list(st))) if stats else None
 
-    def adam(self, lr):
-        self._ck(self.env.L.hk_ppo_adam(self.env.h, self.t, float(lr)))
+    def adam(self, lr, max_grad_norm=None):
+        """one Adam step from GRAD; max_grad_norm (> 0, inf: measure only): the clip-aware step of hk.h "LONG RUNS", see clip_words()"""
+        if max_grad_norm is None:
+            self._ck(self.env.L.hk_ppo_adam(self.env.h, self.t, float(lr)))
+            return
+        if not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm: > 0 (+inf measures only)")
+        self._ck(self.env.L.hk_ppo_adam_clipped(self.env.h, self.t, float(lr), float(max_grad_norm)))
 
-    def update(self, epochs=3, minibatch=512, lr=3e-4, eps=0.2, beta=5e-3):
-        """epochs x (device shuffle, minibatches, Adam), then publish.  -> stats (mean over the last epoch's minibatches)"""
+    def update(self, epochs=3, minibatch=512, lr=3e-4, eps=0.2, beta=5e-3, *, max_grad_norm=None, target_kl=None):
+        """epochs x (device shuffle, minibatches, Adam), then publish.  -> stats (mean over the last epoch's minibatches).
+        max_grad_norm: clip every step by the global L2 norm (inf: measure only); target_kl: no further epoch after one whose mean approx-KL
+        exceeds it.  With either given, last_report is hk_ppo_update_report as a dict (else None)."""
         st = (C.c_float * _lib.HK_PPO_STATS)()
-        self._ck(self.env.L.hk_ppo_update(self.env.h, self.t, int(epochs), int(minibatch), float(lr), float(eps), float(beta), st))
+        if max_grad_norm is None and target_kl is None:
+            self._ck(self.env.L.hk_ppo_update(self.env.h, self.t, int(epochs), int(minibatch), float(lr), float(eps), float(beta), st))
+            self.last_report = None
+            return dict(zip(_lib.PPO_STAT_NAMES, list(st)))
+        o = _lib.PpoUpdateOpts(int(epochs), int(minibatch), float(lr), float(eps), float(beta), _option("max_grad_norm", max_grad_norm, True),
+                               _option("target_kl", target_kl, False), 0)
+        rep = _lib.PpoUpdateReport()
+        self._ck(self.env.L.hk_ppo_update_opt(self.env.h, self.t, C.byref(o), st, C.byref(rep)))
+        self.last_report = {n: getattr(rep, n) for n, _ in _lib.PpoUpdateReport._fields_ if n != "reserved"}
         return dict(zip(_lib.PPO_STAT_NAMES, list(st)))
+
+    def clip_words(self):
+        """-> dict of the HK_PPO_CLIP words (norm, coef of the last clip-aware step; steps, clipped, nonfinite, norm_sum, norm_max since create or
+        the last update with an option); all 0 before the first clip-aware step"""
+        n = self.env.L.hk_ppo_count(self.env.h, self.t, _lib.PPO_FIELDS["clip"])
+        if n < 0:
+            self._ck(n)
+        return dict(zip(_lib.PPO_CLIP_NAMES, [float(x) for x in (self.read("clip") if n else np.zeros(8))]))
+
+    def counters(self):
+        """-> (adam_steps, epochs_done): the Adam step count of the bias corrections and the epoch count that keys the shuffle"""
+        a, e = C.c_int64(0), C.c_int64(0)
+        self._ck(self.env.L.hk_ppo_get_counters(self.env.h, self.t, C.byref(a), C.byref(e)))
+        return int(a.value), int(e.value)
+
+    def set_counters(self, adam_steps, epochs_done):
+        self._ck(self.env.L.hk_ppo_set_counters(self.env.h, self.t, int(adam_steps), int(epochs_done)))
 
     def publish(self):
         self._ck(self.env.L.hk_ppo_publish(self.env.h, self.t))
@@ -253,7 +363,7 @@ class PPOTrainer:
         return ptr, n
 
     def read(self, name):
-        """-> numpy copy of an HK_PPO_* field, float32 (int32 for perm, uint16 for shadow); the handle's stream is synchronised first"""
+        """-> numpy copy of an HK_PPO_* field, float32 (int32 for perm, uint16 for shadow, float64 for clip); the handle's stream is synchronised first"""
         self.env.synchronize()
         ptr, n = self._field(name)
         a = np.zeros(n, _DTYPES.get(name, np.float32))
@@ -262,7 +372,7 @@ class PPOTrainer:
         return a
 
     def views(self):
-        """-> dict field -> torch CUDA tensor ALIASING the trainer's buffer, float32 (int32 for perm, int16 bits for shadow); rollout_views' caveats apply"""
+        """-> dict field -> torch CUDA tensor ALIASING the trainer's buffer, float32 (int32 for perm, int16 bits for shadow, float64 for clip); rollout_views' caveats apply"""
         import torch
 
         class _Ext:
@@ -273,7 +383,7 @@ class PPOTrainer:
             n = self.env.L.hk_ppo_count(self.env.h, self.t, idx)
             ptr = self.env.L.hk_ppo_ptr(self.env.h, self.t, idx) if n > 0 else None
             if ptr:
-                out[name] = torch.as_tensor(_Ext(ptr, n, {"perm": "<i4", "shadow": "<i2"}.get(name, "<f4")), device="cuda:%d" % self.env.built.cfg.device_id)
+                out[name] = torch.as_tensor(_Ext(ptr, n, {"perm": "<i4", "shadow": "<i2", "clip": "<f8"}.get(name, "<f4")), device="cuda:%d" % self.env.built.cfg.device_id)
         return out
 
     def actor_params(self, flat=None):
@@ -315,3 +425,69 @@ class PPOTrainer:
             mean, std = self.read("norm_mean"), self.read("norm_std")
         return Policy([p["W%d" % l] for l in range(L)], [p["b%d" % l] for l in range(L)], p["W_mu"], p["b_mu"], p["log_sigma"], p["W_branch"],
                       p["b_branch"], mean, std, a.stack, a.deterministic, a.seed)
+
+    # ---- exact resume (hk.h "LONG RUNS"): a restored trainer fed the same rollout continues bit for bit
+    def _shapes(self):
+        a, c = self.actor_policy, self.critic_policy
+        return (np.array([a.in_dim, a.hidden, len(a.W), a.n_branch], np.int64), np.array([a.in_dim, c.hidden, len(c.W), 0], np.int64))
+
+    def state_dict(self):
+        """-> dict of numpy arrays and scalars: format, the two network shapes, params / adam_m / adam_v, adam_steps, epochs_done, precision, cfg
+        (for checking only) and, when one was initialised, the normaliser state"""
+        sa, sc = self._shapes()
+        steps, epochs = self.counters()
+        d = dict(format=CHECKPOINT_FORMAT, actor_shape=sa, critic_shape=sc, params=self.read("params"), adam_m=self.read("adam_m"),
+                 adam_v=self.read("adam_v"), adam_steps=steps, epochs_done=epochs, precision=self.precision,
+                 cfg={k: (int(self.cfg[k]) & 0xFFFFFFFF if k == "seed" else int(bool(self.cfg[k])) if k == "normalize_advantages" else float(self.cfg[k]))
+                      for k in DEFAULTS})
+        if self.actor_policy.norm_mean is not None:
+            try:
+                n, mean, m2 = self.normalizer_state()
+                d["normalizer"] = dict(steps=n, mean=mean, m2=m2)
+            except _lib.HkError:          # no normaliser state: the statistics are the frozen ones of the attached policy
+                pass
+        return d
+
+    def load_state_dict(self, d):
+        """validate (ValueError names the field: shapes, cfg — a differing shuffle seed would not continue the permutations), then restore the
+        counters, the three vectors, the precision and the normaliser if present, and publish; the library refuses it while a rollout is open"""
+        if _need(d, "format") != CHECKPOINT_FORMAT:
+            raise ValueError("state: format %r is not %d" % (d["format"], CHECKPOINT_FORMAT))
+        for key, want in zip(("actor_shape", "critic_shape"), self._shapes()):
+            if not np.array_equal(np.asarray(_need(d, key)), want):
+                raise ValueError("state: %s %s differs from the trainer's %s" % (key, list(np.asarray(d[key])), list(want)))
+        cfg = _need(d, "cfg")
+        for k in DEFAULTS:
+            mine = int(self.cfg[k]) & 0xFFFFFFFF if k == "seed" else int(bool(self.cfg[k])) if k == "normalize_advantages" else float(self.cfg[k])
+            if _need(cfg, k, "state cfg") != mine:
+                raise ValueError("state: cfg %s = %r differs from the trainer's %r" % (k, cfg[k], mine))
+        if _need(d, "precision") not in PRECISIONS:
+            raise ValueError("state: precision %r" % (d["precision"],))
+        P = self.env.L.hk_ppo_count(self.env.h, self.t, _lib.PPO_FIELDS["params"])
+        vec = {}
+        for name in ("params", "adam_m", "adam_v"):
+            a = np.asarray(_need(d, name))
+            if a.dtype != np.float32 or a.shape != (P,):
+                raise ValueError("state: %s is float32 [%d]" % (name, P))
+            vec[name] = np.ascontiguousarray(a)
+        norm = d.get("normalizer")
+        if norm is not None:
+            norm = _normalizer_check(_need(norm, "steps", "state normalizer"), _need(norm, "mean", "state normalizer"),
+                                     _need(norm, "m2", "state normalizer"), self.actor_policy.in_dim)
+            if self.actor_policy.norm_mean is None:
+                raise ValueError("state: normalizer given, but the policy was attached without statistics")
+        self.set_counters(_need(d, "adam_steps"), _need(d, "epochs_done"))          # (the library's refusals come first: nothing is written after one)
+        self.env.synchronize()
+        for name, a in vec.items():
+            ptr, _ = self._field(name)
+            _lib.copy_host_to_device(ptr, a.ctypes.data, a.nbytes)
+        self.set_precision(d["precision"])
+        if norm is not None:
+            self.normalizer_load(*norm)
+        self.publish()
+
+    def save(self, path):
+        checkpoint_write(path, self.state_dict())
+
+    def load(self, path):
+        self.load_state_dict(checkpoint_read(path))

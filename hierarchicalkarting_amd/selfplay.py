@@ -7,13 +7,15 @@ bookkeeping on top of three device facilities — the snapshot pool (hk_policy_p
     sp = SelfPlay(env, tr, opponent, window=10, save_steps=20000, swap_steps=10000, max_steps=5_000_000)
     for _ in range(iterations):
         out = sp.iteration(rows=64, epochs=3, minibatch=512, lr=3e-4, eps=0.2, beta=5e-3)      # out["elo"], out["stats"], out["update"]
+    ppo.checkpoint_write(path, sp.state_dict()); ...; sp2.load_state_dict(ppo.checkpoint_read(path))     # ratings, cursor, generator, pool slots
 
 Nothing is computed on the host but ratings, schedules and which slot plays next.  Out of scope: team_change (a trainer is bound to one
 policy), per-env opponents, POCA and LSTM."""
 import ctypes as C
+import json
 import numpy as np
 from .policy import Policy
-from .ppo import param_layout, split_params
+from .ppo import CHECKPOINT_FORMAT, param_layout, split_params
 
 SCHEDULE_MINIMA = dict(lr=1e-10, eps=0.1, beta=1e-5)       # ML-Agents' floors of the three linear decays
 
@@ -106,6 +108,18 @@ class SnapshotPool:
         self.env._ck(self.env.L.hk_policy_pool_get(self.env.h, self.pool, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float))))
         return flat_to_policy(flat, self.like)
 
+    def get_flat(self, slot):
+        """-> the slot's flat float32 vector as it lies on the device (hk_policy_pool_get)"""
+        flat = np.zeros(self.count, np.float32)
+        self.env._ck(self.env.L.hk_policy_pool_get(self.env.h, self.pool, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float))))
+        return flat
+
+    def put_flat(self, slot, flat):
+        flat = np.ascontiguousarray(flat, np.float32)
+        if flat.shape != (self.count,):
+            raise ValueError("SnapshotPool.put_flat: a slot of this pool is float32 [%d]" % self.count)
+        self.env._ck(self.env.L.hk_policy_pool_put(self.env.h, self.pool, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float))))
+
 
 class SelfPlay:
     """ML-Agents' self-play loop around one trainer (the learner) and one attached opponent policy of the same shape.
@@ -194,10 +208,51 @@ class SelfPlay:
                 vals[k] = linear_schedule(vals[k], mins[k], self.steps, self.max_steps)
         return vals["lr"], vals["eps"], vals["beta"]
 
+    # ---- checkpoint of the bookkeeping and the pool (the trainer has its own: PPOTrainer.state_dict)
+    _PICK = {None: -2, "latest": -1}          # an opponent as an integer: as attached, latest, or the window slot itself
+
+    def state_dict(self, include_pool=True):
+        """-> dict of numpy arrays and scalars (ppo.checkpoint_write takes it): elo, ratings, attached_elo, cursor, opponent, steps, last_save,
+        last_swap, history (None -2, "latest" -1, else the slot), the generator's bit_generator.state as a JSON string and, with include_pool,
+        the flat vectors of the filled slots.  Env state and the policies' decision counters are not part of it (env_state / set_env_state)."""
+        code = lambda x: self._PICK.get(x, x)
+        d = dict(format=CHECKPOINT_FORMAT, window=self.window, elo=self.elo, ratings=np.asarray(self.ratings, np.float64), attached_elo=self.attached_elo,
+                 cursor=self.cursor, opponent=int(code(self.opponent)), steps=self.steps, last_save=self.last_save, last_swap=self.last_swap,
+                 history=np.asarray([code(x) for x in self.history], np.int64), rng=json.dumps(self.rng.bit_generator.state))
+        if include_pool:
+            slots = list(range(min(self.cursor, self.window))) + ([self.window] if "latest" in self.history else [])
+            d["pool"] = {"slot%d" % s: self.pool.get_flat(s) for s in slots}
+        return d
+
+    def load_state_dict(self, d):
+        """restore what state_dict stored; the slots are put back, and an opponent that is not None is loaded into the opponent policy (None, "as
+        attached", is the caller's to restore, as it is at construction).  ValueError: a missing key, another format or window"""
+        for k in ("format", "window", "elo", "ratings", "attached_elo", "cursor", "opponent", "steps", "last_save", "last_swap", "history", "rng"):
+            if k not in d:
+                raise ValueError("SelfPlay state: missing key %r" % k)
+        if d["format"] != CHECKPOINT_FORMAT:
+            raise ValueError("SelfPlay state: format %r is not %d" % (d["format"], CHECKPOINT_FORMAT))
+        if int(d["window"]) != self.window or len(d["ratings"]) != self.window:
+            raise ValueError("SelfPlay state: window %r differs from this object's %d" % (d["window"], self.window))
+        pick = lambda c: {v: k for k, v in self._PICK.items()}.get(int(c), int(c))
+        rng_state = json.loads(str(d["rng"]))
+        if rng_state.get("bit_generator") != type(self.rng.bit_generator).__name__:
+            raise ValueError("SelfPlay state: rng is a %r state" % rng_state.get("bit_generator"))
+        for name, flat in sorted(d.get("pool", {}).items()):
+            self.pool.put_flat(int(name[4:]), flat)
+        self.elo, self.attached_elo = float(d["elo"]), float(d["attached_elo"])
+        self.ratings = [float(x) for x in d["ratings"]]
+        self.cursor, self.steps, self.last_save, self.last_swap = int(d["cursor"]), int(d["steps"]), int(d["last_save"]), int(d["last_swap"])
+        self.history = [pick(c) for c in np.asarray(d["history"]).reshape(-1)]
+        self.opponent = pick(d["opponent"])
+        self.rng.bit_generator.state = rng_state
+        if self.opponent is not None:
+            self.pool.load(self.window if self.opponent == "latest" else self.opponent, self.opponent_index)
+
     # ---- one rollout + update
-    def iteration(self, rows, epochs=3, minibatch=512, lr=3e-4, eps=0.2, beta=5e-3, schedules=None, minima=None):
+    def iteration(self, rows, epochs=3, minibatch=512, lr=3e-4, eps=0.2, beta=5e-3, schedules=None, minima=None, **update_opts):
         """rollout begin, step, close; episode_stats of the learner; elo_apply against the current opponent; advantages; update with the
-        scheduled values; then save / swap when due.  -> dict"""
+        scheduled values (update_opts: max_grad_norm / target_kl, passed through; the result then has "report"); then save / swap when due.  -> dict"""
         env, tr = self.env, self.trainer
         env.rollout_begin(rows)
         env.step(int(rows) * env._decision_period)
@@ -207,8 +262,14 @@ class SelfPlay:
         self.record_results(stats["wins"], stats["draws"], stats["losses"])
         lr_t, eps_t, beta_t = self.scheduled(lr, eps, beta, schedules, minima)
         tr.advantages()
-        upd = tr.update(epochs, minibatch, lr_t, eps_t, beta_t)
+        bad = set(update_opts) - {"max_grad_norm", "target_kl"}
+        if bad:
+            raise TypeError("iteration: unknown update options %s" % sorted(bad))
+        upd = tr.update(epochs, minibatch, lr_t, eps_t, beta_t, **update_opts)
         n = env.rollout_rows() * env.E * len(env._policy_slots[tr.index])
         saved, swapped = self.advance(n)
-        return dict(stats=stats, update=upd, elo=self.elo, played=played, lr=lr_t, eps=eps_t, beta=beta_t, steps=self.steps, saved=saved,
-                    swapped=swapped, opponent=self.opponent, opponent_elo=self.opponent_elo())
+        out = dict(stats=stats, update=upd, elo=self.elo, played=played, lr=lr_t, eps=eps_t, beta=beta_t, steps=self.steps, saved=saved,
+                   swapped=swapped, opponent=self.opponent, opponent_elo=self.opponent_elo())
+        if update_opts:
+            out["report"] = tr.last_report
+        return out

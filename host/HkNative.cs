@@ -28,7 +28,7 @@ namespace KartGame.AI.Native
                          HK_RO_TERM_GROUP_REWARD = 12, HK_RO_DONE = 13, HK_RO_RING0 = 14, HK_RO_NEXT_OBS = 15, HK_RO_FIELDS = 16;
         // hk_ppo_field: the PPO trainer's buffers (hk_ppo_ptr / hk_ppo_count); HK_PPO_STATS: L_pi, L_v, entropy, approx-KL, clip fraction, skipped rows
         public const int HK_PPO_PARAMS = 0, HK_PPO_GRAD = 1, HK_PPO_ADAM_M = 2, HK_PPO_ADAM_V = 3, HK_PPO_V_OLD = 4, HK_PPO_ADV = 5, HK_PPO_RET = 6,
-                         HK_PPO_MB_MU = 7, HK_PPO_MB_LOGITS = 8, HK_PPO_MB_VALUE = 9, HK_PPO_PERM = 10, HK_PPO_SHADOW = 11, HK_PPO_NORM_MEAN = 12, HK_PPO_NORM_STD = 13, HK_PPO_FIELDS = 14,
+                         HK_PPO_MB_MU = 7, HK_PPO_MB_LOGITS = 8, HK_PPO_MB_VALUE = 9, HK_PPO_PERM = 10, HK_PPO_SHADOW = 11, HK_PPO_NORM_MEAN = 12, HK_PPO_NORM_STD = 13, HK_PPO_CLIP = 14, HK_PPO_FIELDS = 15,
                          HK_PPO_PREC_F32 = 0, HK_PPO_PREC_BF16 = 1,
                          HK_POLICY_PREC_F32 = 0, HK_POLICY_PREC_BF16 = 1,      // hk_policy_precision
                          HK_PPO_STATS = 6;
@@ -370,6 +370,34 @@ namespace KartGame.AI.Native
         public uint seed;
     }
 
+    // hk_ppo_update_opts / hk_ppo_update_report: hk_ppo_update_opt's options (0: off) and what it did (hk.h "LONG RUNS")
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HkPpoUpdateOpts
+    {
+        public int epochs;
+        public int minibatch;
+        public float lr;
+        public float eps;
+        public float beta;
+        public float max_grad_norm;
+        public float target_kl;
+        public int reserved;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HkPpoUpdateReport
+    {
+        public int epochs_run;
+        public int minibatches_run;
+        public int stopped_by_kl;
+        public int clipped_steps;
+        public int nonfinite_steps;
+        public int reserved;
+        public double last_epoch_kl;
+        public double grad_norm_mean;
+        public double grad_norm_max;
+    }
+
     // hk_episode_stats: returns, lengths and outcomes of the closed rollout's episodes (hk.h "SELF-PLAY")
     [StructLayout(LayoutKind.Sequential)]
     public struct HkEpisodeStats
@@ -462,6 +490,11 @@ namespace KartGame.AI.Native
         [DllImport(Lib)] public static extern int hk_ppo_normalizer_update(IntPtr h, int trainer);
         [DllImport(Lib)] public static extern int hk_ppo_normalizer_get(IntPtr h, int trainer, long* steps, double* mean, double* m2);
         [DllImport(Lib)] public static extern int hk_ppo_normalizer_set(IntPtr h, int trainer, long steps, double* mean, double* m2);
+        // long runs: clip by the global norm, KL stop, and the two counters a resumed trainer needs
+        [DllImport(Lib)] public static extern int hk_ppo_update_opt(IntPtr h, int trainer, HkPpoUpdateOpts* o, float* stats, HkPpoUpdateReport* report);
+        [DllImport(Lib)] public static extern int hk_ppo_adam_clipped(IntPtr h, int trainer, float lr, float maxGradNorm);
+        [DllImport(Lib)] public static extern int hk_ppo_get_counters(IntPtr h, int trainer, long* adamSteps, long* epochsDone);
+        [DllImport(Lib)] public static extern int hk_ppo_set_counters(IntPtr h, int trainer, long adamSteps, long epochsDone);
         // self-play (hk.h "SELF-PLAY"): device slots of saved actors, loaded into an attached opponent; episode statistics of the closed rollout
         [DllImport(Lib)] public static extern int hk_policy_pool_create(IntPtr h, int policy, int slots);
         [DllImport(Lib)] public static extern int hk_policy_pool_save(IntPtr h, int pool, int slot, int policy);

@@ -618,8 +618,42 @@ void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* 
  * next rollout on, rho == 1 and the bit-equal training forward hold as above, in both precisions.  A dimension that never varies keeps M2_k at its
  * initial value, so its std shrinks as 1 / sqrt(N): ML-Agents' behaviour, not guarded.
  * HK_PPO_NORM_MEAN / HK_PPO_NORM_STD (hk_ppo_ptr): the policy's published fp32 statistics themselves, [in_dim]; count 0 on normalize == 0.
+ * LONG RUNS (hk_ppo_update_opt, hk_ppo_adam_clipped, hk_ppo_get_counters / hk_ppo_set_counters; opt-in: a trainer that never calls them computes
+ * what it computed, bit for bit, and allocates nothing more).  Neither clipping nor the KL stop is in ML-Agents' PPO; both are additions.
+ * CLIP by the global L2 norm of the whole flat GRAD vector, actor and critic together (one optimiser, one norm: torch's clip_grad_norm_ over
+ * all parameters), computed on the device:
+ *   norm2 = sum_i (double)g_i (double)g_i in fp64 (a square of an fp32 value is exact in fp64; the only error is the fp64 additions), over a
+ *   partition of GRAD into runs of 4096 elements and in an order both fixed by P alone, no atomics: the same call on the same state gives the
+ *   same bits;  norm = sqrt(norm2) in fp64, correctly rounded;  coef = (float) min(1.0, (double)max_grad_norm / (norm + 1e-6)), rounded to fp32
+ *   once (torch's clip_coef and clamp).  The step is ADAM above, operation for operation, on g'_i = g_i * coef (one fp32 multiply, rounded, no
+ *   fused multiply-add); GRAD itself stays as the minibatch wrote it.  With coef == 1.0f the multiply is exact: max_grad_norm = +inf ("measure
+ *   only") and any bound above the norm give exactly the bits of the plain step.
+ * NON-FINITE GRADIENT: when norm2 is not finite (a NaN or an Inf anywhere in GRAD) the step writes nothing — PARAMS, ADAM_M and ADAM_V keep their
+ * bits — and is counted in CLIP[4]; CLIP[1] is then 0.  Documented departure: the step count s still advances (the host cannot know without a
+ * synchronise), so the bias corrections of the following steps are those of one step more.
+ * HK_PPO_CLIP (hk_ppo_ptr; fp64 [8]; count 0 before the first clip-aware step has allocated it): [0] norm and [1] coef (the fp32 value widened) of
+ * the last clip-aware step; [2] steps taken, [3] steps with coef < 1, [4] non-finite steps, [5] the sum and [6] the maximum of norm over the finite
+ * steps; [7] reserved, 0.  [2 .. 6] accumulate: zero at hk_ppo_create and zeroed, stream-ordered, at the entry of hk_ppo_update_opt.
+ *   hk_ppo_adam_clipped  one clip-aware step from GRAD; max_grad_norm > 0 (+inf allowed), anything else — 0, a negative, a NaN — is refused.
+ *   hk_ppo_update_opt    hk_ppo_update's loop (they share it) with two options; with both 0 the launches issued are exactly hk_ppo_update's.
+ *                        max_grad_norm > 0: every step is the clip-aware one.  target_kl > 0, the KL STOP: the stats accumulator is zeroed at the
+ *                        start of every epoch and read after its last step (one 64-byte copy and a synchronise per epoch, only in this mode); if
+ *                        that epoch's mean approx-KL is > target_kl no further epoch runs.  stats is then that epoch's mean, the epoch count has
+ *                        advanced by the epochs actually run (the next update's permutation key follows on), PERM is the last epoch run, and
+ *                        hk_ppo_publish happens as usual.  The first epoch always runs.  Per epoch, not per minibatch, on purpose: a read per
+ *                        minibatch would serialise the launch-bound small-minibatch update.
+ *                        report (or NULL; non-NULL synchronises): epochs_run, minibatches_run, stopped_by_kl; clipped_steps, nonfinite_steps,
+ *                        grad_norm_mean (over the finite steps) and grad_norm_max of this call from CLIP (0 with clipping off); last_epoch_kl,
+ *                        stats[3] in fp64 before rounding.
+ *   hk_ppo_get_counters / hk_ppo_set_counters   the Adam step count s (it gives c1, c2) and the epoch count k (it keys the shuffle as (seed, k)):
+ *                        the missing piece of RESUME.  A caller restores PARAMS / ADAM_M / ADAM_V through hk_ppo_ptr, the normaliser through
+ *                        hk_ppo_normalizer_set, and these two words; a trainer restored so and fed the same rollout continues bit for bit.  set
+ *                        takes 0 <= each <= INT32_MAX, is refused while a rollout is open (as hk_ppo_publish is) and leaves the advantages as
+ *                        valid as they were.  Either pointer of get may be NULL.
+ * Refused with HK_ERR_INVALID and a message naming the argument, state as it was: a NULL opts, epochs < 1, minibatch < 1, max_grad_norm or target_kl
+ * negative or NaN, target_kl infinite, reserved != 0, and whatever hk_ppo_update / hk_ppo_adam refuse.
  * Out of scope (self-play opponent swaps, episode statistics and ELO: "SELF-PLAY" below): POCA and group rewards, LSTM memory, a normaliser for policies attached with normalize == 0,
- * gradient clipping, multi-GPU gradient all-reduce and bf16 optimiser state.  Everything is asynchronous on hk_stream unless noted. */
+ * multi-GPU gradient all-reduce and bf16 optimiser state.  Everything is asynchronous on hk_stream unless noted. */
 #define HK_PPO_STATS 6
 typedef struct hk_ppo_config {
     float gamma;                    /* 0.99 */
@@ -636,6 +670,7 @@ typedef enum hk_ppo_field {
     HK_PPO_SHADOW,      /* uint16 [P + pad]: PARAMS as bf16; the actor's element i at i, the critic's at i + pad, pad = (8 - n_actor % 8) % 8; once
                            the trainer has been in HK_PPO_PREC_BF16 */
     HK_PPO_NORM_MEAN, HK_PPO_NORM_STD,      /* fp32 [in_dim]: the attached policy's published statistics (NORMALISER) */
+    HK_PPO_CLIP,        /* fp64 [8]: the result words of the clip-aware step (LONG RUNS); once a clip-aware step has run */
     HK_PPO_FIELDS
 } hk_ppo_field;
 typedef enum { HK_PPO_PREC_F32 = 0, HK_PPO_PREC_BF16 = 1 } hk_ppo_precision;
@@ -655,6 +690,20 @@ int hk_ppo_normalizer_init(hk_handle h, int trainer, int64_t steps);
 int hk_ppo_normalizer_update(hk_handle h, int trainer);
 int hk_ppo_normalizer_get(hk_handle h, int trainer, int64_t* steps, double* mean /*[in_dim]*/, double* m2 /*[in_dim]*/);
 int hk_ppo_normalizer_set(hk_handle h, int trainer, int64_t steps, const double* mean /*[in_dim]*/, const double* m2 /*[in_dim]*/);
+typedef struct hk_ppo_update_opts {
+    int32_t epochs, minibatch; float lr, eps, beta;
+    float max_grad_norm;   /* 0: off (the plain Adam kernel, no norm); > 0, +inf allowed: clip-aware step; < 0 or NaN: refused */
+    float target_kl;       /* 0: off; > 0: stop after an epoch whose mean approx-KL exceeds it; < 0 or NaN: refused */
+    int32_t reserved;      /* 0 */
+} hk_ppo_update_opts;
+typedef struct hk_ppo_update_report {
+    int32_t epochs_run, minibatches_run, stopped_by_kl, clipped_steps, nonfinite_steps, reserved;
+    double last_epoch_kl, grad_norm_mean, grad_norm_max;    /* the norm figures 0 with clipping off */
+} hk_ppo_update_report;
+int hk_ppo_update_opt(hk_handle h, int trainer, const hk_ppo_update_opts* o, float* stats /*[HK_PPO_STATS] or NULL*/, hk_ppo_update_report* report /*or NULL*/);
+int hk_ppo_adam_clipped(hk_handle h, int trainer, float lr, float max_grad_norm);   /* one clip-aware step from GRAD; max_grad_norm > 0 */
+int hk_ppo_get_counters(hk_handle h, int trainer, int64_t* adam_steps, int64_t* epochs_done);
+int hk_ppo_set_counters(hk_handle h, int trainer, int64_t adam_steps, int64_t epochs_done);   /* 0 <= each <= INT32_MAX, else refused */
 
 /* ---- SELF-PLAY: snapshot pool, opponent swaps, episode statistics of a closed rollout -------------------------------------
  * What ML-Agents' `self_play:` block needs of the library; the driver (window, save_steps / swap_steps, ELO, the linear schedules) is host

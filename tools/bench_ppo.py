@@ -7,6 +7,9 @@ the other timings run on what they always ran on), and the self-play facilities 
 (episode_stats_ms), hk_policy_pool_save of team 0's actor into a pool slot and hk_policy_pool_load of that slot into team 1's actor, which has
 no trainer (pool_save_ms, pool_load_ms; the load runs last, after every other timing); every timing ends in a device synchronise, medians of --repeats.  One JSON line per --precision; with several, the precisions alternate round by round
 (after a switch: advantages and one untimed update at the large minibatch, which allocate the workspace of that precision).
+--max-grad-norm C / --target-kl T (hk.h "LONG RUNS"): every plain update window is followed, in the same round, by a window of the same update
+with the clip-aware step (C = inf measures only) and / or with the per-epoch KL read (a T above any KL stops nothing): clip_* and kl_* per
+minibatch size, each with its ratio to the same process's plain update.
 FLOP count per trained row (stated, not measured): forward + backward of actor and critic = 3 x forward, forward = 2 x (weights of the trunks
 and heads) per row: 3 x 2 x (312 x 256 + 2 x 256 x 256 + 4 x 256 + 312 x 256 + 2 x 256 x 256 + 256) = 6 x 423 168 = 2.54 MFLOP per row at this shape."""
 import argparse
@@ -29,6 +32,8 @@ def main():
     ap.add_argument("--big", type=int, default=32768, help="the GPU-sized minibatch")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--precision", nargs="+", choices=("f32", "bf16"), default=["f32"], help="hk_ppo_set_precision; several: alternated")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="also time the update with this global-norm bound (inf: measure only)")
+    ap.add_argument("--target-kl", type=float, default=None, help="also time the update with this KL stop (above any KL: nothing stops)")
     a = ap.parse_args()
     import numpy as np
     import hierarchicalkarting_amd as hk
@@ -53,7 +58,9 @@ def main():
     w = K0 * H + 2 * H * H + 4 * H + K0 * H + 2 * H * H + H
     flop_row = 3 * 2 * w
     sizes = (a.big, 512)
-    runs = {p: {"adv": [], "norm": [], **{mb: [] for mb in sizes}} for p in a.precision}
+    extras = {k: v for k, v in (("clip", {"max_grad_norm": a.max_grad_norm}), ("kl", {"target_kl": a.target_kl})) if list(v.values())[0] is not None}
+    runs = {p: {"adv": [], "norm": [], **{mb: [] for mb in sizes}, **{(k, mb): [] for k in extras for mb in sizes}} for p in a.precision}
+    reports = {}
     # what hk_ppo_normalizer_update reads, once each: the trainer's slots of OBS [R][E][S][D] and FIRST [R][E][S], RING0 [E][S][stack - 1][D]
     D, S, stack = env.obs_dim, 2, 4
     norm_bytes = 4 * (R * E * S * D + R * E * S + E * S * (stack - 1) * D)
@@ -87,6 +94,9 @@ def main():
             runs[prec]["adv"].append(timed(tr.advantages))
             for mb in sizes:
                 runs[prec][mb].append(timed(lambda: tr.update(1, mb, 1e-5, 0.2, 5e-3)))
+                for k, opt in extras.items():
+                    runs[prec][(k, mb)].append(timed(lambda: tr.update(1, mb, 1e-5, 0.2, 5e-3, **opt)))
+                    reports[(prec, k, mb)] = tr.last_report
             runs[prec]["norm"].append(timed(tr.normalizer_update))
             tr.normalizer_load(*norm_state)
     sp_runs["load"] = [timed(lambda: pool.load(0, 1)) for _ in range(a.repeats + 1)][1:]       # (the first call is the warm-up)
@@ -103,12 +113,16 @@ def main():
             tf = rows * flop_row / (ms * 1e-3) / 1e12
             res[str(mb)] = {"update_ms_per_epoch": ms, "runs": runs[prec][mb], "rows_per_s": rows / (ms * 1e-3), "tflops": tf,
                             "peak_fraction": tf / PEAK_TF[prec], "update_over_collection": ms / collect_ms}
+            for k in extras:
+                xs = runs[prec][(k, mb)]
+                res[str(mb)].update({k + "_update_ms_per_epoch": statistics.median(xs), k + "_runs": xs, k + "_over_plain": statistics.median(xs) / ms,
+                                     k + "_report": reports[(prec, k, mb)]})
         print(json.dumps({"metric": "PPO update on the RL workload (one actor + critic, one epoch)", "precision": prec,
                           "advantages_ms": statistics.median(runs[prec]["adv"]), "advantages_runs": runs[prec]["adv"], "collect_ms": collect_ms,
                           "normalizer_ms": statistics.median(runs[prec]["norm"]), "normalizer_runs": runs[prec]["norm"], "normalizer_bytes": norm_bytes,
                           "normalizer_hbm_fraction": norm_bytes / (statistics.median(runs[prec]["norm"]) * 1e-3) / (PEAK_HBM_TB * 1e12),
                           **selfplay, "minibatch": res, "config": {"envs": E, "agents": A, "rows": R, "n_rows": n, "flop_per_row": flop_row,
-                                                       "peak_tflops": PEAK_TF[prec]}}))
+                                                       "peak_tflops": PEAK_TF[prec], "max_grad_norm": None if a.max_grad_norm is None else str(a.max_grad_norm), "target_kl": a.target_kl}}))
 
 
 if __name__ == "__main__":
