@@ -8,6 +8,7 @@ from .lq import solve_feedback_lqr, solve_feedback_lqr_batch  # noqa: F401
 from .env import RacingEnv  # noqa: F401
 from .config import make_config  # noqa: F401
 from .policy import Policy  # noqa: F401
+from .poca import PocaCritic, POCATrainer  # noqa: F401
 from .selfplay import SnapshotPool, SelfPlay, elo_expected, elo_apply, linear_schedule  # noqa: F401
 
 

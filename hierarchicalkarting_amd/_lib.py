@@ -39,6 +39,9 @@ HK_PPO_STATS = 6
 HK_PPO_PREC_F32, HK_PPO_PREC_BF16 = 0, 1
 HK_POLICY_PREC_F32, HK_POLICY_PREC_BF16 = 0, 1
 PPO_STAT_NAMES = ("L_pi", "L_v", "entropy", "approx_kl", "clip_fraction", "skipped")
+# POCA trainer (hk_poca_field; hk.h "POCA")
+POCA_FIELDS = {"b_old": 0, "mb_baseline": 1, "team_reward": 2}
+HK_POCA_FIELDS, HK_POCA_STATS, HK_POCA_MAX_GROUP, HK_POCA_HEADS = 3, 2, 4, 4
 PPO_CLIP_NAMES = ("norm", "coef", "steps", "clipped", "nonfinite", "norm_sum", "norm_max", "reserved")      # the HK_PPO_CLIP words (hk.h "LONG RUNS")
 HK_F_ACCEL, HK_F_BRAKE, HK_F_ACTIVE, HK_F_FORWARD_COLLISION, HK_F_HAS_COLLISION, HK_F_CAN_MOVE, HK_F_ENABLED = (1 << i for i in range(7))
 
@@ -188,6 +191,12 @@ class PpoUpdateReport(C.Structure):
         (n, C.c_double) for n in ("last_epoch_kl", "grad_norm_mean", "grad_norm_max")]
 
 
+class PocaCriticDesc(C.Structure):
+    _fields_ = [("hidden", C.c_int32), ("n_layers", C.c_int32), ("reserved0", C.c_int32), ("reserved1", C.c_int32)] + [
+        (n, _fp) for n in ("W_obs", "b_obs", "W_act", "b_act", "W_q", "b_q", "W_k", "b_k", "W_v", "b_v", "W_out", "b_out")] + [
+        ("W", _fp * HK_POLICY_MAX_LAYERS), ("b", _fp * HK_POLICY_MAX_LAYERS), ("w_val", _fp), ("b_val", _fp)]
+
+
 class EpisodeStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("episodes", "partial", "wins", "draws", "losses", "timeouts", "len_sum")] + [
         (n, C.c_double) for n in ("ret_sum", "ret_sumsq", "ret_min", "ret_max", "gret_sum", "gret_sumsq")]
@@ -254,6 +263,10 @@ SYMBOLS = {
     "hk_ppo_adam_clipped": (C.c_int, [_H, C.c_int, C.c_float, C.c_float]),
     "hk_ppo_get_counters": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "hk_ppo_set_counters": (C.c_int, [_H, C.c_int, C.c_int64, C.c_int64]),
+    "hk_ppo_create_poca": (C.c_int, [_H, C.c_int, C.POINTER(PocaCriticDesc), C.POINTER(PpoConfig)]),
+    "hk_poca_ptr": (C.c_void_p, [_H, C.c_int, C.c_int]),
+    "hk_poca_count": (C.c_int, [_H, C.c_int, C.c_int]),
+    "hk_poca_stats": (C.c_int, [_H, C.c_int, _fp]),
     "hk_policy_pool_create": (C.c_int, [_H, C.c_int, C.c_int]),
     "hk_policy_pool_save": (C.c_int, [_H, C.c_int, C.c_int, C.c_int]),
     "hk_policy_pool_load": (C.c_int, [_H, C.c_int, C.c_int, C.c_int]),

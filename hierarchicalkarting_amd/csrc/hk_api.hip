@@ -16,6 +16,7 @@
 #include "hk_policy.h"
 #include "hk_rollout.h"
 #include "hk_ppo.h"
+#include "hk_poca.h"
 #include "hk_selfplay.h"
 #include <dlfcn.h>
 
@@ -234,6 +235,15 @@ struct hk_context {
         bool adv_stale = false;        // the policy's statistics changed after hk_ppo_advantages: V_OLD is the critic on other inputs
         double* clip = nullptr;        // hk.h "LONG RUNS" (nothing before the first clip-aware step): the HK_PPO_CLIP words [8], then the norm's partials [clip_parts]
         int clip_parts = 0;
+        // a POCA trainer (hk.h "POCA"; hk_ppo_create_poca; nothing of this is touched for a PPO trainer): `critic` stays empty, the attention
+        // critic's layout is pnet, its rows (B_OLD, TEAM_REWARD [n]) and its minibatch workspace of pcap groups are allocations of their own
+        bool poca = false;
+        hk::PocaNet pnet;
+        float* prow = nullptr;
+        size_t prow_n = 0;
+        void* pws = nullptr;
+        int pcap = 0, last_mg = 0;
+        bool lb_from_update = false;   // hk_poca_stats: the last L_b came from an update's accumulator
     } ppo[HK_MAX_POLICIES];
     int n_ppo = 0;
     // self-play (hk.h "SELF-PLAY"; hk_selfplay.h); nothing is allocated before the first hk_policy_pool_create / hk_rollout_episode_stats
@@ -424,7 +434,7 @@ void hk_destroy(hk_handle h)
     if (h->pol_scratch) (void)hipFree(h->pol_scratch);
     if (h->ro.buf) (void)hipFree(h->ro.buf);
     for (int p = 0; p < HK_MAX_POLICIES; p++) hk::policy_free(h->policy[p]);
-    for (auto& t : h->ppo) { if (t.param) (void)hipFree(t.param); if (t.rowbuf) (void)hipFree(t.rowbuf); if (t.ws) (void)hipFree(t.ws); if (t.shadow) (void)hipFree(t.shadow); if (t.norm) (void)hipFree(t.norm); if (t.norm_part) (void)hipFree(t.norm_part); if (t.clip) (void)hipFree(t.clip); }
+    for (auto& t : h->ppo) { if (t.param) (void)hipFree(t.param); if (t.rowbuf) (void)hipFree(t.rowbuf); if (t.ws) (void)hipFree(t.ws); if (t.shadow) (void)hipFree(t.shadow); if (t.norm) (void)hipFree(t.norm); if (t.norm_part) (void)hipFree(t.norm_part); if (t.clip) (void)hipFree(t.clip); if (t.prow) (void)hipFree(t.prow); if (t.pws) (void)hipFree(t.pws); }
     for (auto& pl : h->pool) if (pl.buf) (void)hipFree(pl.buf);
     if (h->ep.buf) (void)hipFree(h->ep.buf);
     h->prof.fold();
@@ -1591,9 +1601,240 @@ void ppo_trunk_backward(hipStream_t s, const PpoWs& w, const hk_context::Ppo& t,
     }
 }
 
+// ---- POCA (hk.h "POCA"; device side in hk_poca.h).  Everything below is reached only through a trainer made by hk_ppo_create_poca.
+
+// the POCA workspace at a capacity of G groups: m = G S agent rows, E2 = 2 m entities, NS = (S + 1) G sequences, SR = NS S sequence rows
+struct PocaWs {
+    int *gids, *rid;
+    float *XA, *Zent, *U, *N, *Q, *K, *V, *C, *alpha, *Oz, *O, *Zp;
+    float2 *estat, *ostat;
+    float *Ze[HK_POLICY_MAX_LAYERS], *Ae[HK_POLICY_MAX_LAYERS];
+    float *out, *vrow, *brow, *mb_v, *dout, *d0, *d1, *dZp, *dPre, *dC, *dQs, *dKs, *dVs, *dQ, *dK, *dV, *dR, *dNq, *dNk, *dNv, *dZent, *part;
+    double *rowstat_b, *pacc;
+    float *pstats, *consts;          // consts: {1.0f, 0.0f}
+};
+
+size_t poca_ws_layout(const hk_context::Ppo& t, int S, int G, PocaWs* w)
+{
+    size_t off = 0;
+    char* base = w ? (char*)t.pws : nullptr;
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
+    auto fl = [&](size_t count) { return (float*)take(count * 4); };
+    const hk::PocaNet& pn = t.pnet;
+    const size_t H = pn.hidden, m = (size_t)G * S, E2 = 2 * m, NS = (size_t)(S + 1) * G, SR = NS * S;
+    PocaWs d{};
+    d.gids = (int*)take((size_t)G * 4); d.rid = (int*)take(m * 4);
+    d.XA = fl(m * pn.n_act);
+    d.Zent = fl(E2 * H); d.U = fl(E2 * H); d.N = fl(E2 * H); d.Q = fl(E2 * H); d.K = fl(E2 * H); d.V = fl(E2 * H);
+    d.C = fl(SR * H); d.alpha = fl(NS * hk::POCA_HEADS * hk::POCA_MAXS * hk::POCA_MAXS); d.Oz = fl(SR * H); d.O = fl(SR * H); d.Zp = fl(NS * H);
+    d.estat = (float2*)take(E2 * 8); d.ostat = (float2*)take(SR * 8);
+    for (int l = 0; l < pn.n_layers; l++) { d.Ze[l] = fl(NS * H); d.Ae[l] = fl(NS * H); }
+    d.out = fl(NS); d.vrow = fl(m); d.brow = fl(m); d.mb_v = fl(G); d.dout = fl(NS);
+    d.d0 = fl(NS * H); d.d1 = fl(NS * H); d.dZp = fl(NS * H);
+    d.dPre = fl(SR * H); d.dC = fl(SR * H); d.dQs = fl(SR * H); d.dKs = fl(SR * H); d.dVs = fl(SR * H);
+    d.dQ = fl(E2 * H); d.dK = fl(E2 * H); d.dV = fl(E2 * H); d.dR = fl(E2 * H); d.dNq = fl(E2 * H); d.dNk = fl(E2 * H); d.dNv = fl(E2 * H); d.dZent = fl(E2 * H);
+    const size_t nz = (std::max(SR, E2) + hk::PPO_KCH - 1) / hk::PPO_KCH;          // the longest weight gradient's chunks, the largest one's tile
+    d.part = fl(nz * H * std::max((size_t)pn.n_act, H));
+    d.rowstat_b = (double*)take(m * 8); d.pacc = (double*)take(2 * 8);
+    d.pstats = fl(HK_POCA_STATS); d.consts = fl(2);
+    if (w) *w = d;
+    return off;
+}
+
+int poca_ensure_ws(hk_handle h, hk_context::Ppo& t, int S, int G, PocaWs& w)
+{
+    if (G > t.pcap) {
+        if (t.pws) HK_HIP(h, hipFree(t.pws));
+        t.pws = nullptr; t.pcap = 0; t.last_mg = 0;
+        HK_HIP(h, hipMalloc(&t.pws, poca_ws_layout(t, S, G, nullptr)));
+        t.pcap = G;
+        poca_ws_layout(t, S, t.pcap, &w);
+        const float c[2] = {1.0f, 0.0f};
+        HK_HIP(h, hipMemcpyAsync(w.consts, c, sizeof(c), hipMemcpyHostToDevice, h->stream));
+        HK_HIP(h, hipMemsetAsync(w.pacc, 0, 2 * sizeof(double), h->stream));
+        HK_HIP(h, hipStreamSynchronize(h->stream));          // (c is on this frame)
+    }
+    poca_ws_layout(t, S, t.pcap, &w);
+    return HK_OK;
+}
+
+// the rows' extra buffer of a POCA trainer: B_OLD, TEAM_REWARD [n]
+struct PocaRowBuf { float *b_old, *team; };
+PocaRowBuf poca_rowbuf(const hk_context::Ppo& t) { return PocaRowBuf{t.prow, t.prow + t.n}; }
+
+// a plain fp32 product C [M][N] = EPI(A [M][K] B^T + bias), B [N][K] (a weight as stored) ...
+template <int EPI>
+void poca_lin(hipStream_t s, int M, int N, int K, const float* A, const float* W, const float* bias, float* C, float* Z)
+{
+    ppo_product<EPI>(s, M, N, K, PpoMat(const_cast<float*>(A)), K, true, PpoMat(const_cast<float*>(W)), K, true, bias, PpoMat(C), N, Z, K);
+}
+// ... and C [M][N] = EPI(A [M][K] B), B [K][N]: a delta through a weight
+template <int EPI>
+void poca_lin_t(hipStream_t s, int M, int N, int K, const float* A, const float* W, float* C, float* Z)
+{
+    ppo_product<EPI>(s, M, N, K, PpoMat(const_cast<float*>(A)), K, true, PpoMat(const_cast<float*>(W)), N, false, nullptr, PpoMat(C), N, Z, K);
+}
+
+// the critic's forward over the groups gids[0 .. mg): gather (X0, valid of the PPO workspace w), embeddings, attention, encoder, the head -> pw.out [NS]
+void poca_forward(hipStream_t s, const hk_context::Ppo& t, const hk::PpoRows& P, const PpoWs& w, const PocaWs& pw, const int* gids, int mg, int boot)
+{
+    const hk::PocaNet& pn = t.pnet;
+    const float* prm = t.param;
+    const int S = P.S, H = pn.hidden, in = pn.in_dim, na = pn.n_act, m = mg * S, E2 = 2 * m, NS = (S + 1) * mg, SR = NS * S;
+    hipLaunchKernelGGL(hk::poca_rows_kernel, dim3(nblk(m)), dim3(256), 0, s, gids, mg, S, P.R * P.E, P.E, boot, pw.rid);
+    ppo_gather(s, P, pw.rid, m, boot, w.X0, w.valid);
+    hipLaunchKernelGGL(hk::poca_actfeat_kernel, dim3(nblk((size_t)m * na)), dim3(256), 0, s, P, pw.rid, m, w.X0.f, pw.XA, pn.n_branch);
+    poca_lin<1>(s, m, H, in, w.X0.f, prm + pn.oWobs, prm + pn.obobs, pw.U, pw.Zent);
+    poca_lin<1>(s, m, H, na, pw.XA, prm + pn.oWact, prm + pn.obact, pw.U + (size_t)m * H, pw.Zent + (size_t)m * H);
+    hipLaunchKernelGGL(hk::poca_ln_kernel<false>, dim3(nblk(E2, 4)), dim3(256), 0, s, pw.U, nullptr, E2, H, S, m, pw.N, pw.estat);
+    poca_lin<0>(s, E2, H, H, pw.N, prm + pn.oWq, prm + pn.obq, pw.Q, nullptr);
+    poca_lin<0>(s, E2, H, H, pw.N, prm + pn.oWk, prm + pn.obk, pw.K, nullptr);
+    poca_lin<0>(s, E2, H, H, pw.N, prm + pn.oWv, prm + pn.obv, pw.V, nullptr);
+    hipLaunchKernelGGL(hk::poca_attn_fwd_kernel, dim3(nblk(NS, 4)), dim3(256), 0, s, pw.Q, pw.K, pw.V, NS, S, m, H, pw.C, pw.alpha);
+    poca_lin<0>(s, SR, H, H, pw.C, prm + pn.oWout, prm + pn.obout, pw.Oz, nullptr);
+    hipLaunchKernelGGL(hk::poca_ln_kernel<true>, dim3(nblk(SR, 4)), dim3(256), 0, s, pw.Oz, pw.N, SR, H, S, m, pw.O, pw.ostat);
+    hipLaunchKernelGGL(hk::poca_pool_kernel, dim3(nblk((size_t)NS * H)), dim3(256), 0, s, pw.O, NS, S, H, pw.Zp);
+    for (int l = 0; l < pn.n_layers; l++) poca_lin<1>(s, NS, H, H, l == 0 ? pw.Zp : pw.Ae[l - 1], prm + pn.oW[l], prm + pn.ob[l], pw.Ae[l], pw.Ze[l]);
+    hipLaunchKernelGGL(hk::poca_value_kernel, dim3(nblk(NS)), dim3(256), 0, s, pw.Ae[pn.n_layers - 1], NS, H, prm + pn.owval, prm + pn.obval, pw.out);
+}
+
+// one POCA minibatch of mg group ids: the actor side is ppo_mb's, launch for launch; the critic side is the attention critic
+int poca_mb(hk_handle h, hk_context::Ppo& t, const int32_t* gids, int mg, float eps, float beta, bool acc)
+{
+    const hk::PpoRows P = ppo_rows(h, t);
+    const int S = P.S, m = mg * S;
+    PpoWs w;
+    PocaWs pw;
+    int rc = ppo_ensure_ws(h, t, m, w);
+    if (rc) return rc;
+    if ((rc = poca_ensure_ws(h, t, S, mg, pw))) return rc;
+    hipStream_t s = h->stream;
+    const PpoRowBuf rows = ppo_rowbuf(h, t);
+    const PocaRowBuf prows = poca_rowbuf(t);
+    const float* prm = t.param;
+    float* grad = t.param + t.P;
+    const hk::PpoNet& na = t.actor;
+    const hk::PocaNet& pn = t.pnet;
+    const int Ha = na.hidden, nb = na.n_branch, La = na.n_layers - 1, H = pn.hidden, L = pn.n_layers;
+    const int E2 = 2 * m, NS = (S + 1) * mg, SR = NS * S;
+    poca_forward(s, t, P, w, pw, gids, mg, 0);
+    hipLaunchKernelGGL(hk::poca_scatter_kernel, dim3(nblk(m)), dim3(256), 0, s, pw.out, pw.rid, m, S, t.n, 0, nullptr, nullptr, nullptr, pw.vrow, pw.brow, pw.mb_v);
+    hipLaunchKernelGGL(hk::ppo_count_kernel, dim3(1), dim3(256), 0, s, w.valid, m, w.n_valid);
+    ppo_trunk_forward(s, t, na, w.X0, m, w.Za, w.Aa);
+    // ppo_loss_kernel as it is: its "critic activation" is the row's group value, one wide, under the head (1, 0), so v = fmaf(V, 1, 0) = V
+    hk::PpoLossArgs Lo{};
+    Lo.Aa = w.Aa[La].f; Lo.Ac = pw.vrow;
+    Lo.W_mu = prm + na.oWmu; Lo.b_mu = prm + na.obmu; Lo.log_sigma = prm + na.ols; Lo.W_br = prm + na.oWbr; Lo.b_br = prm + na.obbr;
+    Lo.W_v = pw.consts; Lo.b_v = pw.consts + 1;
+    Lo.v_old = rows.v_old; Lo.adv = rows.adv; Lo.ret = rows.ret;
+    Lo.ids = pw.rid; Lo.valid = w.valid; Lo.n_valid = w.n_valid; Lo.m = m; Lo.n = t.n; Lo.Ha = Ha; Lo.Hc = 1; Lo.nb = nb;
+    Lo.eps = eps; Lo.beta = beta;
+    Lo.dhead = w.dhead; Lo.dls = w.dls; Lo.dv = w.dv; Lo.rowstat = w.rowstat;
+    Lo.mu_out = w.mb_mu; Lo.logit_out = w.mb_logits; Lo.v_out = w.mb_v;
+    hipLaunchKernelGGL(hk::ppo_loss_kernel, dim3(nblk(m)), dim3(256), 0, s, P, Lo);
+    hipLaunchKernelGGL(hk::ppo_stats_kernel, dim3(1), dim3(256), 0, s, w.rowstat, m, w.stats, acc ? w.acc : nullptr);
+    hipLaunchKernelGGL(hk::poca_loss_kernel, dim3(nblk(mg)), dim3(256), 0, s, pw.brow, pw.rid, w.valid, w.n_valid, prows.b_old, rows.ret, w.dv, mg, S, t.n, eps,
+                       pw.dout, pw.rowstat_b);
+    hipLaunchKernelGGL(hk::poca_stats_kernel, dim3(1), dim3(256), 0, s, pw.rowstat_b, m, S, w.n_valid, w.stats, acc ? w.acc : nullptr, pw.pstats,
+                       acc ? pw.pacc : nullptr);
+    // actor: ppo_mb's lines
+    ppo_head_back(s, m, Ha, 1 + nb, w.dhead, hk::PM_MAX_OUT, prm + na.oWmu, prm + na.oWbr, w.Za[La], w.d0);
+    ppo_wgrad(s, w.part, 1 + nb, Ha, m, w.dhead, hk::PM_MAX_OUT, w.Aa[La], Ha, grad + na.oWmu, grad + na.oWbr);
+    ppo_colsum(s, w.dhead, m, hk::PM_MAX_OUT, 1, grad + na.obmu);
+    ppo_colsum(s, w.dhead + 1, m, hk::PM_MAX_OUT, nb, grad + na.obbr);
+    ppo_colsum(s, w.dls, m, 1, 1, grad + na.ols);
+    ppo_trunk_backward(s, w, t, na, grad, m, w.Za, w.Aa, w.d0, w.d1);
+    // critic: the head and the encoder over the NS sequences
+    ppo_head_back(s, NS, H, 1, pw.dout, 1, prm + pn.owval, nullptr, pw.Ze[L - 1], pw.d0);
+    ppo_wgrad(s, pw.part, 1, H, NS, pw.dout, 1, pw.Ae[L - 1], H, grad + pn.owval, nullptr);
+    ppo_colsum(s, pw.dout, NS, 1, 1, grad + pn.obval);
+    float *dcur = pw.d0, *dnext = pw.d1;
+    for (int l = L - 1; l >= 0; l--) {
+        ppo_wgrad(s, pw.part, H, H, NS, dcur, H, l == 0 ? pw.Zp : pw.Ae[l - 1], H, grad + pn.oW[l], nullptr);
+        ppo_colsum(s, dcur, NS, H, H, grad + pn.ob[l]);
+        if (l > 0) {
+            poca_lin_t<2>(s, NS, H, H, dcur, prm + pn.oW[l], dnext, pw.Ze[l - 1]);
+            std::swap(dcur, dnext);
+        }
+    }
+    poca_lin_t<0>(s, NS, H, H, dcur, prm + pn.oW[0], pw.dZp, nullptr);
+    // the pool and the out-LayerNorm, W_out, the attention core
+    hipLaunchKernelGGL(hk::poca_out_bwd_kernel, dim3(nblk(SR, 4)), dim3(256), 0, s, pw.dZp, pw.O, pw.ostat, SR, S, H, pw.dPre);
+    ppo_wgrad(s, pw.part, H, H, SR, pw.dPre, H, pw.C, H, grad + pn.oWout, nullptr);
+    ppo_colsum(s, pw.dPre, SR, H, H, grad + pn.obout);
+    poca_lin_t<0>(s, SR, H, H, pw.dPre, prm + pn.oWout, pw.dC, nullptr);
+    hipLaunchKernelGGL(hk::poca_attn_bwd_kernel, dim3(nblk(NS, 4)), dim3(256), 0, s, pw.Q, pw.K, pw.V, pw.alpha, pw.dC, NS, S, m, H, pw.dQs, pw.dKs, pw.dVs);
+    hipLaunchKernelGGL(hk::poca_entsum_kernel, dim3(nblk((size_t)E2 * H)), dim3(256), 0, s, pw.dQs, pw.dKs, pw.dVs, pw.dPre, S, m, H, pw.dQ, pw.dK, pw.dV, pw.dR);
+    // q, k, v: weights, biases, and the deltas into the normalised entities
+    const struct { float* d; size_t oW, ob; float* dn; } qkv[3] = {{pw.dQ, pn.oWq, pn.obq, pw.dNq}, {pw.dK, pn.oWk, pn.obk, pw.dNk}, {pw.dV, pn.oWv, pn.obv, pw.dNv}};
+    for (const auto& x : qkv) {
+        ppo_wgrad(s, pw.part, H, H, E2, x.d, H, pw.N, H, grad + x.oW, nullptr);
+        ppo_colsum(s, x.d, E2, H, H, grad + x.ob);
+        poca_lin_t<0>(s, E2, H, H, x.d, prm + x.oW, x.dn, nullptr);
+    }
+    hipLaunchKernelGGL(hk::poca_ent_bwd_kernel, dim3(nblk(E2, 4)), dim3(256), 0, s, pw.dR, pw.dNq, pw.dNk, pw.dNv, pw.N, pw.estat, pw.Zent, E2, H, pw.dZent);
+    // the two embeddings
+    ppo_wgrad(s, pw.part, H, pn.in_dim, m, pw.dZent, H, w.X0, pn.in_dim, grad + pn.oWobs, nullptr);
+    ppo_colsum(s, pw.dZent, m, H, H, grad + pn.obobs);
+    float* dza = pw.dZent + (size_t)m * H;
+    ppo_wgrad(s, pw.part, H, pn.n_act, m, dza, H, pw.XA, pn.n_act, grad + pn.oWact, nullptr);
+    ppo_colsum(s, dza, m, H, H, grad + pn.obact);
+    HK_HIP(h, hipGetLastError());
+    t.last_m = m; t.last_mg = mg;
+    return HK_OK;
+}
+
+// hk_ppo_advantages of a POCA trainer: V and B over every group and V over the E bootstrap groups, in chunks; then the lambda-returns
+int poca_advantages(hk_handle h, hk_context::Ppo& t)
+{
+    const hk::PpoRows P = ppo_rows(h, t);
+    const auto& ro = h->ro;
+    const int S = P.S, G = P.R * P.E, n = G * S, nbt = P.E * S;
+    int rc;
+    const size_t need = 3 * (size_t)n + nbt + n;
+    if (need > t.rowbuf_n) {
+        if (t.rowbuf) HK_HIP(h, hipFree(t.rowbuf));
+        t.rowbuf = nullptr; t.rowbuf_n = 0;
+        HK_HIP(h, hipMalloc(&t.rowbuf, need * sizeof(float)));
+        t.rowbuf_n = need;
+    }
+    if (2 * (size_t)n > t.prow_n) {
+        if (t.prow) HK_HIP(h, hipFree(t.prow));
+        t.prow = nullptr; t.prow_n = 0;
+        HK_HIP(h, hipMalloc(&t.prow, 2 * (size_t)n * sizeof(float)));
+        t.prow_n = 2 * (size_t)n;
+    }
+    t.n = n;
+    const PpoRowBuf rows = ppo_rowbuf(h, t);
+    const PocaRowBuf prows = poca_rowbuf(t);
+    const int chunk = std::max(t.pcap, std::min(G + P.E, 4096));
+    PpoWs w;
+    PocaWs pw;
+    if ((rc = ppo_ensure_ws(h, t, chunk * S, w))) return rc;
+    if ((rc = poca_ensure_ws(h, t, S, chunk, pw))) return rc;
+    hipStream_t s = h->stream;
+    for (int base = 0; base < G + P.E; base += chunk) {
+        const int mg = std::min(chunk, G + P.E - base);
+        hipLaunchKernelGGL(hk::ppo_iota_kernel, dim3(nblk(mg)), dim3(256), 0, s, pw.gids, base, mg);
+        poca_forward(s, t, P, w, pw, pw.gids, mg, 1);
+        hipLaunchKernelGGL(hk::poca_scatter_kernel, dim3(nblk(mg * S)), dim3(256), 0, s, pw.out, pw.rid, mg * S, S, n, nbt, rows.v_old, prows.b_old, rows.v_boot,
+                           nullptr, nullptr, nullptr);
+    }
+    hipLaunchKernelGGL(hk::poca_lambda_kernel, dim3(nblk(nbt)), dim3(256), 0, s, P, ro.at<float>(HK_RO_GROUP_REWARD), ro.at<float>(HK_RO_TERM_GROUP_REWARD),
+                       rows.v_old, prows.b_old, rows.v_boot, t.cfg.gamma, t.cfg.lambd, prows.team, rows.adv, rows.ret);
+    if (t.cfg.normalize_advantages) hipLaunchKernelGGL(hk::ppo_adv_norm_kernel, dim3(1), dim3(1024), 0, s, rows.adv, n);
+    HK_HIP(h, hipGetLastError());
+    t.adv_gen = ro.gen;
+    t.perm_valid = false;
+    t.adv_stale = false;
+    t.last_m = 0; t.last_mg = 0;          // the chunks went through the minibatch workspace
+    return HK_OK;
+}
+
 // one minibatch: loss, stats, gradient into GRAD (acc: the update's stats accumulator, or nullptr)
 int ppo_mb(hk_handle h, hk_context::Ppo& t, const int32_t* ids, int m, float eps, float beta, bool acc)
 {
+    if (t.poca) return poca_mb(h, t, ids, m, eps, beta, acc);
     PpoWs w;
     int rc = ppo_ensure_ws(h, t, m, w);
     if (rc) return rc;
@@ -1794,6 +2035,7 @@ int hk_ppo_advantages(hk_handle h, int trainer)
     auto& t = h->ppo[trainer];
     const auto& ro = h->ro;
     if ((rc = ppo_check_rows(h, t, "hk_ppo_advantages"))) return rc;
+    if (t.poca) return poca_advantages(h, t);
     const hk::PpoRows P = ppo_rows(h, t);
     const int n = P.R * P.E * P.S, nbt = P.E * P.S;
     const size_t need = 3 * (size_t)n + nbt + n;
@@ -1837,6 +2079,7 @@ int hk_ppo_minibatch(hk_handle h, int trainer, const int32_t* rows_dev, int m, f
     auto& t = h->ppo[trainer];
     ppo_shadow_refresh(h->stream, t);
     if ((rc = ppo_mb(h, t, rows_dev, m, eps, beta, false))) return rc;
+    t.lb_from_update = false;
     if (stats) {
         PpoWs w;
         ppo_ws_layout(t, t.cap, &w);
@@ -1879,13 +2122,16 @@ int ppo_update_run(hk_handle h, int trainer, bool opt, int epochs, int minibatch
                    float target_kl, float* stats, hk_ppo_update_report* report)
 {
     auto& t = h->ppo[trainer];
-    const int n = t.n;
+    const int per = t.poca ? h->policy[t.policy].q.n_slots : 1;          // a POCA trainer's ids are groups of `per` agent rows
+    const int n = t.n / per;
     const int mb = std::min(minibatch, n), nmb = n / mb;
     const bool kl_stop = target_kl > 0.0f;
     int* perm = ppo_rowbuf(h, t).perm;
     PpoWs w;
+    PocaWs pw{};
     int rc;
-    if ((rc = ppo_ensure_ws(h, t, mb, w))) return rc;
+    if ((rc = ppo_ensure_ws(h, t, mb * per, w))) return rc;
+    if (t.poca && (rc = poca_ensure_ws(h, t, per, mb, pw))) return rc;
     if (max_norm > 0.0f && (rc = ppo_ensure_clip(h, t))) return rc;
     if (opt && t.clip) HK_HIP(h, hipMemsetAsync(t.clip + 2, 0, 5 * sizeof(double), h->stream));       // the accumulating words [2 .. 6]
     ppo_shadow_refresh(h->stream, t);
@@ -1895,6 +2141,7 @@ int ppo_update_run(hk_handle h, int trainer, bool opt, int epochs, int minibatch
     for (int ep = 0; ep < epochs; ep++) {
         const bool last = ep == epochs - 1;
         if (last || kl_stop) HK_HIP(h, hipMemsetAsync(w.acc, 0, 8 * sizeof(double), h->stream));
+        if (t.poca && (last || kl_stop)) HK_HIP(h, hipMemsetAsync(pw.pacc, 0, 2 * sizeof(double), h->stream));
         hipLaunchKernelGGL(hk::ppo_perm_kernel, dim3(nblk(n)), dim3(256), 0, h->stream, perm, n, t.cfg.seed, (uint32_t)t.epochs_done);
         t.epochs_done += 1;
         t.perm_valid = true;
@@ -1911,6 +2158,7 @@ int ppo_update_run(hk_handle h, int trainer, bool opt, int epochs, int minibatch
         }
     }
     if ((rc = hk_ppo_publish(h, trainer))) return rc;
+    t.lb_from_update = true;
     if (stats || report) {
         double words[8] = {};
         if (!have_acc) HK_HIP(h, hipMemcpyAsync(acc, w.acc, sizeof(acc), hipMemcpyDeviceToHost, h->stream));
@@ -2093,6 +2341,7 @@ int hk_ppo_set_precision(hk_handle h, int trainer, int precision)
     if (rc) return rc;
     if (precision != HK_PPO_PREC_F32 && precision != HK_PPO_PREC_BF16) return fail(h, HK_ERR_INVALID, "hk_ppo_set_precision: unknown precision");
     auto& t = h->ppo[trainer];
+    if (t.poca && precision != HK_PPO_PREC_F32) return fail(h, HK_ERR_UNSUPPORTED, "hk_ppo_set_precision: a POCA trainer has no bf16 products (hk.h \"POCA\")");
     if (precision == t.prec) return HK_OK;
     // the workspace is laid out per precision: drop it once the stream is done with it (the next minibatch allocates the other layout)
     HK_HIP(h, hipStreamSynchronize(h->stream));
@@ -2170,6 +2419,11 @@ void* hk_ppo_ptr(hk_handle h, int trainer, int field)
         return t.clip;
     }
     if (t.last_m == 0) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: no minibatch yet"); return nullptr; }
+    if (t.poca && field == HK_PPO_MB_VALUE) {          // one value per group
+        PocaWs pw;
+        poca_ws_layout(t, h->policy[t.policy].q.n_slots, t.pcap, &pw);
+        return pw.mb_v;
+    }
     PpoWs w;
     ppo_ws_layout(t, t.cap, &w);
     return field == HK_PPO_MB_MU ? (void*)w.mb_mu : field == HK_PPO_MB_LOGITS ? (void*)w.mb_logits : (void*)w.mb_v;
@@ -2183,11 +2437,128 @@ int hk_ppo_count(hk_handle h, int trainer, int field)
     if (field < 0 || field >= HK_PPO_FIELDS) return fail(h, HK_ERR_INVALID, "hk_ppo_count: bad field");
     if (field <= HK_PPO_ADAM_V) return (int)t.P;
     if (field <= HK_PPO_RET) return t.adv_gen < 0 ? 0 : t.n;
-    if (field == HK_PPO_PERM) return t.perm_valid ? t.n : 0;
+    if (field == HK_PPO_PERM) return t.perm_valid ? (t.poca ? t.n / h->policy[t.policy].q.n_slots : t.n) : 0;
     if (field == HK_PPO_SHADOW) return t.shadow ? (int)(t.P + t.shadow_pad) : 0;
     if (field == HK_PPO_CLIP) return t.clip ? 8 : 0;
     if (field == HK_PPO_NORM_MEAN || field == HK_PPO_NORM_STD) return h->policy[t.policy].q.normalize ? h->policy[t.policy].q.in_dim : 0;
+    if (t.poca && field == HK_PPO_MB_VALUE) return t.last_mg;
     return field == HK_PPO_MB_LOGITS ? t.last_m * t.actor.n_branch : t.last_m;
+}
+
+int hk_ppo_create_poca(hk_handle h, int policy, const hk_poca_critic_desc* c, const hk_ppo_config* cfg)
+{
+    HK_NEED_ENV(h);
+    const char* fn = "hk_ppo_create_poca: ";
+    auto bad = [&](const char* what) { return fail(h, HK_ERR_INVALID, std::string(fn) + what); };
+    if (policy < 0 || policy >= h->n_policies) return bad("bad policy index");
+    if (h->n_ppo >= HK_MAX_POLICIES) return bad("HK_MAX_POLICIES trainers already exist");
+    if (!c) return bad("NULL critic");
+    if (!h->cfg.rewards) return bad("hk_config.rewards == 0 (the rows carry no rewards)");
+    const hk::PolicyParams& q = h->policy[policy].q;
+    const int S = q.n_slots;
+    if (S < 2 || S > HK_POCA_MAX_GROUP) return bad("the policy's slots are not a group of 2 .. HK_POCA_MAX_GROUP agents");
+    const int team = h->cfg.team_of[q.slots[0]];
+    int members = 0;
+    for (int a = 0; a < h->cfg.num_agents; a++) members += h->cfg.team_of[a] == team;
+    for (int j = 0; j < S; j++) if (h->cfg.team_of[q.slots[j]] != team) return bad("the policy's slots are not on one team");
+    if (members != S) return bad("the policy's slots are not every member of their team");
+    if (c->hidden < 4 || c->hidden > HK_POLICY_MAX_HIDDEN || c->hidden % 4) return bad("hidden is not a multiple of 4 in [4, HK_POLICY_MAX_HIDDEN]");
+    if (c->n_layers < 1 || c->n_layers > HK_POLICY_MAX_LAYERS) return bad("n_layers outside [1, HK_POLICY_MAX_LAYERS]");
+    if (c->reserved0 != 0 || c->reserved1 != 0) return bad("reserved != 0");
+    if (!c->W_obs || !c->b_obs || !c->W_act || !c->b_act || !c->W_q || !c->b_q || !c->W_k || !c->b_k || !c->W_v || !c->b_v || !c->W_out || !c->b_out ||
+        !c->w_val || !c->b_val)
+        return bad("a NULL array");
+    for (int l = 0; l < c->n_layers; l++) if (!c->W[l] || !c->b[l]) return bad("a NULL array (encoder)");
+    hk_ppo_config d{0.99f, 0.95f, 1, 0.9f, 0.999f, 1e-8f, 0u};
+    if (cfg) d = *cfg;
+    if (!(d.adam_beta1 >= 0.0f && d.adam_beta1 < 1.0f && d.adam_beta2 >= 0.0f && d.adam_beta2 < 1.0f && d.adam_eps > 0.0f)) return bad("Adam constants out of range");
+    auto& t = h->ppo[h->n_ppo];
+    t = hk_context::Ppo{};
+    t.policy = policy; t.cfg = d; t.poca = true;
+    t.actor.layout(q.in_dim, q.hidden, q.n_layers, q.n_branch, 0);
+    t.pnet.layout(q.in_dim, q.n_branch, c->hidden, c->n_layers, t.actor.count);
+    const hk::PocaNet& pn = t.pnet;
+    t.P = t.actor.count + pn.count;
+    const size_t H = (size_t)c->hidden, base = t.actor.count;
+    std::vector<float> host(pn.count);
+    auto put = [&](size_t off, const float* src, size_t k) { std::memcpy(&host[off - base], src, k * 4); };
+    put(pn.oWobs, c->W_obs, H * pn.in_dim); put(pn.obobs, c->b_obs, H);
+    put(pn.oWact, c->W_act, H * pn.n_act); put(pn.obact, c->b_act, H);
+    put(pn.oWq, c->W_q, H * H); put(pn.obq, c->b_q, H); put(pn.oWk, c->W_k, H * H); put(pn.obk, c->b_k, H);
+    put(pn.oWv, c->W_v, H * H); put(pn.obv, c->b_v, H); put(pn.oWout, c->W_out, H * H); put(pn.obout, c->b_out, H);
+    for (int l = 0; l < c->n_layers; l++) { put(pn.oW[l], c->W[l], H * H); put(pn.ob[l], c->b[l], H); }
+    put(pn.owval, c->w_val, H); put(pn.obval, c->b_val, 1);
+    hipError_t e = hipMalloc(&t.param, 4 * t.P * sizeof(float));
+    if (e == hipSuccess) e = hipMemsetAsync(t.param, 0, 4 * t.P * sizeof(float), h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t.param + base, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(hk::ppo_publish_kernel<false>, dim3(nblk(t.actor.count)), dim3(256), 0, h->stream, q, t.actor, t.param);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        if (t.param) (void)hipFree(t.param);
+        t = hk_context::Ppo{};
+        return fail(h, HK_ERR_HIP, std::string(fn) + hipGetErrorString(e));
+    }
+    return h->n_ppo++;
+}
+
+extern "C++" {
+namespace {
+// a POCA trainer and field -> 0, or a failure naming fn
+int poca_field_check(hk_handle h, int trainer, int field, const char* fn)
+{
+    if (!h) return fail(nullptr, HK_ERR_INVALID, "NULL handle");
+    if (trainer < 0 || trainer >= h->n_ppo) return fail(h, HK_ERR_INVALID, std::string(fn) + ": bad trainer index");
+    if (!h->ppo[trainer].poca) return fail(h, HK_ERR_INVALID, std::string(fn) + ": not a POCA trainer (hk_ppo_create_poca)");
+    if (field < 0 || field >= HK_POCA_FIELDS) return fail(h, HK_ERR_INVALID, std::string(fn) + ": bad field");
+    return HK_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+void* hk_poca_ptr(hk_handle h, int trainer, int field)
+{
+    if (poca_field_check(h, trainer, field, "hk_poca_ptr")) return nullptr;
+    const auto& t = h->ppo[trainer];
+    if (field == HK_POCA_MB_BASELINE) {
+        if (t.last_mg == 0) { fail(h, HK_ERR_INVALID, "hk_poca_ptr: no minibatch yet"); return nullptr; }
+        PocaWs pw;
+        poca_ws_layout(t, h->policy[t.policy].q.n_slots, t.pcap, &pw);
+        return pw.brow;
+    }
+    if (t.adv_gen < 0) { fail(h, HK_ERR_INVALID, "hk_poca_ptr: hk_ppo_advantages has not run"); return nullptr; }
+    const PocaRowBuf r = poca_rowbuf(t);
+    return field == HK_POCA_B_OLD ? r.b_old : r.team;
+}
+
+int hk_poca_count(hk_handle h, int trainer, int field)
+{
+    int rc = poca_field_check(h, trainer, field, "hk_poca_count");
+    if (rc) return rc;
+    const auto& t = h->ppo[trainer];
+    if (field == HK_POCA_MB_BASELINE) return t.last_m;
+    return t.adv_gen < 0 ? 0 : t.n;
+}
+
+int hk_poca_stats(hk_handle h, int trainer, float* out)
+{
+    int rc = poca_field_check(h, trainer, 0, "hk_poca_stats");
+    if (rc) return rc;
+    if (!out) return fail(h, HK_ERR_INVALID, "hk_poca_stats: NULL out");
+    const auto& t = h->ppo[trainer];
+    if (!t.pws || (t.last_mg == 0 && !t.lb_from_update)) return fail(h, HK_ERR_INVALID, "hk_poca_stats: no minibatch or update yet");
+    PocaWs pw;
+    poca_ws_layout(t, h->policy[t.policy].q.n_slots, t.pcap, &pw);
+    float st[HK_POCA_STATS] = {};
+    double acc[2] = {};
+    HK_HIP(h, hipMemcpyAsync(st, pw.pstats, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+    HK_HIP(h, hipMemcpyAsync(acc, pw.pacc, sizeof(acc), hipMemcpyDeviceToHost, h->stream));
+    HK_HIP(h, hipStreamSynchronize(h->stream));
+    out[0] = t.lb_from_update ? (float)(acc[0] / (acc[1] > 0 ? acc[1] : 1.0)) : st[0];
+    out[1] = 0.0f;
+    return HK_OK;
 }
 
 // ------------------------------------------------------------------ self-play (hk.h "SELF-PLAY"; device side of the statistics in hk_selfplay.h)

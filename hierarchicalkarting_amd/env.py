@@ -10,6 +10,7 @@ RacingEnv  <->  RacingEnvController (+ its KartAgents / ArcadeKarts), E independ
     episode_stats(policy)            returns, lengths, wins / draws / losses of the closed rollout's episodes, reduced on the device
     snapshot_pool(policy, slots)     device slots of saved actors; load one into an attached policy (self-play opponent swaps)
     ppo_trainer(policy)              PPO on the recorded rows, on the device (ppo.PPOTrainer)
+    poca_trainer(policy)             MA-POCA for a team's policy: attention critic, counterfactual baseline, team reward (poca.POCATrainer)
     agent_state() / set_agent_state  snapshot / restore of every KartAgent + ArcadeKart + Rigidbody field
     episode_results()                TelemetryViewer quantities of the last finished episode
 All arrays are numpy views of the ABI structs; all compute happens in the HIP kernels."""
@@ -323,6 +324,11 @@ class RacingEnv:
         """-> ppo.PPOTrainer of an attached policy (hk_ppo_create): it trains on this handle's closed rollouts and publishes into the policy"""
         from .ppo import PPOTrainer
         return PPOTrainer(self, policy_index, critic, **cfg)
+
+    def poca_trainer(self, policy_index, critic=None, **cfg):
+        """-> poca.POCATrainer of an attached policy whose slots are one whole team (hk_ppo_create_poca); critic: a poca.PocaCritic or None (seeded random)"""
+        from .poca import POCATrainer
+        return POCATrainer(self, policy_index, critic, **cfg)
 
     def observe(self):
         self._ck(self.L.hk_observe(self.h))

@@ -218,6 +218,18 @@ def _need(d, key, what="state"):
     return d[key]
 
 
+def check_state(d, kind, actor_shape, critic_shape):
+    """the host-only head of load_state_dict: a checkpoint's format, trainer kind (absent: "ppo") and the two network shapes against the
+    loading trainer's; ValueError names the field"""
+    if _need(d, "format") != CHECKPOINT_FORMAT:
+        raise ValueError("state: format %r is not %d" % (d["format"], CHECKPOINT_FORMAT))
+    if str(d.get("kind", "ppo")) != kind:
+        raise ValueError("state: kind %r is not this trainer's %r" % (str(d.get("kind", "ppo")), kind))
+    for key, want in (("actor_shape", actor_shape), ("critic_shape", critic_shape)):
+        if not np.array_equal(np.asarray(_need(d, key)), np.asarray(want)):
+            raise ValueError("state: %s %s differs from the trainer's %s" % (key, list(np.asarray(d[key])), list(np.asarray(want))))
+
+
 def _option(name, v, inf_ok):
     """an update option as hk_ppo_update_opts takes it: None -> 0 (off); negative, NaN (or infinite) -> ValueError"""
     if v is None:
@@ -231,6 +243,7 @@ def _option(name, v, inf_ok):
 class PPOTrainer:
     """One trainer of RacingEnv `env`'s attached policy `policy_index` (hk_ppo_create).  critic: a Policy with n_branch 0 semantics (its trunk and
     W_mu / b_mu are used) or None for Policy.random-style weights of the actor's shape; precision: "f32" | "bf16" (set_precision); cfg: DEFAULTS' keys."""
+    KIND = "ppo"          # a checkpoint's "kind" entry (absent in a PPO checkpoint: it reads as "ppo"); poca.POCATrainer: "poca"
 
     def __init__(self, env, policy_index, critic=None, precision="f32", **cfg):
         if precision not in PRECISIONS:
@@ -451,11 +464,7 @@ class PPOTrainer:
     def load_state_dict(self, d):
         """validate (ValueError names the field: shapes, cfg — a differing shuffle seed would not continue the permutations), then restore the
         counters, the three vectors, the precision and the normaliser if present, and publish; the library refuses it while a rollout is open"""
-        if _need(d, "format") != CHECKPOINT_FORMAT:
-            raise ValueError("state: format %r is not %d" % (d["format"], CHECKPOINT_FORMAT))
-        for key, want in zip(("actor_shape", "critic_shape"), self._shapes()):
-            if not np.array_equal(np.asarray(_need(d, key)), want):
-                raise ValueError("state: %s %s differs from the trainer's %s" % (key, list(np.asarray(d[key])), list(want)))
+        check_state(d, self.KIND, *self._shapes())
         cfg = _need(d, "cfg")
         for k in DEFAULTS:
             mine = int(self.cfg[k]) & 0xFFFFFFFF if k == "seed" else int(bool(self.cfg[k])) if k == "normalize_advantages" else float(self.cfg[k])

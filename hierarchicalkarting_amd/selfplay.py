@@ -10,7 +10,7 @@ bookkeeping on top of three device facilities — the snapshot pool (hk_policy_p
     ppo.checkpoint_write(path, sp.state_dict()); ...; sp2.load_state_dict(ppo.checkpoint_read(path))     # ratings, cursor, generator, pool slots
 
 Nothing is computed on the host but ratings, schedules and which slot plays next.  Out of scope: team_change (a trainer is bound to one
-policy), per-env opponents, POCA and LSTM."""
+policy), per-env opponents, bf16 POCA and LSTM.  The trainer may be a poca.POCATrainer: nothing here is bound to the critic's kind."""
 import ctypes as C
 import json
 import numpy as np

@@ -32,6 +32,9 @@ namespace KartGame.AI.Native
                          HK_PPO_PREC_F32 = 0, HK_PPO_PREC_BF16 = 1,
                          HK_POLICY_PREC_F32 = 0, HK_POLICY_PREC_BF16 = 1,      // hk_policy_precision
                          HK_PPO_STATS = 6;
+        // hk_poca_field: the extra buffers of a POCA trainer (hk_poca_ptr / hk_poca_count); HK_POCA_STATS: L_b, reserved
+        public const int HK_POCA_B_OLD = 0, HK_POCA_MB_BASELINE = 1, HK_POCA_TEAM_REWARD = 2, HK_POCA_FIELDS = 3, HK_POCA_STATS = 2,
+                         HK_POCA_MAX_GROUP = 4, HK_POCA_HEADS = 4;
         // HierarchicalKartAgent.cs:21-33
         public const int HK_LOW_RL = 0, HK_LOW_MPC = 1, HK_LOW_LQR = 2, HK_LOW_E2E = 3;   // E2E: EndToEndKartAgent
         public const int HK_HIGH_MCTS = 0, HK_HIGH_FIXED = 1, HK_HIGH_NONE = 2;   // NONE: E2E with runQuasiMCTS off
@@ -370,6 +373,38 @@ namespace KartGame.AI.Native
         public uint seed;
     }
 
+    // hk_poca_critic_desc: the initial weights of a POCA trainer's attention critic (hk.h "POCA"); torch layout, W [out][in]
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct HkPocaCriticDesc
+    {
+        public int hidden;
+        public int n_layers;
+        public int reserved0;
+        public int reserved1;
+        public float* W_obs;
+        public float* b_obs;
+        public float* W_act;
+        public float* b_act;
+        public float* W_q;
+        public float* b_q;
+        public float* W_k;
+        public float* b_k;
+        public float* W_v;
+        public float* b_v;
+        public float* W_out;
+        public float* b_out;
+        public float* W0;
+        public float* W1;
+        public float* W2;
+        public float* W3;
+        public float* b0;
+        public float* b1;
+        public float* b2;
+        public float* b3;
+        public float* w_val;
+        public float* b_val;
+    }
+
     // hk_ppo_update_opts / hk_ppo_update_report: hk_ppo_update_opt's options (0: off) and what it did (hk.h "LONG RUNS")
     [StructLayout(LayoutKind.Sequential)]
     public struct HkPpoUpdateOpts
@@ -495,6 +530,11 @@ namespace KartGame.AI.Native
         [DllImport(Lib)] public static extern int hk_ppo_adam_clipped(IntPtr h, int trainer, float lr, float maxGradNorm);
         [DllImport(Lib)] public static extern int hk_ppo_get_counters(IntPtr h, int trainer, long* adamSteps, long* epochsDone);
         [DllImport(Lib)] public static extern int hk_ppo_set_counters(IntPtr h, int trainer, long adamSteps, long epochsDone);
+        // POCA (hk.h "POCA"): a trainer whose critic is the team's attention critic; every hk_ppo_* entry point takes its index
+        [DllImport(Lib)] public static extern int hk_ppo_create_poca(IntPtr h, int policy, HkPocaCriticDesc* critic, HkPpoConfig* cfg);
+        [DllImport(Lib)] public static extern IntPtr hk_poca_ptr(IntPtr h, int trainer, int field);
+        [DllImport(Lib)] public static extern int hk_poca_count(IntPtr h, int trainer, int field);
+        [DllImport(Lib)] public static extern int hk_poca_stats(IntPtr h, int trainer, float* stats);
         // self-play (hk.h "SELF-PLAY"): device slots of saved actors, loaded into an attached opponent; episode statistics of the closed rollout
         [DllImport(Lib)] public static extern int hk_policy_pool_create(IntPtr h, int policy, int slots);
         [DllImport(Lib)] public static extern int hk_policy_pool_save(IntPtr h, int pool, int slot, int policy);

@@ -532,7 +532,7 @@ void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* 
  * weights from an hk_policy_desc (W[], b[] the trunk, W_mu / b_mu the value head, n_branch = 0, in_dim = the actor's; hidden / n_layers
  * within the actor's limits, other fields ignored).  It shares no weight with the actor (ML-Agents shared_critic: false).
  * REWARD, DONE: r_t = DONE ? TERM_REWARD : REWARD (rollout.transition_rewards); every DONE != 0, the time-out (2) included, is terminal.
- * GROUP_REWARD is not used: PPO ignores group rewards (POCA is out of scope).
+ * GROUP_REWARD is not used: PPO ignores group rewards (a POCA trainer, "POCA" below, is what reads them).
  * GAE per (e, j), backwards over t, V = V_OLD (the critic at hk_ppo_advantages), V_R = the bootstrap value, A_R = 0:
  *   delta_t = r_t + gamma (1 - d_t) V_{t+1} - V_t;   A_t = delta_t + gamma lambd (1 - d_t) A_{t+1};   RET_t = A_t + V_t
  * normalize_advantages: ADV = (A - mean) / (std + 1e-10) over all n rows (population std; mean and std in fp64, fixed order); RET keeps A unnormalised.
@@ -652,7 +652,7 @@ void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* 
  *                        valid as they were.  Either pointer of get may be NULL.
  * Refused with HK_ERR_INVALID and a message naming the argument, state as it was: a NULL opts, epochs < 1, minibatch < 1, max_grad_norm or target_kl
  * negative or NaN, target_kl infinite, reserved != 0, and whatever hk_ppo_update / hk_ppo_adam refuse.
- * Out of scope (self-play opponent swaps, episode statistics and ELO: "SELF-PLAY" below): POCA and group rewards, LSTM memory, a normaliser for policies attached with normalize == 0,
+ * Out of scope (self-play opponent swaps, episode statistics and ELO: "SELF-PLAY" below; POCA and group rewards: "POCA" below): LSTM memory, a normaliser for policies attached with normalize == 0,
  * multi-GPU gradient all-reduce and bf16 optimiser state.  Everything is asynchronous on hk_stream unless noted. */
 #define HK_PPO_STATS 6
 typedef struct hk_ppo_config {
@@ -705,6 +705,68 @@ int hk_ppo_adam_clipped(hk_handle h, int trainer, float lr, float max_grad_norm)
 int hk_ppo_get_counters(hk_handle h, int trainer, int64_t* adam_steps, int64_t* epochs_done);
 int hk_ppo_set_counters(hk_handle h, int trainer, int64_t adam_steps, int64_t epochs_done);   /* 0 <= each <= INT32_MAX, else refused */
 
+/* ---- POCA: a centralised attention critic, a counterfactual baseline per agent, lambda-returns of the team reward -----------
+ * MA-POCA as ML-Agents 2.0 defines it, for the reference's team behaviours (trainer_type: poca).  mlagents was not available to compare
+ * against: the rules written here are the contract (as for the ghost trainer's outcome rule in "SELF-PLAY").
+ * A POCA trainer is a CRITIC KIND of the trainer table: hk_ppo_create_poca returns a trainer index and every hk_ppo_* entry point takes it.  A
+ * trainer made by hk_ppo_create computes what it computed, bit for bit, issues the launches it issued and allocates nothing more.
+ * GROUP: the S agent slots of `policy` in one env; 2 <= S <= HK_POCA_MAX_GROUP, all on one team (hk_config.team_of) and every member of it.
+ * Every episode end of the reference is EndGroupEpisode, so a group is always complete: there is no attention mask, and ML-Agents' "normalised
+ * agent count" input, the constant +1, is dropped (b_val absorbs it) — a documented departure.
+ * ROWS, IDS: agent rows as in PPO, id = (t E + e) S + j, n = R E S.  A minibatch id of a POCA trainer is a GROUP id g = t E + e in [0, R E); it
+ * stands for the agent rows g S + j.  Under hk_ppo_update / hk_ppo_update_opt `minibatch` counts groups, the permutation is over R E and PERM is
+ * int32 [R E].  MB_MU, MB_LOGITS: [m_g S] (x n_branch); MB_VALUE [m_g], one per group; HK_POCA_MB_BASELINE [m_g S].  V_OLD, ADV, RET, HK_POCA_B_OLD,
+ * HK_POCA_TEAM_REWARD: [n]; V_OLD holds the group's value once per j.  A group id outside [0, R E) is skipped; stats[5] counts skipped GROUPS.
+ * PARAMS / GRAD / ADAM_M / ADAM_V: the actor part exactly as in PPO, then the critic in the order of hk_poca_critic_desc: W_obs, b_obs, W_act,
+ * b_act, W_q, b_q, W_k, b_k, W_v, b_v, W_out, b_out, W[0], b[0], ..., w_val, b_val (torch layout, W [out][in]).
+ * CRITIC, all fp32.  x_j [in_dim]: the actor's normalised, clipped stacked input of slot j (the actor's normaliser, read in place);
+ * a_j = [RAW_j, onehot(BRANCH_j)] [1 + n_branch].
+ *   obs entity  uo_j = swish(W_obs x_j + b_obs);   act entity  ua_j = swish(W_act [x_j ; a_j] + b_act)   (one product over the gathered [x ; a])
+ *   value sequence (uo_0 ... uo_{S-1});   baseline sequence of agent i: (uo_i, then ua_k for k != i, k ascending)
+ *   LN(u) = (u - mean u) / sqrt(var u + 1e-5), population variance over H, no affine
+ *   n_s = LN(u_s);  q_s = W_q n_s + b_q;  k_s, v_s alike      (they depend on the entity alone: computed once for a group's 2 S entities)
+ *   per head h of HK_POCA_HEADS (width H / 4): score_sr = <q_s^h, k_r^h> / sqrt(H) — the square root of the EMBEDDING size, not the head's (ML-Agents)
+ *   alpha_s. = softmax_r(score_sr), the row maximum subtracted;  c_s^h = sum_r alpha_sr v_r^h;  c_s = the four heads side by side
+ *   o_s = LN(W_out c_s + b_out + n_s);   z = (1 / S) sum_s o_s     (ML-Agents divides by S + 1e-7: dropped, a documented departure)
+ *   y = n_layers x swish(Linear H -> H)(z);   output = <w_val, y> + b_val: ONE head, shared by value and baseline
+ *   V(t, e) = the output of the value sequence;   B(t, e, i) = the output of agent i's baseline sequence
+ * hk_ppo_advantages on a POCA trainer: V and B over every row, V over the E bootstrap groups, in chunks.  With r, g the transition forms
+ * DONE ? TERM_* : * of REWARD and GROUP_REWARD (ML-Agents' lambda_return with add_groupmate_rewards):
+ *   rho_{t,e,i} = (sum_k r_{t,e,k}, k ascending, fp32) + g_{t,e,i}                                     -> HK_POCA_TEAM_REWARD
+ *   G_{R,i} = V_R (bootstrap);  G_{t,i} = rho_{t,i} + gamma (1 - d_t) [(1 - lambd) V_{t+1} + lambd G_{t+1,i}];  every DONE != 0 terminal
+ *   RET = G;  A = G - B;  ADV = normalize_advantages ? (A - mean) / (std + 1e-10) over n (fp64, fixed order) : A;  V_OLD = V, HK_POCA_B_OLD = B
+ * LOSS over a minibatch of m = m_g S valid agent rows: L_pi, H, approx-KL and the clip fraction exactly PPO's, on ADV.  Both value losses are
+ * PPO's clipped form as means over the m rows, against RET: L_v of v = the row's group value against V_OLD, L_b of b against B_OLD.
+ *   L = L_pi + 0.5 (L_v + 0.5 L_b) - beta mean H.       stats[1] stays L_v; L_b comes through hk_poca_stats.
+ * In the backward, an entity's gradient is the sum of its sequences' contributions in sequence order.  No float atomics anywhere: the same
+ * call on the same state gives the same bits.
+ * hk_ppo_adam, hk_ppo_adam_clipped (one norm over actor and POCA critic), hk_ppo_update, hk_ppo_update_opt, hk_ppo_publish, the counters, the
+ * normaliser, hk_ppo_ptr / hk_ppo_count and the self-play pool's refusal rule work on a POCA trainer with no further change of meaning.
+ * hk_ppo_set_precision(HK_PPO_PREC_BF16) on a POCA trainer: HK_ERR_UNSUPPORTED, the state as it was.
+ * hk_ppo_create_poca refuses with HK_ERR_INVALID and a message, nothing allocated: S outside [2, HK_POCA_MAX_GROUP]; slots that are not one
+ * whole team; hidden not a multiple of 4 or outside [4, HK_POLICY_MAX_HIDDEN]; n_layers outside [1, HK_POLICY_MAX_LAYERS]; a NULL array;
+ * reserved != 0; hk_config.rewards == 0; a bad policy index, a full trainer table or Adam constants out of range (as hk_ppo_create).
+ * hk_poca_ptr / hk_poca_count: an HK_POCA_* field of a POCA trainer (another trainer or field is refused).  hk_poca_stats (synchronises):
+ * [0] L_b belonging to the stats the last hk_ppo_minibatch / hk_ppo_update(_opt) returned, [1] reserved, 0.
+ * Out of scope: bf16 products for the POCA critic, LSTM memory, groups that lose members mid-episode (attention masks), a critic normaliser
+ * separate from the actor's, multi-GPU gradient all-reduce. */
+#define HK_POCA_MAX_GROUP 4
+#define HK_POCA_HEADS 4
+typedef struct hk_poca_critic_desc {
+    int32_t hidden, n_layers, reserved0, reserved1;   /* H % 4 == 0, 4 <= H <= HK_POLICY_MAX_HIDDEN; 1 <= n_layers <= HK_POLICY_MAX_LAYERS */
+    const float *W_obs, *b_obs;      /* [H][in_dim], [H]                  obs-only entity embedding           */
+    const float *W_act, *b_act;      /* [H][in_dim + 1 + n_branch], [H]   obs+action entity embedding         */
+    const float *W_q, *b_q, *W_k, *b_k, *W_v, *b_v, *W_out, *b_out;   /* [H][H], [H] each                     */
+    const float *W[HK_POLICY_MAX_LAYERS], *b[HK_POLICY_MAX_LAYERS];   /* encoder, [H][H], [H]                 */
+    const float *w_val, *b_val;      /* [H], [1]: ONE head, shared by value and baseline                      */
+} hk_poca_critic_desc;
+typedef enum hk_poca_field { HK_POCA_B_OLD = 0, HK_POCA_MB_BASELINE, HK_POCA_TEAM_REWARD, HK_POCA_FIELDS } hk_poca_field;
+#define HK_POCA_STATS 2              /* [0] L_b, [1] reserved 0 */
+int hk_ppo_create_poca(hk_handle h, int policy, const hk_poca_critic_desc* critic, const hk_ppo_config* cfg);
+void* hk_poca_ptr(hk_handle h, int trainer, int field);
+int hk_poca_count(hk_handle h, int trainer, int field);
+int hk_poca_stats(hk_handle h, int trainer, float* out /*[HK_POCA_STATS]*/);   /* synchronises; L_b belonging to the stats the last minibatch / update returned */
+
 /* ---- SELF-PLAY: snapshot pool, opponent swaps, episode statistics of a closed rollout -------------------------------------
  * What ML-Agents' `self_play:` block needs of the library; the driver (window, save_steps / swap_steps, ELO, the linear schedules) is host
  * code: hierarchicalkarting_amd/selfplay.py.  Everything here is opt-in: a handle that never calls these entry points computes what it
@@ -748,7 +810,7 @@ int hk_ppo_set_counters(hk_handle h, int trainer, int64_t adam_steps, int64_t ep
  * here and have no order, so a rollout's W wins, D draws and L losses are applied as n = W + D + L sequential steps of the MEAN result
  * s = (W + D / 2) / n: change = k (s - 1 / (1 + 10^((r_opp - r_learner) / 400))), r_learner += change, r_opp -= change.  Order-free, equal to
  * ML-Agents' sequence when all results agree, and self-limiting where a one-shot change of n (s - e) would move ratings by thousands of points.
- * Out of scope: team_change (a trainer is bound to one policy), per-env opponents, POCA and LSTM. */
+ * Out of scope: team_change (a trainer is bound to one policy), per-env opponents, bf16 POCA and LSTM. */
 #define HK_MAX_POOLS 8
 #define HK_POOL_MAX_SLOTS 64
 int hk_policy_pool_create(hk_handle h, int policy, int slots);
