@@ -279,6 +279,7 @@ static int finish_ticks(hk_context* h);      // lazy completion of the last hk_s
 static int meter_copy(hk_context* h, bool in_order);      // the games-per-launch meter on its way to pinned memory (defined with step_ticks)
 static int throttle_mark(hk_context* h, int r);           // long lazy calls: stay a bounded number of rounds ahead of the GPU, look at the meter (defined with step_ticks)
 static int verify_optimistic(hk_context* h); // the completion guard of optimistic fixed-round calls, looked at; laggards finished (defined with step_ticks)
+static void ppo_release(hk_context::Ppo& t); // every device allocation of a trainer freed, the slot empty again (defined with the PPO trainer)
 // a search launch that runs on the side stream beside the chunks of a planner + actor handle (step_ticks): the handle's stream waits for it — before another
 // search launch (they share the tree arena), before the chunk that uses its plans, before anything reads the planner state
 // Two halves on two streams, JOINED LAZILY (round 6).  A short folded call used to end with its parts' streams joined into the handle's stream — and the next
@@ -434,7 +435,7 @@ void hk_destroy(hk_handle h)
     if (h->pol_scratch) (void)hipFree(h->pol_scratch);
     if (h->ro.buf) (void)hipFree(h->ro.buf);
     for (int p = 0; p < HK_MAX_POLICIES; p++) hk::policy_free(h->policy[p]);
-    for (auto& t : h->ppo) { if (t.param) (void)hipFree(t.param); if (t.rowbuf) (void)hipFree(t.rowbuf); if (t.ws) (void)hipFree(t.ws); if (t.shadow) (void)hipFree(t.shadow); if (t.norm) (void)hipFree(t.norm); if (t.norm_part) (void)hipFree(t.norm_part); if (t.clip) (void)hipFree(t.clip); if (t.prow) (void)hipFree(t.prow); if (t.pws) (void)hipFree(t.pws); }
+    for (auto& t : h->ppo) ppo_release(t);
     for (auto& pl : h->pool) if (pl.buf) (void)hipFree(pl.buf);
     if (h->ep.buf) (void)hipFree(h->ep.buf);
     h->prof.fold();
@@ -1440,13 +1441,19 @@ struct PpoWs {
     float *mb_mu, *mb_logits, *mb_v;
 };
 
+// one allocation handed out front to back in 256-byte steps (base nullptr: only the size is wanted)
+struct PpoBump {
+    char* base;
+    size_t off = 0;
+    char* take(size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; }
+};
+
 size_t ppo_ws_layout(const hk_context::Ppo& t, int M, PpoWs* w)
 {
-    size_t off = 0;
-    char* base = w ? (char*)t.ws : nullptr;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
+    PpoBump a{w ? (char*)t.ws : nullptr};
     const bool bf = t.prec == HK_PPO_PREC_BF16;
-    auto mat = [&](size_t count, bool bits) { char* p = take(count * (bits ? 2 : 4)); return bits ? PpoMat((uint16_t*)p) : PpoMat((float*)p); };
+    auto mat = [&](size_t count, bool bits) { char* p = a.take(count * (bits ? 2 : 4)); return bits ? PpoMat((uint16_t*)p) : PpoMat((float*)p); };
+    auto fl = [&](size_t count) { return (float*)a.take(count * 4); };
     const size_t Mz = (size_t)M;
     const int Ha = t.actor.hidden, Hc = t.critic.hidden, Hm = std::max(Ha, Hc), in = t.actor.in_dim, nb = t.actor.n_branch;
     size_t mn = (size_t)(1 + nb) * Ha;                          // the largest weight gradient: a layer's H x K, or the heads'
@@ -1454,36 +1461,45 @@ size_t ppo_ws_layout(const hk_context::Ppo& t, int M, PpoWs* w)
     mn = std::max(mn, (size_t)Hc * std::max(in, Hc));
     const size_t nz = (Mz + hk::PPO_KCH - 1) / hk::PPO_KCH;
     PpoWs d{};
-    d.ids = (int*)take(Mz * 4); d.valid = (int*)take(Mz * 4); d.n_valid = (int*)take(16);
+    d.ids = (int*)a.take(Mz * 4); d.valid = (int*)a.take(Mz * 4); d.n_valid = (int*)a.take(16);
     d.X0 = mat(Mz * in, bf);
-    for (int l = 0; l < t.actor.n_layers; l++) { d.Za[l] = (float*)take(Mz * Ha * 4); d.Aa[l] = mat(Mz * Ha, bf && l < t.actor.n_layers - 1); }
-    for (int l = 0; l < t.critic.n_layers; l++) { d.Zc[l] = (float*)take(Mz * Hc * 4); d.Ac[l] = mat(Mz * Hc, bf && l < t.critic.n_layers - 1); }
+    for (int l = 0; l < t.actor.n_layers; l++) { d.Za[l] = fl(Mz * Ha); d.Aa[l] = mat(Mz * Ha, bf && l < t.actor.n_layers - 1); }
+    for (int l = 0; l < t.critic.n_layers; l++) { d.Zc[l] = fl(Mz * Hc); d.Ac[l] = mat(Mz * Hc, bf && l < t.critic.n_layers - 1); }
     d.d0 = mat(Mz * Hm, bf); d.d1 = mat(Mz * Hm, bf);
-    d.dhead = (float*)take(Mz * hk::PM_MAX_OUT * 4); d.dls = (float*)take(Mz * 4); d.dv = (float*)take(Mz * 4);
-    d.part = (float*)take(nz * mn * 4);
-    d.stats = (float*)take(8 * 4);
-    d.rowstat = (double*)take(Mz * 6 * 8); d.acc = (double*)take(8 * 8);
-    d.mb_mu = (float*)take(Mz * 4); d.mb_logits = (float*)take(Mz * nb * 4); d.mb_v = (float*)take(Mz * 4);
+    d.dhead = fl(Mz * hk::PM_MAX_OUT); d.dls = fl(Mz); d.dv = fl(Mz);
+    d.part = fl(nz * mn);
+    d.stats = fl(8);
+    d.rowstat = (double*)a.take(Mz * 6 * 8); d.acc = (double*)a.take(8 * 8);
+    d.mb_mu = fl(Mz); d.mb_logits = fl(Mz * nb); d.mb_v = fl(Mz);
     if (w) *w = d;
-    return off;
+    return a.off;
 }
 
-int ppo_drop_ws(hk_handle h, hk_context::Ppo& t)
+// the workspace as it is allocated now
+PpoWs ppo_ws(const hk_context::Ppo& t) { PpoWs w; ppo_ws_layout(t, t.cap, &w); return w; }
+
+// p freed (when it holds anything) and cleared
+template <typename T> hipError_t ppo_free(T*& p) { T* old = p; p = nullptr; return old ? hipFree(old) : hipSuccess; }
+
+// a device buffer that only grows: below `need` units it is freed and allocated anew at `bytes` (nothing is kept); a failure leaves *p nullptr, *have 0
+template <typename T, typename N>
+int ppo_grow(hk_handle h, T** p, N* have, N need, size_t bytes)
 {
-    if (t.ws) HK_HIP(h, hipFree(t.ws));
-    t.ws = nullptr; t.cap = 0; t.last_m = 0;
+    if (need <= *have) return HK_OK;
+    *have = 0;
+    HK_HIP(h, ppo_free(*p));
+    HK_HIP(h, hipMalloc((void**)p, bytes));
+    *have = need;
     return HK_OK;
 }
 
 int ppo_ensure_ws(hk_handle h, hk_context::Ppo& t, int M, PpoWs& w)
 {
     if (M > t.cap) {
-        int rc = ppo_drop_ws(h, t);
-        if (rc) return rc;
-        HK_HIP(h, hipMalloc(&t.ws, ppo_ws_layout(t, M, nullptr)));
-        t.cap = M;
+        t.last_m = 0;
+        if (int rc = ppo_grow(h, &t.ws, &t.cap, M, ppo_ws_layout(t, M, nullptr))) return rc;
     }
-    ppo_ws_layout(t, t.cap, &w);
+    w = ppo_ws(t);
     return HK_OK;
 }
 
@@ -1561,11 +1577,11 @@ void ppo_head_back(hipStream_t s, int m, int H, int n_out, const float* dhead, i
     else hipLaunchKernelGGL(hk::ppo_head_back_kernel, grid, dim3(256), 0, s, m, H, n_out, dhead, ldd, W0, W1, Z, dA.f);
 }
 
-// a network's layer l as the trunk products read it ([out][in]): PARAMS, or their bf16 shadow (the critic's shadow_pad elements on)
-PpoMat ppo_weights(const hk_context::Ppo& t, const hk::PpoNet& net, int l)
+// the weight at PARAMS offset o as the trunk products read it: PARAMS, or their bf16 shadow (what follows the actor shadow_pad elements on)
+PpoMat ppo_weights(const hk_context::Ppo& t, size_t o)
 {
-    if (t.prec != HK_PPO_PREC_BF16) return t.param + net.oW[l];
-    return t.shadow + net.oW[l] + (&net == &t.critic ? t.shadow_pad : 0);
+    if (t.prec != HK_PPO_PREC_BF16) return t.param + o;
+    return t.shadow + o + (o >= t.actor.count ? t.shadow_pad : 0);
 }
 
 // HK_PPO_PREC_BF16: PARAMS rounded into the shadow — after Adam, and at every entry point, since PARAMS is writable through hk_ppo_ptr
@@ -1575,30 +1591,88 @@ void ppo_shadow_refresh(hipStream_t s, const hk_context::Ppo& t)
     hipLaunchKernelGGL(hk::ppo_shadow_kernel, dim3(nblk(t.P)), dim3(256), 0, s, t.param, t.shadow, t.P, t.actor.count, t.shadow_pad);
 }
 
+// The trunk functions serve a PpoNet and the POCA critic's encoder (hk::PocaNet's oW / ob, n_layers layers of hidden x hidden on the pooled
+// sequences): what a trunk's first layer reads
+inline int ppo_trunk_in(const hk::PpoNet& net) { return net.in_dim; }
+inline int ppo_trunk_in(const hk::PocaNet& net) { return net.hidden; }
+
 // trunk forward on X0: Z[l] = W_l a_{l-1} + b_l (MFMA, k ascending; fp32), A[l] = swish(Z[l]) in the kind the workspace gave it
-void ppo_trunk_forward(hipStream_t s, const hk_context::Ppo& t, const hk::PpoNet& net, PpoMat X0, int m, float* const* Z, const PpoMat* A)
+template <typename Net>
+void ppo_trunk_forward(hipStream_t s, const hk_context::Ppo& t, const Net& net, PpoMat X0, int m, float* const* Z, const PpoMat* A)
 {
     const int H = net.hidden;
     for (int l = 0; l < net.n_layers; l++) {
-        const int K = l == 0 ? net.in_dim : H;
-        ppo_product<1>(s, m, H, K, l == 0 ? X0 : A[l - 1], K, true, ppo_weights(t, net, l), K, true, t.param + net.ob[l], A[l], H, Z[l], K);
+        const int K = l == 0 ? ppo_trunk_in(net) : H;
+        ppo_product<1>(s, m, H, K, l == 0 ? X0 : A[l - 1], K, true, ppo_weights(t, net.oW[l]), K, true, t.param + net.ob[l], A[l], H, Z[l], K);
     }
 }
 
-// trunk backward from dcur = dL / dZ[L - 1]: weight and bias gradients into grad, delta through W_l * swish' (dnext: the other delta buffer)
-void ppo_trunk_backward(hipStream_t s, const PpoWs& w, const hk_context::Ppo& t, const hk::PpoNet& net, float* grad, int m, float* const* Z, const PpoMat* A,
-                        PpoMat dcur, PpoMat dnext)
+// trunk backward from dcur = dL / dZ[L - 1]: weight and bias gradients into GRAD (through part), delta through W_l * swish' (dnext: the other
+// delta buffer; one swap per layer above the first).  -> the buffer that holds dL / dZ[0]
+template <typename Net>
+PpoMat ppo_trunk_backward(hipStream_t s, const hk_context::Ppo& t, const Net& net, float* part, PpoMat X0, int m, float* const* Z, const PpoMat* A, PpoMat dcur,
+                          PpoMat dnext)
 {
     const int H = net.hidden;
+    float* grad = t.param + t.P;
     for (int l = net.n_layers - 1; l >= 0; l--) {
-        const int K = l == 0 ? net.in_dim : H;
-        ppo_wgrad(s, w.part, H, K, m, dcur, H, l == 0 ? w.X0 : A[l - 1], K, grad + net.oW[l], nullptr);
+        const int K = l == 0 ? ppo_trunk_in(net) : H;
+        ppo_wgrad(s, part, H, K, m, dcur, H, l == 0 ? X0 : A[l - 1], K, grad + net.oW[l], nullptr);
         ppo_colsum(s, dcur, m, H, H, grad + net.ob[l]);
         if (l > 0) {
-            ppo_product<2>(s, m, H, H, dcur, H, true, ppo_weights(t, net, l), H, false, nullptr, dnext, H, Z[l - 1], H);
+            ppo_product<2>(s, m, H, H, dcur, H, true, ppo_weights(t, net.oW[l]), H, false, nullptr, dnext, H, Z[l - 1], H);
             std::swap(dcur, dnext);
         }
     }
+    return dcur;
+}
+
+// a value head's backward (W, b at PARAMS offsets oW, ob; H wide under the last activations A of pre-activations Z): the delta dv [m] into d0 = dL / dZ,
+// and the head's gradients
+void ppo_value_head_back(hipStream_t s, const hk_context::Ppo& t, float* part, int m, int H, float* dv, size_t oW, size_t ob, const float* Z, PpoMat A, PpoMat d0)
+{
+    float* grad = t.param + t.P;
+    ppo_head_back(s, m, H, 1, dv, 1, t.param + oW, nullptr, Z, d0);
+    ppo_wgrad(s, part, 1, H, m, dv, 1, A, H, grad + oW, nullptr);
+    ppo_colsum(s, dv, m, 1, 1, grad + ob);
+}
+
+// What differs between the trainers under ppo_loss_kernel: what stands in for the critic's last activation [m][Hc], the value head, the row ids
+struct PpoValueIn { const float* Ac; int Hc; const float *W_v, *b_v; const int* ids; };
+
+// the actor half of a minibatch, first part: ppo_loss_kernel and ppo_stats_kernel on the actor's last activations and the value input c
+// (acc: into the update's stats accumulator too)
+void ppo_actor_loss(hk_handle h, const hk_context::Ppo& t, const hk::PpoRows& P, const PpoWs& w, const PpoValueIn& c, int m, float eps, float beta, bool acc)
+{
+    const PpoRowBuf rows = ppo_rowbuf(h, t);
+    const float* prm = t.param;
+    const hk::PpoNet& na = t.actor;
+    hk::PpoLossArgs L{};
+    L.Aa = w.Aa[na.n_layers - 1].f; L.Ac = c.Ac;
+    L.W_mu = prm + na.oWmu; L.b_mu = prm + na.obmu; L.log_sigma = prm + na.ols; L.W_br = prm + na.oWbr; L.b_br = prm + na.obbr;
+    L.W_v = c.W_v; L.b_v = c.b_v;
+    L.v_old = rows.v_old; L.adv = rows.adv; L.ret = rows.ret;
+    L.ids = c.ids; L.valid = w.valid; L.n_valid = w.n_valid; L.m = m; L.n = t.n; L.Ha = na.hidden; L.Hc = c.Hc; L.nb = na.n_branch;
+    L.eps = eps; L.beta = beta;
+    L.dhead = w.dhead; L.dls = w.dls; L.dv = w.dv; L.rowstat = w.rowstat;
+    L.mu_out = w.mb_mu; L.logit_out = w.mb_logits; L.v_out = w.mb_v;
+    hipLaunchKernelGGL(hk::ppo_loss_kernel, dim3(nblk(m)), dim3(256), 0, h->stream, P, L);
+    hipLaunchKernelGGL(hk::ppo_stats_kernel, dim3(1), dim3(256), 0, h->stream, w.rowstat, m, w.stats, acc ? w.acc : nullptr);
+}
+
+// ... second part: the heads' backward (vector ALU; their gradients fp32 in both precisions), then the trunk's
+void ppo_actor_backward(hipStream_t s, const hk_context::Ppo& t, const PpoWs& w, int m)
+{
+    const float* prm = t.param;
+    float* grad = t.param + t.P;
+    const hk::PpoNet& na = t.actor;
+    const int Ha = na.hidden, nb = na.n_branch, La = na.n_layers - 1;
+    ppo_head_back(s, m, Ha, 1 + nb, w.dhead, hk::PM_MAX_OUT, prm + na.oWmu, prm + na.oWbr, w.Za[La], w.d0);
+    ppo_wgrad(s, w.part, 1 + nb, Ha, m, w.dhead, hk::PM_MAX_OUT, w.Aa[La], Ha, grad + na.oWmu, grad + na.oWbr);
+    ppo_colsum(s, w.dhead, m, hk::PM_MAX_OUT, 1, grad + na.obmu);
+    ppo_colsum(s, w.dhead + 1, m, hk::PM_MAX_OUT, nb, grad + na.obbr);
+    ppo_colsum(s, w.dls, m, 1, 1, grad + na.ols);
+    ppo_trunk_backward(s, t, na, w.part, w.X0, m, w.Za, w.Aa, w.d0, w.d1);
 }
 
 // ---- POCA (hk.h "POCA"; device side in hk_poca.h).  Everything below is reached only through a trainer made by hk_ppo_create_poca.
@@ -1608,7 +1682,7 @@ struct PocaWs {
     int *gids, *rid;
     float *XA, *Zent, *U, *N, *Q, *K, *V, *C, *alpha, *Oz, *O, *Zp;
     float2 *estat, *ostat;
-    float *Ze[HK_POLICY_MAX_LAYERS], *Ae[HK_POLICY_MAX_LAYERS];
+    float* Ze[HK_POLICY_MAX_LAYERS]; PpoMat Ae[HK_POLICY_MAX_LAYERS];          // the encoder, as the trunk functions take it (always fp32)
     float *out, *vrow, *brow, *mb_v, *dout, *d0, *d1, *dZp, *dPre, *dC, *dQs, *dKs, *dVs, *dQ, *dK, *dV, *dR, *dNq, *dNk, *dNv, *dZent, *part;
     double *rowstat_b, *pacc;
     float *pstats, *consts;          // consts: {1.0f, 0.0f}
@@ -1616,18 +1690,16 @@ struct PocaWs {
 
 size_t poca_ws_layout(const hk_context::Ppo& t, int S, int G, PocaWs* w)
 {
-    size_t off = 0;
-    char* base = w ? (char*)t.pws : nullptr;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
-    auto fl = [&](size_t count) { return (float*)take(count * 4); };
+    PpoBump a{w ? (char*)t.pws : nullptr};
+    auto fl = [&](size_t count) { return (float*)a.take(count * 4); };
     const hk::PocaNet& pn = t.pnet;
     const size_t H = pn.hidden, m = (size_t)G * S, E2 = 2 * m, NS = (size_t)(S + 1) * G, SR = NS * S;
     PocaWs d{};
-    d.gids = (int*)take((size_t)G * 4); d.rid = (int*)take(m * 4);
+    d.gids = (int*)a.take((size_t)G * 4); d.rid = (int*)a.take(m * 4);
     d.XA = fl(m * pn.n_act);
     d.Zent = fl(E2 * H); d.U = fl(E2 * H); d.N = fl(E2 * H); d.Q = fl(E2 * H); d.K = fl(E2 * H); d.V = fl(E2 * H);
     d.C = fl(SR * H); d.alpha = fl(NS * hk::POCA_HEADS * hk::POCA_MAXS * hk::POCA_MAXS); d.Oz = fl(SR * H); d.O = fl(SR * H); d.Zp = fl(NS * H);
-    d.estat = (float2*)take(E2 * 8); d.ostat = (float2*)take(SR * 8);
+    d.estat = (float2*)a.take(E2 * 8); d.ostat = (float2*)a.take(SR * 8);
     for (int l = 0; l < pn.n_layers; l++) { d.Ze[l] = fl(NS * H); d.Ae[l] = fl(NS * H); }
     d.out = fl(NS); d.vrow = fl(m); d.brow = fl(m); d.mb_v = fl(G); d.dout = fl(NS);
     d.d0 = fl(NS * H); d.d1 = fl(NS * H); d.dZp = fl(NS * H);
@@ -1635,26 +1707,27 @@ size_t poca_ws_layout(const hk_context::Ppo& t, int S, int G, PocaWs* w)
     d.dQ = fl(E2 * H); d.dK = fl(E2 * H); d.dV = fl(E2 * H); d.dR = fl(E2 * H); d.dNq = fl(E2 * H); d.dNk = fl(E2 * H); d.dNv = fl(E2 * H); d.dZent = fl(E2 * H);
     const size_t nz = (std::max(SR, E2) + hk::PPO_KCH - 1) / hk::PPO_KCH;          // the longest weight gradient's chunks, the largest one's tile
     d.part = fl(nz * H * std::max((size_t)pn.n_act, H));
-    d.rowstat_b = (double*)take(m * 8); d.pacc = (double*)take(2 * 8);
+    d.rowstat_b = (double*)a.take(m * 8); d.pacc = (double*)a.take(2 * 8);
     d.pstats = fl(HK_POCA_STATS); d.consts = fl(2);
     if (w) *w = d;
-    return off;
+    return a.off;
 }
 
-int poca_ensure_ws(hk_handle h, hk_context::Ppo& t, int S, int G, PocaWs& w)
+// the workspace as it is allocated now
+PocaWs poca_ws(hk_handle h, const hk_context::Ppo& t) { PocaWs pw; poca_ws_layout(t, h->policy[t.policy].q.n_slots, t.pcap, &pw); return pw; }
+
+int poca_ensure_ws(hk_handle h, hk_context::Ppo& t, int G, PocaWs& w)
 {
     if (G > t.pcap) {
-        if (t.pws) HK_HIP(h, hipFree(t.pws));
-        t.pws = nullptr; t.pcap = 0; t.last_mg = 0;
-        HK_HIP(h, hipMalloc(&t.pws, poca_ws_layout(t, S, G, nullptr)));
-        t.pcap = G;
-        poca_ws_layout(t, S, t.pcap, &w);
+        t.last_mg = 0;
+        if (int rc = ppo_grow(h, &t.pws, &t.pcap, G, poca_ws_layout(t, h->policy[t.policy].q.n_slots, G, nullptr))) return rc;
+        w = poca_ws(h, t);
         const float c[2] = {1.0f, 0.0f};
         HK_HIP(h, hipMemcpyAsync(w.consts, c, sizeof(c), hipMemcpyHostToDevice, h->stream));
         HK_HIP(h, hipMemsetAsync(w.pacc, 0, 2 * sizeof(double), h->stream));
         HK_HIP(h, hipStreamSynchronize(h->stream));          // (c is on this frame)
     }
-    poca_ws_layout(t, S, t.pcap, &w);
+    w = poca_ws(h, t);
     return HK_OK;
 }
 
@@ -1694,11 +1767,11 @@ void poca_forward(hipStream_t s, const hk_context::Ppo& t, const hk::PpoRows& P,
     poca_lin<0>(s, SR, H, H, pw.C, prm + pn.oWout, prm + pn.obout, pw.Oz, nullptr);
     hipLaunchKernelGGL(hk::poca_ln_kernel<true>, dim3(nblk(SR, 4)), dim3(256), 0, s, pw.Oz, pw.N, SR, H, S, m, pw.O, pw.ostat);
     hipLaunchKernelGGL(hk::poca_pool_kernel, dim3(nblk((size_t)NS * H)), dim3(256), 0, s, pw.O, NS, S, H, pw.Zp);
-    for (int l = 0; l < pn.n_layers; l++) poca_lin<1>(s, NS, H, H, l == 0 ? pw.Zp : pw.Ae[l - 1], prm + pn.oW[l], prm + pn.ob[l], pw.Ae[l], pw.Ze[l]);
-    hipLaunchKernelGGL(hk::poca_value_kernel, dim3(nblk(NS)), dim3(256), 0, s, pw.Ae[pn.n_layers - 1], NS, H, prm + pn.owval, prm + pn.obval, pw.out);
+    ppo_trunk_forward(s, t, pn, pw.Zp, NS, pw.Ze, pw.Ae);
+    hipLaunchKernelGGL(hk::poca_value_kernel, dim3(nblk(NS)), dim3(256), 0, s, pw.Ae[pn.n_layers - 1].f, NS, H, prm + pn.owval, prm + pn.obval, pw.out);
 }
 
-// one POCA minibatch of mg group ids: the actor side is ppo_mb's, launch for launch; the critic side is the attention critic
+// one POCA minibatch of mg group ids: the actor side is ppo_mb's (ppo_actor_loss, ppo_actor_backward); the critic side is the attention critic
 int poca_mb(hk_handle h, hk_context::Ppo& t, const int32_t* gids, int mg, float eps, float beta, bool acc)
 {
     const hk::PpoRows P = ppo_rows(h, t);
@@ -1707,57 +1780,30 @@ int poca_mb(hk_handle h, hk_context::Ppo& t, const int32_t* gids, int mg, float 
     PocaWs pw;
     int rc = ppo_ensure_ws(h, t, m, w);
     if (rc) return rc;
-    if ((rc = poca_ensure_ws(h, t, S, mg, pw))) return rc;
+    if ((rc = poca_ensure_ws(h, t, mg, pw))) return rc;
     hipStream_t s = h->stream;
     const PpoRowBuf rows = ppo_rowbuf(h, t);
     const PocaRowBuf prows = poca_rowbuf(t);
     const float* prm = t.param;
     float* grad = t.param + t.P;
-    const hk::PpoNet& na = t.actor;
     const hk::PocaNet& pn = t.pnet;
-    const int Ha = na.hidden, nb = na.n_branch, La = na.n_layers - 1, H = pn.hidden, L = pn.n_layers;
+    const int H = pn.hidden, L = pn.n_layers;
     const int E2 = 2 * m, NS = (S + 1) * mg, SR = NS * S;
     poca_forward(s, t, P, w, pw, gids, mg, 0);
     hipLaunchKernelGGL(hk::poca_scatter_kernel, dim3(nblk(m)), dim3(256), 0, s, pw.out, pw.rid, m, S, t.n, 0, nullptr, nullptr, nullptr, pw.vrow, pw.brow, pw.mb_v);
     hipLaunchKernelGGL(hk::ppo_count_kernel, dim3(1), dim3(256), 0, s, w.valid, m, w.n_valid);
-    ppo_trunk_forward(s, t, na, w.X0, m, w.Za, w.Aa);
+    ppo_trunk_forward(s, t, t.actor, w.X0, m, w.Za, w.Aa);
     // ppo_loss_kernel as it is: its "critic activation" is the row's group value, one wide, under the head (1, 0), so v = fmaf(V, 1, 0) = V
-    hk::PpoLossArgs Lo{};
-    Lo.Aa = w.Aa[La].f; Lo.Ac = pw.vrow;
-    Lo.W_mu = prm + na.oWmu; Lo.b_mu = prm + na.obmu; Lo.log_sigma = prm + na.ols; Lo.W_br = prm + na.oWbr; Lo.b_br = prm + na.obbr;
-    Lo.W_v = pw.consts; Lo.b_v = pw.consts + 1;
-    Lo.v_old = rows.v_old; Lo.adv = rows.adv; Lo.ret = rows.ret;
-    Lo.ids = pw.rid; Lo.valid = w.valid; Lo.n_valid = w.n_valid; Lo.m = m; Lo.n = t.n; Lo.Ha = Ha; Lo.Hc = 1; Lo.nb = nb;
-    Lo.eps = eps; Lo.beta = beta;
-    Lo.dhead = w.dhead; Lo.dls = w.dls; Lo.dv = w.dv; Lo.rowstat = w.rowstat;
-    Lo.mu_out = w.mb_mu; Lo.logit_out = w.mb_logits; Lo.v_out = w.mb_v;
-    hipLaunchKernelGGL(hk::ppo_loss_kernel, dim3(nblk(m)), dim3(256), 0, s, P, Lo);
-    hipLaunchKernelGGL(hk::ppo_stats_kernel, dim3(1), dim3(256), 0, s, w.rowstat, m, w.stats, acc ? w.acc : nullptr);
+    ppo_actor_loss(h, t, P, w, PpoValueIn{pw.vrow, 1, pw.consts, pw.consts + 1, pw.rid}, m, eps, beta, acc);
     hipLaunchKernelGGL(hk::poca_loss_kernel, dim3(nblk(mg)), dim3(256), 0, s, pw.brow, pw.rid, w.valid, w.n_valid, prows.b_old, rows.ret, w.dv, mg, S, t.n, eps,
                        pw.dout, pw.rowstat_b);
     hipLaunchKernelGGL(hk::poca_stats_kernel, dim3(1), dim3(256), 0, s, pw.rowstat_b, m, S, w.n_valid, w.stats, acc ? w.acc : nullptr, pw.pstats,
                        acc ? pw.pacc : nullptr);
-    // actor: ppo_mb's lines
-    ppo_head_back(s, m, Ha, 1 + nb, w.dhead, hk::PM_MAX_OUT, prm + na.oWmu, prm + na.oWbr, w.Za[La], w.d0);
-    ppo_wgrad(s, w.part, 1 + nb, Ha, m, w.dhead, hk::PM_MAX_OUT, w.Aa[La], Ha, grad + na.oWmu, grad + na.oWbr);
-    ppo_colsum(s, w.dhead, m, hk::PM_MAX_OUT, 1, grad + na.obmu);
-    ppo_colsum(s, w.dhead + 1, m, hk::PM_MAX_OUT, nb, grad + na.obbr);
-    ppo_colsum(s, w.dls, m, 1, 1, grad + na.ols);
-    ppo_trunk_backward(s, w, t, na, grad, m, w.Za, w.Aa, w.d0, w.d1);
-    // critic: the head and the encoder over the NS sequences
-    ppo_head_back(s, NS, H, 1, pw.dout, 1, prm + pn.owval, nullptr, pw.Ze[L - 1], pw.d0);
-    ppo_wgrad(s, pw.part, 1, H, NS, pw.dout, 1, pw.Ae[L - 1], H, grad + pn.owval, nullptr);
-    ppo_colsum(s, pw.dout, NS, 1, 1, grad + pn.obval);
-    float *dcur = pw.d0, *dnext = pw.d1;
-    for (int l = L - 1; l >= 0; l--) {
-        ppo_wgrad(s, pw.part, H, H, NS, dcur, H, l == 0 ? pw.Zp : pw.Ae[l - 1], H, grad + pn.oW[l], nullptr);
-        ppo_colsum(s, dcur, NS, H, H, grad + pn.ob[l]);
-        if (l > 0) {
-            poca_lin_t<2>(s, NS, H, H, dcur, prm + pn.oW[l], dnext, pw.Ze[l - 1]);
-            std::swap(dcur, dnext);
-        }
-    }
-    poca_lin_t<0>(s, NS, H, H, dcur, prm + pn.oW[0], pw.dZp, nullptr);
+    ppo_actor_backward(s, t, w, m);
+    // critic: the head and the encoder over the NS sequences, then the encoder's input
+    ppo_value_head_back(s, t, pw.part, NS, H, pw.dout, pn.owval, pn.obval, pw.Ze[L - 1], pw.Ae[L - 1], pw.d0);
+    const PpoMat dz0 = ppo_trunk_backward(s, t, pn, pw.part, pw.Zp, NS, pw.Ze, pw.Ae, pw.d0, pw.d1);
+    poca_lin_t<0>(s, NS, H, H, dz0.f, prm + pn.oW[0], pw.dZp, nullptr);
     // the pool and the out-LayerNorm, W_out, the attention core
     hipLaunchKernelGGL(hk::poca_out_bwd_kernel, dim3(nblk(SR, 4)), dim3(256), 0, s, pw.dZp, pw.O, pw.ostat, SR, S, H, pw.dPre);
     ppo_wgrad(s, pw.part, H, H, SR, pw.dPre, H, pw.C, H, grad + pn.oWout, nullptr);
@@ -1784,34 +1830,20 @@ int poca_mb(hk_handle h, hk_context::Ppo& t, const int32_t* gids, int mg, float 
     return HK_OK;
 }
 
-// hk_ppo_advantages of a POCA trainer: V and B over every group and V over the E bootstrap groups, in chunks; then the lambda-returns
-int poca_advantages(hk_handle h, hk_context::Ppo& t)
+// hk_ppo_advantages of a POCA trainer, between the frame's two halves: V and B over every group and V over the E bootstrap groups, in chunks; then
+// the lambda-returns
+int poca_values_and_returns(hk_handle h, hk_context::Ppo& t, const hk::PpoRows& P)
 {
-    const hk::PpoRows P = ppo_rows(h, t);
     const auto& ro = h->ro;
     const int S = P.S, G = P.R * P.E, n = G * S, nbt = P.E * S;
     int rc;
-    const size_t need = 3 * (size_t)n + nbt + n;
-    if (need > t.rowbuf_n) {
-        if (t.rowbuf) HK_HIP(h, hipFree(t.rowbuf));
-        t.rowbuf = nullptr; t.rowbuf_n = 0;
-        HK_HIP(h, hipMalloc(&t.rowbuf, need * sizeof(float)));
-        t.rowbuf_n = need;
-    }
-    if (2 * (size_t)n > t.prow_n) {
-        if (t.prow) HK_HIP(h, hipFree(t.prow));
-        t.prow = nullptr; t.prow_n = 0;
-        HK_HIP(h, hipMalloc(&t.prow, 2 * (size_t)n * sizeof(float)));
-        t.prow_n = 2 * (size_t)n;
-    }
-    t.n = n;
     const PpoRowBuf rows = ppo_rowbuf(h, t);
     const PocaRowBuf prows = poca_rowbuf(t);
     const int chunk = std::max(t.pcap, std::min(G + P.E, 4096));
     PpoWs w;
     PocaWs pw;
     if ((rc = ppo_ensure_ws(h, t, chunk * S, w))) return rc;
-    if ((rc = poca_ensure_ws(h, t, S, chunk, pw))) return rc;
+    if ((rc = poca_ensure_ws(h, t, chunk, pw))) return rc;
     hipStream_t s = h->stream;
     for (int base = 0; base < G + P.E; base += chunk) {
         const int mg = std::min(chunk, G + P.E - base);
@@ -1822,12 +1854,31 @@ int poca_advantages(hk_handle h, hk_context::Ppo& t)
     }
     hipLaunchKernelGGL(hk::poca_lambda_kernel, dim3(nblk(nbt)), dim3(256), 0, s, P, ro.at<float>(HK_RO_GROUP_REWARD), ro.at<float>(HK_RO_TERM_GROUP_REWARD),
                        rows.v_old, prows.b_old, rows.v_boot, t.cfg.gamma, t.cfg.lambd, prows.team, rows.adv, rows.ret);
-    if (t.cfg.normalize_advantages) hipLaunchKernelGGL(hk::ppo_adv_norm_kernel, dim3(1), dim3(1024), 0, s, rows.adv, n);
-    HK_HIP(h, hipGetLastError());
-    t.adv_gen = ro.gen;
-    t.perm_valid = false;
-    t.adv_stale = false;
-    t.last_m = 0; t.last_mg = 0;          // the chunks went through the minibatch workspace
+    t.last_m = 0; t.last_mg = 0;          // the chunks went through the minibatch workspace (only here: see hk_ppo_advantages)
+    return HK_OK;
+}
+
+// ... and of a PPO trainer: the critic over every row and the E S bootstrap rows, in chunks; then GAE
+int ppo_values_and_gae(hk_handle h, hk_context::Ppo& t, const hk::PpoRows& P)
+{
+    const int n = t.n, nbt = P.E * P.S;
+    const PpoRowBuf rows = ppo_rowbuf(h, t);
+    PpoWs w;
+    const int chunk = std::max(t.cap, std::min(n + nbt, 16384));
+    int rc = ppo_ensure_ws(h, t, chunk, w);
+    if (rc) return rc;
+    hipStream_t s = h->stream;
+    const hk::PpoNet& nc = t.critic;
+    ppo_shadow_refresh(s, t);          // (only here: see hk_ppo_advantages)
+    for (int base = 0; base < n + nbt; base += chunk) {
+        const int m = std::min(chunk, n + nbt - base);
+        hipLaunchKernelGGL(hk::ppo_iota_kernel, dim3(nblk(m)), dim3(256), 0, s, w.ids, base, m);
+        ppo_gather(s, P, w.ids, m, 1, w.X0, w.valid);
+        ppo_trunk_forward(s, t, nc, w.X0, m, w.Zc, w.Ac);
+        hipLaunchKernelGGL(hk::ppo_value_kernel, dim3(nblk(m)), dim3(256), 0, s, w.Ac[nc.n_layers - 1].f, m, nc.hidden, t.param + nc.oWmu, t.param + nc.obmu,
+                           w.ids, n, nbt, rows.v_old, rows.v_boot);
+    }
+    hipLaunchKernelGGL(hk::ppo_gae_kernel, dim3(nblk(nbt)), dim3(256), 0, s, P, rows.v_old, rows.v_boot, t.cfg.gamma, t.cfg.lambd, rows.adv, rows.ret);
     return HK_OK;
 }
 
@@ -1840,38 +1891,18 @@ int ppo_mb(hk_handle h, hk_context::Ppo& t, const int32_t* ids, int m, float eps
     if (rc) return rc;
     hipStream_t s = h->stream;
     const hk::PpoRows P = ppo_rows(h, t);
-    const PpoRowBuf rows = ppo_rowbuf(h, t);
     const float* prm = t.param;
-    float* grad = t.param + t.P;
-    const hk::PpoNet &na = t.actor, &nc = t.critic;
-    const int Ha = na.hidden, Hc = nc.hidden, nb = na.n_branch, La = na.n_layers - 1, Lc = nc.n_layers - 1;      // La, Lc: the last trunk layers
+    const hk::PpoNet& nc = t.critic;
+    const int Hc = nc.hidden, Lc = nc.n_layers - 1;      // Lc: the last trunk layer
     ppo_gather(s, P, ids, m, 0, w.X0, w.valid);
     hipLaunchKernelGGL(hk::ppo_count_kernel, dim3(1), dim3(256), 0, s, w.valid, m, w.n_valid);
-    ppo_trunk_forward(s, t, na, w.X0, m, w.Za, w.Aa);
+    ppo_trunk_forward(s, t, t.actor, w.X0, m, w.Za, w.Aa);
     ppo_trunk_forward(s, t, nc, w.X0, m, w.Zc, w.Ac);
-    hk::PpoLossArgs L{};
-    L.Aa = w.Aa[La].f; L.Ac = w.Ac[Lc].f;
-    L.W_mu = prm + na.oWmu; L.b_mu = prm + na.obmu; L.log_sigma = prm + na.ols; L.W_br = prm + na.oWbr; L.b_br = prm + na.obbr;
-    L.W_v = prm + nc.oWmu; L.b_v = prm + nc.obmu;
-    L.v_old = rows.v_old; L.adv = rows.adv; L.ret = rows.ret;
-    L.ids = ids; L.valid = w.valid; L.n_valid = w.n_valid; L.m = m; L.n = t.n; L.Ha = Ha; L.Hc = Hc; L.nb = nb;
-    L.eps = eps; L.beta = beta;
-    L.dhead = w.dhead; L.dls = w.dls; L.dv = w.dv; L.rowstat = w.rowstat;
-    L.mu_out = w.mb_mu; L.logit_out = w.mb_logits; L.v_out = w.mb_v;
-    hipLaunchKernelGGL(hk::ppo_loss_kernel, dim3(nblk(m)), dim3(256), 0, s, P, L);
-    hipLaunchKernelGGL(hk::ppo_stats_kernel, dim3(1), dim3(256), 0, s, w.rowstat, m, w.stats, acc ? w.acc : nullptr);
-    // actor: the heads (vector ALU; their gradients fp32 in both precisions), then the trunk
-    ppo_head_back(s, m, Ha, 1 + nb, w.dhead, hk::PM_MAX_OUT, prm + na.oWmu, prm + na.oWbr, w.Za[La], w.d0);
-    ppo_wgrad(s, w.part, 1 + nb, Ha, m, w.dhead, hk::PM_MAX_OUT, w.Aa[La], Ha, grad + na.oWmu, grad + na.oWbr);
-    ppo_colsum(s, w.dhead, m, hk::PM_MAX_OUT, 1, grad + na.obmu);
-    ppo_colsum(s, w.dhead + 1, m, hk::PM_MAX_OUT, nb, grad + na.obbr);
-    ppo_colsum(s, w.dls, m, 1, 1, grad + na.ols);
-    ppo_trunk_backward(s, w, t, na, grad, m, w.Za, w.Aa, w.d0, w.d1);
+    ppo_actor_loss(h, t, P, w, PpoValueIn{w.Ac[Lc].f, Hc, prm + nc.oWmu, prm + nc.obmu, ids}, m, eps, beta, acc);
+    ppo_actor_backward(s, t, w, m);
     // critic
-    ppo_head_back(s, m, Hc, 1, w.dv, 1, prm + nc.oWmu, nullptr, w.Zc[Lc], w.d0);
-    ppo_wgrad(s, w.part, 1, Hc, m, w.dv, 1, w.Ac[Lc], Hc, grad + nc.oWmu, nullptr);
-    ppo_colsum(s, w.dv, m, 1, 1, grad + nc.obmu);
-    ppo_trunk_backward(s, w, t, nc, grad, m, w.Zc, w.Ac, w.d0, w.d1);
+    ppo_value_head_back(s, t, w.part, m, Hc, w.dv, nc.oWmu, nc.obmu, w.Zc[Lc], w.Ac[Lc], w.d0);
+    ppo_trunk_backward(s, t, nc, w.part, w.X0, m, w.Zc, w.Ac, w.d0, w.d1);
     HK_HIP(h, hipGetLastError());
     t.last_m = m;
     return HK_OK;
@@ -1911,12 +1942,18 @@ int ppo_adam_step(hk_handle h, hk_context::Ppo& t, float lr, float max_norm = 0.
     return HK_OK;
 }
 
+// what changes or reads state that an open rollout owns
+int ppo_refuse_open(hk_handle h, const char* fn)
+{
+    return h->ro.open ? fail(h, HK_ERR_INVALID, std::string(fn) + ": refused while a rollout is open (hk_rollout_close first)") : HK_OK;
+}
+
 int ppo_check(hk_handle h, int trainer, const char* fn, bool need_adv)
 {
     if (trainer < 0 || trainer >= h->n_ppo) return fail(h, HK_ERR_INVALID, std::string(fn) + ": bad trainer index");
     const auto& t = h->ppo[trainer];
     if (!need_adv) return HK_OK;
-    if (h->ro.open) return fail(h, HK_ERR_INVALID, std::string(fn) + ": refused while a rollout is open (hk_rollout_close first)");
+    if (int rc = ppo_refuse_open(h, fn)) return rc;
     if (t.adv_gen != h->ro.gen) return fail(h, HK_ERR_INVALID, std::string(fn) + ": hk_ppo_advantages has not run on the current rollout");
     if (t.adv_stale) return fail(h, HK_ERR_INVALID, std::string(fn) + ": the actor's normaliser changed after hk_ppo_advantages (run it again)");
     return HK_OK;
@@ -1927,7 +1964,7 @@ int ppo_check_rows(hk_handle h, const hk_context::Ppo& t, const char* fn)
 {
     const auto& ro = h->ro;
     const std::string f(fn);
-    if (ro.open) return fail(h, HK_ERR_INVALID, f + ": refused while a rollout is open (hk_rollout_close first)");
+    if (int rc = ppo_refuse_open(h, fn)) return rc;
     if (ro.R == 0 || !ro.buf) return fail(h, HK_ERR_INVALID, f + ": no rollout yet (hk_rollout_begin ... hk_rollout_close)");
     if (ro.rows < 1) return fail(h, HK_ERR_INVALID, f + ": the rollout closed with no completed row");
     if (t.policy >= ro.npol) return fail(h, HK_ERR_INVALID, f + ": the rollout began before the trainer's actor was attached");
@@ -1942,7 +1979,7 @@ int ppo_norm_check(hk_handle h, int trainer, const char* fn, bool need_state)
     const auto& t = h->ppo[trainer];
     const std::string f(fn);
     if (!h->policy[t.policy].q.normalize) return fail(h, HK_ERR_INVALID, f + ": the policy was attached with normalize == 0 (it has no statistics)");
-    if (h->ro.open) return fail(h, HK_ERR_INVALID, f + ": refused while a rollout is open (hk_rollout_close first)");
+    if ((rc = ppo_refuse_open(h, fn))) return rc;
     if (need_state && t.norm_steps < 1) return fail(h, HK_ERR_INVALID, f + ": no normaliser state (hk_ppo_normalizer_init or hk_ppo_normalizer_set first)");
     return HK_OK;
 }
@@ -1978,39 +2015,30 @@ void ppo_norm_stale(hk_handle h, int policy)
     for (int i = 0; i < h->n_ppo; i++) if (h->ppo[i].policy == policy) h->ppo[i].adv_stale = true;
 }
 
-}  // namespace
-}  // extern "C++"
-
-int hk_ppo_create(hk_handle h, int policy, const hk_policy_desc* c, const hk_ppo_config* cfg)
+// hk_ppo_create and hk_ppo_create_poca (fn): the checks both start with, critic_checks() (the entry point's own refusals, in their place in the
+// order), the config, the slot and the actor's layout; pack_critic(t, host) lays the critic out behind the actor and packs its parameters in
+// that order; then PARAMS .. ADAM_V [4][P], zeroed, the critic uploaded and the actor's weights copied from the policy.  -> the trainer's index
+template <typename Checks, typename Pack>
+int ppo_create(hk_handle h, const char* fn, int policy, bool have_critic, const hk_ppo_config* cfg, Checks critic_checks, Pack pack_critic)
 {
-    HK_NEED_ENV(h);
-    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, "hk_ppo_create: bad policy index");
-    if (h->n_ppo >= HK_MAX_POLICIES) return fail(h, HK_ERR_INVALID, "hk_ppo_create: HK_MAX_POLICIES trainers already exist");
+    const std::string f = std::string(fn) + ": ";
+    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, f + "bad policy index");
+    if (h->n_ppo >= HK_MAX_POLICIES) return fail(h, HK_ERR_INVALID, f + "HK_MAX_POLICIES trainers already exist");
+    if (!have_critic) return fail(h, HK_ERR_INVALID, f + "NULL critic");
     const hk::PolicyParams& q = h->policy[policy].q;
-    if (!c) return fail(h, HK_ERR_INVALID, "hk_ppo_create: NULL critic");
-    if (c->in_dim != q.in_dim) return fail(h, HK_ERR_INVALID, "hk_ppo_create: the critic's in_dim differs from the actor's");
-    if (c->hidden < 32 || c->hidden > HK_POLICY_MAX_HIDDEN || c->hidden % 32 || c->n_layers < 1 || c->n_layers > HK_POLICY_MAX_LAYERS || c->n_branch != 0)
-        return fail(h, HK_ERR_INVALID, "hk_ppo_create: critic hidden / n_layers out of the actor's limits, or n_branch != 0");
-    for (int l = 0; l < c->n_layers; l++) if (!c->W[l] || !c->b[l]) return fail(h, HK_ERR_INVALID, "hk_ppo_create: NULL critic layer weights");
-    if (!c->W_mu || !c->b_mu) return fail(h, HK_ERR_INVALID, "hk_ppo_create: NULL critic value head");
+    int rc = critic_checks(q);
+    if (rc) return rc;
     hk_ppo_config d{0.99f, 0.95f, 1, 0.9f, 0.999f, 1e-8f, 0u};
     if (cfg) d = *cfg;
     if (!(d.adam_beta1 >= 0.0f && d.adam_beta1 < 1.0f && d.adam_beta2 >= 0.0f && d.adam_beta2 < 1.0f && d.adam_eps > 0.0f))
-        return fail(h, HK_ERR_INVALID, "hk_ppo_create: Adam constants out of range");
+        return fail(h, HK_ERR_INVALID, f + "Adam constants out of range");
     auto& t = h->ppo[h->n_ppo];
     t = hk_context::Ppo{};
     t.policy = policy; t.cfg = d;
     t.actor.layout(q.in_dim, q.hidden, q.n_layers, q.n_branch, 0);
-    t.critic.layout(q.in_dim, c->hidden, c->n_layers, 0, t.actor.count);
-    t.P = t.actor.count + t.critic.count;
-    std::vector<float> host(t.critic.count);
-    for (int l = 0; l < c->n_layers; l++) {
-        const size_t nw = (size_t)c->hidden * (l == 0 ? c->in_dim : c->hidden);
-        std::memcpy(&host[t.critic.oW[l] - t.actor.count], c->W[l], nw * 4);
-        std::memcpy(&host[t.critic.ob[l] - t.actor.count], c->b[l], (size_t)c->hidden * 4);
-    }
-    std::memcpy(&host[t.critic.oWmu - t.actor.count], c->W_mu, (size_t)c->hidden * 4);
-    host[t.critic.obmu - t.actor.count] = c->b_mu[0];
+    std::vector<float> host;
+    pack_critic(t, host);
+    t.P = t.actor.count + host.size();
     hipError_t e = hipMalloc(&t.param, 4 * t.P * sizeof(float));
     if (e == hipSuccess) e = hipMemsetAsync(t.param, 0, 4 * t.P * sizeof(float), h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(t.param + t.actor.count, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
@@ -2020,11 +2048,45 @@ int hk_ppo_create(hk_handle h, int policy, const hk_policy_desc* c, const hk_ppo
     }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) {          // (the slot is not taken: free what was allocated)
-        if (t.param) (void)hipFree(t.param);
-        t = hk_context::Ppo{};
-        return fail(h, HK_ERR_HIP, std::string("hk_ppo_create: ") + hipGetErrorString(e));
+        ppo_release(t);
+        return fail(h, HK_ERR_HIP, f + hipGetErrorString(e));
     }
     return h->n_ppo++;
+}
+
+}  // namespace
+}  // extern "C++"
+
+static void ppo_release(hk_context::Ppo& t)
+{
+    (void)ppo_free(t.param); (void)ppo_free(t.rowbuf); (void)ppo_free(t.ws); (void)ppo_free(t.shadow); (void)ppo_free(t.norm);
+    (void)ppo_free(t.norm_part); (void)ppo_free(t.clip); (void)ppo_free(t.prow); (void)ppo_free(t.pws);
+    t = hk_context::Ppo{};
+}
+
+int hk_ppo_create(hk_handle h, int policy, const hk_policy_desc* c, const hk_ppo_config* cfg)
+{
+    HK_NEED_ENV(h);
+    auto checks = [&](const hk::PolicyParams& q) {
+        if (c->in_dim != q.in_dim) return fail(h, HK_ERR_INVALID, "hk_ppo_create: the critic's in_dim differs from the actor's");
+        if (c->hidden < 32 || c->hidden > HK_POLICY_MAX_HIDDEN || c->hidden % 32 || c->n_layers < 1 || c->n_layers > HK_POLICY_MAX_LAYERS || c->n_branch != 0)
+            return fail(h, HK_ERR_INVALID, "hk_ppo_create: critic hidden / n_layers out of the actor's limits, or n_branch != 0");
+        for (int l = 0; l < c->n_layers; l++) if (!c->W[l] || !c->b[l]) return fail(h, HK_ERR_INVALID, "hk_ppo_create: NULL critic layer weights");
+        if (!c->W_mu || !c->b_mu) return fail(h, HK_ERR_INVALID, "hk_ppo_create: NULL critic value head");
+        return (int)HK_OK;
+    };
+    auto pack = [&](hk_context::Ppo& t, std::vector<float>& host) {
+        t.critic.layout(t.actor.in_dim, c->hidden, c->n_layers, 0, t.actor.count);
+        host.resize(t.critic.count);
+        for (int l = 0; l < c->n_layers; l++) {
+            const size_t nw = (size_t)c->hidden * (l == 0 ? c->in_dim : c->hidden);
+            std::memcpy(&host[t.critic.oW[l] - t.actor.count], c->W[l], nw * 4);
+            std::memcpy(&host[t.critic.ob[l] - t.actor.count], c->b[l], (size_t)c->hidden * 4);
+        }
+        std::memcpy(&host[t.critic.oWmu - t.actor.count], c->W_mu, (size_t)c->hidden * 4);
+        host[t.critic.obmu - t.actor.count] = c->b_mu[0];
+    };
+    return ppo_create(h, "hk_ppo_create", policy, c != nullptr, cfg, checks, pack);
 }
 
 int hk_ppo_advantages(hk_handle h, int trainer)
@@ -2035,34 +2097,17 @@ int hk_ppo_advantages(hk_handle h, int trainer)
     auto& t = h->ppo[trainer];
     const auto& ro = h->ro;
     if ((rc = ppo_check_rows(h, t, "hk_ppo_advantages"))) return rc;
-    if (t.poca) return poca_advantages(h, t);
+    // The frame both trainers share: the rows' buffers and t.n, the trainer's own chunk loop and lambda / GAE kernel, then the normalisation and
+    // the marks.  Two asymmetries inside the trainers' parts are intended.  ppo_shadow_refresh is issued on the PPO path only: a POCA trainer is
+    // always fp32 and has no shadow.  last_m / last_mg are zeroed on the POCA path only, so the MB fields of a POCA trainer read "no minibatch
+    // yet" after this call while a PPO trainer's keep what its last minibatch wrote (the PPO chunks write none of mb_mu / mb_logits / mb_v).
     const hk::PpoRows P = ppo_rows(h, t);
-    const int n = P.R * P.E * P.S, nbt = P.E * P.S;
-    const size_t need = 3 * (size_t)n + nbt + n;
-    if (need > t.rowbuf_n) {
-        if (t.rowbuf) HK_HIP(h, hipFree(t.rowbuf));
-        t.rowbuf = nullptr; t.rowbuf_n = 0;
-        HK_HIP(h, hipMalloc(&t.rowbuf, need * sizeof(float)));
-        t.rowbuf_n = need;
-    }
-    t.n = n;
-    const PpoRowBuf rows = ppo_rowbuf(h, t);
-    PpoWs w;
-    const int chunk = std::max(t.cap, std::min(n + nbt, 16384));
-    if ((rc = ppo_ensure_ws(h, t, chunk, w))) return rc;
-    hipStream_t s = h->stream;
-    const hk::PpoNet& nc = t.critic;
-    ppo_shadow_refresh(s, t);
-    for (int base = 0; base < n + nbt; base += chunk) {
-        const int m = std::min(chunk, n + nbt - base);
-        hipLaunchKernelGGL(hk::ppo_iota_kernel, dim3(nblk(m)), dim3(256), 0, s, w.ids, base, m);
-        ppo_gather(s, P, w.ids, m, 1, w.X0, w.valid);
-        ppo_trunk_forward(s, t, nc, w.X0, m, w.Zc, w.Ac);
-        hipLaunchKernelGGL(hk::ppo_value_kernel, dim3(nblk(m)), dim3(256), 0, s, w.Ac[nc.n_layers - 1].f, m, nc.hidden, t.param + nc.oWmu, t.param + nc.obmu,
-                           w.ids, n, nbt, rows.v_old, rows.v_boot);
-    }
-    hipLaunchKernelGGL(hk::ppo_gae_kernel, dim3(nblk(nbt)), dim3(256), 0, s, P, rows.v_old, rows.v_boot, t.cfg.gamma, t.cfg.lambd, rows.adv, rows.ret);
-    if (t.cfg.normalize_advantages) hipLaunchKernelGGL(hk::ppo_adv_norm_kernel, dim3(1), dim3(1024), 0, s, rows.adv, n);
+    const size_t n = (size_t)P.R * P.E * P.S, nbt = (size_t)P.E * P.S;
+    if ((rc = ppo_grow(h, &t.rowbuf, &t.rowbuf_n, 3 * n + nbt + n, (3 * n + nbt + n) * sizeof(float)))) return rc;
+    if (t.poca && (rc = ppo_grow(h, &t.prow, &t.prow_n, 2 * n, 2 * n * sizeof(float)))) return rc;
+    t.n = (int)n;
+    if ((rc = t.poca ? poca_values_and_returns(h, t, P) : ppo_values_and_gae(h, t, P))) return rc;
+    if (t.cfg.normalize_advantages) hipLaunchKernelGGL(hk::ppo_adv_norm_kernel, dim3(1), dim3(1024), 0, h->stream, ppo_rowbuf(h, t).adv, t.n);
     HK_HIP(h, hipGetLastError());
     t.adv_gen = ro.gen;
     t.perm_valid = false;
@@ -2081,9 +2126,7 @@ int hk_ppo_minibatch(hk_handle h, int trainer, const int32_t* rows_dev, int m, f
     if ((rc = ppo_mb(h, t, rows_dev, m, eps, beta, false))) return rc;
     t.lb_from_update = false;
     if (stats) {
-        PpoWs w;
-        ppo_ws_layout(t, t.cap, &w);
-        HK_HIP(h, hipMemcpyAsync(stats, w.stats, HK_PPO_STATS * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HK_HIP(h, hipMemcpyAsync(stats, ppo_ws(t).stats, HK_PPO_STATS * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HK_HIP(h, hipStreamSynchronize(h->stream));
     }
     return HK_OK;
@@ -2102,7 +2145,7 @@ int hk_ppo_publish(hk_handle h, int trainer)
     HK_NEED_ENV(h);
     int rc = ppo_check(h, trainer, "hk_ppo_publish", false);
     if (rc) return rc;
-    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_ppo_publish: refused while a rollout is open (hk_rollout_close first)");
+    if ((rc = ppo_refuse_open(h, "hk_ppo_publish"))) return rc;
     auto& t = h->ppo[trainer];
     hipLaunchKernelGGL(hk::ppo_publish_kernel<true>, dim3(nblk(t.actor.count)), dim3(256), 0, h->stream, h->policy[t.policy].q, t.actor, t.param);
     HK_HIP(h, hipGetLastError());
@@ -2131,7 +2174,7 @@ int ppo_update_run(hk_handle h, int trainer, bool opt, int epochs, int minibatch
     PocaWs pw{};
     int rc;
     if ((rc = ppo_ensure_ws(h, t, mb * per, w))) return rc;
-    if (t.poca && (rc = poca_ensure_ws(h, t, per, mb, pw))) return rc;
+    if (t.poca && (rc = poca_ensure_ws(h, t, mb, pw))) return rc;
     if (max_norm > 0.0f && (rc = ppo_ensure_clip(h, t))) return rc;
     if (opt && t.clip) HK_HIP(h, hipMemsetAsync(t.clip + 2, 0, 5 * sizeof(double), h->stream));       // the accumulating words [2 .. 6]
     ppo_shadow_refresh(h->stream, t);
@@ -2239,7 +2282,7 @@ int hk_ppo_set_counters(hk_handle h, int trainer, int64_t adam_steps, int64_t ep
     HK_NEED_ENV(h);
     int rc = ppo_check(h, trainer, "hk_ppo_set_counters", false);
     if (rc) return rc;
-    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_ppo_set_counters: refused while a rollout is open (hk_rollout_close first)");
+    if ((rc = ppo_refuse_open(h, "hk_ppo_set_counters"))) return rc;
     if (adam_steps < 0 || adam_steps > INT32_MAX) return fail(h, HK_ERR_INVALID, "hk_ppo_set_counters: adam_steps outside [0, INT32_MAX]");
     if (epochs_done < 0 || epochs_done > INT32_MAX) return fail(h, HK_ERR_INVALID, "hk_ppo_set_counters: epochs_done outside [0, INT32_MAX]");
     auto& t = h->ppo[trainer];
@@ -2314,12 +2357,7 @@ int hk_ppo_normalizer_update(hk_handle h, int trainer)
     ipw = (ipw + trip - 1) / trip * trip;
     if (items + ipw > 0x7FFFFFFFLL) return fail(h, HK_ERR_UNSUPPORTED, "hk_ppo_normalizer_update: more than 2^31 recorded observations");
     const int nwg = (int)((items + ipw - 1) / ipw);
-    if (nwg > t.norm_part_wg) {
-        if (t.norm_part) HK_HIP(h, hipFree(t.norm_part));
-        t.norm_part = nullptr; t.norm_part_wg = 0;
-        HK_HIP(h, hipMalloc(&t.norm_part, (size_t)nwg * W * sizeof(double)));
-        t.norm_part_wg = nwg;
-    }
+    if ((rc = ppo_grow(h, &t.norm_part, &t.norm_part_wg, nwg, (size_t)nwg * W * sizeof(double)))) return rc;
     hipStream_t s = h->stream;
     double* sums = t.norm + 2 * (size_t)K;
     const dim3 grid(nwg, (P.stack + hk::PPO_NORM_Q - 1) / hk::PPO_NORM_Q, (P.D + 255) / 256);
@@ -2345,7 +2383,8 @@ int hk_ppo_set_precision(hk_handle h, int trainer, int precision)
     if (precision == t.prec) return HK_OK;
     // the workspace is laid out per precision: drop it once the stream is done with it (the next minibatch allocates the other layout)
     HK_HIP(h, hipStreamSynchronize(h->stream));
-    if ((rc = ppo_drop_ws(h, t))) return rc;
+    t.cap = 0; t.last_m = 0;
+    HK_HIP(h, ppo_free(t.ws));
     if (precision == HK_PPO_PREC_BF16 && !t.shadow) {
         t.shadow_pad = (8 - t.actor.count % 8) % 8;
         HK_HIP(h, hipMalloc(&t.shadow, (t.P + t.shadow_pad) * sizeof(uint16_t)));
@@ -2420,12 +2459,9 @@ void* hk_ppo_ptr(hk_handle h, int trainer, int field)
     }
     if (t.last_m == 0) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: no minibatch yet"); return nullptr; }
     if (t.poca && field == HK_PPO_MB_VALUE) {          // one value per group
-        PocaWs pw;
-        poca_ws_layout(t, h->policy[t.policy].q.n_slots, t.pcap, &pw);
-        return pw.mb_v;
+        return poca_ws(h, t).mb_v;
     }
-    PpoWs w;
-    ppo_ws_layout(t, t.cap, &w);
+    const PpoWs w = ppo_ws(t);
     return field == HK_PPO_MB_MU ? (void*)w.mb_mu : field == HK_PPO_MB_LOGITS ? (void*)w.mb_logits : (void*)w.mb_v;
 }
 
@@ -2448,60 +2484,40 @@ int hk_ppo_count(hk_handle h, int trainer, int field)
 int hk_ppo_create_poca(hk_handle h, int policy, const hk_poca_critic_desc* c, const hk_ppo_config* cfg)
 {
     HK_NEED_ENV(h);
-    const char* fn = "hk_ppo_create_poca: ";
-    auto bad = [&](const char* what) { return fail(h, HK_ERR_INVALID, std::string(fn) + what); };
-    if (policy < 0 || policy >= h->n_policies) return bad("bad policy index");
-    if (h->n_ppo >= HK_MAX_POLICIES) return bad("HK_MAX_POLICIES trainers already exist");
-    if (!c) return bad("NULL critic");
-    if (!h->cfg.rewards) return bad("hk_config.rewards == 0 (the rows carry no rewards)");
-    const hk::PolicyParams& q = h->policy[policy].q;
-    const int S = q.n_slots;
-    if (S < 2 || S > HK_POCA_MAX_GROUP) return bad("the policy's slots are not a group of 2 .. HK_POCA_MAX_GROUP agents");
-    const int team = h->cfg.team_of[q.slots[0]];
-    int members = 0;
-    for (int a = 0; a < h->cfg.num_agents; a++) members += h->cfg.team_of[a] == team;
-    for (int j = 0; j < S; j++) if (h->cfg.team_of[q.slots[j]] != team) return bad("the policy's slots are not on one team");
-    if (members != S) return bad("the policy's slots are not every member of their team");
-    if (c->hidden < 4 || c->hidden > HK_POLICY_MAX_HIDDEN || c->hidden % 4) return bad("hidden is not a multiple of 4 in [4, HK_POLICY_MAX_HIDDEN]");
-    if (c->n_layers < 1 || c->n_layers > HK_POLICY_MAX_LAYERS) return bad("n_layers outside [1, HK_POLICY_MAX_LAYERS]");
-    if (c->reserved0 != 0 || c->reserved1 != 0) return bad("reserved != 0");
-    if (!c->W_obs || !c->b_obs || !c->W_act || !c->b_act || !c->W_q || !c->b_q || !c->W_k || !c->b_k || !c->W_v || !c->b_v || !c->W_out || !c->b_out ||
-        !c->w_val || !c->b_val)
-        return bad("a NULL array");
-    for (int l = 0; l < c->n_layers; l++) if (!c->W[l] || !c->b[l]) return bad("a NULL array (encoder)");
-    hk_ppo_config d{0.99f, 0.95f, 1, 0.9f, 0.999f, 1e-8f, 0u};
-    if (cfg) d = *cfg;
-    if (!(d.adam_beta1 >= 0.0f && d.adam_beta1 < 1.0f && d.adam_beta2 >= 0.0f && d.adam_beta2 < 1.0f && d.adam_eps > 0.0f)) return bad("Adam constants out of range");
-    auto& t = h->ppo[h->n_ppo];
-    t = hk_context::Ppo{};
-    t.policy = policy; t.cfg = d; t.poca = true;
-    t.actor.layout(q.in_dim, q.hidden, q.n_layers, q.n_branch, 0);
-    t.pnet.layout(q.in_dim, q.n_branch, c->hidden, c->n_layers, t.actor.count);
-    const hk::PocaNet& pn = t.pnet;
-    t.P = t.actor.count + pn.count;
-    const size_t H = (size_t)c->hidden, base = t.actor.count;
-    std::vector<float> host(pn.count);
-    auto put = [&](size_t off, const float* src, size_t k) { std::memcpy(&host[off - base], src, k * 4); };
-    put(pn.oWobs, c->W_obs, H * pn.in_dim); put(pn.obobs, c->b_obs, H);
-    put(pn.oWact, c->W_act, H * pn.n_act); put(pn.obact, c->b_act, H);
-    put(pn.oWq, c->W_q, H * H); put(pn.obq, c->b_q, H); put(pn.oWk, c->W_k, H * H); put(pn.obk, c->b_k, H);
-    put(pn.oWv, c->W_v, H * H); put(pn.obv, c->b_v, H); put(pn.oWout, c->W_out, H * H); put(pn.obout, c->b_out, H);
-    for (int l = 0; l < c->n_layers; l++) { put(pn.oW[l], c->W[l], H * H); put(pn.ob[l], c->b[l], H); }
-    put(pn.owval, c->w_val, H); put(pn.obval, c->b_val, 1);
-    hipError_t e = hipMalloc(&t.param, 4 * t.P * sizeof(float));
-    if (e == hipSuccess) e = hipMemsetAsync(t.param, 0, 4 * t.P * sizeof(float), h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(t.param + base, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(hk::ppo_publish_kernel<false>, dim3(nblk(t.actor.count)), dim3(256), 0, h->stream, q, t.actor, t.param);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        if (t.param) (void)hipFree(t.param);
-        t = hk_context::Ppo{};
-        return fail(h, HK_ERR_HIP, std::string(fn) + hipGetErrorString(e));
-    }
-    return h->n_ppo++;
+    auto bad = [&](const char* what) { return fail(h, HK_ERR_INVALID, std::string("hk_ppo_create_poca: ") + what); };
+    auto checks = [&](const hk::PolicyParams& q) {
+        if (!h->cfg.rewards) return bad("hk_config.rewards == 0 (the rows carry no rewards)");
+        const int S = q.n_slots;
+        if (S < 2 || S > HK_POCA_MAX_GROUP) return bad("the policy's slots are not a group of 2 .. HK_POCA_MAX_GROUP agents");
+        const int team = h->cfg.team_of[q.slots[0]];
+        int members = 0;
+        for (int a = 0; a < h->cfg.num_agents; a++) members += h->cfg.team_of[a] == team;
+        for (int j = 0; j < S; j++) if (h->cfg.team_of[q.slots[j]] != team) return bad("the policy's slots are not on one team");
+        if (members != S) return bad("the policy's slots are not every member of their team");
+        if (c->hidden < 4 || c->hidden > HK_POLICY_MAX_HIDDEN || c->hidden % 4) return bad("hidden is not a multiple of 4 in [4, HK_POLICY_MAX_HIDDEN]");
+        if (c->n_layers < 1 || c->n_layers > HK_POLICY_MAX_LAYERS) return bad("n_layers outside [1, HK_POLICY_MAX_LAYERS]");
+        if (c->reserved0 != 0 || c->reserved1 != 0) return bad("reserved != 0");
+        if (!c->W_obs || !c->b_obs || !c->W_act || !c->b_act || !c->W_q || !c->b_q || !c->W_k || !c->b_k || !c->W_v || !c->b_v || !c->W_out || !c->b_out ||
+            !c->w_val || !c->b_val)
+            return bad("a NULL array");
+        for (int l = 0; l < c->n_layers; l++) if (!c->W[l] || !c->b[l]) return bad("a NULL array (encoder)");
+        return (int)HK_OK;
+    };
+    auto pack = [&](hk_context::Ppo& t, std::vector<float>& host) {
+        t.poca = true;
+        t.pnet.layout(t.actor.in_dim, t.actor.n_branch, c->hidden, c->n_layers, t.actor.count);
+        const hk::PocaNet& pn = t.pnet;
+        const size_t H = (size_t)c->hidden, base = t.actor.count;
+        host.resize(pn.count);
+        auto put = [&](size_t off, const float* src, size_t k) { std::memcpy(&host[off - base], src, k * 4); };
+        put(pn.oWobs, c->W_obs, H * pn.in_dim); put(pn.obobs, c->b_obs, H);
+        put(pn.oWact, c->W_act, H * pn.n_act); put(pn.obact, c->b_act, H);
+        put(pn.oWq, c->W_q, H * H); put(pn.obq, c->b_q, H); put(pn.oWk, c->W_k, H * H); put(pn.obk, c->b_k, H);
+        put(pn.oWv, c->W_v, H * H); put(pn.obv, c->b_v, H); put(pn.oWout, c->W_out, H * H); put(pn.obout, c->b_out, H);
+        for (int l = 0; l < c->n_layers; l++) { put(pn.oW[l], c->W[l], H * H); put(pn.ob[l], c->b[l], H); }
+        put(pn.owval, c->w_val, H); put(pn.obval, c->b_val, 1);
+    };
+    return ppo_create(h, "hk_ppo_create_poca", policy, c != nullptr, cfg, checks, pack);
 }
 
 extern "C++" {
@@ -2524,9 +2540,7 @@ void* hk_poca_ptr(hk_handle h, int trainer, int field)
     const auto& t = h->ppo[trainer];
     if (field == HK_POCA_MB_BASELINE) {
         if (t.last_mg == 0) { fail(h, HK_ERR_INVALID, "hk_poca_ptr: no minibatch yet"); return nullptr; }
-        PocaWs pw;
-        poca_ws_layout(t, h->policy[t.policy].q.n_slots, t.pcap, &pw);
-        return pw.brow;
+        return poca_ws(h, t).brow;
     }
     if (t.adv_gen < 0) { fail(h, HK_ERR_INVALID, "hk_poca_ptr: hk_ppo_advantages has not run"); return nullptr; }
     const PocaRowBuf r = poca_rowbuf(t);
@@ -2549,8 +2563,7 @@ int hk_poca_stats(hk_handle h, int trainer, float* out)
     if (!out) return fail(h, HK_ERR_INVALID, "hk_poca_stats: NULL out");
     const auto& t = h->ppo[trainer];
     if (!t.pws || (t.last_mg == 0 && !t.lb_from_update)) return fail(h, HK_ERR_INVALID, "hk_poca_stats: no minibatch or update yet");
-    PocaWs pw;
-    poca_ws_layout(t, h->policy[t.policy].q.n_slots, t.pcap, &pw);
+    const PocaWs pw = poca_ws(h, t);
     float st[HK_POCA_STATS] = {};
     double acc[2] = {};
     HK_HIP(h, hipMemcpyAsync(st, pw.pstats, sizeof(st), hipMemcpyDeviceToHost, h->stream));
@@ -2638,7 +2651,7 @@ int hk_policy_pool_load(hk_handle h, int pool, int slot, int policy)
     if (rc) return rc;
     const auto& pl = h->pool[pool];
     if (!((pl.filled >> slot) & 1ull)) return fail(h, HK_ERR_INVALID, "hk_policy_pool_load: the slot has never been written (hk_policy_pool_save / hk_policy_pool_put)");
-    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_policy_pool_load: refused while a rollout is open (hk_rollout_close first)");
+    if ((rc = ppo_refuse_open(h, "hk_policy_pool_load"))) return rc;
     for (int i = 0; i < h->n_ppo; i++)
         if (h->ppo[i].policy == policy)
             return fail(h, HK_ERR_INVALID, "hk_policy_pool_load: the policy has a PPO trainer (its master weights would disagree with what plays)");
@@ -2690,7 +2703,7 @@ int hk_rollout_episode_stats(hk_handle h, int policy, hk_episode_stats* out)
     if (!out) return fail(h, HK_ERR_INVALID, std::string(fn) + ": NULL pointer");
     if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, std::string(fn) + ": bad policy index");
     if (!h->cfg.rewards) return fail(h, HK_ERR_INVALID, std::string(fn) + ": hk_config.rewards == 0 (the rows carry no rewards)");
-    if (ro.open) return fail(h, HK_ERR_INVALID, std::string(fn) + ": refused while a rollout is open (hk_rollout_close first)");
+    if (int rc = ppo_refuse_open(h, fn)) return rc;
     if (ro.R == 0 || !ro.buf) return fail(h, HK_ERR_INVALID, std::string(fn) + ": no rollout yet (hk_rollout_begin ... hk_rollout_close)");
     if (ro.rows < 1) return fail(h, HK_ERR_INVALID, std::string(fn) + ": the rollout closed with no completed row");
     if (policy >= ro.npol) return fail(h, HK_ERR_INVALID, std::string(fn) + ": the rollout began before the policy was attached");

@@ -1,6 +1,7 @@
-"""POCA trainer on the device (include/hk.h "POCA") against the float64 torch restatement (poca_restate.py).  Three cases: 24 envs of 2v2 Oval
+"""POCA trainer on the device (include/hk.h "POCA") against the float64 torch restatement (poca_restate.py).  Four cases: 24 envs of 2v2 Oval
 with a stochastic 312 -> 256 x 3 actor on slots [0, 1] and a critic of H = 256, 2 layers; the same with H = 36 (a head width of 9), 1 layer;
-8 envs of the 8-agent default wiring (4v4) with the policy on slots [0 .. 3] and H = 64, so S = 4.  R = 90 decisions of period 2 with
+8 envs of the 8-agent default wiring (4v4) with the policy on slots [0 .. 3] and H = 64, so S = 4; the first set-up again with a critic of
+H = 12, 3 layers.  R = 90 decisions of period 2 with
 max_episode_steps 150: episodes end inside the rollout."""
 import functools
 
@@ -23,6 +24,10 @@ CASES = {
     "h256": dict(E=24, A=4, slots=[0, 1], other=[2, 3], actor=(256, 3), H=256, L=2),
     "h36": dict(E=24, A=4, slots=[0, 1], other=[2, 3], actor=(256, 3), H=36, L=1),
     "s4": dict(E=8, A=8, slots=[0, 1, 2, 3], other=[4, 5, 6, 7], actor=(64, 2), H=64, L=2),
+    # three encoder layers: the backward swaps its two delta buffers once per layer above the first, so an even number of swaps only runs here
+    # (H = 12 is the smallest width with more than one channel per head).  The env and the actors are h36's: 8 envs of 2v2 under a 64 x 2 actor
+    # record no episode end or no group reward in 90 decisions, which _host refuses.
+    "l3": dict(E=24, A=4, slots=[0, 1], other=[2, 3], actor=(256, 3), H=12, L=3),
 }
 
 
@@ -194,7 +199,7 @@ def test_gradients_against_autograd():
     _gradient_case("h256", (1, 31, 32, 33, None))
 
 
-@pytest.mark.parametrize("case", ["h36", "s4"])
+@pytest.mark.parametrize("case", ["h36", "s4", "l3"])
 def test_gradients_against_autograd_odd_head_width_and_four_agents(case):
     _gradient_case(case, (33,))
 
