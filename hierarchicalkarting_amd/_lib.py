@@ -18,6 +18,7 @@ HK_MAX_POLICIES = 4
 HK_POLICY_MAX_LAYERS = 4
 HK_POLICY_MAX_IN = 1280
 HK_POLICY_MAX_HIDDEN = 256
+HK_POLICY_MAX_MEMORY = 256
 HK_MAX_POOLS = 8
 HK_POOL_MAX_SLOTS = 64
 
@@ -29,7 +30,8 @@ HK_MODE_RACE, HK_MODE_TRAINING, HK_MODE_EXPERIMENT = 0, 1, 2
 RO_FIELDS = {n: (i, dt) for i, (n, dt) in enumerate([
     ("obs", "<f4"), ("first", "<i4"), ("steer", "<f4"), ("branch", "<i4"), ("raw", "<f4"), ("mu", "<f4"), ("logits", "<f4"),
     ("logp_cont", "<f4"), ("logp_disc", "<f4"), ("reward", "<f4"), ("group_reward", "<f4"), ("term_reward", "<f4"),
-    ("term_group_reward", "<f4"), ("done", "<i4"), ("ring0", "<f4"), ("next_obs", "<f4")])}
+    ("term_group_reward", "<f4"), ("done", "<i4"), ("ring0", "<f4"), ("next_obs", "<f4"),
+    ("memory", "<f4"), ("next_memory", "<f4")])}       # the last two: recurrent actors only (no elements, NULL pointer otherwise)
 HK_RO_FIELDS = len(RO_FIELDS)
 # PPO trainer (hk_ppo_field): name -> index;  stats of hk_ppo_minibatch / hk_ppo_update
 PPO_FIELDS = {n: i for i, n in enumerate(("params", "grad", "adam_m", "adam_v", "v_old", "adv", "ret", "mb_mu", "mb_logits", "mb_value", "perm", "shadow",
@@ -176,6 +178,10 @@ class PolicyDesc(C.Structure):
                 ("W_mu", _fp), ("b_mu", _fp), ("log_sigma", _fp), ("W_branch", _fp), ("b_branch", _fp)]
 
 
+class PolicyLstmDesc(C.Structure):
+    _fields_ = [("memory_size", C.c_int32), ("reserved", C.c_int32), ("W_ih", _fp), ("W_hh", _fp), ("b_ih", _fp), ("b_hh", _fp)]
+
+
 class PpoConfig(C.Structure):
     _fields_ = [("gamma", C.c_float), ("lambd", C.c_float), ("normalize_advantages", C.c_int32), ("adam_beta1", C.c_float),
                 ("adam_beta2", C.c_float), ("adam_eps", C.c_float), ("seed", C.c_uint32)]
@@ -239,6 +245,11 @@ SYMBOLS = {
     "hk_policy_set_precision": (C.c_int, [_H, C.c_int, C.c_int]),
     "hk_policy_get_precision": (C.c_int, [_H, C.c_int]),
     "hk_policy_forward": (C.c_int, [_H, C.c_int, C.c_int, _fp, _fp, _fp]),
+    "hk_policy_attach_lstm": (C.c_int, [_H, C.POINTER(PolicyDesc), C.POINTER(PolicyLstmDesc), C.POINTER(C.c_int32), C.c_int, C.c_int]),
+    "hk_policy_memory_size": (C.c_int, [_H, C.c_int]),
+    "hk_policy_forward_mem": (C.c_int, [_H, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
+    "hk_policy_memory_get": (C.c_int, [_H, C.c_int, _fp]),
+    "hk_policy_memory_set": (C.c_int, [_H, C.c_int, _fp]),
     "hk_get_actions": (C.c_int, [_H, _fp, C.POINTER(C.c_int32)]),
     "hk_rollout_begin": (C.c_int, [_H, C.c_int]),
     "hk_rollout_rows": (C.c_int, [_H]),

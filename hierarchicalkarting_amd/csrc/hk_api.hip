@@ -201,6 +201,7 @@ struct hk_context {
         int npol = 0;                  // actors attached when it began (the ones it has rows of)
         int started = 0, rows = 0;     // decisions taken / intervals completed since begin
         int obs_dim = 0, nbm = 0, smax = 1;
+        int mem_max = 0;               // the largest 2m of the recurrent actors (0: none; MEMORY / NEXT_MEMORY have no elements)
         uint32_t driven = 0;           // agent slots an actor drives
         void* buf = nullptr;
         size_t bytes = 0;
@@ -1137,6 +1138,11 @@ static int policy_decide(hk_handle h)
         const hk::PolicyDevice& pd = h->policy[p];
         const int pairs = E * pd.q.n_slots;
         const int w = (int)(decision % (unsigned long long)pd.q.stack);
+        if (pd.lq.m > 0) {          // a recurrent actor: its memory is cleared by the stack's own test, before the stack kernel rewrites the epoch word
+            hipLaunchKernelGGL(hk::policy_memory_kernel, dim3((pairs + 3) / 4), dim3(256), 0, h->stream, pd.q, pd.lq, E, A, h->dev.envs, h->dev.slot_of,
+                               ro.open ? ro.row<float>(HK_RO_MEMORY, t, ea, ro.mem_max) : nullptr, ro.mem_max);
+            HK_HIP(h, hipGetLastError());
+        }
         hipLaunchKernelGGL(hk::policy_stack_kernel, dim3((pairs + 3) / 4), dim3(256), 0, h->stream, pd.q, E, A, h->dev.envs, h->dev.slot_of,
                            h->dev.obs, w, ro.open ? ro.row<float>(HK_RO_OBS, t, ea, ro.obs_dim) : nullptr, ro.open ? ro.row<int>(HK_RO_FIRST, t, ea) : nullptr);
         HK_HIP(h, hipGetLastError());
@@ -1219,9 +1225,16 @@ int hk_step(hk_handle h, int n_ticks)
 
 int hk_policy_attach(hk_handle h, const hk_policy_desc* desc, const int32_t* agent_slots, int n_slots, int decision_period)
 {
+    return hk_policy_attach_lstm(h, desc, nullptr, agent_slots, n_slots, decision_period);
+}
+
+// lstm == nullptr: hk_policy_attach (every check, message and launch of it)
+int hk_policy_attach_lstm(hk_handle h, const hk_policy_desc* desc, const hk_policy_lstm_desc* lstm, const int32_t* agent_slots, int n_slots, int decision_period)
+{
     HK_NEED_ENV(h);
     if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_policy_attach: refused while a rollout is open (hk_rollout_close first)");
     int rc = hk::policy_validate(desc, h->err);
+    if (!rc && lstm) rc = hk::policy_lstm_validate(lstm, h->err);
     if (rc) { g_last_error = h->err; return rc; }
     if (!agent_slots || n_slots < 1 || n_slots > h->cfg.num_agents || decision_period < 1)
         return fail(h, HK_ERR_INVALID, "hk_policy_attach: bad agent_slots / decision_period");
@@ -1241,22 +1254,28 @@ int hk_policy_attach(hk_handle h, const hk_policy_desc* desc, const int32_t* age
         return fail(h, HK_ERR_INVALID, "hk_policy_attach: decision_period differs from the policies already attached (DecisionRequester is per handle)");
     h->ep.moved = true;
     const int idx = h->n_policies;
-    rc = hk::policy_upload(h->policy[idx], desc, idx, hk_obs_dim(h), agent_slots, n_slots, h->cfg.num_envs, h->stream, h->err);
+    rc = hk::policy_upload(h->policy[idx], desc, idx, hk_obs_dim(h), agent_slots, n_slots, h->cfg.num_envs, h->stream, h->err, lstm ? lstm->memory_size / 2 : 0);
+    if (!rc && lstm) rc = hk::policy_lstm_upload(h->policy[idx], lstm, h->cfg.num_envs, h->stream, h->err);
     if (rc) { hk::policy_free(h->policy[idx]); g_last_error = h->err; return rc; }
     h->decision_period = decision_period;
     h->n_policies = idx + 1;
     return idx;
 }
 
-int hk_policy_forward(hk_handle h, int policy, int rows, const float* obs, float* mu, float* logits)
+// hk_policy_forward (with_mem false: a policy without memory) and hk_policy_forward_mem (with_mem: one with): the staging buffer holds the
+// rows' inputs, mu, logits and — with memory — the rows' memory, which the kernel updates in place
+static int policy_forward(hk_handle h, const char* fn, bool with_mem, int policy, int rows, const float* obs, const float* mem_in, float* mu, float* logits, float* mem_out)
 {
     HK_NEED_ENV(h);
-    if (policy < 0 || policy >= h->n_policies || rows < 0) return fail(h, HK_ERR_INVALID, "hk_policy_forward: bad policy / rows");
-    if (rows == 0) return HK_OK;
-    if (!obs || !mu || !logits) return fail(h, HK_ERR_INVALID, "hk_policy_forward: NULL pointer");
+    const std::string f = fn;
+    if (policy < 0 || policy >= h->n_policies || rows < 0) return fail(h, HK_ERR_INVALID, f + ": bad policy / rows");
     const hk::PolicyDevice& pd = h->policy[policy];
-    const size_t n_in = (size_t)rows * pd.q.in_dim, n_lg = (size_t)rows * pd.q.n_branch;
-    const size_t total = (n_in + rows + n_lg) * sizeof(float);
+    if (!with_mem && pd.lq.m > 0) return fail(h, HK_ERR_UNSUPPORTED, f + ": the policy has memory (a recurrent actor): use hk_policy_forward_mem");
+    if (with_mem && pd.lq.m == 0) return fail(h, HK_ERR_INVALID, f + ": the policy has no memory (policy: attached without an LSTM): use hk_policy_forward");
+    if (rows == 0) return HK_OK;
+    if (!obs || !mu || !logits) return fail(h, HK_ERR_INVALID, f + ": NULL pointer");
+    const size_t n_in = (size_t)rows * pd.q.in_dim, n_lg = (size_t)rows * pd.q.n_branch, n_mem = (size_t)rows * 2 * pd.lq.m;
+    const size_t total = (n_in + rows + n_lg + n_mem) * sizeof(float);
     if (total > h->pol_scratch_bytes) {
         if (h->pol_scratch) HK_HIP(h, hipFree(h->pol_scratch));
         h->pol_scratch = nullptr; h->pol_scratch_bytes = 0;
@@ -1266,16 +1285,64 @@ int hk_policy_forward(hk_handle h, int policy, int rows, const float* obs, float
     float* d_in = (float*)h->pol_scratch;
     float* d_mu = d_in + n_in;
     float* d_lg = d_mu + rows;
+    float* d_mem = n_mem ? d_lg + n_lg : nullptr;
     HK_HIP(h, hipMemcpyAsync(d_in, obs, n_in * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (n_mem && mem_in) HK_HIP(h, hipMemcpyAsync(d_mem, mem_in, n_mem * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    else if (n_mem) HK_HIP(h, hipMemsetAsync(d_mem, 0, n_mem * sizeof(float), h->stream));
     hipEvent_t e = h->prof.begin(h->stream);
-    int rc = hk::policy_launch_mlp(pd, rows, d_in, pd.q.stack - 1, 0ull, 0, h->cfg.num_agents, d_mu, d_lg, nullptr, nullptr, hk::PolicyRec{}, h->stream, h->err);
+    int rc = hk::policy_launch_mlp(pd, rows, d_in, pd.q.stack - 1, 0ull, 0, h->cfg.num_agents, d_mu, d_lg, nullptr, nullptr, hk::PolicyRec{}, h->stream, h->err, d_mem);
     if (rc) { g_last_error = h->err; return rc; }
     h->prof.end(3, e, h->stream);
     HK_HIP(h, hipMemcpyAsync(mu, d_mu, rows * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipMemcpyAsync(logits, d_lg, n_lg * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (n_mem && mem_out) HK_HIP(h, hipMemcpyAsync(mem_out, d_mem, n_mem * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipStreamSynchronize(h->stream));
     return HK_OK;
 }
+
+int hk_policy_forward(hk_handle h, int policy, int rows, const float* obs, float* mu, float* logits)
+{
+    return policy_forward(h, "hk_policy_forward", false, policy, rows, obs, nullptr, mu, logits, nullptr);
+}
+
+int hk_policy_forward_mem(hk_handle h, int policy, int rows, const float* obs, const float* mem_in, float* mu, float* logits, float* mem_out)
+{
+    return policy_forward(h, "hk_policy_forward_mem", true, policy, rows, obs, mem_in, mu, logits, mem_out);
+}
+
+int hk_policy_memory_size(hk_handle h, int policy)
+{
+    if (!h) return fail(nullptr, HK_ERR_INVALID, "NULL handle");
+    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, "hk_policy_memory_size: bad policy index");
+    return 2 * h->policy[policy].lq.m;
+}
+
+// hk_policy_memory_get (set false) / hk_policy_memory_set
+static int policy_memory_copy(hk_handle h, const char* fn, bool set, int policy, float* mem)
+{
+    HK_NEED_ENV(h);
+    const std::string f = fn;
+    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, f + ": bad policy index");
+    const hk::PolicyDevice& pd = h->policy[policy];
+    if (pd.lq.m == 0) return fail(h, HK_ERR_INVALID, f + ": the policy has no memory (policy: attached without an LSTM)");
+    if (!mem) return fail(h, HK_ERR_INVALID, f + ": NULL mem");
+    if (set && h->ro.open) return fail(h, HK_ERR_INVALID, f + ": refused while a rollout is open (hk_rollout_close first)");
+    const int pairs = h->cfg.num_envs * pd.q.n_slots;
+    const size_t bytes = (size_t)pairs * 2 * pd.lq.m * sizeof(float);
+    if (set) {
+        h->ep.moved = true;
+        HK_HIP(h, hipMemcpyAsync(pd.lq.mem, mem, bytes, hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(hk::policy_epoch_current_kernel, dim3((pairs + 255) / 256), dim3(256), 0, h->stream, pd.q, h->cfg.num_envs, h->dev.envs, h->dev.slot_of);
+        HK_HIP(h, hipGetLastError());
+    } else {
+        HK_HIP(h, hipMemcpyAsync(mem, pd.lq.mem, bytes, hipMemcpyDeviceToHost, h->stream));
+    }
+    HK_HIP(h, hipStreamSynchronize(h->stream));
+    return HK_OK;
+}
+
+int hk_policy_memory_get(hk_handle h, int policy, float* mem) { return policy_memory_copy(h, "hk_policy_memory_get", false, policy, mem); }
+int hk_policy_memory_set(hk_handle h, int policy, const float* mem) { return policy_memory_copy(h, "hk_policy_memory_set", true, policy, const_cast<float*>(mem)); }
 
 int hk_policy_set_precision(hk_handle h, int policy, int precision)
 {
@@ -1284,6 +1351,8 @@ int hk_policy_set_precision(hk_handle h, int policy, int precision)
     if (precision != HK_POLICY_PREC_F32 && precision != HK_POLICY_PREC_BF16) return fail(h, HK_ERR_INVALID, "hk_policy_set_precision: unknown precision");
     if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_policy_set_precision: refused while a rollout is open (hk_rollout_close first)");
     hk::PolicyDevice& pd = h->policy[policy];
+    if (precision == HK_POLICY_PREC_BF16 && pd.lq.m > 0)
+        return fail(h, HK_ERR_UNSUPPORTED, "hk_policy_set_precision: precision HK_POLICY_PREC_BF16 on a policy with memory (the cell has no bf16 form)");
     if (precision == HK_POLICY_PREC_BF16 && !pd.wbf) {
         // the second allocation: every layer's fragment-major bf16 copy, built on the stream from the CURRENT fp32 copies (so after a publish too)
         size_t off[HK_POLICY_MAX_LAYERS + 1] = {};
@@ -1331,9 +1400,10 @@ int hk_rollout_begin(hk_handle h, int rows)
     if (!h->cfg.auto_reset) return fail(h, HK_ERR_UNSUPPORTED, "hk_rollout_begin: auto_reset == 0 (an ended episode is parked, never reset)");
     auto& ro = h->ro;
     const int E = h->cfg.num_envs, A = h->cfg.num_agents, D = hk_obs_dim(h);
-    int nbm = 1, smax = 1;
+    int nbm = 1, smax = 1, mem_max = 0;
     uint32_t driven = 0;
     for (int p = 0; p < h->n_policies; p++) {
+        mem_max = std::max(mem_max, 2 * h->policy[p].lq.m);
         nbm = std::max(nbm, h->policy[p].q.n_branch);
         smax = std::max(smax, h->policy[p].q.stack);
         for (int j = 0; j < h->policy[p].q.n_slots; j++) driven |= 1u << h->policy[p].q.slots[j];
@@ -1343,6 +1413,7 @@ int hk_rollout_begin(hk_handle h, int rows)
     for (int f = 0; f < HK_RO_FIELDS; f++) elems[f] = ra;
     elems[HK_RO_OBS] = ra * D; elems[HK_RO_LOGITS] = ra * nbm; elems[HK_RO_DONE] = (size_t)rows * E;
     elems[HK_RO_RING0] = ea * (smax - 1) * D; elems[HK_RO_NEXT_OBS] = ea * D;
+    elems[HK_RO_MEMORY] = ra * mem_max; elems[HK_RO_NEXT_MEMORY] = ea * mem_max;      // (no recurrent actor: no elements, no bytes)
     elems[HK_RO_FIELDS] = E; elems[HK_RO_FIELDS + 1] = 1;
     size_t off[HK_RO_FIELDS + 2], total = 0;
     for (int f = 0; f < HK_RO_FIELDS + 2; f++) { off[f] = total; total += (elems[f] * 4 + 255) & ~(size_t)255; }
@@ -1353,7 +1424,7 @@ int hk_rollout_begin(hk_handle h, int rows)
         ro.bytes = total;
     }
     std::memcpy(ro.off, off, sizeof(off));
-    ro.R = rows; ro.started = 0; ro.rows = 0; ro.obs_dim = D; ro.nbm = nbm; ro.smax = smax; ro.driven = driven;
+    ro.R = rows; ro.started = 0; ro.rows = 0; ro.obs_dim = D; ro.nbm = nbm; ro.smax = smax; ro.mem_max = mem_max; ro.driven = driven;
     {   // the episode statistics' carry (hk.h "SELF-PLAY" CARRY): what the statistics of the rollout just closed wrote becomes this one's carry-in
         auto& ep = h->ep;
         bool any = false;
@@ -1395,6 +1466,16 @@ int hk_rollout_close(hk_handle h)
     // the bootstrap observation: the observe kernel without its reward events, so that the next decision raises them as usual
     int rc = hk::env_launch_observe_quiet(h->dev, h->cfg, ro.driven, ro.at<float>(HK_RO_NEXT_OBS), h->stream, h->err);
     if (rc) { g_last_error = h->err; return rc; }
+    // the bootstrap memory of the recurrent actors: what the last completed row left, zero where its interval ended the episode
+    for (int p = 0; p < h->n_policies && ro.mem_max > 0; p++) {
+        const hk::PolicyDevice& pd = h->policy[p];
+        if (pd.lq.m == 0) continue;
+        const int E = h->cfg.num_envs;
+        const size_t n = (size_t)E * pd.q.n_slots * 2 * pd.lq.m;
+        hipLaunchKernelGGL(hk::rollout_next_memory_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, pd.q, pd.lq, E, h->cfg.num_agents,
+                           ro.rows > 0 ? ro.row<int>(HK_RO_DONE, ro.rows - 1, (size_t)E) : nullptr, ro.at<float>(HK_RO_NEXT_MEMORY), ro.mem_max);
+        HK_HIP(h, hipGetLastError());
+    }
     ro.open = false;
     h->ep.moved = false;
     int bad = 0;
@@ -1409,6 +1490,10 @@ void* hk_rollout_ptr(hk_handle h, int field)
     if (!h) { fail(nullptr, HK_ERR_INVALID, "NULL handle"); return nullptr; }
     if (field < 0 || field >= HK_RO_FIELDS) { fail(h, HK_ERR_INVALID, "hk_rollout_ptr: bad field"); return nullptr; }
     if (!h->ro.buf || h->ro.R == 0) { fail(h, HK_ERR_INVALID, "hk_rollout_ptr: no rollout yet (hk_rollout_begin)"); return nullptr; }
+    if ((field == HK_RO_MEMORY || field == HK_RO_NEXT_MEMORY) && h->ro.mem_max == 0) {
+        fail(h, HK_ERR_INVALID, "hk_rollout_ptr: field MEMORY / NEXT_MEMORY has no elements (the rollout has no recurrent actor)");
+        return nullptr;
+    }
     return h->ro.at<void>(field);
 }
 
@@ -2024,6 +2109,7 @@ int ppo_create(hk_handle h, const char* fn, int policy, bool have_critic, const 
     const std::string f = std::string(fn) + ": ";
     if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, f + "bad policy index");
     if (h->n_ppo >= HK_MAX_POLICIES) return fail(h, HK_ERR_INVALID, f + "HK_MAX_POLICIES trainers already exist");
+    if (h->policy[policy].lq.m > 0) return fail(h, HK_ERR_UNSUPPORTED, f + "policy: a recurrent actor (recurrent training is out of scope: hk.h \"RECURRENT ACTORS\")");
     if (!have_critic) return fail(h, HK_ERR_INVALID, f + "NULL critic");
     const hk::PolicyParams& q = h->policy[policy].q;
     int rc = critic_checks(q);
@@ -2587,6 +2673,7 @@ int pool_check(hk_handle h, const char* fn, int pool, int slot, int policy)
     if (slot < 0 || slot >= pl.slots) return fail(h, HK_ERR_INVALID, f + ": bad slot index");
     if (policy == -1) return HK_OK;
     if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, f + ": bad policy index");
+    if (h->policy[policy].lq.m > 0) return fail(h, HK_ERR_UNSUPPORTED, f + ": policy: a recurrent actor (snapshot pools of recurrent actors are out of scope)");
     const hk::PolicyParams& q = h->policy[policy].q;
     if (q.in_dim != pl.in_dim || q.stack != pl.stack || q.hidden != pl.hidden || q.n_layers != pl.n_layers || q.n_branch != pl.n_branch ||
         (q.normalize != 0) != (pl.normalize != 0))
@@ -2605,6 +2692,7 @@ int hk_policy_pool_create(hk_handle h, int policy, int slots)
     if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, "hk_policy_pool_create: bad policy index");
     if (slots < 1 || slots > HK_POOL_MAX_SLOTS) return fail(h, HK_ERR_INVALID, "hk_policy_pool_create: slots outside [1, HK_POOL_MAX_SLOTS]");
     if (h->n_pools >= HK_MAX_POOLS) return fail(h, HK_ERR_INVALID, "hk_policy_pool_create: HK_MAX_POOLS pools already exist");
+    if (h->policy[policy].lq.m > 0) return fail(h, HK_ERR_UNSUPPORTED, "hk_policy_pool_create: policy: a recurrent actor (snapshot pools of recurrent actors are out of scope)");
     const hk::PolicyParams& q = h->policy[policy].q;
     hk_context::Pool pl;
     pl.in_dim = q.in_dim; pl.stack = q.stack; pl.hidden = q.hidden; pl.n_layers = q.n_layers; pl.n_branch = q.n_branch; pl.normalize = q.normalize != 0;

@@ -6,6 +6,8 @@
 //   policy_mlp_kernel       normalise -> n x (Linear + Swish) -> {mu, logits} -> sample -> latch steer / branch
 //                           (HK_POLICY_PREC_BF16, opt-in per policy: policy_mlp_bf16_kernel, hk_policy_bf16.h — the same decision with the
 //                           trunk on the bf16 matrix cores; everything said of arithmetic below is the default precision's)
+//                           (a policy with memory — hk_policy_attach_lstm: policy_memory_kernel before the stack kernel, then policy_lstm_kernel
+//                           in place of policy_mlp_kernel: the same trunk, one LSTM cell, the heads on h'; hk_policy_lstm.h)
 //
 // policy_mlp_kernel: one workgroup (8 waves) per tile of 64 rows (row = one agent's stacked observation).  The tile's
 // activations live TRANSPOSED in LDS (At[k][row], row stride 65 floats: conflict-free for the column writes of the loader
@@ -72,9 +74,20 @@ struct PolicyBf16 {
     const uint16_t* Wf[HK_POLICY_MAX_LAYERS];   // fragment-major [column block][k step][lane][8]; nullptr until the first switch
 };
 
+// A recurrent actor's cell (hk_policy_lstm.h; hk.h "RECURRENT ACTORS"), an argument of policy_lstm_kernel alone.  m == 0: the policy has no memory.
+struct PolicyLstm {
+    int m;                                   // memory_size / 2: hidden units of the cell, a multiple of 32 in [32, 128]
+    const float4* Wq_ih;                     // W_ih^T [hidden][4m] in PolicyParams::Wq's group-major form: [hidden / 8][2][4m] x {4 k-steps}
+    const float4* Wq_hh;                     // W_hh^T [m][4m], likewise
+    const float* b;                          // [4m] fp32(b_ih + b_hh), gates i f g o
+    float* mem;                              // [E][n_slots][2m] = [h | c], indexed like the ring; nullptr for a forward-only policy
+};
+
 struct PolicyDevice {
     PolicyParams q{};
     PolicyBf16 bq{};
+    PolicyLstm lq{};
+    float* wlstm = nullptr;                  // the allocation behind lq's weights (hk_policy_attach_lstm)
     float* weights = nullptr;                // one allocation behind every const float* above
     uint16_t* wbf = nullptr;                 // the second allocation, behind bq.Wf: made by the first switch to HK_POLICY_PREC_BF16
     int prec = HK_POLICY_PREC_F32;           // hk_policy_set_precision: which chain policy_launch_mlp runs
@@ -481,9 +494,10 @@ inline int policy_validate(const hk_policy_desc* d, std::string& err)
 
 // upload (weights of the hidden layers transposed to [k][hidden]); E == 0: no ring (a forward-only policy)
 inline int policy_upload(PolicyDevice& pd, const hk_policy_desc* d, int index, int obs_dim, const int32_t* slots, int n_slots,
-                         int E, hipStream_t stream, std::string& err)
+                         int E, hipStream_t stream, std::string& err, int head_width = 0)
 {
     const int H = d->hidden, K0 = d->in_dim;
+    const int HW = head_width ? head_width : H;          // what the heads read: the last activation, or h' of a recurrent actor (m wide)
     std::vector<float> host;
     auto put = [&](const float* src, size_t n) { size_t off = host.size(); host.insert(host.end(), src, src + n); return off; };
     size_t o_mean = 0, o_std = 0, o_W[HK_POLICY_MAX_LAYERS], o_b[HK_POLICY_MAX_LAYERS], o_Wq[HK_POLICY_MAX_LAYERS];
@@ -509,8 +523,8 @@ inline int policy_upload(PolicyDevice& pd, const hk_policy_desc* d, int index, i
                 for (int j = 0; j < H; j++)
                     for (int q4 = 0; q4 < 4; q4++) wq[(((size_t)g * 2 + hf) * H + j) * 4 + q4] = wt2[(size_t)(8 * g + 2 * q4 + hf) * H + j];
     }
-    const size_t o_wmu = put(d->W_mu, H), o_bmu = put(d->b_mu, 1), o_ls = put(d->log_sigma, 1);
-    const size_t o_wbr = put(d->W_branch, (size_t)d->n_branch * H), o_bbr = put(d->b_branch, d->n_branch);
+    const size_t o_wmu = put(d->W_mu, HW), o_bmu = put(d->b_mu, 1), o_ls = put(d->log_sigma, 1);
+    const size_t o_wbr = put(d->W_branch, (size_t)d->n_branch * HW), o_bbr = put(d->b_branch, d->n_branch);
     hipError_t e;
     if ((e = hipMalloc(&pd.weights, host.size() * sizeof(float))) != hipSuccess ||
         (e = hipMemcpyAsync(pd.weights, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, stream)) != hipSuccess ||
@@ -556,12 +570,15 @@ inline int policy_upload(PolicyDevice& pd, const hk_policy_desc* d, int index, i
 
 }  // namespace hk
 #include "hk_policy_bf16.h"      // policy_mlp_bf16_kernel: the same decision on the bf16 matrix cores (HK_POLICY_PREC_BF16)
+#include "hk_policy_lstm.h"      // policy_lstm_kernel: the trunk, then one LSTM cell, the heads on h' (a policy with memory)
 namespace hk {
 
 inline void policy_free(PolicyDevice& pd)
 {
     if (pd.weights) (void)hipFree(pd.weights);
     if (pd.wbf) (void)hipFree(pd.wbf);
+    if (pd.wlstm) (void)hipFree(pd.wlstm);
+    if (pd.lq.mem) (void)hipFree(pd.lq.mem);
     if (pd.q.ring) (void)hipFree(pd.q.ring);
     if (pd.q.epoch) (void)hipFree(pd.q.epoch);
     pd = PolicyDevice{};
@@ -569,9 +586,30 @@ inline void policy_free(PolicyDevice& pd)
 
 inline int policy_launch_mlp(const PolicyDevice& pd, int rows, const float* src, int w, unsigned long long decision,
                              int env_id_base, int A, float* mu_out, float* logit_out, float* act_steer, int* act_branch,
-                             const PolicyRec& rec, hipStream_t stream, std::string& err)
+                             const PolicyRec& rec, hipStream_t stream, std::string& err, float* lstm_mem = nullptr)
 {
     if (rows <= 0) return HK_OK;
+    if (pd.lq.m > 0) {
+        // a policy with memory: policy_lstm_kernel on lstm_mem [rows][2m] (nullptr: the policy's own buffer), read and rewritten in place
+        float* mem = lstm_mem ? lstm_mem : pd.lq.mem;
+        if (!mem) { err = "policy_lstm_kernel: no memory buffer"; return HK_ERR_INVALID; }
+        {
+            static std::mutex mu;
+            static unsigned long long done_mask = 0ull;     // bit d: device d has the attribute (as below)
+            int dev = 0;
+            (void)hipGetDevice(&dev);
+            std::lock_guard<std::mutex> lk(mu);
+            if (dev < 0 || dev >= 64 || !((done_mask >> dev) & 1ull)) {
+                (void)hipFuncSetAttribute((const void*)policy_lstm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                if (dev >= 0 && dev < 64) done_mask |= 1ull << dev;
+            }
+        }
+        hipLaunchKernelGGL(policy_lstm_kernel, dim3((rows + PM_TILE - 1) / PM_TILE), dim3(PM_THREADS), policy_lstm_lds_bytes(pd.q, pd.lq), stream, pd.q, pd.lq, mem,
+                           rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { err = std::string("policy_lstm_kernel: ") + hipGetErrorString(e); return HK_ERR_HIP; }
+        return HK_OK;
+    }
     const bool bf = pd.prec == HK_POLICY_PREC_BF16;
     if (bf && !pd.wbf) { err = "policy_mlp_bf16_kernel: the policy has no bf16 weights"; return HK_ERR_INVALID; }
     const size_t lds = bf ? policy_bf16_lds_bytes(pd.q) : policy_lds_bytes(pd.q);

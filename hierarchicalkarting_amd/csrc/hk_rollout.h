@@ -1,7 +1,7 @@
 // hk_rollout.h — device side of the rollout recorder (contract in include/hk.h, host side in hk_api.hip).  What a decision writes comes
 // from policy_stack_kernel (OBS, FIRST) and the epilogue of policy_mlp_kernel (actions, RAW, heads, log-probabilities); the tick kernel
 // stores TERM_* at ResetGame (hk_env_step.h phase_begin, reward instantiations only).  Here: the two snapshots of hk_rollout_begin and the
-// kernel that closes an interval.
+// kernel that closes an interval.  (MEMORY / NEXT_MEMORY of recurrent actors: policy_memory_kernel / rollout_next_memory_kernel, hk_policy_lstm.h.)
 #pragma once
 #include "hk_policy.h"
 

@@ -131,7 +131,11 @@ class RacingEnv:
             raise ValueError("precision: one of %s" % sorted(self.POLICY_PRECISIONS))
         d, _keep = policy.desc()
         slots = np.ascontiguousarray(agent_slots, np.int32)
-        rc = self.L.hk_policy_attach(self.h, C.byref(d), slots.ctypes.data_as(C.POINTER(C.c_int32)), len(slots), int(decision_period))
+        ld = policy.lstm_desc()
+        if ld is None:
+            rc = self.L.hk_policy_attach(self.h, C.byref(d), slots.ctypes.data_as(C.POINTER(C.c_int32)), len(slots), int(decision_period))
+        else:           # a recurrent actor (hk.h "RECURRENT ACTORS")
+            rc = self.L.hk_policy_attach_lstm(self.h, C.byref(d), C.byref(ld), slots.ctypes.data_as(C.POINTER(C.c_int32)), len(slots), int(decision_period))
         if rc < 0:
             self._ck(rc)
         self._policies = getattr(self, "_policies", []) + [policy]
@@ -154,15 +158,42 @@ class RacingEnv:
             self._ck(rc)
         return {v: k for k, v in self.POLICY_PRECISIONS.items()}[rc]
 
-    def policy_forward(self, index, obs):
-        """the actor alone on stacked observations [rows, in_dim] -> (mu [rows], logits [rows, n_branch])"""
+    def policy_forward(self, index, obs, memory=None):
+        """the actor alone on stacked observations [rows, in_dim] -> (mu [rows], logits [rows, n_branch]); a recurrent actor takes
+        memory [rows, memory_size] (None: zeros) and returns (mu, logits, memory_out [rows, memory_size]); its own memory is not touched"""
         pol = self._policies[index]
         obs = np.ascontiguousarray(obs, np.float32).reshape(-1, pol.in_dim)
         mu = np.zeros(obs.shape[0], np.float32)
         lg = np.zeros((obs.shape[0], pol.n_branch), np.float32)
         fp = C.POINTER(C.c_float)
-        self._ck(self.L.hk_policy_forward(self.h, int(index), obs.shape[0], obs.ctypes.data_as(fp), mu.ctypes.data_as(fp), lg.ctypes.data_as(fp)))
-        return mu, lg
+        if not pol.memory_size:
+            if memory is not None:
+                raise ValueError("policy %d has no memory" % index)
+            self._ck(self.L.hk_policy_forward(self.h, int(index), obs.shape[0], obs.ctypes.data_as(fp), mu.ctypes.data_as(fp), lg.ctypes.data_as(fp)))
+            return mu, lg
+        mem_in = None
+        if memory is not None:
+            mem_in = np.ascontiguousarray(memory, np.float32).reshape(obs.shape[0], pol.memory_size)
+        out = np.zeros((obs.shape[0], pol.memory_size), np.float32)
+        self._ck(self.L.hk_policy_forward_mem(self.h, int(index), obs.shape[0], obs.ctypes.data_as(fp), None if mem_in is None else mem_in.ctypes.data_as(fp),
+                                              mu.ctypes.data_as(fp), lg.ctypes.data_as(fp), out.ctypes.data_as(fp)))
+        return mu, lg, out
+
+    def policy_memory(self, index):
+        """-> [E, n_slots, memory_size]: the memory [h | c] of a recurrent actor's agents (synchronises)"""
+        pol = self._policies[index]
+        a = np.zeros((self.E, len(self._policy_slots[index]), pol.memory_size), np.float32)
+        self._ck(self.L.hk_policy_memory_get(self.h, int(index), a.ctypes.data_as(C.POINTER(C.c_float))))
+        return a
+
+    def set_policy_memory(self, index, array):
+        """write the memory of a recurrent actor's agents ([E, n_slots, memory_size]); it belongs to the episodes the envs are in now
+        (hk.h hk_policy_memory_set); refused while a rollout is open"""
+        pol = self._policies[index]
+        a = np.ascontiguousarray(array, np.float32)
+        if a.shape != (self.E, len(self._policy_slots[index]), pol.memory_size):
+            raise ValueError("memory: expected shape %s" % ((self.E, len(self._policy_slots[index]), pol.memory_size),))
+        self._ck(self.L.hk_policy_memory_set(self.h, int(index), a.ctypes.data_as(C.POINTER(C.c_float))))
 
     def lq_debug(self, env, ego):
         d = _lib.LqDebug()
@@ -269,8 +300,12 @@ class RacingEnv:
         pols = getattr(self, "_policies", [])
         nbm = max([p.n_branch for p in pols] + [1])
         smax = max([p.stack for p in pols] + [1])
+        mem_max = max([p.memory_size for p in pols] + [0])
         sh = {n: (R, E, A) for n in _lib.RO_FIELDS}
-        sh.update(obs=(R, E, A, D), logits=(R, E, A, nbm), done=(R, E), ring0=(E, A, smax - 1, D), next_obs=(E, A, D))
+        sh.update(obs=(R, E, A, D), logits=(R, E, A, nbm), done=(R, E), ring0=(E, A, smax - 1, D), next_obs=(E, A, D),
+                  memory=(R, E, A, mem_max), next_memory=(E, A, mem_max))
+        if mem_max == 0:          # no recurrent actor: the two fields have no elements and no pointer
+            del sh["memory"], sh["next_memory"]
         return sh
 
     def rollout_views(self):

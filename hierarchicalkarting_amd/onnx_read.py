@@ -73,13 +73,14 @@ def tensor(b):
 
 
 def attribute(b):
-    name = ""; val = None; ints = []; floats = []
+    name = ""; val = None; ints = []; floats = []; strings = []
     for f, w, v in fields(b):
         if f == 1: name = bytes(v).decode()
         elif f == 2: val = struct.unpack("<f", v)[0]
         elif f == 3: val = v if v < (1 << 63) else v - (1 << 64)
         elif f == 4: val = bytes(v)
         elif f == 5: val = tensor(v)[1]
+        elif f == 9: strings.append(bytes(v))          # (an LSTM node's `activations`)
         elif f == 8:
             if w == 0: ints.append(v)
             else:
@@ -88,7 +89,7 @@ def attribute(b):
                     d, j = _varint(v, j); ints.append(d if d < (1 << 63) else d - (1 << 64))
         elif f == 7:
             floats += list(struct.unpack("<%df" % (len(v) // 4), bytes(v))) if w == 2 else [struct.unpack("<f", v)[0]]
-    if val is None: val = ints if ints else floats
+    if val is None: val = ints if ints else (floats if floats or not strings else strings)
     return name, val
 
 

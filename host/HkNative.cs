@@ -25,7 +25,9 @@ namespace KartGame.AI.Native
         // hk_rollout_field: the buffers of the rollout recorder (hk_rollout_ptr)
         public const int HK_RO_OBS = 0, HK_RO_FIRST = 1, HK_RO_STEER = 2, HK_RO_BRANCH = 3, HK_RO_RAW = 4, HK_RO_MU = 5, HK_RO_LOGITS = 6,
                          HK_RO_LOGP_CONT = 7, HK_RO_LOGP_DISC = 8, HK_RO_REWARD = 9, HK_RO_GROUP_REWARD = 10, HK_RO_TERM_REWARD = 11,
-                         HK_RO_TERM_GROUP_REWARD = 12, HK_RO_DONE = 13, HK_RO_RING0 = 14, HK_RO_NEXT_OBS = 15, HK_RO_FIELDS = 16;
+                         HK_RO_TERM_GROUP_REWARD = 12, HK_RO_DONE = 13, HK_RO_RING0 = 14, HK_RO_NEXT_OBS = 15, HK_RO_MEMORY = 16,
+                         HK_RO_NEXT_MEMORY = 17, HK_RO_FIELDS = 18;      // MEMORY / NEXT_MEMORY: recurrent actors only (NULL pointer otherwise)
+        public const int HK_POLICY_MAX_MEMORY = 256;
         // hk_ppo_field: the PPO trainer's buffers (hk_ppo_ptr / hk_ppo_count); HK_PPO_STATS: L_pi, L_v, entropy, approx-KL, clip fraction, skipped rows
         public const int HK_PPO_PARAMS = 0, HK_PPO_GRAD = 1, HK_PPO_ADAM_M = 2, HK_PPO_ADAM_V = 3, HK_PPO_V_OLD = 4, HK_PPO_ADV = 5, HK_PPO_RET = 6,
                          HK_PPO_MB_MU = 7, HK_PPO_MB_LOGITS = 8, HK_PPO_MB_VALUE = 9, HK_PPO_PERM = 10, HK_PPO_SHADOW = 11, HK_PPO_NORM_MEAN = 12, HK_PPO_NORM_STD = 13, HK_PPO_CLIP = 14, HK_PPO_FIELDS = 15,
@@ -360,6 +362,18 @@ namespace KartGame.AI.Native
         public float* b_branch;
     }
 
+    // hk_policy_lstm_desc: the LSTM cell of a recurrent actor (NetworkSettings.memory; torch layout, gates i f g o; m = memory_size / 2)
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct HkPolicyLstmDesc
+    {
+        public int memory_size;
+        public int reserved;
+        public float* W_ih;       // [4m][hidden]
+        public float* W_hh;       // [4m][m]
+        public float* b_ih;       // [4m]
+        public float* b_hh;       // [4m]
+    }
+
     // hk_ppo_config: the trainer's constants (ML-Agents trainer_config: gamma, lambd; torch's Adam defaults)
     [StructLayout(LayoutKind.Sequential)]
     public struct HkPpoConfig
@@ -502,6 +516,12 @@ namespace KartGame.AI.Native
         [DllImport(Lib)] public static extern int hk_policy_set_precision(IntPtr h, int policy, int precision);
         [DllImport(Lib)] public static extern int hk_policy_get_precision(IntPtr h, int policy);
         [DllImport(Lib)] public static extern int hk_policy_forward(IntPtr h, int policy, int rows, float* obs, float* mu, float* logits);
+        // recurrent actors (hk.h "RECURRENT ACTORS"): memory [h | c] of 2m floats per (env, agent slot); lstm == null is hk_policy_attach
+        [DllImport(Lib)] public static extern int hk_policy_attach_lstm(IntPtr h, HkPolicyDesc* desc, HkPolicyLstmDesc* lstm, int* agentSlots, int nSlots, int decisionPeriod);
+        [DllImport(Lib)] public static extern int hk_policy_memory_size(IntPtr h, int policy);
+        [DllImport(Lib)] public static extern int hk_policy_forward_mem(IntPtr h, int policy, int rows, float* obs, float* memIn, float* mu, float* logits, float* memOut);
+        [DllImport(Lib)] public static extern int hk_policy_memory_get(IntPtr h, int policy, float* mem);
+        [DllImport(Lib)] public static extern int hk_policy_memory_set(IntPtr h, int policy, float* mem);
         [DllImport(Lib)] public static extern int hk_get_actions(IntPtr h, float* steer, int* branch);
         // rollout recorder: every decision of the attached actors writes a row of device buffers (fields: hk.h hk_rollout_field)
         [DllImport(Lib)] public static extern int hk_rollout_begin(IntPtr h, int rows);

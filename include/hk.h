@@ -477,6 +477,47 @@ int hk_policy_set_precision(hk_handle h, int policy, int precision);
 int hk_policy_get_precision(hk_handle h, int policy);
 /* The MLP alone on caller-supplied stacked observations (host pointers): mu[rows], logits[rows][n_branch]; in the policy's precision. */
 int hk_policy_forward(hk_handle h, int policy, int rows, const float* obs /*[rows][in_dim]*/, float* mu, float* logits);
+/* RECURRENT ACTORS: the ML-Agents NetworkBody with `memory: {memory_size, sequence_length}` (the reference's *-LSTM behaviours use
+ * memory_size 256 on a 128 x 3 trunk).  With m = memory_size / 2 the actor is: normalise, the n x (Linear + Swish) of above giving a[hidden], ONE
+ * LSTM cell, and the heads on h' (W_mu [m], W_branch [n_branch][m] in the hk_policy_desc given to hk_policy_attach_lstm):
+ *   z_g[j] = b_g[j] + sum_k W_ih[g m + j][k] a[k]  (k = 0 .. hidden - 1 ascending)
+ *                   + sum_k W_hh[g m + j][k] h[k]  (k = 0 .. m - 1 ascending, continuing the same fmaf chain)
+ *            g in {i, f, g, o}, torch's order; b = fp32(b_ih + b_hh), summed once on the host at attach
+ *   i = sigma(z_i)  f = sigma(z_f)  g~ = tanh(z_g)  o = sigma(z_o)      c' = fmaf(f, c, i g~)      h' = o tanh(c')
+ *   mu = W_mu h' + b_mu     logits = W_branch h' + b_branch              (fmaf chains over m, ascending)
+ * sigma and tanh are hk_sigmoidf / hk_tanhf_fast of csrc/hk_policy_lstm.h, fp32 on hk_expf_fast_core like the Swish; the gate products run on
+ * v_mfma_f32_32x32x2_f32 with the accumulator seeded with b, bit for bit the chain written above.  A host build of the same functions
+ * (tests/policy_lstm_host_check.cpp) reproduces mu, logits and the memory bit for bit.  Sampling, the clip, the arg-max, both
+ * log-probabilities and the recorder's row are the fp32 tail of a plain actor, unchanged, applied to h'.
+ * MEMORY of an (env, agent slot) is [h (m) | c (m)], hidden state first (ML-Agents' torch.cat([h, c])), fp32, kept in a device buffer of the
+ * policy [E][n_slots][2m] indexed by LOGICAL env like the observation stack.  It is all zero at the first decision of an episode: the test is
+ * the one that clears the stack (FIRST of the recorder), so hk_reset of some or all envs clears their memory at their next decision.
+ *   hk_policy_attach_lstm    hk_policy_attach plus the cell.  A NULL lstm desc IS hk_policy_attach, launch for launch.
+ *   hk_policy_memory_size    2m of the policy, 0 when it has no memory, < 0 an hk_status
+ *   hk_policy_forward_mem    the actor alone on caller-supplied rows (host pointers): mem_in [rows][2m] (NULL: zeros) -> mu, logits and, when
+ *                            mem_out is not NULL, the memory after the cell.  The policy's own memory is not touched.  Synchronises.
+ *   hk_policy_memory_get     the policy's memory [E][n_slots][2m] to the host; synchronises
+ *   hk_policy_memory_set     ... from the host.  What is set belongs to the episode each env is in NOW: the next decision keeps it (and does
+ *                            not clear the observation stack) unless the episode changes first, which is what lets a race with a recurrent
+ *                            actor resume on another handle after hk_set_agent_state / hk_set_env_state.
+ * Refused with HK_ERR_INVALID, state as it was, hk_last_error naming the argument: memory_size odd; m not a multiple of 32 or outside
+ * [32, 128]; a NULL weight pointer; reserved != 0; hk_policy_memory_set while a rollout is open; hk_policy_forward_mem, hk_policy_memory_get
+ * or hk_policy_memory_set on a policy without memory or with a NULL array.  Refused with HK_ERR_UNSUPPORTED on a policy WITH memory:
+ * hk_policy_forward (use hk_policy_forward_mem), hk_policy_set_precision(HK_POLICY_PREC_BF16), hk_ppo_create, hk_ppo_create_poca,
+ * hk_policy_pool_create / _save / _load.
+ * Out of scope: recurrent training (see "PPO trainer"), bf16 for the cell, snapshot pools and self-play swaps of recurrent actors, m above
+ * 128, stacked or bidirectional LSTMs, and a CPU-oracle restatement (the bit reference is the host build named above). */
+#define HK_POLICY_MAX_MEMORY 256          /* memory_size; m = memory_size / 2, a multiple of 32 in [32, 128] */
+typedef struct hk_policy_lstm_desc {
+    int32_t memory_size, reserved;
+    const float *W_ih /*[4m][hidden]*/, *W_hh /*[4m][m]*/, *b_ih /*[4m]*/, *b_hh /*[4m]*/;   /* torch layout, gates i f g o */
+} hk_policy_lstm_desc;
+int hk_policy_attach_lstm(hk_handle h, const hk_policy_desc* desc, const hk_policy_lstm_desc* lstm, const int32_t* agent_slots, int n_slots, int decision_period);
+int hk_policy_memory_size(hk_handle h, int policy);
+int hk_policy_forward_mem(hk_handle h, int policy, int rows, const float* obs /*[rows][in_dim]*/, const float* mem_in /*[rows][2m], NULL: zeros*/,
+                          float* mu, float* logits, float* mem_out /*[rows][2m] or NULL*/);
+int hk_policy_memory_get(hk_handle h, int policy, float* mem /*[E][n_slots][2m]*/);
+int hk_policy_memory_set(hk_handle h, int policy, const float* mem);
 /* The actions currently latched for every agent (what the policies / hk_set_actions wrote): steer[E][A], branch[E][A] */
 int hk_get_actions(hk_handle h, float* steer, int32_t* branch);
 
@@ -501,6 +542,15 @@ int hk_get_actions(hk_handle h, float* steer, int32_t* branch);
  *   RING0 f32 [E][A][stack_max - 1][obs_dim]   the stack contents before decision 0, oldest first, right-aligned (an actor of stack s uses
  *                              the last s - 1 entries; zeros where empty): with OBS and FIRST every stacked input of the rollout can be rebuilt
  *   NEXT_OBS f32 [E][A][obs_dim]   written by hk_rollout_close: the observation of the decision after the last row (bootstrap input)
+ *   MEMORY f32 [R][E][A][mem_max]   recurrent actors ("RECURRENT ACTORS" above) only: the memory [h | c] decision t READ, after the episode
+ *                              zeroing and before the cell; mem_max = the largest 2m of the handle's actors, entries of slots whose actor has
+ *                              none stay 0.  A row is self-contained: MU / LOGITS of row t follow from its stacked input and MEMORY[t] alone,
+ *                              MEMORY[t + 1] is the cell's output at row t unless FIRST[t + 1], and MEMORY[t] == 0 exactly where FIRST[t] == 1.
+ *                              4 * 2m bytes per row and agent (1 KiB at m = 128: 3.3 x the OBS row of obs_dim 78).
+ *   NEXT_MEMORY f32 [E][A][mem_max]   written by hk_rollout_close beside NEXT_OBS: the memory after the last completed row, zero where
+ *                              DONE of that row != 0 (the bootstrap memory)
+ *                              On a handle without a recurrent actor both have no elements: hk_rollout_ptr returns NULL for them (with a
+ *                              message), nothing is allocated for them and no launch is added.
  * A trainer's transition reward of row t is DONE ? TERM_REWARD : REWARD; TERM_REWARD + REWARD is every AddReward of the interval.
  * hk_rollout_begin allocates (or reuses) and zeroes the buffers, snapshots RING0 and the episode counters.  Refused (HK_ERR_INVALID):
  * no actor attached, a rollout already open, the Academy step not on a decision (a multiple of decision_period), rows < 1;
@@ -514,6 +564,7 @@ int hk_get_actions(hk_handle h, float* steer, int32_t* branch);
 typedef enum hk_rollout_field {
     HK_RO_OBS = 0, HK_RO_FIRST, HK_RO_STEER, HK_RO_BRANCH, HK_RO_RAW, HK_RO_MU, HK_RO_LOGITS, HK_RO_LOGP_CONT, HK_RO_LOGP_DISC,
     HK_RO_REWARD, HK_RO_GROUP_REWARD, HK_RO_TERM_REWARD, HK_RO_TERM_GROUP_REWARD, HK_RO_DONE, HK_RO_RING0, HK_RO_NEXT_OBS,
+    HK_RO_MEMORY, HK_RO_NEXT_MEMORY,
     HK_RO_FIELDS
 } hk_rollout_field;
 int hk_rollout_begin(hk_handle h, int rows);
@@ -652,7 +703,8 @@ void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* 
  *                        valid as they were.  Either pointer of get may be NULL.
  * Refused with HK_ERR_INVALID and a message naming the argument, state as it was: a NULL opts, epochs < 1, minibatch < 1, max_grad_norm or target_kl
  * negative or NaN, target_kl infinite, reserved != 0, and whatever hk_ppo_update / hk_ppo_adam refuse.
- * Out of scope (self-play opponent swaps, episode statistics and ELO: "SELF-PLAY" below; POCA and group rewards: "POCA" below): LSTM memory, a normaliser for policies attached with normalize == 0,
+ * Out of scope (self-play opponent swaps, episode statistics and ELO: "SELF-PLAY" below; POCA and group rewards: "POCA" below): training a recurrent actor (truncated BPTT over the recorder's MEMORY / FIRST rows, a recurrent critic, sequence_length minibatches: hk_ppo_create
+ * refuses a policy with memory, "RECURRENT ACTORS" above), a normaliser for policies attached with normalize == 0,
  * multi-GPU gradient all-reduce and bf16 optimiser state.  Everything is asynchronous on hk_stream unless noted. */
 #define HK_PPO_STATS 6
 typedef struct hk_ppo_config {
@@ -748,7 +800,7 @@ int hk_ppo_set_counters(hk_handle h, int trainer, int64_t adam_steps, int64_t ep
  * reserved != 0; hk_config.rewards == 0; a bad policy index, a full trainer table or Adam constants out of range (as hk_ppo_create).
  * hk_poca_ptr / hk_poca_count: an HK_POCA_* field of a POCA trainer (another trainer or field is refused).  hk_poca_stats (synchronises):
  * [0] L_b belonging to the stats the last hk_ppo_minibatch / hk_ppo_update(_opt) returned, [1] reserved, 0.
- * Out of scope: bf16 products for the POCA critic, LSTM memory, groups that lose members mid-episode (attention masks), a critic normaliser
+ * Out of scope: bf16 products for the POCA critic, recurrent training (hk_ppo_create_poca refuses a policy with memory), groups that lose members mid-episode (attention masks), a critic normaliser
  * separate from the actor's, multi-GPU gradient all-reduce. */
 #define HK_POCA_MAX_GROUP 4
 #define HK_POCA_HEADS 4
@@ -810,7 +862,8 @@ int hk_poca_stats(hk_handle h, int trainer, float* out /*[HK_POCA_STATS]*/);   /
  * here and have no order, so a rollout's W wins, D draws and L losses are applied as n = W + D + L sequential steps of the MEAN result
  * s = (W + D / 2) / n: change = k (s - 1 / (1 + 10^((r_opp - r_learner) / 400))), r_learner += change, r_opp -= change.  Order-free, equal to
  * ML-Agents' sequence when all results agree, and self-limiting where a one-shot change of n (s - e) would move ratings by thousands of points.
- * Out of scope: team_change (a trainer is bound to one policy), per-env opponents, bf16 POCA and LSTM. */
+ * Out of scope: team_change (a trainer is bound to one policy), per-env opponents, bf16 POCA, and snapshot pools or swaps of
+ * recurrent actors (hk_policy_pool_create / _save / _load refuse a policy with memory). */
 #define HK_MAX_POOLS 8
 #define HK_POOL_MAX_SLOTS 64
 int hk_policy_pool_create(hk_handle h, int policy, int slots);

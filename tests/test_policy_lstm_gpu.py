@@ -1,0 +1,306 @@
+"""Recurrent actors on the device (policy_lstm_kernel, hk.h "RECURRENT ACTORS") against the host twin
+(tests/policy_lstm_host_check.cpp: the same HK_HD sigmoid / tanh / cell, the contract's k-ascending fmaf chains), bit for bit: the forward
+tap, the closed loop through hk_step replayed from the recorder's MEMORY / FIRST rows, call patterns, resets, get / set, a recurrent and a
+plain actor on one handle, and the refusals.
+
+The smallest input with a K remainder modulo 8: hk_policy_attach requires in_dim == hk_obs_dim * stack, and the smallest observation is 54
+(2 agents), so 4 x 13 = 52 cannot be attached; stack 2 x 54 = 108 has the same remainder (4) and is what the forward tests use beside the
+env's real in_dim 216."""
+import ctypes as C
+import numpy as np
+import pytest
+import policy_lstm_twin as TW
+from hierarchicalkarting_amd import _lib
+from hierarchicalkarting_amd.policy import Policy
+from hierarchicalkarting_amd.rollout import stacked_inputs
+from parity import assert_bits_equal
+from rollout_restate import logp_cont, logp_disc
+
+pytestmark = pytest.mark.gpu
+RL, P = _lib.HK_LOW_RL, 2
+
+
+def _env(E, **kw):
+    import hierarchicalkarting_amd as hk
+    kw.setdefault("low_mode", [RL, RL])
+    g = hk.RacingEnv(hk.make_config(E, 2, **kw))
+    g.reset()
+    return g
+
+
+def _refused(fn, *a):
+    with pytest.raises(_lib.HkError) as e:
+        fn(*a)
+    return e.value.code, str(e.value)
+
+
+# (H, m): one unit block with idle waves; the reference shape; two column blocks per wave with two unit blocks; an odd block count; the largest
+@pytest.mark.parametrize("H,m", [(32, 32), (128, 128), (256, 64), (96, 96), (256, 128)])
+def test_forward_against_the_twin(H, m):
+    g = _env(2)
+    D = g.obs_dim
+    pols = [Policy.random(D * 2, H, 2, 3, stack=2, seed=H + m, memory_size=2 * m),
+            Policy.random(D * 4, H, 3, 3, stack=4, seed=H + m + 1, memory_size=2 * m, normalize=(H != 96))]
+    assert pols[0].in_dim % 8 == 4 and pols[1].in_dim == 216
+    for k, pol in enumerate(pols):
+        assert g.attach_policy(pol, [k], P) == k
+        assert g.L.hk_policy_memory_size(g.h, k) == 2 * m
+    r = np.random.default_rng(7 * H + m)
+    for k, pol in enumerate(pols):
+        for rows in (1, 63, 64, 65, 130):           # the tile edges, a last tile of one row, more than two tiles
+            obs = (r.standard_normal((rows, pol.in_dim)) * 4).astype(np.float32)
+            mem = r.uniform(-1.0, 1.0, (rows, 2 * m)).astype(np.float32)
+            got = g.policy_forward(k, obs, mem)
+            want = TW.step(pol, obs, mem)
+            for x, y, n in zip(got, want, ("mu", "logits", "mem_out")):
+                assert_bits_equal(x, y, (H, m, k, rows, n))
+            assert np.abs(got[2]).max() > 1e-3 and np.isfinite(got[0]).all()
+            for x, y, n in zip(g.policy_forward(k, obs, mem), got, ("mu", "logits", "mem_out")):      # the same call twice
+                assert_bits_equal(x, y, (H, m, k, rows, n, "again"))
+            if rows in (1, 65):
+                null = g.policy_forward(k, obs, None)
+                for x, y, z, n in zip(null, g.policy_forward(k, obs, np.zeros_like(mem)), TW.step(pol, obs, None), ("mu", "logits", "mem_out")):
+                    assert_bits_equal(x, y, (H, m, k, rows, n, "NULL == zeros"))
+                    assert_bits_equal(x, z, (H, m, k, rows, n, "NULL vs twin"))
+                # two chained calls == two twin steps
+                obs2 = (r.standard_normal((rows, pol.in_dim)) * 4).astype(np.float32)
+                for x, y, n in zip(g.policy_forward(k, obs2, got[2]), TW.step(pol, obs2, want[2]), ("mu", "logits", "mem_out")):
+                    assert_bits_equal(x, y, (H, m, k, rows, n, "chained"))
+    assert not g.policy_memory(0).any()              # the tap leaves the policy's own memory alone
+
+
+def _replay(ro, pol, slots, tag):
+    """every row of a recorded rollout from its stacked input and MEMORY[t] alone, through the twin; -> the twin's memory after the last row"""
+    R, E = ro["obs"].shape[:2]
+    S, mm = len(slots), pol.memory_size
+    x = stacked_inputs(ro, slots, pol.stack)
+    first = ro["first"][:, :, slots]
+    mem = ro["memory"][:, :, slots, :mm]
+    zero = ~mem.any(axis=-1)
+    assert np.array_equal(zero, first == 1), tag            # zero exactly where the episode starts
+    out = None
+    for t in range(R):
+        mu, lg, out = TW.step(pol, x[t].reshape(E * S, -1), mem[t].reshape(E * S, mm))
+        assert_bits_equal(ro["mu"][t][:, slots].reshape(-1), mu, (tag, t, "mu"))
+        assert_bits_equal(ro["logits"][t][:, slots, :pol.n_branch].reshape(E * S, -1), lg, (tag, t, "logits"))
+        if t + 1 < R:
+            keep = first[t + 1].reshape(-1) == 0
+            assert_bits_equal(mem[t + 1].reshape(E * S, mm)[keep], out[keep], (tag, t, "memory chain"))
+    return out.reshape(E, S, mm)
+
+
+def _lstm_actor(D, seed=3, **kw):
+    return Policy.random(D * 4, 128, 3, 3, seed=seed, memory_size=256, **kw)
+
+
+def _stagger(g):
+    """82 ticks in which the envs with env % 4 == k restart their episode at tick 2k: with max_episode_steps = 100 (the smallest allowed) the
+    time-outs of the four groups, two ticks apart from tick 100 on, fall into different rows of a 12-row rollout begun here (ticks 82 .. 106),
+    one group's into the last row — whichever tick of an interval the time-out counts from"""
+    for k in (1, 2, 3):
+        g.step(2)
+        g.reset(np.arange(k, g.E, 4, dtype=np.int32))
+    g.step(76)
+
+
+def test_closed_loop_replayed_from_the_recorder():
+    E, R = 70, 12                                           # 140 rows a decision: three tiles of 64, the last partial
+    g = _env(E, rewards=1, max_episode_steps=100, jitter_seed=9)
+    pol = _lstm_actor(g.obs_dim)
+    g.attach_policy(pol, [0, 1], P)
+    _stagger(g)
+    g.rollout_begin(R)
+    for n in (1, 3, 2, 7, 11):
+        g.step(n)
+    assert g.rollout_rows() == R
+    live = g.policy_memory(0)
+    g.rollout_close()
+    ro = g.rollout()
+    assert ro["memory"].shape == (R, E, 2, 256) and ro["next_memory"].shape == (E, 2, 256)
+    assert (ro["done"][:R - 1] != 0).any() and (ro["first"][1:] == 1).any() and (ro["first"] == 0).any()
+    assert (ro["done"][R - 1] != 0).any() and (ro["done"][R - 1] == 0).any()       # NEXT_MEMORY: both sides of its rule
+    last = _replay(ro, pol, [0, 1], "closed loop")
+    assert_bits_equal(live, last, "hk_policy_memory_get after the last row")
+    want = np.where((ro["done"][R - 1] != 0)[:, None, None], np.float32(0), last)
+    assert_bits_equal(ro["next_memory"], want, "NEXT_MEMORY")
+    raw, mu, lg, br = ro["raw"], ro["mu"], ro["logits"], ro["branch"]
+    assert np.allclose(ro["logp_cont"], logp_cont(raw, mu, pol.log_sigma[0]), rtol=1e-6, atol=2e-6)
+    assert np.allclose(ro["logp_disc"], logp_disc(lg, br), rtol=1e-6, atol=2e-6)
+    assert_bits_equal(ro["steer"], np.clip(raw, np.float32(-3), np.float32(3)) / np.float32(3), "steer")
+    assert (raw != mu).mean() > 0.9
+
+
+def test_call_patterns():
+    """hk_step(2) x 12, hk_step(24) and a mixed split on equal seeds: every recorder field and the final memory, bit for bit"""
+    outs = []
+    for calls in ((2,) * 12, (24,), (1, 3, 7, 2, 11)):
+        g = _env(70, rewards=1, max_episode_steps=100, jitter_seed=9)
+        g.attach_policy(_lstm_actor(g.obs_dim), [0, 1], P)
+        _stagger(g)
+        g.rollout_begin(12)
+        for n in calls:
+            g.step(n)
+        g.rollout_close()
+        outs.append((g.rollout(), g.policy_memory(0), g.agent_state()))
+    for ro, mem, st in outs[1:]:
+        assert sorted(ro) == sorted(outs[0][0])
+        for name in ro:
+            assert_bits_equal(ro[name], outs[0][0][name], name)
+        assert_bits_equal(mem, outs[0][1], "memory")
+        assert_bits_equal(st, outs[0][2], "agent_state")
+
+
+def test_resets_and_get_set():
+    g = _env(70, jitter_seed=5)
+    pol = _lstm_actor(g.obs_dim, deterministic=True)
+    g.attach_policy(pol, [0, 1], P)
+    g.step(8)
+    before = g.policy_memory(0)
+    assert before.any(axis=-1).all()
+    some = np.array([1, 5, 64, 69], np.int32)
+    g.reset(some)
+    g.rollout_begin(2)
+    g.step(4)
+    g.rollout_close()
+    ro = g.rollout()
+    hit = np.zeros(70, bool); hit[some] = True
+    assert (ro["first"][0][hit] == 1).all() and (ro["first"][0][~hit] == 0).all() and not ro["first"][1].any()
+    assert not ro["memory"][0][hit].any()
+    assert_bits_equal(ro["memory"][0][~hit], before[~hit], "the other envs continue their chain")
+    _replay(ro, pol, [0, 1], "after hk_reset")
+    # set then get
+    r = np.random.default_rng(2)
+    mem = r.uniform(-1, 1, before.shape).astype(np.float32)
+    g.set_policy_memory(0, mem)
+    assert_bits_equal(g.policy_memory(0), mem, "set / get")
+    g.rollout_begin(1)
+    g.step(2)
+    g.rollout_close()
+    ro = g.rollout()
+    assert not ro["first"].any()
+    assert_bits_equal(ro["memory"][0], mem, "the decision after hk_policy_memory_set reads what was set")
+
+
+def test_race_resumes_on_a_second_handle():
+    """agent and env state, and the actor's memory, carried to a fresh handle: the race continues bit for bit (a stack of one observation,
+    which the next decision rewrites whole, and a deterministic actor: the observation stack and the sampling counter are not part of what
+    hk_get_agent_state / hk_policy_memory_get carry)"""
+    def make():
+        g = _env(70, jitter_seed=6)
+        pol = Policy.random(g.obs_dim, 128, 3, 3, stack=1, seed=8, deterministic=True, memory_size=256)
+        g.attach_policy(pol, [0, 1], P)
+        return g
+    a, b = make(), make()
+    a.step(10)
+    b.set_agent_state(a.agent_state()); b.set_env_state(a.env_state())
+    b.set_policy_memory(0, a.policy_memory(0))
+    for n in (2, 5, 9):
+        a.step(n); b.step(n)
+        assert_bits_equal(a.agent_state(), b.agent_state(), ("agent_state", n))
+        assert_bits_equal(a.get_actions()[0], b.get_actions()[0], ("steer", n))
+        assert_bits_equal(a.policy_memory(0), b.policy_memory(0), ("memory", n))
+    assert len(np.unique(a.get_actions()[0])) > 8
+
+
+def test_recurrent_and_plain_actor_on_one_handle():
+    g = _env(70, rewards=1, max_episode_steps=100, jitter_seed=3)
+    rec, plain = _lstm_actor(g.obs_dim, seed=4), Policy.random(g.obs_dim * 4, 128, 3, 3, seed=5)
+    assert g.attach_policy(rec, [0], P) == 0 and g.attach_policy(plain, [1], P) == 1
+    assert g.L.hk_policy_memory_size(g.h, 0) == 256 and g.L.hk_policy_memory_size(g.h, 1) == 0
+    g.step(90)
+    g.rollout_begin(10)
+    g.step(20)
+    g.rollout_close()
+    ro = g.rollout()
+    assert (ro["done"] != 0).any()
+    _replay(ro, rec, [0], "recurrent beside plain")
+    assert not ro["memory"][:, :, 1].any() and not ro["next_memory"][:, 1].any()
+    x = stacked_inputs(ro, [1], 4)
+    mu, lg = g.policy_forward(1, x.reshape(-1, plain.in_dim))
+    assert_bits_equal(mu, ro["mu"][:, :, 1].reshape(-1), "plain mu")
+    assert_bits_equal(lg, ro["logits"][:, :, 1, :3].reshape(-1, 3), "plain logits")
+
+
+def test_no_change_without_the_feature():
+    a, b = _env(20, jitter_seed=2), _env(20, jitter_seed=2)
+    pol = Policy.random(a.obs_dim * 4, 128, 3, 3, seed=6)
+    assert a.attach_policy(pol, [0, 1], P) == 0
+    d, _keep = pol.desc()
+    slots = np.array([0, 1], np.int32)
+    assert b.L.hk_policy_attach_lstm(b.h, C.byref(d), None, slots.ctypes.data_as(C.POINTER(C.c_int32)), 2, P) == 0
+    b._policies, b._policy_slots = [pol], [[0, 1]]
+    for e in (a, b):
+        assert e.L.hk_policy_memory_size(e.h, 0) == 0
+        e.rollout_begin(6)
+        e.step(12)
+        e.rollout_close()
+        for f in ("memory", "next_memory"):
+            assert e.L.hk_rollout_ptr(e.h, _lib.RO_FIELDS[f][0]) is None
+            assert b"MEMORY" in e.L.hk_last_error(e.h)
+    ra, rb = a.rollout(), b.rollout()
+    assert "memory" not in ra and "next_memory" not in ra and sorted(ra) == sorted(rb)
+    for name in ra:
+        assert_bits_equal(ra[name], rb[name], name)
+    assert_bits_equal(a.get_actions()[0], b.get_actions()[0], "steer")
+    assert np.array_equal(a.get_actions()[1], b.get_actions()[1])
+
+
+def test_refusals():
+    g = _env(4, jitter_seed=1)
+    D = g.obs_dim
+    good = _lstm_actor(D)
+    slots = np.array([0], np.int32)
+    ip = slots.ctypes.data_as(C.POINTER(C.c_int32))
+    d, _keep = good.desc()
+
+    def attach(**change):
+        ld = good.lstm_desc()
+        for k, v in change.items():
+            setattr(ld, k, v)
+        rc = g.L.hk_policy_attach_lstm(g.h, C.byref(d), C.byref(ld), ip, 1, P)
+        return rc, g.L.hk_last_error(g.h).decode()
+
+    null = C.POINTER(C.c_float)()
+    for change, word in (({"memory_size": 255}, "memory_size"), ({"memory_size": 96}, "memory_size"), ({"memory_size": 0}, "memory_size"),
+                         ({"memory_size": 320}, "memory_size"), ({"W_ih": null}, "W_ih"), ({"W_hh": null}, "W_hh"), ({"b_ih": null}, "b_ih"),
+                         ({"b_hh": null}, "b_hh"), ({"reserved": 1}, "reserved")):
+        rc, msg = attach(**change)
+        assert rc == _lib.HK_ERR_INVALID and word in msg, (change, rc, msg)
+    # nothing was attached by the refused calls: the next attach is policy 0
+    assert g.attach_policy(good, [0], P) == 0
+    plain = Policy.random(D * 4, 128, 3, 3, seed=5)
+    assert g.attach_policy(plain, [1], P) == 1
+    g.step(6)
+    obs = np.random.default_rng(0).standard_normal((9, good.in_dim)).astype(np.float32)
+    mem0, out0 = g.policy_memory(0), g.policy_forward(0, obs, None)
+    fp = C.POINTER(C.c_float)
+    buf = np.zeros(64, np.float32)
+
+    def unsupported(rc, word):
+        msg = g.L.hk_last_error(g.h).decode()
+        assert rc == _lib.HK_ERR_UNSUPPORTED and word in msg, (rc, msg)
+
+    unsupported(g.L.hk_policy_forward(g.h, 0, 9, obs.ctypes.data_as(fp), buf.ctypes.data_as(fp), buf.ctypes.data_as(fp)), "hk_policy_forward_mem")
+    unsupported(g.L.hk_policy_set_precision(g.h, 0, _lib.HK_POLICY_PREC_BF16), "precision")
+    assert g.policy_precision(0) == "f32"
+    unsupported(g.L.hk_ppo_create(g.h, 0, None, None), "policy")
+    unsupported(g.L.hk_ppo_create_poca(g.h, 0, None, None), "policy")
+    unsupported(g.L.hk_policy_pool_create(g.h, 0, 2), "policy")
+    pool = g.L.hk_policy_pool_create(g.h, 1, 2)
+    assert pool == 0
+    unsupported(g.L.hk_policy_pool_save(g.h, pool, 0, 0), "policy")
+    # a policy without memory
+    code, msg = _refused(g.policy_memory, 1)
+    assert code == _lib.HK_ERR_INVALID and "policy" in msg
+    rc = g.L.hk_policy_forward_mem(g.h, 1, 9, obs.ctypes.data_as(fp), None, buf.ctypes.data_as(fp), buf.ctypes.data_as(fp), None)
+    assert rc == _lib.HK_ERR_INVALID and "hk_policy_forward" in g.L.hk_last_error(g.h).decode()
+    # hk_policy_memory_set while a rollout is open
+    g.rollout_begin(2)
+    code, msg = _refused(g.set_policy_memory, 0, np.ones_like(mem0))
+    assert code == _lib.HK_ERR_INVALID and "rollout" in msg
+    g.rollout_close()
+    # precision, memory and the published weights are as they were
+    assert_bits_equal(g.policy_memory(0), mem0, "memory after the refusals")
+    for x, y in zip(g.policy_forward(0, obs, None), out0):
+        assert_bits_equal(x, y, "forward after the refusals")
+    assert g.policy_precision(0) == "f32" and g.policy_precision(1) == "f32"
