@@ -132,6 +132,28 @@ __device__ __forceinline__ float pm_logp_disc(const float* lg, int nb, int best,
     return (lg[pick] - lg[best]) - hk_logf(tot);
 }
 
+// The stack ring: where logical input k of a row (observation k / obs_dim of the stack, oldest first) lives in the row's ring, whose slot w
+// holds the newest observation (w = stack - 1 for plain oldest-first rows): ((w + 1 + k / obs_dim) % stack) * obs_dim + k % obs_dim
+__device__ __forceinline__ int pm_ring_offset(const PolicyParams& Q, int w, int k)
+{
+    const int i = k / Q.obs_dim, kk = k - i * Q.obs_dim;
+    int slot = w + 1 + i; slot -= (slot >= Q.stack) ? Q.stack : 0;
+    return slot * Q.obs_dim + kk;
+}
+// The episode word PolicyParams::epoch is compared with and set to: it changes whenever the env starts another episode
+__device__ __forceinline__ int pm_episode_word(const hk_env_state& es) { return es.episodes_done + es.initial_started; }
+// The group-major weight layout (PolicyParams::Wq, PolicyLstm::Wq_*) of a matrix with N output columns: the float index of k-step j (of 4) of
+// (group of 8 inputs g, lane half, column), which holds W[k = 8 g + 2 j + half][col]
+HK_HD size_t pm_wq_index(int g, int half, int col, int j, int N) { return (((size_t)g * 2 + half) * N + col) * 4 + j; }
+// ... filled from a torch-layout matrix W [N][K]: the whole groups of 8 inputs, (K / 8) * 8 * N floats at wq
+inline void pm_wq_fill(float* wq, const float* W, int N, int K)
+{
+    for (int g = 0; g < K / 8; g++)
+        for (int hf = 0; hf < 2; hf++)
+            for (int col = 0; col < N; col++)
+                for (int j = 0; j < 4; j++) wq[pm_wq_index(g, hf, col, j, N)] = W[(size_t)col * K + 8 * g + 2 * j + hf];
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // StackingSensor.  One wave per (env, slot), four to a block; w = ring slot that receives the newest observation.  (Round 5: a wave needs no block
 // barrier — the epoch word is read by every lane before lane 0 rewrites it, the zero fill precedes the copy in program order — and a pair moves
@@ -145,7 +167,7 @@ __global__ __launch_bounds__(256) void policy_stack_kernel(PolicyParams Q, int E
     if (pair >= E * Q.n_slots) return;                         // (wave-uniform)
     const int env = pair / Q.n_slots, j = pair % Q.n_slots;
     const hk_env_state* es = &envs_by_slot[slot_of[env]];      // env words are stored by lane-group slot (hk_env_device.h)
-    const int ep = es->episodes_done + es->initial_started;
+    const int ep = pm_episode_word(*es);
     const bool stale = Q.epoch[pair] != ep;                    // every lane reads the word; lane 0 rewrites it below, after this load in program order
     float* ring = Q.ring + (size_t)pair * Q.in_dim;
     if (stale) {
@@ -242,9 +264,10 @@ __device__ __forceinline__ void pm_gemm(f32x16& acc0, f32x16& acc1, const float*
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The tail of a decision, from the heads to the recorder's stores, as a function: policy_mlp_bf16_kernel's (hk_policy_bf16.h).  It is
+// The tail of a decision, from the heads to the recorder's stores, as a function: policy_mlp_bf16_kernel's and policy_lstm_kernel's.  It is
 // policy_mlp_kernel's tail word for word; that kernel keeps its own inline copy (see there).  At: the last layer's fp32 post-activations
-// [k][PM_LD] in LDS, complete (a barrier precedes the call); head: PM_MAX_OUT x PM_TILE floats of LDS beside it; tid = threadIdx.x, H = hidden.
+// [k][PM_LD] in LDS, complete (a barrier precedes the call); head: PM_MAX_OUT x PM_TILE floats of LDS beside it; tid = threadIdx.x, H = the
+// heads' width (hidden; m of a recurrent actor).
 __device__ __forceinline__ void pm_tail(const PolicyParams& Q, const float* At, float* head, int rows, int row0, unsigned long long decision,
                                         int env_id_base, int A, float* mu_out, float* logit_out, float* act_steer, int* act_branch, const PolicyRec& rec, int tid, int H)
 {
@@ -306,7 +329,7 @@ __device__ __forceinline__ void pm_tail(const PolicyParams& Q, const float* At, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// src: [rows][in_dim]; logical element k of a row lives at ((w + 1 + k / obs_dim) % stack) * obs_dim + k % obs_dim
+// src: [rows][in_dim]; logical element k of a row lives at pm_ring_offset(Q, w, k)
 // (w = stack - 1 for plain oldest-first rows).  Outputs: mu_out / logit_out when non-null; act_steer / act_branch
 // (indexed [env][agent], row = env * n_slots + j) when non-null, and then the rollout row `rec` when rec.raw is non-null.
 // MODE: how the (H / 32) x 2 blocks of a layer fall on the 8 waves — 0: one block per wave (H <= 128), 1: two blocks per
@@ -360,6 +383,7 @@ __global__ __launch_bounds__(PM_THREADS, MODE == 2 ? 2 : 4) void policy_mlp_kern
                     const int kl = lane + 64 * m, k = kb + kl;
                     soff[m] = -1; mean[m] = 0.0f; sdev[m] = 1.0f;
                     if (kl < kc) {
+                        // (pm_ring_offset's rule written out: with the call MODE 0 and 2 get another listing, which has not been timed)
                         const int i = k / Q.obs_dim, kk = k - i * Q.obs_dim;
                         int slot = w + 1 + i; slot -= (slot >= Q.stack) ? Q.stack : 0;
                         soff[m] = slot * Q.obs_dim + kk;
@@ -413,8 +437,8 @@ __global__ __launch_bounds__(PM_THREADS, MODE == 2 ? 2 : 4) void policy_mlp_kern
         __syncthreads();
     }
 
-    // (the tail below is pm_tail's text: calling pm_tail here took one VGPR off every MODE of this kernel, whose resource rows are held
-    // fixed, so it keeps its own copy — change both together)
+    // (the tail below is pm_tail's text.  Calling pm_tail here was measured against this copy, libraries alternated: the three MODEs came out
+    // 0.4 - 1.5 % slower per launch, several times the run-to-run spread, so the kernel keeps its own copy — change both together)
     // ---- heads: out 0 = mu, 1.. = branch logits; thread -> (out = tid / 64, row = tid % 64)
     {
         const int out = tid >> 6, r = tid & 63;
@@ -514,14 +538,8 @@ inline int policy_upload(PolicyDevice& pd, const hk_policy_desc* d, int index, i
         // the group-major copy (PolicyParams::Wq): whole groups of 8 inputs
         while (host.size() % 4) host.push_back(0.0f);
         o_Wq[l] = host.size();
-        const int ngr = K / 8;
-        host.resize(host.size() + (size_t)ngr * 2 * H * 4);
-        float* wq = host.data() + o_Wq[l];
-        const float* wt2 = host.data() + o_W[l];
-        for (int g = 0; g < ngr; g++)
-            for (int hf = 0; hf < 2; hf++)
-                for (int j = 0; j < H; j++)
-                    for (int q4 = 0; q4 < 4; q4++) wq[(((size_t)g * 2 + hf) * H + j) * 4 + q4] = wt2[(size_t)(8 * g + 2 * q4 + hf) * H + j];
+        host.resize(host.size() + (size_t)(K / 8) * 8 * H);
+        pm_wq_fill(host.data() + o_Wq[l], d->W[l], H, K);
     }
     const size_t o_wmu = put(d->W_mu, HW), o_bmu = put(d->b_mu, 1), o_ls = put(d->log_sigma, 1);
     const size_t o_wbr = put(d->W_branch, (size_t)d->n_branch * HW), o_bbr = put(d->b_branch, d->n_branch);
@@ -584,67 +602,49 @@ inline void policy_free(PolicyDevice& pd)
     pd = PolicyDevice{};
 }
 
+// The actor kernels use ~68 KB of dynamic LDS and more, above the 64 KB default: raise the limit once per DEVICE (the attribute belongs to
+// the device's code object; a second handle on another device needs it too).  Guarded by a mutex: handles of different
+// devices may be driven from different host threads.
+inline void policy_raise_lds_limit_once()
+{
+    static std::mutex mu;
+    static unsigned long long done_mask = 0ull;     // bit d: device d has the attribute
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lk(mu);
+    if (dev >= 0 && dev < 64 && ((done_mask >> dev) & 1ull)) return;
+    for (const void* k : {(const void*)policy_mlp_kernel<0>, (const void*)policy_mlp_kernel<1>, (const void*)policy_mlp_kernel<2>,
+                          (const void*)policy_mlp_bf16_kernel<false>, (const void*)policy_mlp_bf16_kernel<true>, (const void*)policy_lstm_kernel})
+        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (dev >= 0 && dev < 64) done_mask |= 1ull << dev;
+}
+
 inline int policy_launch_mlp(const PolicyDevice& pd, int rows, const float* src, int w, unsigned long long decision,
                              int env_id_base, int A, float* mu_out, float* logit_out, float* act_steer, int* act_branch,
                              const PolicyRec& rec, hipStream_t stream, std::string& err, float* lstm_mem = nullptr)
 {
     if (rows <= 0) return HK_OK;
-    if (pd.lq.m > 0) {
-        // a policy with memory: policy_lstm_kernel on lstm_mem [rows][2m] (nullptr: the policy's own buffer), read and rewritten in place
-        float* mem = lstm_mem ? lstm_mem : pd.lq.mem;
-        if (!mem) { err = "policy_lstm_kernel: no memory buffer"; return HK_ERR_INVALID; }
-        {
-            static std::mutex mu;
-            static unsigned long long done_mask = 0ull;     // bit d: device d has the attribute (as below)
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            std::lock_guard<std::mutex> lk(mu);
-            if (dev < 0 || dev >= 64 || !((done_mask >> dev) & 1ull)) {
-                (void)hipFuncSetAttribute((const void*)policy_lstm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (dev >= 0 && dev < 64) done_mask |= 1ull << dev;
-            }
-        }
-        hipLaunchKernelGGL(policy_lstm_kernel, dim3((rows + PM_TILE - 1) / PM_TILE), dim3(PM_THREADS), policy_lstm_lds_bytes(pd.q, pd.lq), stream, pd.q, pd.lq, mem,
+    // every actor kernel: (Q, its own arguments `own`, the common ones)
+    auto launch = [&](auto kernel, const char* name, size_t lds, auto... own) {
+        policy_raise_lds_limit_once();
+        hipLaunchKernelGGL(kernel, dim3((rows + PM_TILE - 1) / PM_TILE), dim3(PM_THREADS), lds, stream, pd.q, own...,
                            rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
         hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { err = std::string("policy_lstm_kernel: ") + hipGetErrorString(e); return HK_ERR_HIP; }
+        if (e != hipSuccess) { err = std::string(name) + ": " + hipGetErrorString(e); return HK_ERR_HIP; }
         return HK_OK;
+    };
+    const int H = pd.q.hidden;
+    if (pd.lq.m > 0) {
+        // a policy with memory: lstm_mem [rows][2m] (nullptr: the policy's own buffer), read and rewritten in place
+        float* mem = lstm_mem ? lstm_mem : pd.lq.mem;
+        if (!mem) { err = "policy_lstm_kernel: no memory buffer"; return HK_ERR_INVALID; }
+        return launch(policy_lstm_kernel, "policy_lstm_kernel", policy_lstm_lds_bytes(pd.q, pd.lq), pd.lq, mem);
     }
-    const bool bf = pd.prec == HK_POLICY_PREC_BF16;
-    if (bf && !pd.wbf) { err = "policy_mlp_bf16_kernel: the policy has no bf16 weights"; return HK_ERR_INVALID; }
-    const size_t lds = bf ? policy_bf16_lds_bytes(pd.q) : policy_lds_bytes(pd.q);
-    // the kernels use ~68 KB of dynamic LDS, above the 64 KB default: raise the limit once per DEVICE (the attribute belongs to
-    // the device's code object; a second handle on another device needs it too).  Guarded by a mutex: handles of different
-    // devices may be driven from different host threads.
-    {
-        static std::mutex mu;
-        static unsigned long long done_mask = 0ull;     // bit d: device d has the attribute
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev < 0 || dev >= 64 || !((done_mask >> dev) & 1ull)) {
-            (void)hipFuncSetAttribute((const void*)policy_mlp_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)policy_mlp_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)policy_mlp_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)policy_mlp_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)policy_mlp_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (dev >= 0 && dev < 64) done_mask |= 1ull << dev;
-        }
+    if (pd.prec == HK_POLICY_PREC_BF16) {
+        if (!pd.wbf) { err = "policy_mlp_bf16_kernel: the policy has no bf16 weights"; return HK_ERR_INVALID; }
+        return launch(H <= 128 ? policy_mlp_bf16_kernel<false> : policy_mlp_bf16_kernel<true>, "policy_mlp_bf16_kernel", policy_bf16_lds_bytes(pd.q), pd.bq);
     }
-    const dim3 grid((rows + PM_TILE - 1) / PM_TILE), block(PM_THREADS);
-    if (bf && pd.q.hidden <= 128)
-        hipLaunchKernelGGL(policy_mlp_bf16_kernel<false>, grid, block, lds, stream, pd.q, pd.bq, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
-    else if (bf)
-        hipLaunchKernelGGL(policy_mlp_bf16_kernel<true>, grid, block, lds, stream, pd.q, pd.bq, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
-    else if (pd.q.hidden <= 128)
-        hipLaunchKernelGGL(policy_mlp_kernel<0>, grid, block, lds, stream, pd.q, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
-    else if (pd.q.hidden == 256)
-        hipLaunchKernelGGL(policy_mlp_kernel<1>, grid, block, lds, stream, pd.q, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
-    else
-        hipLaunchKernelGGL(policy_mlp_kernel<2>, grid, block, lds, stream, pd.q, rows, src, w, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { err = std::string(bf ? "policy_mlp_bf16_kernel: " : "policy_mlp_kernel: ") + hipGetErrorString(e); return HK_ERR_HIP; }
-    return HK_OK;
+    return launch(H <= 128 ? policy_mlp_kernel<0> : H == 256 ? policy_mlp_kernel<1> : policy_mlp_kernel<2>, "policy_mlp_kernel", policy_lds_bytes(pd.q));
 }
 
 }  // namespace hk

@@ -151,9 +151,7 @@ __global__ __launch_bounds__(PM_THREADS, 4) void policy_mlp_bf16_kernel(PolicyPa
                         const int kl = 2 * (lane + 64 * m) + e, k = kb + kl;
                         soff[m][e] = -1; mean[m][e] = 0.0f; sdev[m][e] = 1.0f;
                         if (kl < kc && k < K0) {
-                            const int i = k / Q.obs_dim, kk = k - i * Q.obs_dim;
-                            int slot = w + 1 + i; slot -= (slot >= Q.stack) ? Q.stack : 0;
-                            soff[m][e] = slot * Q.obs_dim + kk;
+                            soff[m][e] = pm_ring_offset(Q, w, k);
                             if (Q.normalize) { mean[m][e] = Q.mean[k]; sdev[m][e] = Q.std[k]; }
                         }
                     }

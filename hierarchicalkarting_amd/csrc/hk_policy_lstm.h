@@ -62,7 +62,7 @@ inline size_t policy_lstm_lds_bytes(const PolicyParams& q, const PolicyLstm& l)
     return ((size_t)(kmax + l.m) * PM_LD + (size_t)PM_MAX_OUT * PM_TILE) * sizeof(float);
 }
 
-// The first decision of an episode starts from zero memory: the `stale` test of policy_stack_kernel, word for word, on the epoch word that
+// The first decision of an episode starts from zero memory: the `stale` test of policy_stack_kernel (pm_episode_word) on the epoch word that
 // kernel rewrites — so this one is issued BEFORE it, and FIRST == 1 if and only if the memory read is zero.  One wave per (env, slot).
 // rec_mem (an open rollout's MEMORY row, [E][A][mem_max]; nullptr: not recording): the memory the decision reads, after the clear.
 __global__ __launch_bounds__(256) void policy_memory_kernel(PolicyParams Q, PolicyLstm L, int E, int A, const hk_env_state* envs_by_slot, const int* slot_of,
@@ -73,8 +73,7 @@ __global__ __launch_bounds__(256) void policy_memory_kernel(PolicyParams Q, Poli
     if (pair >= E * Q.n_slots) return;                         // (wave-uniform)
     const int env = pair / Q.n_slots, j = pair % Q.n_slots;
     const hk_env_state* es = &envs_by_slot[slot_of[env]];
-    const int ep = es->episodes_done + es->initial_started;
-    const bool stale = Q.epoch[pair] != ep;
+    const bool stale = Q.epoch[pair] != pm_episode_word(*es);
     float* mem = L.mem + (size_t)pair * 2 * L.m;
     float* rec = rec_mem ? rec_mem + ((size_t)env * A + Q.slots[j]) * mem_max : nullptr;
     for (int k = t; k < 2 * L.m; k += 64) {
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(256) void policy_epoch_current_kernel(PolicyParams 
     const int pair = blockIdx.x * blockDim.x + threadIdx.x;
     if (pair >= E * Q.n_slots) return;
     const hk_env_state* es = &envs_by_slot[slot_of[pair / Q.n_slots]];
-    Q.epoch[pair] = es->episodes_done + es->initial_started;
+    Q.epoch[pair] = pm_episode_word(*es);
 }
 
 // hk_rollout_close: NEXT_MEMORY [E][A][mem_max] = the memory after the last completed row, zero where that row's interval ended an episode
@@ -154,7 +153,8 @@ __device__ __forceinline__ void pl_gemm4(f32x16 (&z)[4], const float* ap, const 
 
 // Arguments as policy_mlp_kernel's, plus L (the cell's weights) and mem [rows][2m], read and rewritten in place (the policy's own buffer in
 // hk_step, a staging copy in hk_policy_forward_mem).  The trunk below is policy_mlp_kernel<2>'s text (the per-wave mixed form serves every
-// hidden size here: at one workgroup per CU the register budget that made MODE 0 / 1 worth having is not binding); change both together.
+// hidden size here: at one workgroup per CU the register budget that made MODE 0 / 1 worth having is not binding).  A trunk function shared
+// with that kernel was measured: this kernel came out 1.3 - 1.7 % slower per launch, so it keeps its copy; change both together.
 __global__ __launch_bounds__(PM_THREADS, 2) void policy_lstm_kernel(PolicyParams Q, PolicyLstm L, float* mem, int rows, const float* src, int w,
                                                                      unsigned long long decision, int env_id_base, int A,
                                                                      float* mu_out, float* logit_out, float* act_steer, int* act_branch, PolicyRec rec)
@@ -205,9 +205,7 @@ __global__ __launch_bounds__(PM_THREADS, 2) void policy_lstm_kernel(PolicyParams
                     const int kl = lane + 64 * mm, k = kb + kl;
                     soff[mm] = -1; mean[mm] = 0.0f; sdev[mm] = 1.0f;
                     if (kl < kc) {
-                        const int i = k / Q.obs_dim, kk = k - i * Q.obs_dim;
-                        int slot = w + 1 + i; slot -= (slot >= Q.stack) ? Q.stack : 0;
-                        soff[mm] = slot * Q.obs_dim + kk;
+                        soff[mm] = pm_ring_offset(Q, w, k);
                         if (Q.normalize) { mean[mm] = Q.mean[k]; sdev[mm] = Q.std[k]; }
                     }
                 }
@@ -314,14 +312,10 @@ inline int policy_lstm_upload(PolicyDevice& pd, const hk_policy_lstm_desc* l, in
 {
     const int m = l->memory_size / 2, N = 4 * m, H = pd.q.hidden;
     std::vector<float> host;
-    auto lay = [&](const float* W, int K) {              // -> offset of [K / 8][2][N] x {4 k-steps}: element (g, half, col)[j] = W[col][8 g + 2 j + half]
+    auto lay = [&](const float* W, int K) {              // -> offset of W [N][K] in the group-major form (pm_wq_fill)
         const size_t off = host.size();
         host.resize(off + (size_t)K * N);
-        float* wq = host.data() + off;
-        for (int g = 0; g < K / 8; g++)
-            for (int hf = 0; hf < 2; hf++)
-                for (int col = 0; col < N; col++)
-                    for (int j = 0; j < 4; j++) wq[(((size_t)g * 2 + hf) * N + col) * 4 + j] = W[(size_t)col * K + 8 * g + 2 * j + hf];
+        pm_wq_fill(host.data() + off, W, N, K);
         return off;
     };
     const size_t o_ih = lay(l->W_ih, H), o_hh = lay(l->W_hh, m), o_b = host.size();

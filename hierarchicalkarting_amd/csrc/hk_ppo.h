@@ -701,11 +701,8 @@ __global__ __launch_bounds__(256) void ppo_publish_kernel(PolicyParams Q, PpoNet
             const size_t w = idx - net.oW[l];
             const int jj = (int)(w / K), k = (int)(w % K);
             mv(Q.Wt[l], (size_t)k * H + jj);
-            if (TO_POLICY && k < (K / 8) * 8) {      // the group-major copy: element (g, half, col)[q4] = W[8 g + 2 q4 + half][col]
-                const int g = k >> 3, r = k & 7, q4 = r >> 1, hf = r & 1;
-                float* wq = const_cast<float*>(reinterpret_cast<const float*>(Q.Wq[l]));
-                wq[(((size_t)g * 2 + hf) * H + jj) * 4 + q4] = flat[idx];
-            }
+            if (TO_POLICY && k < (K / 8) * 8)        // the group-major copy: k = 8 g + 2 j + half
+                const_cast<float*>(reinterpret_cast<const float*>(Q.Wq[l]))[pm_wq_index(k >> 3, k & 1, jj, (k & 7) >> 1, H)] = flat[idx];
             return;
         }
         if (idx >= net.ob[l] && idx < net.ob[l] + H) { mv(Q.b[l], idx - net.ob[l]); return; }

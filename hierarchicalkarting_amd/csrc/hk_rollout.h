@@ -15,11 +15,10 @@ __global__ __launch_bounds__(256) void rollout_ring0_kernel(PolicyParams Q, int 
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)E * Q.n_slots * per) return;
     const size_t pair = idx / per, r = idx % per;
-    const int i = (int)(r / Q.obs_dim), k = (int)(r % Q.obs_dim);
     const int env = (int)(pair / Q.n_slots), j = (int)(pair % Q.n_slots);
-    int slot = w0 + 1 + i; slot -= slot >= Q.stack ? Q.stack : 0;
-    const size_t dst = (((size_t)env * A + Q.slots[j]) * (smax - 1) + (smax - Q.stack) + i) * Q.obs_dim + k;
-    ring0[dst] = Q.ring[pair * Q.in_dim + (size_t)slot * Q.obs_dim + k];
+    // (entry i = r / obs_dim of the s - 1 lands on entry smax - s + i of the row's smax - 1)
+    const size_t dst = (((size_t)env * A + Q.slots[j]) * (smax - 1) + (smax - Q.stack)) * Q.obs_dim + r;
+    ring0[dst] = Q.ring[pair * Q.in_dim + pm_ring_offset(Q, w0, (int)r)];
 }
 
 // the episode counters an interval's DONE is measured against (env words by lane-group slot, as policy_stack_kernel reads them)

@@ -34,8 +34,9 @@ def _refused(fn, *a):
     return e.value.code, str(e.value)
 
 
-# (H, m): one unit block with idle waves; the reference shape; two column blocks per wave with two unit blocks; an odd block count; the largest
-@pytest.mark.parametrize("H,m", [(32, 32), (128, 128), (256, 64), (96, 96), (256, 128)])
+# (H, m): one unit block with idle waves; the reference shape; two column blocks per wave with two unit blocks; an odd block count; the largest;
+# five column blocks, so that waves 0 and 1 hold a second block of another column (pm_gemm<true, false>), and six waves idle through the cell
+@pytest.mark.parametrize("H,m", [(32, 32), (128, 128), (256, 64), (96, 96), (256, 128), (160, 32)])
 def test_forward_against_the_twin(H, m):
     g = _env(2)
     D = g.obs_dim

@@ -16,7 +16,7 @@ ap.add_argument("--repeats", type=int, default=5, help="windows per precision (>
 a = ap.parse_args()
 E = a.envs
 out = {}
-for (A, stack, hidden, layers) in ((4, 4, 256, 3), (4, 4, 128, 3), (4, 8, 256, 3)):
+for (A, stack, hidden, layers) in ((4, 4, 256, 3), (4, 4, 128, 3), (4, 8, 256, 3), (4, 4, 192, 3)):      # (hidden 192: policy_mlp_kernel<2>)
     env = hk.RacingEnv(hk.make_config(E, A, low_mode=[_lib.HK_LOW_RL] * A, jitter_seed=1))
     in_dim = env.obs_dim * stack
     pol = Policy.random(in_dim, hidden, layers, stack=stack, seed=1)
