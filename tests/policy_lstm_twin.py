@@ -1,6 +1,6 @@
 """Build and run the host twin of policy_lstm_kernel (tests/policy_lstm_host_check.cpp): the bit reference of a recurrent actor.
-Test infrastructure shared by tests/test_policy_lstm_cpu.py and tests/test_policy_lstm_gpu.py; nothing is preloaded, the sanitizers are
-linked into the stand-alone program."""
+Test infrastructure shared by tests/test_policy_lstm_cpu.py, tests/test_policy_lstm_gpu.py and tests/test_policy_lstm_fields_gpu.py; nothing is
+preloaded, the sanitizers are linked into the stand-alone program."""
 import os
 import subprocess
 import tempfile
@@ -56,6 +56,45 @@ def step(pol, obs, mem=None, sanitize=True):
         a = np.fromfile(cout, "<f4")
     assert a.size == rows * (1 + nb + mm)
     return a[:rows].copy(), a[rows:rows * (1 + nb)].reshape(rows, nb).copy(), a[rows * (1 + nb):].reshape(rows, mm).copy()
+
+
+# ---- what the GPU tests of both files share (tests/test_policy_lstm_gpu.py, tests/test_policy_lstm_fields_gpu.py)
+def rl_env(E, A=2, **kw):
+    """a reset field of E envs with A karts, every kart LowMode RL"""
+    import hierarchicalkarting_amd as hk
+    from hierarchicalkarting_amd import _lib
+    kw.setdefault("low_mode", [_lib.HK_LOW_RL] * A)
+    g = hk.RacingEnv(hk.make_config(E, A, **kw))
+    g.reset()
+    return g
+
+
+def lstm_actor(D, seed=3, **kw):
+    """the reference shape on a stack of 4 observations of width D: -> 128 x 3 -> m = 128"""
+    from hierarchicalkarting_amd.policy import Policy
+    return Policy.random(D * 4, 128, 3, 3, seed=seed, memory_size=256, **kw)
+
+
+def replay(ro, pol, slots, tag):
+    """every row of a recorded rollout from its stacked input and MEMORY[t] alone, through the twin; -> the twin's memory after the last row"""
+    from hierarchicalkarting_amd.rollout import stacked_inputs
+    from parity import assert_bits_equal
+    R, E = ro["obs"].shape[:2]
+    S, mm = len(slots), pol.memory_size
+    x = stacked_inputs(ro, slots, pol.stack)
+    first = ro["first"][:, :, slots]
+    mem = ro["memory"][:, :, slots, :mm]
+    zero = ~mem.any(axis=-1)
+    assert np.array_equal(zero, first == 1), tag            # zero exactly where the episode starts
+    out = None
+    for t in range(R):
+        mu, lg, out = step(pol, x[t].reshape(E * S, -1), mem[t].reshape(E * S, mm))
+        assert_bits_equal(ro["mu"][t][:, slots].reshape(-1), mu, (tag, t, "mu"))
+        assert_bits_equal(ro["logits"][t][:, slots, :pol.n_branch].reshape(E * S, -1), lg, (tag, t, "logits"))
+        if t + 1 < R:
+            keep = first[t + 1].reshape(-1) == 0
+            assert_bits_equal(mem[t + 1].reshape(E * S, mm)[keep], out[keep], (tag, t, "memory chain"))
+    return out.reshape(E, S, mm)
 
 
 def sweep():

@@ -15,12 +15,16 @@ import policy_lstm_twin as TW                             # noqa: E402
 from hierarchicalkarting_amd.policy import Policy         # noqa: E402
 
 # (in_dim, stack, hidden, n_layers, m, rows, seed): the K remainder modulo 8, an odd block count, the reference shape on a 4-agent input
-CASES = [(52, 4, 32, 1, 32, 24, 11), (52, 4, 96, 2, 96, 24, 12), (312, 4, 128, 3, 128, 24, 13), (216, 4, 256, 2, 64, 24, 14)]
-# Measured here on CASES: the twin's largest absolute deviation from the float64 restatement over mu, logits and the memory is 1.135e-06
-# (the H = 256 case; 4.3e-07 .. 7.9e-07 on the others: fp32 chains of up to 312 terms and the <= 2 ulp exp); the tolerance is 4 x that,
-# rounded up to one significant digit.  The mutated restatements are 0.89 .. 2.6 away: five orders of magnitude more.
-TWIN_MAX_DEV = 1.135e-06
-TWIN_TOL = 5e-06
+CASES = [(52, 4, 32, 1, 32, 24, 11), (52, 4, 96, 2, 96, 24, 12), (312, 4, 128, 3, 128, 24, 13), (216, 4, 256, 2, 64, 24, 14),
+         # the widths tests/test_policy_lstm_fields_gpu.py holds the kernel to: three layer-0 chunks at the largest footprint, a chunked input
+         # with remainder 2 modulo 8 on an odd block count, one observation of a 4-kart field
+         (624, 8, 256, 2, 128, 24, 15), (546, 7, 96, 2, 96, 24, 16), (78, 1, 160, 1, 32, 24, 17)]
+# Measured here on CASES: the twin's largest absolute deviation from the float64 restatement over mu, logits and the memory is 1.672e-06
+# (the 624 -> 256 x 2 -> m = 128 case: fp32 chains of up to 624 terms and the <= 2 ulp exp; 1.135e-06 on 216 -> 256 x 2 -> m = 64, which set
+# the figure before the 624-, 546- and 78-input cases joined, and 4.3e-07 .. 1.0e-06 on the others); the tolerance is 4 x that, rounded up to
+# one significant digit.  The mutated restatements are 0.76 .. 2.6 away: five orders of magnitude more.
+TWIN_MAX_DEV = 1.672e-06
+TWIN_TOL = 7e-06
 # the largest absolute error of hk_sigmoidf / hk_tanhf_fast over every finite fp32 input against libm in double, measured once
 # (8.931e-08 and 8.994e-08, recorded rounded up)
 SIGMOID_MAX_ERR = 8.94e-08
@@ -45,7 +49,7 @@ def _dev(a, b):
 
 
 def test_twin_matches_float64_restatement(twin_results):
-    """the twin (fp32, the kernel's arithmetic) against the float64 restatement: measured deviation 1.135e-06, asserted 5e-06 (4 x, rounded
+    """the twin (fp32, the kernel's arithmetic) against the float64 restatement: measured deviation 1.672e-06, asserted 7e-06 (4 x, rounded
     up); each of the four mutated restatements must miss that tolerance by at least 100 x, which proves the inputs discriminate"""
     worst = 0.0
     for c, (pol, obs, mem) in twin_results:

@@ -21,11 +21,7 @@ RL, P = _lib.HK_LOW_RL, 2
 
 
 def _env(E, **kw):
-    import hierarchicalkarting_amd as hk
-    kw.setdefault("low_mode", [RL, RL])
-    g = hk.RacingEnv(hk.make_config(E, 2, **kw))
-    g.reset()
-    return g
+    return TW.rl_env(E, 2, **kw)
 
 
 def _refused(fn, *a):
@@ -70,28 +66,7 @@ def test_forward_against_the_twin(H, m):
     assert not g.policy_memory(0).any()              # the tap leaves the policy's own memory alone
 
 
-def _replay(ro, pol, slots, tag):
-    """every row of a recorded rollout from its stacked input and MEMORY[t] alone, through the twin; -> the twin's memory after the last row"""
-    R, E = ro["obs"].shape[:2]
-    S, mm = len(slots), pol.memory_size
-    x = stacked_inputs(ro, slots, pol.stack)
-    first = ro["first"][:, :, slots]
-    mem = ro["memory"][:, :, slots, :mm]
-    zero = ~mem.any(axis=-1)
-    assert np.array_equal(zero, first == 1), tag            # zero exactly where the episode starts
-    out = None
-    for t in range(R):
-        mu, lg, out = TW.step(pol, x[t].reshape(E * S, -1), mem[t].reshape(E * S, mm))
-        assert_bits_equal(ro["mu"][t][:, slots].reshape(-1), mu, (tag, t, "mu"))
-        assert_bits_equal(ro["logits"][t][:, slots, :pol.n_branch].reshape(E * S, -1), lg, (tag, t, "logits"))
-        if t + 1 < R:
-            keep = first[t + 1].reshape(-1) == 0
-            assert_bits_equal(mem[t + 1].reshape(E * S, mm)[keep], out[keep], (tag, t, "memory chain"))
-    return out.reshape(E, S, mm)
-
-
-def _lstm_actor(D, seed=3, **kw):
-    return Policy.random(D * 4, 128, 3, 3, seed=seed, memory_size=256, **kw)
+_replay, _lstm_actor = TW.replay, TW.lstm_actor          # (shared with tests/test_policy_lstm_fields_gpu.py)
 
 
 def _stagger(g):
