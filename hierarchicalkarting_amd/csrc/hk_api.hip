@@ -322,6 +322,61 @@ int fail(hk_context* h, int code, const std::string& msg)
             return fail((h), HK_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// The hk:: launch functions report through h->err only: the thread-local copy (hk_last_error(NULL)) follows here.  Functions that
+// went through fail() have set both and are returned from with a plain `if (int rc = ...) return rc;`.
+inline int hand_off(hk_context* h, int rc)
+{
+    if (rc) g_last_error = h->err;
+    return rc;
+}
+#define HK_TRY(h, call) do { if (int rc_ = hand_off((h), (call))) return rc_; } while (0)
+
+// p freed (when it holds anything) and cleared
+template <typename T> hipError_t dev_free(T*& p) { T* old = p; p = nullptr; return old ? hipFree(old) : hipSuccess; }
+
+// a device buffer that only grows: below `need` units it is freed and allocated anew at `bytes` (nothing is kept); a failure leaves *p nullptr, *have 0
+template <typename T, typename N>
+int dev_grow(hk_context* h, T** p, N* have, N need, size_t bytes)
+{
+    if (need <= *have) return HK_OK;
+    *have = 0;
+    HK_HIP(h, dev_free(*p));
+    HK_HIP(h, hipMalloc((void**)p, bytes));
+    *have = need;
+    return HK_OK;
+}
+
+inline unsigned nblk(size_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
+inline size_t n_karts(const hk_context* h) { return (size_t)h->cfg.num_envs * h->cfg.num_agents; }
+
+// Settling the handle before an entry point touches its state, written once: what the calls before left open is brought to the handle's
+// stream, in this order.  `what` names the steps; each SETTLE_* constant below is one present use (DESIGN.md §2 "Settling the handle" has the table and says
+// which rows are inherited rather than judged).  The mask is a constant at every call site, so each use folds to its own steps.
+enum : unsigned {
+    SETTLE_ENV = 1,          // the handle must have an environment
+    SETTLE_SPLIT = 2,        // join the open parts of a split call (split_join)
+    SETTLE_LAZY = 4,         // finish the laggards of a lazily completed call (finish_ticks)
+    SETTLE_OPT = 8,          // look at the guard of optimistic fixed-round calls (verify_optimistic)
+    SETTLE_MCTS = 16,        // join the planner's side stream (mcts_join_async)
+    SETTLE_ALL = SETTLE_ENV | SETTLE_SPLIT | SETTLE_LAZY | SETTLE_OPT | SETTLE_MCTS,      // every entry point that reads or writes the state
+    SETTLE_STEP = SETTLE_ENV | SETTLE_LAZY,                   // hk_step: the calls of a host that steps tick by tick follow each other without a look at the device
+    SETTLE_SYNC = SETTLE_SPLIT | SETTLE_LAZY | SETTLE_OPT,    // hk_synchronize
+    SETTLE_PROF = SETTLE_SPLIT | SETTLE_LAZY,                 // hk_prof_reset, hk_prof_read
+    SETTLE_STREAM = SETTLE_SPLIT,                             // hk_stream, which asks only while parts are open
+};
+__attribute__((always_inline)) inline int settle(hk_context* h, unsigned what)
+{
+    if (!h) return fail(nullptr, HK_ERR_INVALID, "NULL handle");
+    if ((what & SETTLE_ENV) && !h->env_ready) return fail(h, HK_ERR_INVALID, "handle has no environment");
+    HK_HIP(h, hipSetDevice(h->device));
+    if ((what & SETTLE_SPLIT) && split_join(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)");
+    if ((what & SETTLE_LAZY) && h->step_pending) { int rc = finish_ticks(h); if (rc) return rc; }
+    if ((what & SETTLE_OPT) && h->opt_pending) { int rc = verify_optimistic(h); if (rc) return rc; }
+    if ((what & SETTLE_MCTS) && mcts_join_async(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (planner side stream)");
+    return HK_OK;
+}
+#define HK_NEED_ENV(h) do { if (int rc_ = settle((h), SETTLE_ALL)) return rc_; } while (0)
+
 int device_count()
 {
     int n = 0;
@@ -455,18 +510,14 @@ void hk_destroy(hk_handle h)
 void* hk_stream(hk_handle h)
 {
     if (!h) return nullptr;
-    if (h->split_open && (hipSetDevice(h->device) != hipSuccess || split_join(h))) return nullptr;       // (work the caller puts on the stream must come behind both parts)
+    if (h->split_open && settle(h, SETTLE_STREAM)) return nullptr;       // (work the caller puts on the stream must come behind both parts)
     return (void*)h->stream;
 }
 const char* hk_schedule_info(hk_handle h) { return h ? h->sched.c_str() : ""; }
 
 int hk_synchronize(hk_handle h)
 {
-    if (!h) return HK_ERR_INVALID;
-    HK_HIP(h, hipSetDevice(h->device));
-    if (split_join(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)");
-    if (h->step_pending) { int rc = finish_ticks(h); if (rc) return rc; }
-    if (h->opt_pending) { int rc = verify_optimistic(h); if (rc) return rc; }
+    if (int rc = settle(h, SETTLE_SYNC)) return rc;
     HK_HIP(h, hipStreamSynchronize(h->stream));
     return HK_OK;
 }
@@ -511,12 +562,7 @@ int hk_lq_solve_batch(hk_handle h, int batch, int N, const double* A, const doub
     const size_t n = 4 * (size_t)N, b = (size_t)batch;
     const size_t szA = b * N * 16, szB = b * N * 8, szQ = b * N * n * n, szq = b * N * n, szR = b * N * 4, szx = b * n, szu = b * 2;
     const size_t total = (szA + szB + szQ + szq + szR + szx + szu) * sizeof(double);
-    if (total > h->lq_scratch_bytes) {
-        if (h->lq_scratch) HK_HIP(h, hipFree(h->lq_scratch));
-        h->lq_scratch = nullptr; h->lq_scratch_bytes = 0;
-        HK_HIP(h, hipMalloc(&h->lq_scratch, total));
-        h->lq_scratch_bytes = total;
-    }
+    if (int rc = dev_grow(h, &h->lq_scratch, &h->lq_scratch_bytes, total, total)) return rc;
     double* d = (double*)h->lq_scratch;
     double *dA = d, *dB = dA + szA, *dQ = dB + szB, *dq = dQ + szQ, *dR = dq + szq, *dx = dR + szR, *du = dx + szx;
     HK_HIP(h, hipMemcpyAsync(dA, A, szA * 8, hipMemcpyHostToDevice, h->stream));
@@ -537,38 +583,18 @@ int hk_lq_solve_batch(hk_handle h, int batch, int N, const double* A, const doub
 }
 
 // ------------------------------------------------------------------ environment
-#define HK_NEED_ENV(h)                                                                     \
-    do {                                                                                   \
-        if (!(h)) return fail(nullptr, HK_ERR_INVALID, "NULL handle");                     \
-        if (!(h)->env_ready) return fail((h), HK_ERR_INVALID, "handle has no environment"); \
-        HK_HIP((h), hipSetDevice((h)->device));                                            \
-        if (split_join(h)) return fail((h), HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)"); \
-        if ((h)->step_pending) { int rc_ = finish_ticks(h); if (rc_) return rc_; }         \
-        if ((h)->opt_pending) { int rc_ = verify_optimistic(h); if (rc_) return rc_; }     \
-        if (mcts_join_async(h)) return fail((h), HK_ERR_HIP, "hipStreamWaitEvent (planner side stream)"); \
-    } while (0)
-// hk_step itself: the calls of a host that steps tick by tick follow each other without a look at the device
-#define HK_NEED_ENV_STEP(h)                                                                \
-    do {                                                                                   \
-        if (!(h)) return fail(nullptr, HK_ERR_INVALID, "NULL handle");                     \
-        if (!(h)->env_ready) return fail((h), HK_ERR_INVALID, "handle has no environment"); \
-        HK_HIP((h), hipSetDevice((h)->device));                                            \
-        if ((h)->step_pending) { int rc_ = finish_ticks(h); if (rc_) return rc_; }         \
-    } while (0)
-
 int hk_reset(hk_handle h, const int32_t* env_ids, int n, int experiment_num)
 {
     HK_NEED_ENV(h);
     if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_reset: refused while a rollout is open (hk_rollout_close first)");
     h->ep.moved = true;                         // (the episode statistics' carry ends here: hk.h "SELF-PLAY" CARRY)
-    int rc = hk::env_reset(h->dev, h->cfg, env_ids, n, experiment_num, h->stream, h->err);
-    if (rc) { g_last_error = h->err; return rc; }
+    HK_TRY(h, hk::env_reset(h->dev, h->cfg, env_ids, n, experiment_num, h->stream, h->err));
     h->lock_tick = env_ids ? -1 : 0;            // every env stands on episode step 0 again / some do: the field is no longer known to be in lock-step
     // the agents were reset: their observation stacks start from zeros again (env_reset left the ids in dev.env_ids)
     for (int p = 0; p < h->n_policies; p++) {
         const int cnt = (env_ids ? n : h->cfg.num_envs) * h->policy[p].q.n_slots;
         if (cnt <= 0) continue;
-        hipLaunchKernelGGL(hk::policy_invalidate_kernel, dim3((cnt + 255) / 256), dim3(256), 0, h->stream, h->policy[p].q,
+        hipLaunchKernelGGL(hk::policy_invalidate_kernel, dim3(nblk(cnt)), dim3(256), 0, h->stream, h->policy[p].q,
                            env_ids ? h->dev.env_ids : nullptr, env_ids ? n : h->cfg.num_envs);
         HK_HIP(h, hipGetLastError());
     }
@@ -579,7 +605,7 @@ int hk_set_actions(hk_handle h, const float* steer, const int32_t* branch)
 {
     HK_NEED_ENV(h);
     if (!steer || !branch) return fail(h, HK_ERR_INVALID, "hk_set_actions: NULL pointer");
-    const size_t cnt = (size_t)h->cfg.num_envs * h->cfg.num_agents;
+    const size_t cnt = n_karts(h);
     HK_HIP(h, hipMemcpyAsync(h->dev.act_steer, steer, cnt * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HK_HIP(h, hipMemcpyAsync(h->dev.act_branch, branch, cnt * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HK_HIP(h, hipStreamSynchronize(h->stream));
@@ -606,8 +632,7 @@ static int issue_rounds(hk_handle h, int rounds)
         // the rounds issued below count toward the next one, so the count restarts at `rounds`.  (One part: counted round by round, below.)
         if ((d.rounds_since_regroup += rounds) >= d.regroup_rounds) {
             if (split_join(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)");
-            int rcg = hk::env_launch_regroup(d, h->cfg, h->stream, h->err);
-            if (rcg) { g_last_error = h->err; return rcg; }
+            HK_TRY(h, hk::env_launch_regroup(d, h->cfg, h->stream, h->err));
             d.rounds_since_regroup = rounds;
         }
     }
@@ -675,16 +700,14 @@ static int issue_rounds(hk_handle h, int rounds)
     // a folded split call (nothing follows its rounds on the handle's stream: no guard kernel, no report) leaves its parts open for the next one; any other
     // call, and any error, joins
     if (K > 1 && (!h->fold_split || rc) && split_join(h) && !rc) rc = fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)");
-    if (rc) g_last_error = h->err;
-    return rc;
+    return hand_off(h, rc);
 }
 
 // guard kernel + (lazy mode) its report on the way to pinned host memory
 static int issue_check(hk_handle h, bool lazy)
 {
     if (lazy) HK_HIP(h, hipMemsetAsync(h->dev.status + 1, 0, 2 * sizeof(int), h->stream));
-    int rc = hk::env_launch_check(h->dev, h->cfg, lazy, h->stream, h->err);
-    if (rc) { g_last_error = h->err; return rc; }
+    HK_TRY(h, hk::env_launch_check(h->dev, h->cfg, lazy, h->stream, h->err));
     if (lazy) HK_HIP(h, hipMemcpyAsync(h->done_host, h->dev.status + 1, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (lazy) return meter_copy(h, true);          // (the caller synchronises before it looks at either)
     return HK_OK;
@@ -700,18 +723,15 @@ static int finish_ticks(hk_handle h)
         HK_HIP(h, hipStreamSynchronize(h->stream));
         const int maxleft = h->done_host[0], waiting = h->done_host[1];
         if (maxleft <= 0 && !waiting) { h->step_pending = false; break; }
-        int rc = hk::env_launch_regroup(h->dev, h->cfg, h->stream, h->err);      // the laggards into the first lane groups
-        if (rc) { g_last_error = h->err; return rc; }
+        HK_TRY(h, hk::env_launch_regroup(h->dev, h->cfg, h->stream, h->err));      // the laggards into the first lane groups
         packed = true;
         h->split = false;                // ... which all lie in the first half: the tail runs as one batch on one stream (part 0: its round parity goes on)
         // Rounds for the slowest env if it met no further multi-player game (+ 1), not for the worst case (a round per cadence): the
         // batch ends with a look at the device anyway, and two thirds of the worst-case rounds used to find nothing to do (94 of 141 in
         // the headline's 3 072-tick call, ~18 us each).  An env that does park on every solve tick still gets a third of its ticks per batch.
         const int cap = std::max(h->dev.P.run_cap, hk::solve_cadence(h->cfg));
-        rc = issue_rounds(h, (maxleft + cap - 1) / cap + 1);
-        if (rc) return rc;
-        rc = issue_check(h, true);
-        if (rc) return rc;
+        if (int rc = issue_rounds(h, (maxleft + cap - 1) / cap + 1)) return rc;
+        if (int rc = issue_check(h, true)) return rc;
     }
     if (h->step_pending) { h->step_pending = false; return fail(h, HK_ERR_HIP, "hk_step: an env did not complete its ticks (internal scheduling error)"); }
     // The laggards — the envs that met the most multi-player games, and will meet the next ones — now sit side by side in the first lane groups.  With the
@@ -955,8 +975,7 @@ static int launch_side_search(hk_handle h, int side_waves)
     HK_HIP(h, hipEventRecord(h->ev_mcts_go, h->stream));
     HK_HIP(h, hipStreamWaitEvent(h->mcts_stream, h->ev_mcts_go, 0));
     h->dev.mcts_side_waves = side_waves;
-    const int rc = hk::env_flush_mcts_on(h->dev, h->stream, h->mcts_stream, h->err);
-    if (rc) { g_last_error = h->err; return rc; }
+    HK_TRY(h, hk::env_flush_mcts_on(h->dev, h->stream, h->mcts_stream, h->err));
     HK_HIP(h, hipEventRecord(h->ev_mcts_done, h->mcts_stream));
     return HK_OK;
 }
@@ -1012,8 +1031,7 @@ static int step_pause(hk_handle h, const CallPlan& p)
             rc = issue_rounds(h, stretch_rounds);
         }
         if (rc) return rc;
-        rc = hk::env_flush_mcts(h->dev, h->stream, h->err);
-        if (rc) { g_last_error = h->err; return rc; }
+        HK_TRY(h, hk::env_flush_mcts(h->dev, h->stream, h->err));
         if ((rc = issue_check(h, true))) return rc;
         HK_HIP(h, hipStreamSynchronize(h->stream));
         maxleft = h->done_host[0];
@@ -1039,8 +1057,7 @@ static int step_rounds(hk_handle h, const CallPlan& p)
     if (rc) return rc;
     if (p.rounds > main_rounds) {
         if (!p.planner && h->n_policies == 0) {
-            rc = hk::env_launch_regroup(h->dev, h->cfg, h->stream, h->err);
-            if (rc) { g_last_error = h->err; return rc; }
+            HK_TRY(h, hk::env_launch_regroup(h->dev, h->cfg, h->stream, h->err));
         }
         if ((rc = issue_rounds(h, p.rounds - main_rounds))) return rc;
     }
@@ -1053,8 +1070,7 @@ static int step_rounds(hk_handle h, const CallPlan& p)
     }
     if (p.planner && !p.short_call) {
         // searches requested in the last rounds of a long call run before it returns
-        rc = hk::env_flush_mcts(h->dev, h->stream, h->err);
-        if (rc) { g_last_error = h->err; return rc; }
+        HK_TRY(h, hk::env_flush_mcts(h->dev, h->stream, h->err));
     }
     if (!p.fold && (rc = issue_check(h, p.lazy))) return rc;
     h->step_pending = p.lazy;
@@ -1082,12 +1098,11 @@ static int step_ticks(hk_handle h, int n_ticks)
     int rc;
     if (p.planner && h->dev.mcts_ticks > 0 && (!p.short_call || h->dev.mcts_ticks + n_ticks > p.defer || p.t_req >= 0)) {
         if (mcts_join_async(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (planner side stream)");
-        rc = hk::env_flush_mcts(h->dev, h->stream, h->err);
-        if (rc) { g_last_error = h->err; return rc; }
+        HK_TRY(h, hk::env_flush_mcts(h->dev, h->stream, h->err));
     }
     apply_plan(h, p);
     if (p.fold) h->arm_ticks = n_ticks;
-    else if ((rc = hk::env_launch_arm(h->dev, h->cfg, n_ticks, h->stream, h->err))) { g_last_error = h->err; return rc; }
+    else HK_TRY(h, hk::env_launch_arm(h->dev, h->cfg, n_ticks, h->stream, h->err));
     return p.pause ? step_pause(h, p) : step_rounds(h, p);
 }
 
@@ -1126,8 +1141,7 @@ static int policy_decide(hk_handle h)
     uint32_t need = 0;                      // only the agents some attached actor drives are observed here
     for (int p = 0; p < h->n_policies; p++)
         for (int j = 0; j < h->policy[p].q.n_slots; j++) need |= 1u << h->policy[p].q.slots[j];
-    int rc = hk::env_launch_observe(h->dev, h->cfg, need, h->stream, h->err);
-    if (rc) { g_last_error = h->err; return rc; }
+    HK_TRY(h, hk::env_launch_observe(h->dev, h->cfg, need, h->stream, h->err));
     const unsigned long long decision = (unsigned long long)(h->academy_step / h->decision_period);
     const int E = h->cfg.num_envs, A = h->cfg.num_agents;
     // an open rollout: this decision writes row t (hk_rollout.h)
@@ -1159,9 +1173,8 @@ static int policy_decide(hk_handle h)
         const int pairs = E * pd.q.n_slots;
         const int w = (int)(decision % (unsigned long long)pd.q.stack);
         hipEvent_t e = h->prof.begin(h->stream);
-        rc = hk::policy_launch_mlp(pd, pairs, pd.q.ring, w, decision, h->cfg.env_id_base, A, nullptr, nullptr, h->dev.act_steer,
-                                   h->dev.act_branch, rec, h->stream, h->err);
-        if (rc) { g_last_error = h->err; return rc; }
+        HK_TRY(h, hk::policy_launch_mlp(pd, pairs, pd.q.ring, w, decision, h->cfg.env_id_base, A, nullptr, nullptr, h->dev.act_steer,
+                                   h->dev.act_branch, rec, h->stream, h->err));
         h->prof.end(3, e, h->stream);
     }
     if (ro.open) h->ro.started += 1;
@@ -1174,7 +1187,7 @@ static int rollout_close_interval(hk_handle h, int t)
     const auto& ro = h->ro;
     const int E = h->cfg.num_envs, A = h->cfg.num_agents;
     const size_t ea = (size_t)E * A;
-    hipLaunchKernelGGL(hk::rollout_close_kernel, dim3((unsigned)((ea + 255) / 256)), dim3(256), 0, h->stream, h->dev.agents, h->dev.envs, h->dev.slot_of, E, A,
+    hipLaunchKernelGGL(hk::rollout_close_kernel, dim3(nblk(ea)), dim3(256), 0, h->stream, h->dev.agents, h->dev.envs, h->dev.slot_of, E, A,
                        ro.driven, ro.row<float>(HK_RO_REWARD, t, ea), ro.row<float>(HK_RO_GROUP_REWARD, t, ea), ro.row<int>(HK_RO_DONE, t, (size_t)E),
                        ro.at<int>(HK_RO_FIELDS), ro.at<int>(HK_RO_FIELDS + 1));
     HK_HIP(h, hipGetLastError());
@@ -1184,7 +1197,7 @@ static int rollout_close_interval(hk_handle h, int t)
 
 int hk_step(hk_handle h, int n_ticks)
 {
-    HK_NEED_ENV_STEP(h);
+    if (int rc = settle(h, SETTLE_STEP)) return rc;
     if (n_ticks < 0) return fail(h, HK_ERR_INVALID, "hk_step: n_ticks < 0");
     if (n_ticks == 0) return HK_OK;
     h->ep.moved = true;                         // (cleared by hk_rollout_close: a step after it ends the episode statistics' carry)
@@ -1209,7 +1222,7 @@ int hk_step(hk_handle h, int n_ticks)
         if (chunk > left) chunk = left;
         const bool rec_term = h->ro.open && h->dev.rw.sec_time;       // the terminal rewards of this chunk's resets go to the open row
         if (rec_term) {
-            const size_t ea = (size_t)h->cfg.num_envs * h->cfg.num_agents;
+            const size_t ea = n_karts(h);
             h->dev.rw.term_step = h->ro.row<float>(HK_RO_TERM_REWARD, h->ro.started - 1, ea);
             h->dev.rw.term_group = h->ro.row<float>(HK_RO_TERM_GROUP_REWARD, h->ro.started - 1, ea);
         }
@@ -1233,9 +1246,8 @@ int hk_policy_attach_lstm(hk_handle h, const hk_policy_desc* desc, const hk_poli
 {
     HK_NEED_ENV(h);
     if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_policy_attach: refused while a rollout is open (hk_rollout_close first)");
-    int rc = hk::policy_validate(desc, h->err);
-    if (!rc && lstm) rc = hk::policy_lstm_validate(lstm, h->err);
-    if (rc) { g_last_error = h->err; return rc; }
+    HK_TRY(h, hk::policy_validate(desc, h->err));
+    if (lstm) HK_TRY(h, hk::policy_lstm_validate(lstm, h->err));
     if (!agent_slots || n_slots < 1 || n_slots > h->cfg.num_agents || decision_period < 1)
         return fail(h, HK_ERR_INVALID, "hk_policy_attach: bad agent_slots / decision_period");
     if (h->n_policies >= HK_MAX_POLICIES) return fail(h, HK_ERR_INVALID, "hk_policy_attach: HK_MAX_POLICIES policies already attached");
@@ -1254,9 +1266,9 @@ int hk_policy_attach_lstm(hk_handle h, const hk_policy_desc* desc, const hk_poli
         return fail(h, HK_ERR_INVALID, "hk_policy_attach: decision_period differs from the policies already attached (DecisionRequester is per handle)");
     h->ep.moved = true;
     const int idx = h->n_policies;
-    rc = hk::policy_upload(h->policy[idx], desc, idx, hk_obs_dim(h), agent_slots, n_slots, h->cfg.num_envs, h->stream, h->err, lstm ? lstm->memory_size / 2 : 0);
+    int rc = hk::policy_upload(h->policy[idx], desc, idx, hk_obs_dim(h), agent_slots, n_slots, h->cfg.num_envs, h->stream, h->err, lstm ? lstm->memory_size / 2 : 0);
     if (!rc && lstm) rc = hk::policy_lstm_upload(h->policy[idx], lstm, h->cfg.num_envs, h->stream, h->err);
-    if (rc) { hk::policy_free(h->policy[idx]); g_last_error = h->err; return rc; }
+    if (rc) { hk::policy_free(h->policy[idx]); return hand_off(h, rc); }
     h->decision_period = decision_period;
     h->n_policies = idx + 1;
     return idx;
@@ -1276,12 +1288,7 @@ static int policy_forward(hk_handle h, const char* fn, bool with_mem, int policy
     if (!obs || !mu || !logits) return fail(h, HK_ERR_INVALID, f + ": NULL pointer");
     const size_t n_in = (size_t)rows * pd.q.in_dim, n_lg = (size_t)rows * pd.q.n_branch, n_mem = (size_t)rows * 2 * pd.lq.m;
     const size_t total = (n_in + rows + n_lg + n_mem) * sizeof(float);
-    if (total > h->pol_scratch_bytes) {
-        if (h->pol_scratch) HK_HIP(h, hipFree(h->pol_scratch));
-        h->pol_scratch = nullptr; h->pol_scratch_bytes = 0;
-        HK_HIP(h, hipMalloc(&h->pol_scratch, total));
-        h->pol_scratch_bytes = total;
-    }
+    if (int rc = dev_grow(h, &h->pol_scratch, &h->pol_scratch_bytes, total, total)) return rc;
     float* d_in = (float*)h->pol_scratch;
     float* d_mu = d_in + n_in;
     float* d_lg = d_mu + rows;
@@ -1290,8 +1297,7 @@ static int policy_forward(hk_handle h, const char* fn, bool with_mem, int policy
     if (n_mem && mem_in) HK_HIP(h, hipMemcpyAsync(d_mem, mem_in, n_mem * sizeof(float), hipMemcpyHostToDevice, h->stream));
     else if (n_mem) HK_HIP(h, hipMemsetAsync(d_mem, 0, n_mem * sizeof(float), h->stream));
     hipEvent_t e = h->prof.begin(h->stream);
-    int rc = hk::policy_launch_mlp(pd, rows, d_in, pd.q.stack - 1, 0ull, 0, h->cfg.num_agents, d_mu, d_lg, nullptr, nullptr, hk::PolicyRec{}, h->stream, h->err, d_mem);
-    if (rc) { g_last_error = h->err; return rc; }
+    HK_TRY(h, hk::policy_launch_mlp(pd, rows, d_in, pd.q.stack - 1, 0ull, 0, h->cfg.num_agents, d_mu, d_lg, nullptr, nullptr, hk::PolicyRec{}, h->stream, h->err, d_mem));
     h->prof.end(3, e, h->stream);
     HK_HIP(h, hipMemcpyAsync(mu, d_mu, rows * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipMemcpyAsync(logits, d_lg, n_lg * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -1332,7 +1338,7 @@ static int policy_memory_copy(hk_handle h, const char* fn, bool set, int policy,
     if (set) {
         h->ep.moved = true;
         HK_HIP(h, hipMemcpyAsync(pd.lq.mem, mem, bytes, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(hk::policy_epoch_current_kernel, dim3((pairs + 255) / 256), dim3(256), 0, h->stream, pd.q, h->cfg.num_envs, h->dev.envs, h->dev.slot_of);
+        hipLaunchKernelGGL(hk::policy_epoch_current_kernel, dim3(nblk(pairs)), dim3(256), 0, h->stream, pd.q, h->cfg.num_envs, h->dev.envs, h->dev.slot_of);
         HK_HIP(h, hipGetLastError());
     } else {
         HK_HIP(h, hipMemcpyAsync(mem, pd.lq.mem, bytes, hipMemcpyDeviceToHost, h->stream));
@@ -1382,7 +1388,7 @@ int hk_get_actions(hk_handle h, float* steer, int32_t* branch)
 {
     HK_NEED_ENV(h);
     if (!steer || !branch) return fail(h, HK_ERR_INVALID, "hk_get_actions: NULL pointer");
-    const size_t cnt = (size_t)h->cfg.num_envs * h->cfg.num_agents;
+    const size_t cnt = n_karts(h);
     HK_HIP(h, hipMemcpyAsync(steer, h->dev.act_steer, cnt * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipMemcpyAsync(branch, h->dev.act_branch, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipStreamSynchronize(h->stream));
@@ -1417,12 +1423,8 @@ int hk_rollout_begin(hk_handle h, int rows)
     elems[HK_RO_FIELDS] = E; elems[HK_RO_FIELDS + 1] = 1;
     size_t off[HK_RO_FIELDS + 2], total = 0;
     for (int f = 0; f < HK_RO_FIELDS + 2; f++) { off[f] = total; total += (elems[f] * 4 + 255) & ~(size_t)255; }
-    if (total > ro.bytes) {
-        if (ro.buf) HK_HIP(h, hipFree(ro.buf));
-        ro.buf = nullptr; ro.bytes = 0; ro.R = 0;
-        HK_HIP(h, hipMalloc(&ro.buf, total));
-        ro.bytes = total;
-    }
+    if (total > ro.bytes) ro.R = 0;          // (a grown buffer holds no rollout until this one's rows are set below)
+    if (int rc = dev_grow(h, &ro.buf, &ro.bytes, total, total)) return rc;
     std::memcpy(ro.off, off, sizeof(off));
     ro.R = rows; ro.started = 0; ro.rows = 0; ro.obs_dim = D; ro.nbm = nbm; ro.smax = smax; ro.mem_max = mem_max; ro.driven = driven;
     {   // the episode statistics' carry (hk.h "SELF-PLAY" CARRY): what the statistics of the rollout just closed wrote becomes this one's carry-in
@@ -1441,11 +1443,11 @@ int hk_rollout_begin(hk_handle h, int rows)
         const hk::PolicyParams& q = h->policy[p].q;
         const size_t n = (size_t)E * q.n_slots * (q.stack - 1) * D;
         if (n == 0) continue;
-        hipLaunchKernelGGL(hk::rollout_ring0_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, q, E, A, (int)(decision % (unsigned long long)q.stack),
+        hipLaunchKernelGGL(hk::rollout_ring0_kernel, dim3(nblk(n)), dim3(256), 0, h->stream, q, E, A, (int)(decision % (unsigned long long)q.stack),
                            smax, ro.at<float>(HK_RO_RING0));
         HK_HIP(h, hipGetLastError());
     }
-    hipLaunchKernelGGL(hk::rollout_epoch_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, h->dev.envs, h->dev.slot_of, E, ro.at<int>(HK_RO_FIELDS));
+    hipLaunchKernelGGL(hk::rollout_epoch_kernel, dim3(nblk(E)), dim3(256), 0, h->stream, h->dev.envs, h->dev.slot_of, E, ro.at<int>(HK_RO_FIELDS));
     HK_HIP(h, hipGetLastError());
     ro.open = true;
     return HK_OK;
@@ -1464,15 +1466,14 @@ int hk_rollout_close(hk_handle h)
     if (!ro.open) return fail(h, HK_ERR_INVALID, "hk_rollout_close: no rollout is open");
     if (h->academy_step % h->decision_period != 0) return fail(h, HK_ERR_INVALID, "hk_rollout_close: mid-interval (step to the next decision first)");
     // the bootstrap observation: the observe kernel without its reward events, so that the next decision raises them as usual
-    int rc = hk::env_launch_observe_quiet(h->dev, h->cfg, ro.driven, ro.at<float>(HK_RO_NEXT_OBS), h->stream, h->err);
-    if (rc) { g_last_error = h->err; return rc; }
+    HK_TRY(h, hk::env_launch_observe_quiet(h->dev, h->cfg, ro.driven, ro.at<float>(HK_RO_NEXT_OBS), h->stream, h->err));
     // the bootstrap memory of the recurrent actors: what the last completed row left, zero where its interval ended the episode
     for (int p = 0; p < h->n_policies && ro.mem_max > 0; p++) {
         const hk::PolicyDevice& pd = h->policy[p];
         if (pd.lq.m == 0) continue;
         const int E = h->cfg.num_envs;
         const size_t n = (size_t)E * pd.q.n_slots * 2 * pd.lq.m;
-        hipLaunchKernelGGL(hk::rollout_next_memory_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, pd.q, pd.lq, E, h->cfg.num_agents,
+        hipLaunchKernelGGL(hk::rollout_next_memory_kernel, dim3(nblk(n)), dim3(256), 0, h->stream, pd.q, pd.lq, E, h->cfg.num_agents,
                            ro.rows > 0 ? ro.row<int>(HK_RO_DONE, ro.rows - 1, (size_t)E) : nullptr, ro.at<float>(HK_RO_NEXT_MEMORY), ro.mem_max);
         HK_HIP(h, hipGetLastError());
     }
@@ -1563,26 +1564,11 @@ size_t ppo_ws_layout(const hk_context::Ppo& t, int M, PpoWs* w)
 // the workspace as it is allocated now
 PpoWs ppo_ws(const hk_context::Ppo& t) { PpoWs w; ppo_ws_layout(t, t.cap, &w); return w; }
 
-// p freed (when it holds anything) and cleared
-template <typename T> hipError_t ppo_free(T*& p) { T* old = p; p = nullptr; return old ? hipFree(old) : hipSuccess; }
-
-// a device buffer that only grows: below `need` units it is freed and allocated anew at `bytes` (nothing is kept); a failure leaves *p nullptr, *have 0
-template <typename T, typename N>
-int ppo_grow(hk_handle h, T** p, N* have, N need, size_t bytes)
-{
-    if (need <= *have) return HK_OK;
-    *have = 0;
-    HK_HIP(h, ppo_free(*p));
-    HK_HIP(h, hipMalloc((void**)p, bytes));
-    *have = need;
-    return HK_OK;
-}
-
 int ppo_ensure_ws(hk_handle h, hk_context::Ppo& t, int M, PpoWs& w)
 {
     if (M > t.cap) {
         t.last_m = 0;
-        if (int rc = ppo_grow(h, &t.ws, &t.cap, M, ppo_ws_layout(t, M, nullptr))) return rc;
+        if (int rc = dev_grow(h, &t.ws, &t.cap, M, ppo_ws_layout(t, M, nullptr))) return rc;
     }
     w = ppo_ws(t);
     return HK_OK;
@@ -1613,8 +1599,6 @@ hk::PpoRows ppo_rows(hk_handle h, const hk_context::Ppo& t)
     for (int j = 0; j < HK_MAX_AGENTS; j++) P.slots[j] = q.slots[j];
     return P;
 }
-
-inline unsigned nblk(size_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
 
 void ppo_gather(hipStream_t s, const hk::PpoRows& P, const int* ids, int m, int boot, PpoMat X0, int* valid)
 {
@@ -1805,7 +1789,7 @@ int poca_ensure_ws(hk_handle h, hk_context::Ppo& t, int G, PocaWs& w)
 {
     if (G > t.pcap) {
         t.last_mg = 0;
-        if (int rc = ppo_grow(h, &t.pws, &t.pcap, G, poca_ws_layout(t, h->policy[t.policy].q.n_slots, G, nullptr))) return rc;
+        if (int rc = dev_grow(h, &t.pws, &t.pcap, G, poca_ws_layout(t, h->policy[t.policy].q.n_slots, G, nullptr))) return rc;
         w = poca_ws(h, t);
         const float c[2] = {1.0f, 0.0f};
         HK_HIP(h, hipMemcpyAsync(w.consts, c, sizeof(c), hipMemcpyHostToDevice, h->stream));
@@ -2145,8 +2129,8 @@ int ppo_create(hk_handle h, const char* fn, int policy, bool have_critic, const 
 
 static void ppo_release(hk_context::Ppo& t)
 {
-    (void)ppo_free(t.param); (void)ppo_free(t.rowbuf); (void)ppo_free(t.ws); (void)ppo_free(t.shadow); (void)ppo_free(t.norm);
-    (void)ppo_free(t.norm_part); (void)ppo_free(t.clip); (void)ppo_free(t.prow); (void)ppo_free(t.pws);
+    (void)dev_free(t.param); (void)dev_free(t.rowbuf); (void)dev_free(t.ws); (void)dev_free(t.shadow); (void)dev_free(t.norm);
+    (void)dev_free(t.norm_part); (void)dev_free(t.clip); (void)dev_free(t.prow); (void)dev_free(t.pws);
     t = hk_context::Ppo{};
 }
 
@@ -2189,8 +2173,8 @@ int hk_ppo_advantages(hk_handle h, int trainer)
     // yet" after this call while a PPO trainer's keep what its last minibatch wrote (the PPO chunks write none of mb_mu / mb_logits / mb_v).
     const hk::PpoRows P = ppo_rows(h, t);
     const size_t n = (size_t)P.R * P.E * P.S, nbt = (size_t)P.E * P.S;
-    if ((rc = ppo_grow(h, &t.rowbuf, &t.rowbuf_n, 3 * n + nbt + n, (3 * n + nbt + n) * sizeof(float)))) return rc;
-    if (t.poca && (rc = ppo_grow(h, &t.prow, &t.prow_n, 2 * n, 2 * n * sizeof(float)))) return rc;
+    if ((rc = dev_grow(h, &t.rowbuf, &t.rowbuf_n, 3 * n + nbt + n, (3 * n + nbt + n) * sizeof(float)))) return rc;
+    if (t.poca && (rc = dev_grow(h, &t.prow, &t.prow_n, 2 * n, 2 * n * sizeof(float)))) return rc;
     t.n = (int)n;
     if ((rc = t.poca ? poca_values_and_returns(h, t, P) : ppo_values_and_gae(h, t, P))) return rc;
     if (t.cfg.normalize_advantages) hipLaunchKernelGGL(hk::ppo_adv_norm_kernel, dim3(1), dim3(1024), 0, h->stream, ppo_rowbuf(h, t).adv, t.n);
@@ -2443,7 +2427,7 @@ int hk_ppo_normalizer_update(hk_handle h, int trainer)
     ipw = (ipw + trip - 1) / trip * trip;
     if (items + ipw > 0x7FFFFFFFLL) return fail(h, HK_ERR_UNSUPPORTED, "hk_ppo_normalizer_update: more than 2^31 recorded observations");
     const int nwg = (int)((items + ipw - 1) / ipw);
-    if ((rc = ppo_grow(h, &t.norm_part, &t.norm_part_wg, nwg, (size_t)nwg * W * sizeof(double)))) return rc;
+    if ((rc = dev_grow(h, &t.norm_part, &t.norm_part_wg, nwg, (size_t)nwg * W * sizeof(double)))) return rc;
     hipStream_t s = h->stream;
     double* sums = t.norm + 2 * (size_t)K;
     const dim3 grid(nwg, (P.stack + hk::PPO_NORM_Q - 1) / hk::PPO_NORM_Q, (P.D + 255) / 256);
@@ -2470,7 +2454,7 @@ int hk_ppo_set_precision(hk_handle h, int trainer, int precision)
     // the workspace is laid out per precision: drop it once the stream is done with it (the next minibatch allocates the other layout)
     HK_HIP(h, hipStreamSynchronize(h->stream));
     t.cap = 0; t.last_m = 0;
-    HK_HIP(h, ppo_free(t.ws));
+    HK_HIP(h, dev_free(t.ws));
     if (precision == HK_PPO_PREC_BF16 && !t.shadow) {
         t.shadow_pad = (8 - t.actor.count % 8) % 8;
         HK_HIP(h, hipMalloc(&t.shadow, (t.P + t.shadow_pad) * sizeof(uint16_t)));
@@ -2838,9 +2822,8 @@ int hk_get_observations(hk_handle h, float* obs)
 {
     HK_NEED_ENV(h);
     if (!obs) return fail(h, HK_ERR_INVALID, "hk_get_observations: NULL pointer");
-    int rc = hk::env_launch_observe(h->dev, h->cfg, 0xFFFFFFFFu, h->stream, h->err);
-    if (rc) { g_last_error = h->err; return rc; }
-    const size_t cnt = (size_t)h->cfg.num_envs * h->cfg.num_agents * hk_obs_dim(h);
+    HK_TRY(h, hk::env_launch_observe(h->dev, h->cfg, 0xFFFFFFFFu, h->stream, h->err));
+    const size_t cnt = n_karts(h) * hk_obs_dim(h);
     HK_HIP(h, hipMemcpyAsync(obs, h->dev.obs, cnt * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipStreamSynchronize(h->stream));
     return HK_OK;
@@ -2867,9 +2850,9 @@ int hk_get_agent_state(hk_handle h, hk_agent_state* out)
     HK_NEED_ENV(h);
     if (!out) return fail(h, HK_ERR_INVALID, "NULL pointer");
     { int rc = check_device_status(h); if (rc) return rc; }
-    const size_t cnt = (size_t)h->cfg.num_envs * h->cfg.num_agents;
+    const size_t cnt = n_karts(h);
     // the per-tick fields live in the hot tiles (hk_env_device.h): gather them into the records first
-    { int rc = hk::ga_ops(h->dev).launch_hot_gather(h->dev, h->cfg, h->stream, h->err); if (rc) { g_last_error = h->err; return rc; } }
+    HK_TRY(h, hk::ga_ops(h->dev).launch_hot_gather(h->dev, h->cfg, h->stream, h->err));
     HK_HIP(h, hipMemcpyAsync(out, h->dev.agents, cnt * sizeof(hk_agent_state), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipStreamSynchronize(h->stream));
     return HK_OK;
@@ -2880,7 +2863,7 @@ int hk_set_agent_state(hk_handle h, const hk_agent_state* in)
     HK_NEED_ENV(h);
     if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_set_agent_state: refused while a rollout is open (hk_rollout_close first)");
     if (!in) return fail(h, HK_ERR_INVALID, "NULL pointer");
-    const size_t cnt = (size_t)h->cfg.num_envs * h->cfg.num_agents;
+    const size_t cnt = n_karts(h);
     // the device divides by the section count with a multiply-shift that is exact for 0 <= x < 2^32 / L (hk_env_device.h div_L): a rewound or
     // hand-built record outside that range would index the track tables with garbage
     {
@@ -2892,8 +2875,8 @@ int hk_set_agent_state(hk_handle h, const hk_agent_state* in)
     h->dev.P.hold_dedupe = 0;          // the host moves karts by hand: a held kart is no longer guaranteed to be where its last solve saw it
     h->ep.moved = true;
     HK_HIP(h, hipMemcpyAsync(h->dev.agents, in, cnt * sizeof(hk_agent_state), hipMemcpyHostToDevice, h->stream));
-    { int rc = hk::ga_ops(h->dev).launch_hot_scatter(h->dev, h->cfg, h->stream, h->err); if (rc) { g_last_error = h->err; return rc; } }
-    { int rc = hk::env_mcts_invalidate(h->dev, h->cfg, h->stream, h->err); if (rc) { g_last_error = h->err; return rc; } }   // plans were rewritten
+    HK_TRY(h, hk::ga_ops(h->dev).launch_hot_scatter(h->dev, h->cfg, h->stream, h->err));
+    HK_TRY(h, hk::env_mcts_invalidate(h->dev, h->cfg, h->stream, h->err));   // plans were rewritten
     HK_HIP(h, hipStreamSynchronize(h->stream));
     return HK_OK;
 }
@@ -2903,7 +2886,7 @@ int hk_get_env_state(hk_handle h, hk_env_state* out)
     HK_NEED_ENV(h);
     if (!out) return fail(h, HK_ERR_INVALID, "NULL pointer");
     { int rc = check_device_status(h); if (rc) return rc; }
-    { int rc = hk::ga_ops(h->dev).launch_envs_gather(h->dev, h->cfg, h->stream, h->err); if (rc) { g_last_error = h->err; return rc; } }
+    HK_TRY(h, hk::ga_ops(h->dev).launch_envs_gather(h->dev, h->cfg, h->stream, h->err));
     HK_HIP(h, hipMemcpyAsync(out, h->dev.envs_stage, (size_t)h->cfg.num_envs * sizeof(hk_env_state), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipStreamSynchronize(h->stream));
     return HK_OK;
@@ -2918,7 +2901,7 @@ int hk_set_env_state(hk_handle h, const hk_env_state* in)
     h->lock_tick = -1;                 // (the host wrote episode steps)
     h->ep.moved = true;
     HK_HIP(h, hipMemcpyAsync(h->dev.envs_stage, in, (size_t)h->cfg.num_envs * sizeof(hk_env_state), hipMemcpyHostToDevice, h->stream));
-    { int rc = hk::ga_ops(h->dev).launch_envs_scatter(h->dev, h->cfg, h->stream, h->err); if (rc) { g_last_error = h->err; return rc; } }   // (progress words sanitized on the way)
+    HK_TRY(h, hk::ga_ops(h->dev).launch_envs_scatter(h->dev, h->cfg, h->stream, h->err));   // (progress words sanitized on the way)
     HK_HIP(h, hipStreamSynchronize(h->stream));
     return HK_OK;
 }
@@ -2927,7 +2910,7 @@ int hk_get_episode_results(hk_handle h, hk_episode_result* out)
 {
     HK_NEED_ENV(h);
     if (!out) return fail(h, HK_ERR_INVALID, "NULL pointer");
-    const size_t cnt = (size_t)h->cfg.num_envs * h->cfg.num_agents;
+    const size_t cnt = n_karts(h);
     HK_HIP(h, hipMemcpyAsync(out, h->dev.results, cnt * sizeof(hk_episode_result), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipStreamSynchronize(h->stream));
     return HK_OK;
@@ -2950,12 +2933,29 @@ int hk_comm_init(hk_handle h, int world_size, int rank, const void* id)
     HK_NEED_ENV(h);
     if (!id || world_size < 1 || rank < 0 || rank >= world_size) return fail(h, HK_ERR_INVALID, "hk_comm_init: bad world_size / rank / id");
     if (h->comm) return fail(h, HK_ERR_INVALID, "hk_comm_init: this handle already has a communicator");
-    if (!g_rccl.load(h->err)) { g_last_error = h->err; return HK_ERR_UNSUPPORTED; }
+    if (!g_rccl.load(h->err)) return hand_off(h, HK_ERR_UNSUPPORTED);
     RcclId rid;
     std::memcpy(rid.internal, id, HK_COMM_ID_BYTES);
     const int rc = g_rccl.CommInitRank(&h->comm, world_size, rid, rank);
     if (rc != 0) { h->comm = nullptr; return fail(h, HK_ERR_HIP, "ncclCommInitRank: " + g_rccl.why(rc)); }
     h->comm_world = world_size; h->comm_rank = rank;
+    return HK_OK;
+}
+
+// The size exchange of both gathers: this rank's word `mine` out, every rank's word (rank order) back in `all`; synchronises the handle's stream.
+// gather_cnt holds the W gathered words and, behind them, this rank's own.
+static int gather_words(hk_handle h, unsigned long long mine, std::vector<unsigned long long>& all)
+{
+    const int W = h->comm_world;
+    const size_t bytes = (size_t)W * sizeof(mine);
+    if (int rc = dev_grow(h, &h->gather_cnt, &h->gather_cnt_bytes, bytes + sizeof(mine), bytes + sizeof(mine))) return rc;
+    unsigned long long* d_cnt = (unsigned long long*)h->gather_cnt;
+    HK_HIP(h, hipMemcpyAsync(d_cnt + W, &mine, sizeof(mine), hipMemcpyHostToDevice, h->stream));
+    const int rc = g_rccl.AllGather(d_cnt + W, d_cnt, sizeof(mine), /*ncclChar*/ 0, h->comm, h->stream);
+    if (rc != 0) return fail(h, HK_ERR_HIP, "ncclAllGather (sizes): " + g_rccl.why(rc));
+    all.resize((size_t)W);
+    HK_HIP(h, hipMemcpyAsync(all.data(), d_cnt, bytes, hipMemcpyDeviceToHost, h->stream));
+    HK_HIP(h, hipStreamSynchronize(h->stream));
     return HK_OK;
 }
 
@@ -2966,24 +2966,11 @@ int hk_gather_results(hk_handle h, hk_episode_result* all)
     if (!h->comm) return fail(h, HK_ERR_INVALID, "hk_gather_results: call hk_comm_init first");
     { int rc = check_device_status(h); if (rc) return rc; }
     const int W = h->comm_world;
-    const size_t local = (size_t)h->cfg.num_envs * h->cfg.num_agents * sizeof(hk_episode_result);
+    const size_t local = n_karts(h) * sizeof(hk_episode_result);
     // Ranks may hold different env counts (a contiguous split of a total that the world size does not divide): exchange the
     // byte counts first (8 bytes per rank), pad every contribution to the largest, gather, and trim on the way to the host.
-    const size_t cnt_bytes = (size_t)W * sizeof(unsigned long long);
-    if (cnt_bytes + sizeof(unsigned long long) > h->gather_cnt_bytes) {
-        if (h->gather_cnt) HK_HIP(h, hipFree(h->gather_cnt));
-        h->gather_cnt = nullptr; h->gather_cnt_bytes = 0;
-        HK_HIP(h, hipMalloc(&h->gather_cnt, cnt_bytes + sizeof(unsigned long long)));
-        h->gather_cnt_bytes = cnt_bytes + sizeof(unsigned long long);
-    }
-    unsigned long long* d_cnt = (unsigned long long*)h->gather_cnt;          // [W] gathered, [W] = this rank's word
-    const unsigned long long mine = (unsigned long long)local;
-    HK_HIP(h, hipMemcpyAsync(d_cnt + W, &mine, sizeof(mine), hipMemcpyHostToDevice, h->stream));
-    int rc = g_rccl.AllGather(d_cnt + W, d_cnt, sizeof(unsigned long long), /*ncclChar*/ 0, h->comm, h->stream);
-    if (rc != 0) return fail(h, HK_ERR_HIP, "ncclAllGather (sizes): " + g_rccl.why(rc));
-    std::vector<unsigned long long> cnt((size_t)W);
-    HK_HIP(h, hipMemcpyAsync(cnt.data(), d_cnt, cnt_bytes, hipMemcpyDeviceToHost, h->stream));
-    HK_HIP(h, hipStreamSynchronize(h->stream));
+    std::vector<unsigned long long> cnt;
+    if (int rc = gather_words(h, (unsigned long long)local, cnt)) return rc;
     size_t per = 0;
     for (int r = 0; r < W; r++) {
         if (cnt[r] % ((size_t)h->cfg.num_agents * sizeof(hk_episode_result)) != 0)
@@ -2991,12 +2978,7 @@ int hk_gather_results(hk_handle h, hk_episode_result* all)
         per = cnt[r] > per ? (size_t)cnt[r] : per;
     }
     const size_t total = per * (size_t)W + per;                              // [W] padded slots + this rank's padded send slot
-    if (total > h->gather_bytes) {
-        if (h->gather_buf) HK_HIP(h, hipFree(h->gather_buf));
-        h->gather_buf = nullptr; h->gather_bytes = 0;
-        HK_HIP(h, hipMalloc(&h->gather_buf, total));
-        h->gather_bytes = total;
-    }
+    if (int rc = dev_grow(h, &h->gather_buf, &h->gather_bytes, total, total)) return rc;
     char* buf = (char*)h->gather_buf;
     const void* send = h->dev.results;
     if (local < per) {                                                       // pad this rank's contribution
@@ -3005,7 +2987,7 @@ int hk_gather_results(hk_handle h, hk_episode_result* all)
         send = buf + per * W;
     }
     // bytes on the wire (ncclChar): the records are plain data, identical layout on every rank
-    rc = g_rccl.AllGather(send, buf, per, /*ncclChar*/ 0, h->comm, h->stream);
+    const int rc = g_rccl.AllGather(send, buf, per, /*ncclChar*/ 0, h->comm, h->stream);
     if (rc != 0) return fail(h, HK_ERR_HIP, "ncclAllGather: " + g_rccl.why(rc));
     char* out = (char*)all;
     for (int r = 0; r < W; r++) {                                            // rank r's rows, trimmed to what it holds
@@ -3022,21 +3004,8 @@ int hk_gather_count(hk_handle h, int64_t* total_envs)
     if (!total_envs) return fail(h, HK_ERR_INVALID, "hk_gather_count: NULL pointer");
     if (!h->comm) return fail(h, HK_ERR_INVALID, "hk_gather_count: call hk_comm_init first");
     const int W = h->comm_world;
-    const size_t cnt_bytes = (size_t)W * sizeof(unsigned long long);
-    if (cnt_bytes + sizeof(unsigned long long) > h->gather_cnt_bytes) {
-        if (h->gather_cnt) HK_HIP(h, hipFree(h->gather_cnt));
-        h->gather_cnt = nullptr; h->gather_cnt_bytes = 0;
-        HK_HIP(h, hipMalloc(&h->gather_cnt, cnt_bytes + sizeof(unsigned long long)));
-        h->gather_cnt_bytes = cnt_bytes + sizeof(unsigned long long);
-    }
-    unsigned long long* d_cnt = (unsigned long long*)h->gather_cnt;
-    const unsigned long long mine = (unsigned long long)h->cfg.num_envs;
-    HK_HIP(h, hipMemcpyAsync(d_cnt + W, &mine, sizeof(mine), hipMemcpyHostToDevice, h->stream));
-    const int rc = g_rccl.AllGather(d_cnt + W, d_cnt, sizeof(unsigned long long), /*ncclChar*/ 0, h->comm, h->stream);
-    if (rc != 0) return fail(h, HK_ERR_HIP, "ncclAllGather (sizes): " + g_rccl.why(rc));
-    std::vector<unsigned long long> cnt((size_t)W);
-    HK_HIP(h, hipMemcpyAsync(cnt.data(), d_cnt, cnt_bytes, hipMemcpyDeviceToHost, h->stream));
-    HK_HIP(h, hipStreamSynchronize(h->stream));
+    std::vector<unsigned long long> cnt;
+    if (int rc = gather_words(h, (unsigned long long)h->cfg.num_envs, cnt)) return rc;
     int64_t t = 0;
     for (int r = 0; r < W; r++) t += (int64_t)cnt[r];
     *total_envs = t;
@@ -3057,9 +3026,9 @@ int hk_get_rewards(hk_handle h, float* reward, float* group_reward)
     if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_get_rewards: refused while a rollout is open (hk_rollout_close first)");
     if (!reward || !group_reward) return fail(h, HK_ERR_INVALID, "NULL pointer");
     { int rc = check_device_status(h); if (rc) return rc; }
-    const size_t cnt = (size_t)h->cfg.num_envs * h->cfg.num_agents;
+    const size_t cnt = n_karts(h);
     float* d_r = h->dev.reward_out;
-    { int rc = hk::ga_ops(h->dev).launch_rewards_read(h->dev, (int)cnt, d_r, d_r + cnt, h->stream, h->err); if (rc) { g_last_error = h->err; return rc; } }
+    HK_TRY(h, hk::ga_ops(h->dev).launch_rewards_read(h->dev, (int)cnt, d_r, d_r + cnt, h->stream, h->err));
     HK_HIP(h, hipMemcpyAsync(reward, d_r, cnt * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipMemcpyAsync(group_reward, d_r + cnt, cnt * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipStreamSynchronize(h->stream));
@@ -3071,11 +3040,10 @@ int hk_get_mcts_state(hk_handle h, hk_mcts_state* out)
     HK_NEED_ENV(h);
     if (!out) return fail(h, HK_ERR_INVALID, "NULL pointer");
     { int rc = check_device_status(h); if (rc) return rc; }
-    const size_t cnt = (size_t)h->cfg.num_envs * h->cfg.num_agents;
+    const size_t cnt = n_karts(h);
     if (!h->dev.mcts.st) { std::memset(out, 0, cnt * sizeof(hk_mcts_state)); return HK_OK; }
     if (h->dev.mcts_ticks > 0) {          // searches deferred by short hk_step calls: `pend` must be there when the host looks
-        int rc = hk::env_flush_mcts(h->dev, h->stream, h->err);
-        if (rc) { g_last_error = h->err; return rc; }
+        HK_TRY(h, hk::env_flush_mcts(h->dev, h->stream, h->err));
     }
     HK_HIP(h, hipMemcpyAsync(out, h->dev.mcts.st, cnt * sizeof(hk_mcts_state), hipMemcpyDeviceToHost, h->stream));
     HK_HIP(h, hipStreamSynchronize(h->stream));
@@ -3098,23 +3066,15 @@ int hk_get_lq_debug(hk_handle h, int env, int ego, hk_lq_debug* out)
 // the handle like every other getter — laggards of a lazily completed call, the completion guard of optimistic short calls, a search launch on the
 // planner's side stream — so that what the pointer shows, once the handle's stream has been synchronised, is the state hk_synchronize would leave.
 // The work is issued on the handle's stream; a pointer taken BEFORE a later hk_step shows that step's results only after the next getter / hk_synchronize.
-static bool settle_for_pointer(hk_handle h)
-{
-    if (!h || !h->env_ready) return false;
-    if (hipSetDevice(h->device) != hipSuccess) return false;
-    if (split_join(h)) return false;
-    if (h->step_pending && finish_ticks(h) != HK_OK) return false;
-    if (h->opt_pending && verify_optimistic(h) != HK_OK) return false;
-    if (mcts_join_async(h)) return false;
-    return true;
-}
+// (a NULL handle or one without an environment leaves the messages alone, as the pointer getters below do)
+static bool settle_for_pointer(hk_handle h) { return h && h->env_ready && settle(h, SETTLE_ALL) == HK_OK; }
 void* hk_device_results_ptr(hk_handle h) { return settle_for_pointer(h) ? (void*)h->dev.results : nullptr; }
 void* hk_device_agents_ptr(hk_handle h)
 {
     // a SNAPSHOT: the per-tick fields are gathered from the hot tiles into the records (asynchronously, on the handle's stream) by this call;
     // after further hk_step calls the pointer has to be requested again
     if (!settle_for_pointer(h)) return nullptr;
-    if (hk::ga_ops(h->dev).launch_hot_gather(h->dev, h->cfg, h->stream, h->err) != HK_OK) { g_last_error = h->err; return nullptr; }
+    if (hand_off(h, hk::ga_ops(h->dev).launch_hot_gather(h->dev, h->cfg, h->stream, h->err)) != HK_OK) return nullptr;
     return (void*)h->dev.agents;
 }
 void* hk_device_obs_ptr(hk_handle h) { return settle_for_pointer(h) ? (void*)h->dev.obs : nullptr; }
@@ -3123,25 +3083,21 @@ void* hk_device_act_branch_ptr(hk_handle h) { return (h && h->env_ready) ? (void
 void* hk_device_reward_ptr(hk_handle h) { return (h && h->env_ready) ? (void*)h->dev.reward_out : nullptr; }
 void* hk_device_group_reward_ptr(hk_handle h)
 {
-    return (h && h->env_ready && h->dev.reward_out) ? (void*)(h->dev.reward_out + (size_t)h->cfg.num_envs * h->cfg.num_agents) : nullptr;
+    return (h && h->env_ready && h->dev.reward_out) ? (void*)(h->dev.reward_out + n_karts(h)) : nullptr;
 }
 
 int hk_observe(hk_handle h)
 {
     HK_NEED_ENV(h);
-    int rc = hk::env_launch_observe(h->dev, h->cfg, 0xFFFFFFFFu, h->stream, h->err);
-    if (rc) g_last_error = h->err;
-    return rc;
+    return hand_off(h, hk::env_launch_observe(h->dev, h->cfg, 0xFFFFFFFFu, h->stream, h->err));
 }
 
 int hk_rewards_device(hk_handle h)
 {
     HK_NEED_ENV(h);
     if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_rewards_device: refused while a rollout is open (hk_rollout_close first)");
-    const size_t cnt = (size_t)h->cfg.num_envs * h->cfg.num_agents;
-    int rc = hk::ga_ops(h->dev).launch_rewards_read(h->dev, (int)cnt, h->dev.reward_out, h->dev.reward_out + cnt, h->stream, h->err);
-    if (rc) g_last_error = h->err;
-    return rc;
+    const size_t cnt = n_karts(h);
+    return hand_off(h, hk::ga_ops(h->dev).launch_rewards_read(h->dev, (int)cnt, h->dev.reward_out, h->dev.reward_out + cnt, h->stream, h->err));
 }
 
 int hk_prof_enable(hk_handle h, int on)
@@ -3154,10 +3110,7 @@ int hk_prof_enable(hk_handle h, int on)
 
 int hk_prof_reset(hk_handle h)
 {
-    if (!h) return HK_ERR_INVALID;
-    HK_HIP(h, hipSetDevice(h->device));
-    if (split_join(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)");
-    if (h->step_pending) { int rc = finish_ticks(h); if (rc) return rc; }
+    if (int rc = settle(h, SETTLE_PROF)) return rc;
     HK_HIP(h, hipStreamSynchronize(h->stream));
     h->prof.fold();
     for (int s = 0; s < HK_PROF_STAGES; s++) { h->prof.ms[s] = 0; h->prof.n[s] = 0; }
@@ -3200,10 +3153,7 @@ int hk_prof_meter(hk_handle h, int64_t* words)
 
 int hk_prof_read(hk_handle h, double* ms, int64_t* launches)
 {
-    if (!h) return HK_ERR_INVALID;
-    HK_HIP(h, hipSetDevice(h->device));
-    if (split_join(h)) return fail(h, HK_ERR_HIP, "hipStreamWaitEvent (the parts of a split call)");
-    if (h->step_pending) { int rc = finish_ticks(h); if (rc) return rc; }
+    if (int rc = settle(h, SETTLE_PROF)) return rc;
     HK_HIP(h, hipStreamSynchronize(h->stream));
     h->prof.fold();
     for (int s = 0; s < HK_PROF_STAGES; s++) {
