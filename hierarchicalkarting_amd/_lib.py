@@ -36,6 +36,7 @@ HK_RO_FIELDS = len(RO_FIELDS)
 # PPO trainer (hk_ppo_field): name -> index;  stats of hk_ppo_minibatch / hk_ppo_update
 PPO_FIELDS = {n: i for i, n in enumerate(("params", "grad", "adam_m", "adam_v", "v_old", "adv", "ret", "mb_mu", "mb_logits", "mb_value", "perm", "shadow",
                                                "norm_mean", "norm_std", "clip"))}
+PPO_RECURRENT_FIELDS = {"mb_memory": 32}      # hk_ppo_recurrent_field: taken by hk_ppo_ptr / hk_ppo_count of a recurrent trainer, outside [0, HK_PPO_FIELDS)
 HK_PPO_FIELDS = len(PPO_FIELDS)
 HK_PPO_STATS = 6
 HK_PPO_PREC_F32, HK_PPO_PREC_BF16 = 0, 1
@@ -187,6 +188,10 @@ class PpoConfig(C.Structure):
                 ("adam_beta2", C.c_float), ("adam_eps", C.c_float), ("seed", C.c_uint32)]
 
 
+class PpoRecurrentDesc(C.Structure):
+    _fields_ = [("sequence_length", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PpoUpdateOpts(C.Structure):
     _fields_ = [("epochs", C.c_int32), ("minibatch", C.c_int32), ("lr", C.c_float), ("eps", C.c_float), ("beta", C.c_float),
                 ("max_grad_norm", C.c_float), ("target_kl", C.c_float), ("reserved", C.c_int32)]
@@ -256,6 +261,7 @@ SYMBOLS = {
     "hk_rollout_close": (C.c_int, [_H]),
     "hk_rollout_ptr": (C.c_void_p, [_H, C.c_int]),
     "hk_ppo_create": (C.c_int, [_H, C.c_int, C.POINTER(PolicyDesc), C.POINTER(PpoConfig)]),
+    "hk_ppo_create_recurrent": (C.c_int, [_H, C.c_int, C.POINTER(PolicyDesc), C.POINTER(PpoConfig), C.POINTER(PpoRecurrentDesc)]),
     "hk_ppo_advantages": (C.c_int, [_H, C.c_int]),
     "hk_ppo_minibatch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, _fp]),
     "hk_ppo_adam": (C.c_int, [_H, C.c_int, C.c_float]),

@@ -16,6 +16,7 @@
 #include "hk_policy.h"
 #include "hk_rollout.h"
 #include "hk_ppo.h"
+#include "hk_ppo_lstm.h"
 #include "hk_poca.h"
 #include "hk_selfplay.h"
 #include <dlfcn.h>
@@ -245,6 +246,12 @@ struct hk_context {
         void* pws = nullptr;
         int pcap = 0, last_mg = 0;
         bool lb_from_update = false;   // hk_poca_stats: the last L_b came from an update's accumulator
+        // a recurrent trainer (hk.h "PPO trainer" RECURRENT; hk_ppo_create_recurrent; nothing of this is touched for the other kinds): seq_len > 0,
+        // the cell and the m-wide heads at lnet's offsets of the actor part (actor.oWmu .. are lnet's), a workspace of its own for rcap rows
+        int seq_len = 0, n_seq = 0;
+        hk::PpoLstmNet lnet;
+        void* rws = nullptr;
+        int rcap = 0, last_ms = 0;
     } ppo[HK_MAX_POLICIES];
     int n_ppo = 0;
     // self-play (hk.h "SELF-PLAY"; hk_selfplay.h); nothing is allocated before the first hk_policy_pool_create / hk_rollout_episode_stats
@@ -1951,10 +1958,120 @@ int ppo_values_and_gae(hk_handle h, hk_context::Ppo& t, const hk::PpoRows& P)
     return HK_OK;
 }
 
+// ---- recurrent training (hk.h "PPO trainer" RECURRENT; device side in hk_ppo_lstm.h).  Everything below is reached only through a
+// trainer made by hk_ppo_create_recurrent.
+
+// the recurrent workspace at a capacity of M = L ms rows (Ppo::rws; sized by the minibatch, never by the rollout)
+struct PpoLstmWs {
+    int *rowids, *first;
+    float *mem0, *bsum, *GZ, *hnew, *mbmem, *hprev, *cprev, *dH, *drec, *dcar, *part;
+};
+
+size_t ppo_lstm_ws_layout(const hk_context::Ppo& t, int M, PpoLstmWs* w)
+{
+    PpoBump a{w ? (char*)t.rws : nullptr};
+    auto fl = [&](size_t count) { return (float*)a.take(count * 4); };
+    const size_t Mz = (size_t)M, mc = (size_t)t.lnet.m;
+    const size_t ms = (Mz + t.seq_len - 1) / t.seq_len;          // sequences at this capacity: M = L ms
+    const int Ha = t.actor.hidden, Hc = t.critic.hidden, in = t.actor.in_dim, nb = t.actor.n_branch;
+    // the largest weight gradient: the cell's 4m x max(H, m), a trunk layer's, or the heads'; a sequence is at least one row, so ms <= M
+    size_t mn = 4 * mc * std::max((size_t)Ha, mc);
+    mn = std::max(mn, (size_t)(1 + nb) * mc);
+    mn = std::max(mn, (size_t)Ha * std::max(in, Ha));
+    mn = std::max(mn, (size_t)Hc * std::max(in, Hc));
+    const size_t nz = (Mz + hk::PPO_KCH - 1) / hk::PPO_KCH;
+    PpoLstmWs d{};
+    d.rowids = (int*)a.take(Mz * 4); d.first = (int*)a.take(Mz * 4);
+    d.mem0 = fl(ms * 2 * mc); d.bsum = fl(4 * mc);
+    d.GZ = fl(Mz * 4 * mc); d.hnew = fl(Mz * mc); d.mbmem = fl(Mz * 2 * mc); d.hprev = fl(Mz * mc); d.cprev = fl(Mz * mc); d.dH = fl(Mz * mc);
+    d.drec = fl(ms * mc); d.dcar = fl(ms * mc);
+    d.part = fl(nz * mn);
+    if (w) *w = d;
+    return a.off;
+}
+
+PpoLstmWs ppo_lstm_ws(const hk_context::Ppo& t) { PpoLstmWs w; ppo_lstm_ws_layout(t, t.rcap, &w); return w; }
+
+// one recurrent minibatch: ms sequence ids -> M = L ms time-major rows; loss, stats, gradient into GRAD
+int ppo_lstm_mb(hk_handle h, hk_context::Ppo& t, const int32_t* sids, int ms, float eps, float beta, bool acc)
+{
+    const int L = t.seq_len, mc = t.lnet.m, N = 4 * mc;
+    if ((long long)L * ms > 0x3FFFFFFF) return fail(h, HK_ERR_INVALID, "hk_ppo_minibatch: m x sequence_length rows do not fit");
+    const int M = L * ms;
+    PpoWs w;
+    int rc = ppo_ensure_ws(h, t, M, w);
+    if (rc) return rc;
+    if (M > t.rcap && (rc = dev_grow(h, &t.rws, &t.rcap, M, ppo_lstm_ws_layout(t, M, nullptr)))) return rc;
+    const PpoLstmWs r = ppo_lstm_ws(t);
+    hipStream_t s = h->stream;
+    const hk::PpoRows P = ppo_rows(h, t);
+    const auto& ro = h->ro;
+    float* prm = t.param;
+    float* grad = t.param + t.P;
+    const hk::PpoNet& na = t.actor;
+    const hk::PpoNet& nc = t.critic;
+    const hk::PpoLstmNet& ln = t.lnet;
+    const int Ha = na.hidden, nb = na.n_branch, La = na.n_layers - 1, Hc = nc.hidden, Lc = nc.n_layers - 1;
+    // rows
+    hipLaunchKernelGGL(hk::ppo_lstm_expand_kernel, dim3(nblk((size_t)M + (size_t)ms * 2 * mc)), dim3(256), 0, s, P, ro.at<float>(HK_RO_MEMORY), ro.mem_max, sids,
+                       ms, L, t.n_seq, mc, r.rowids, r.first, r.mem0);
+    ppo_gather(s, P, r.rowids, M, 0, w.X0, w.valid);
+    hipLaunchKernelGGL(hk::ppo_count_kernel, dim3(1), dim3(256), 0, s, w.valid, M, w.n_valid);
+    // forward: the trunks over all rows, the input projection, then the L steps
+    ppo_trunk_forward(s, t, na, w.X0, M, w.Za, w.Aa);
+    ppo_trunk_forward(s, t, nc, w.X0, M, w.Zc, w.Ac);
+    hipLaunchKernelGGL(hk::ppo_lstm_bsum_kernel, dim3(nblk(N)), dim3(256), 0, s, prm + ln.obih, prm + ln.obhh, N, r.bsum);
+    ppo_product<0>(s, M, N, Ha, w.Aa[La], Ha, true, PpoMat(prm + ln.oWih), Ha, true, r.bsum, PpoMat(r.GZ), N, nullptr, Ha);
+    const dim3 sgrid(nblk(mc, hk::PPO_TN), nblk(ms, hk::PPO_TM));
+    for (int tau = 0; tau < L; tau++)
+        hipLaunchKernelGGL(hk::ppo_lstm_step_kernel, sgrid, dim3(256), 0, s, tau, ms, mc, prm + ln.oWhh, r.mem0, r.first, r.GZ, r.hnew, r.mbmem, r.hprev, r.cprev);
+    // loss on h' (width m), per-row ids
+    {
+        const PpoRowBuf rows = ppo_rowbuf(h, t);
+        hk::PpoLossArgs A{};
+        A.Aa = r.hnew; A.Ac = w.Ac[Lc].f;
+        A.W_mu = prm + ln.oWmu; A.b_mu = prm + ln.obmu; A.log_sigma = prm + ln.ols; A.W_br = prm + ln.oWbr; A.b_br = prm + ln.obbr;
+        A.W_v = prm + nc.oWmu; A.b_v = prm + nc.obmu;
+        A.v_old = rows.v_old; A.adv = rows.adv; A.ret = rows.ret;
+        A.ids = r.rowids; A.valid = w.valid; A.n_valid = w.n_valid; A.m = M; A.n = t.n; A.Ha = mc; A.Hc = Hc; A.nb = nb;
+        A.eps = eps; A.beta = beta;
+        A.dhead = w.dhead; A.dls = w.dls; A.dv = w.dv; A.rowstat = w.rowstat;
+        A.mu_out = w.mb_mu; A.logit_out = w.mb_logits; A.v_out = w.mb_v;
+        hipLaunchKernelGGL(hk::ppo_loss_kernel, dim3(nblk(M)), dim3(256), 0, s, P, A);
+        hipLaunchKernelGGL(hk::ppo_lstm_stats_kernel, dim3(1), dim3(256), 0, s, w.rowstat, M, sids, ms, t.n_seq, w.stats, acc ? w.acc : nullptr);
+    }
+    // backward: the heads (on h'), the L steps in reverse, the cell's weight gradients over all rows at once, then the trunk
+    ppo_wgrad(s, r.part, 1 + nb, mc, M, w.dhead, hk::PM_MAX_OUT, PpoMat(r.hnew), mc, grad + ln.oWmu, grad + ln.oWbr);
+    ppo_colsum(s, w.dhead, M, hk::PM_MAX_OUT, 1, grad + ln.obmu);
+    ppo_colsum(s, w.dhead + 1, M, hk::PM_MAX_OUT, nb, grad + ln.obbr);
+    ppo_colsum(s, w.dls, M, 1, 1, grad + ln.ols);
+    hipLaunchKernelGGL(hk::ppo_lstm_head_back_kernel, dim3(nblk((size_t)M * mc)), dim3(256), 0, s, M, mc, 1 + nb, w.dhead, hk::PM_MAX_OUT, prm + ln.oWmu,
+                       prm + ln.oWbr, r.dH);
+    for (int tau = L - 1; tau >= 0; tau--) {
+        hipLaunchKernelGGL(hk::ppo_lstm_back_kernel, dim3(nblk((size_t)ms * mc)), dim3(256), 0, s, tau, ms, mc, (int)(tau == L - 1), r.first, r.dH, r.drec, r.mbmem,
+                           r.cprev, r.GZ, r.dcar);
+        if (tau > 0)          // the recurrent delta to tau - 1: dG_tau [ms][4m] W_hh [4m][m]
+            ppo_product<0>(s, ms, mc, N, PpoMat(r.GZ + (size_t)tau * ms * N), N, true, PpoMat(prm + ln.oWhh), mc, false, nullptr, PpoMat(r.drec), mc, nullptr, N);
+    }
+    ppo_wgrad(s, r.part, N, Ha, M, PpoMat(r.GZ), N, w.Aa[La], Ha, grad + ln.oWih, nullptr);
+    ppo_wgrad(s, r.part, N, mc, M, PpoMat(r.GZ), N, PpoMat(r.hprev), mc, grad + ln.oWhh, nullptr);
+    ppo_colsum(s, PpoMat(r.GZ), M, N, N, grad + ln.obih);
+    HK_HIP(h, hipMemcpyAsync(grad + ln.obhh, grad + ln.obih, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));      // both biases: the same gradient
+    ppo_product<2>(s, M, Ha, N, PpoMat(r.GZ), N, true, PpoMat(prm + ln.oWih), Ha, false, nullptr, w.d0, Ha, w.Za[La], N);
+    ppo_trunk_backward(s, t, na, r.part, w.X0, M, w.Za, w.Aa, w.d0, w.d1);
+    // critic (feed-forward on the stacked input, as a plain trainer's)
+    ppo_value_head_back(s, t, r.part, M, Hc, w.dv, nc.oWmu, nc.obmu, w.Zc[Lc], w.Ac[Lc], w.d0);
+    ppo_trunk_backward(s, t, nc, r.part, w.X0, M, w.Zc, w.Ac, w.d0, w.d1);
+    HK_HIP(h, hipGetLastError());
+    t.last_m = M; t.last_ms = ms;
+    return HK_OK;
+}
+
 // one minibatch: loss, stats, gradient into GRAD (acc: the update's stats accumulator, or nullptr)
 int ppo_mb(hk_handle h, hk_context::Ppo& t, const int32_t* ids, int m, float eps, float beta, bool acc)
 {
     if (t.poca) return poca_mb(h, t, ids, m, eps, beta, acc);
+    if (t.seq_len) return ppo_lstm_mb(h, t, ids, m, eps, beta, acc);
     PpoWs w;
     int rc = ppo_ensure_ws(h, t, m, w);
     if (rc) return rc;
@@ -2087,13 +2204,16 @@ void ppo_norm_stale(hk_handle h, int policy)
 // hk_ppo_create and hk_ppo_create_poca (fn): the checks both start with, critic_checks() (the entry point's own refusals, in their place in the
 // order), the config, the slot and the actor's layout; pack_critic(t, host) lays the critic out behind the actor and packs its parameters in
 // that order; then PARAMS .. ADAM_V [4][P], zeroed, the critic uploaded and the actor's weights copied from the policy.  -> the trainer's index
+// seq_len > 0: the call is hk_ppo_create_recurrent — the policy must HAVE memory, and the actor part carries the cell and the m-wide heads
 template <typename Checks, typename Pack>
-int ppo_create(hk_handle h, const char* fn, int policy, bool have_critic, const hk_ppo_config* cfg, Checks critic_checks, Pack pack_critic)
+int ppo_create(hk_handle h, const char* fn, int policy, bool have_critic, const hk_ppo_config* cfg, Checks critic_checks, Pack pack_critic, int seq_len = 0)
 {
     const std::string f = std::string(fn) + ": ";
     if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, f + "bad policy index");
     if (h->n_ppo >= HK_MAX_POLICIES) return fail(h, HK_ERR_INVALID, f + "HK_MAX_POLICIES trainers already exist");
-    if (h->policy[policy].lq.m > 0) return fail(h, HK_ERR_UNSUPPORTED, f + "policy: a recurrent actor (recurrent training is out of scope: hk.h \"RECURRENT ACTORS\")");
+    if (!seq_len && h->policy[policy].lq.m > 0)
+        return fail(h, HK_ERR_UNSUPPORTED, f + "policy: a recurrent actor (train it through hk_ppo_create_recurrent: hk.h \"PPO trainer\" RECURRENT)");
+    if (seq_len && h->policy[policy].lq.m == 0) return fail(h, HK_ERR_INVALID, f + "policy: an actor without memory (train it through hk_ppo_create)");
     if (!have_critic) return fail(h, HK_ERR_INVALID, f + "NULL critic");
     const hk::PolicyParams& q = h->policy[policy].q;
     int rc = critic_checks(q);
@@ -2106,6 +2226,18 @@ int ppo_create(hk_handle h, const char* fn, int policy, bool have_critic, const 
     t = hk_context::Ppo{};
     t.policy = policy; t.cfg = d;
     t.actor.layout(q.in_dim, q.hidden, q.n_layers, q.n_branch, 0);
+    hk::PpoNet trunk = t.actor;          // what ppo_publish_kernel moves
+    if (seq_len) {
+        // the trunk as laid out; the cell and the m-wide heads behind it (PpoLstmNet); the actor's head offsets follow
+        hk::PpoLstmNet& ln = t.lnet;
+        ln.layout(q.hidden, h->policy[policy].lq.m, q.n_branch, t.actor.oWmu);
+        t.seq_len = seq_len;
+        t.actor.oWmu = ln.oWmu; t.actor.obmu = ln.obmu; t.actor.ols = ln.ols; t.actor.oWbr = ln.oWbr; t.actor.obbr = ln.obbr;
+        t.actor.count = ln.end;
+        trunk.count = ln.oWih;
+        trunk.n_branch = 0;
+        trunk.oWmu = trunk.obmu = trunk.ols = trunk.oWbr = trunk.obbr = trunk.count;      // (no element of the trunk matches a head)
+    }
     std::vector<float> host;
     pack_critic(t, host);
     t.P = t.actor.count + host.size();
@@ -2113,7 +2245,10 @@ int ppo_create(hk_handle h, const char* fn, int policy, bool have_critic, const 
     if (e == hipSuccess) e = hipMemsetAsync(t.param, 0, 4 * t.P * sizeof(float), h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(t.param + t.actor.count, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(hk::ppo_publish_kernel<false>, dim3(nblk(t.actor.count)), dim3(256), 0, h->stream, q, t.actor, t.param);
+        hipLaunchKernelGGL(hk::ppo_publish_kernel<false>, dim3(nblk(trunk.count)), dim3(256), 0, h->stream, q, trunk, t.param);
+        if (seq_len)
+            hipLaunchKernelGGL(hk::ppo_lstm_publish_kernel<false>, dim3(nblk(t.lnet.end - t.lnet.oWih)), dim3(256), 0, h->stream, q, h->policy[policy].lq,
+                               h->policy[policy].braw, t.lnet, t.param);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -2130,19 +2265,22 @@ int ppo_create(hk_handle h, const char* fn, int policy, bool have_critic, const 
 static void ppo_release(hk_context::Ppo& t)
 {
     (void)dev_free(t.param); (void)dev_free(t.rowbuf); (void)dev_free(t.ws); (void)dev_free(t.shadow); (void)dev_free(t.norm);
-    (void)dev_free(t.norm_part); (void)dev_free(t.clip); (void)dev_free(t.prow); (void)dev_free(t.pws);
+    (void)dev_free(t.norm_part); (void)dev_free(t.clip); (void)dev_free(t.prow); (void)dev_free(t.pws); (void)dev_free(t.rws);
     t = hk_context::Ppo{};
 }
 
-int hk_ppo_create(hk_handle h, int policy, const hk_policy_desc* c, const hk_ppo_config* cfg)
+extern "C++" {
+namespace {
+// hk_ppo_create and hk_ppo_create_recurrent: the feed-forward critic's checks and packing (fn names the entry point in the messages)
+int ppo_create_ff(hk_handle h, const char* fn, int policy, const hk_policy_desc* c, const hk_ppo_config* cfg, int seq_len)
 {
-    HK_NEED_ENV(h);
+    const std::string f = std::string(fn) + ": ";
     auto checks = [&](const hk::PolicyParams& q) {
-        if (c->in_dim != q.in_dim) return fail(h, HK_ERR_INVALID, "hk_ppo_create: the critic's in_dim differs from the actor's");
+        if (c->in_dim != q.in_dim) return fail(h, HK_ERR_INVALID, f + "the critic's in_dim differs from the actor's");
         if (c->hidden < 32 || c->hidden > HK_POLICY_MAX_HIDDEN || c->hidden % 32 || c->n_layers < 1 || c->n_layers > HK_POLICY_MAX_LAYERS || c->n_branch != 0)
-            return fail(h, HK_ERR_INVALID, "hk_ppo_create: critic hidden / n_layers out of the actor's limits, or n_branch != 0");
-        for (int l = 0; l < c->n_layers; l++) if (!c->W[l] || !c->b[l]) return fail(h, HK_ERR_INVALID, "hk_ppo_create: NULL critic layer weights");
-        if (!c->W_mu || !c->b_mu) return fail(h, HK_ERR_INVALID, "hk_ppo_create: NULL critic value head");
+            return fail(h, HK_ERR_INVALID, f + "critic hidden / n_layers out of the actor's limits, or n_branch != 0");
+        for (int l = 0; l < c->n_layers; l++) if (!c->W[l] || !c->b[l]) return fail(h, HK_ERR_INVALID, f + "NULL critic layer weights");
+        if (!c->W_mu || !c->b_mu) return fail(h, HK_ERR_INVALID, f + "NULL critic value head");
         return (int)HK_OK;
     };
     auto pack = [&](hk_context::Ppo& t, std::vector<float>& host) {
@@ -2156,7 +2294,24 @@ int hk_ppo_create(hk_handle h, int policy, const hk_policy_desc* c, const hk_ppo
         std::memcpy(&host[t.critic.oWmu - t.actor.count], c->W_mu, (size_t)c->hidden * 4);
         host[t.critic.obmu - t.actor.count] = c->b_mu[0];
     };
-    return ppo_create(h, "hk_ppo_create", policy, c != nullptr, cfg, checks, pack);
+    return ppo_create(h, fn, policy, c != nullptr, cfg, checks, pack, seq_len);
+}
+}  // namespace
+}  // extern "C++"
+
+int hk_ppo_create(hk_handle h, int policy, const hk_policy_desc* c, const hk_ppo_config* cfg)
+{
+    HK_NEED_ENV(h);
+    return ppo_create_ff(h, "hk_ppo_create", policy, c, cfg, 0);
+}
+
+int hk_ppo_create_recurrent(hk_handle h, int policy, const hk_policy_desc* c, const hk_ppo_config* cfg, const hk_ppo_recurrent_desc* r)
+{
+    HK_NEED_ENV(h);
+    if (!r) return fail(h, HK_ERR_INVALID, "hk_ppo_create_recurrent: NULL r (the hk_ppo_recurrent_desc)");
+    if (r->sequence_length < 1) return fail(h, HK_ERR_INVALID, "hk_ppo_create_recurrent: sequence_length < 1");
+    if (r->reserved != 0) return fail(h, HK_ERR_INVALID, "hk_ppo_create_recurrent: reserved != 0");
+    return ppo_create_ff(h, "hk_ppo_create_recurrent", policy, c, cfg, r->sequence_length);
 }
 
 int hk_ppo_advantages(hk_handle h, int trainer)
@@ -2176,6 +2331,10 @@ int hk_ppo_advantages(hk_handle h, int trainer)
     if ((rc = dev_grow(h, &t.rowbuf, &t.rowbuf_n, 3 * n + nbt + n, (3 * n + nbt + n) * sizeof(float)))) return rc;
     if (t.poca && (rc = dev_grow(h, &t.prow, &t.prow_n, 2 * n, 2 * n * sizeof(float)))) return rc;
     t.n = (int)n;
+    if (t.seq_len) {
+        const long long nseq = (long long)((P.R + t.seq_len - 1) / t.seq_len) * P.E * P.S;
+        t.n_seq = (int)nseq;          // (<= n)
+    }
     if ((rc = t.poca ? poca_values_and_returns(h, t, P) : ppo_values_and_gae(h, t, P))) return rc;
     if (t.cfg.normalize_advantages) hipLaunchKernelGGL(hk::ppo_adv_norm_kernel, dim3(1), dim3(1024), 0, h->stream, ppo_rowbuf(h, t).adv, t.n);
     HK_HIP(h, hipGetLastError());
@@ -2217,6 +2376,17 @@ int hk_ppo_publish(hk_handle h, int trainer)
     if (rc) return rc;
     if ((rc = ppo_refuse_open(h, "hk_ppo_publish"))) return rc;
     auto& t = h->ppo[trainer];
+    if (t.seq_len) {          // the trunk through ppo_publish_kernel (a net that ends before the cell), then the cell and the m-wide heads
+        hk::PpoNet trunk = t.actor;
+        trunk.count = t.lnet.oWih;
+        trunk.n_branch = 0;
+        trunk.oWmu = trunk.obmu = trunk.ols = trunk.oWbr = trunk.obbr = trunk.count;
+        hipLaunchKernelGGL(hk::ppo_publish_kernel<true>, dim3(nblk(trunk.count)), dim3(256), 0, h->stream, h->policy[t.policy].q, trunk, t.param);
+        hipLaunchKernelGGL(hk::ppo_lstm_publish_kernel<true>, dim3(nblk(t.lnet.end - t.lnet.oWih)), dim3(256), 0, h->stream, h->policy[t.policy].q,
+                           h->policy[t.policy].lq, h->policy[t.policy].braw, t.lnet, t.param);
+        HK_HIP(h, hipGetLastError());
+        return HK_OK;
+    }
     hipLaunchKernelGGL(hk::ppo_publish_kernel<true>, dim3(nblk(t.actor.count)), dim3(256), 0, h->stream, h->policy[t.policy].q, t.actor, t.param);
     HK_HIP(h, hipGetLastError());
     // the bf16 inference copies, when the policy has them: rebuilt from the fp32 copies just written (each an exact copy of its master, so every
@@ -2236,14 +2406,15 @@ int ppo_update_run(hk_handle h, int trainer, bool opt, int epochs, int minibatch
 {
     auto& t = h->ppo[trainer];
     const int per = t.poca ? h->policy[t.policy].q.n_slots : 1;          // a POCA trainer's ids are groups of `per` agent rows
-    const int n = t.n / per;
+    const int n = t.seq_len ? t.n_seq : t.n / per;          // a recurrent trainer's ids are sequences of seq_len rows
     const int mb = std::min(minibatch, n), nmb = n / mb;
     const bool kl_stop = target_kl > 0.0f;
     int* perm = ppo_rowbuf(h, t).perm;
     PpoWs w;
     PocaWs pw{};
     int rc;
-    if ((rc = ppo_ensure_ws(h, t, mb * per, w))) return rc;
+    if (t.seq_len && (long long)mb * t.seq_len > 0x3FFFFFFF) return fail(h, HK_ERR_INVALID, "hk_ppo_update: minibatch x sequence_length rows do not fit");
+    if ((rc = ppo_ensure_ws(h, t, t.seq_len ? mb * t.seq_len : mb * per, w))) return rc;
     if (t.poca && (rc = poca_ensure_ws(h, t, mb, pw))) return rc;
     if (max_norm > 0.0f && (rc = ppo_ensure_clip(h, t))) return rc;
     if (opt && t.clip) HK_HIP(h, hipMemsetAsync(t.clip + 2, 0, 5 * sizeof(double), h->stream));       // the accumulating words [2 .. 6]
@@ -2450,6 +2621,8 @@ int hk_ppo_set_precision(hk_handle h, int trainer, int precision)
     if (precision != HK_PPO_PREC_F32 && precision != HK_PPO_PREC_BF16) return fail(h, HK_ERR_INVALID, "hk_ppo_set_precision: unknown precision");
     auto& t = h->ppo[trainer];
     if (t.poca && precision != HK_PPO_PREC_F32) return fail(h, HK_ERR_UNSUPPORTED, "hk_ppo_set_precision: a POCA trainer has no bf16 products (hk.h \"POCA\")");
+    if (t.seq_len && precision != HK_PPO_PREC_F32)
+        return fail(h, HK_ERR_UNSUPPORTED, "hk_ppo_set_precision: precision: a recurrent trainer has no bf16 products (hk.h \"PPO trainer\" RECURRENT)");
     if (precision == t.prec) return HK_OK;
     // the workspace is laid out per precision: drop it once the stream is done with it (the next minibatch allocates the other layout)
     HK_HIP(h, hipStreamSynchronize(h->stream));
@@ -2503,7 +2676,7 @@ void* hk_ppo_ptr(hk_handle h, int trainer, int field)
     if (!h) { fail(nullptr, HK_ERR_INVALID, "NULL handle"); return nullptr; }
     if (trainer < 0 || trainer >= h->n_ppo) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: bad trainer index"); return nullptr; }
     const auto& t = h->ppo[trainer];
-    if (field < 0 || field >= HK_PPO_FIELDS) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: bad field"); return nullptr; }
+    if ((field < 0 || field >= HK_PPO_FIELDS) && field != HK_PPO_MB_MEMORY) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: bad field"); return nullptr; }
     if (field <= HK_PPO_ADAM_V) return t.param + (size_t)field * t.P;
     if (field <= HK_PPO_RET) {
         if (t.adv_gen < 0) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: hk_ppo_advantages has not run"); return nullptr; }
@@ -2527,7 +2700,9 @@ void* hk_ppo_ptr(hk_handle h, int trainer, int field)
         if (!t.clip) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: no clip-aware step yet"); return nullptr; }
         return t.clip;
     }
+    if (field == HK_PPO_MB_MEMORY && !t.seq_len) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: HK_PPO_MB_MEMORY belongs to a recurrent trainer"); return nullptr; }
     if (t.last_m == 0) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: no minibatch yet"); return nullptr; }
+    if (field == HK_PPO_MB_MEMORY) return ppo_lstm_ws(t).mbmem;
     if (t.poca && field == HK_PPO_MB_VALUE) {          // one value per group
         return poca_ws(h, t).mb_v;
     }
@@ -2540,10 +2715,11 @@ int hk_ppo_count(hk_handle h, int trainer, int field)
     if (!h) return fail(nullptr, HK_ERR_INVALID, "NULL handle");
     if (trainer < 0 || trainer >= h->n_ppo) return fail(h, HK_ERR_INVALID, "hk_ppo_count: bad trainer index");
     const auto& t = h->ppo[trainer];
-    if (field < 0 || field >= HK_PPO_FIELDS) return fail(h, HK_ERR_INVALID, "hk_ppo_count: bad field");
+    if ((field < 0 || field >= HK_PPO_FIELDS) && field != HK_PPO_MB_MEMORY) return fail(h, HK_ERR_INVALID, "hk_ppo_count: bad field");
     if (field <= HK_PPO_ADAM_V) return (int)t.P;
     if (field <= HK_PPO_RET) return t.adv_gen < 0 ? 0 : t.n;
-    if (field == HK_PPO_PERM) return t.perm_valid ? (t.poca ? t.n / h->policy[t.policy].q.n_slots : t.n) : 0;
+    if (field == HK_PPO_PERM) return t.perm_valid ? (t.seq_len ? t.n_seq : t.poca ? t.n / h->policy[t.policy].q.n_slots : t.n) : 0;
+    if (field == HK_PPO_MB_MEMORY) return t.seq_len ? t.last_m * 2 * t.lnet.m : 0;
     if (field == HK_PPO_SHADOW) return t.shadow ? (int)(t.P + t.shadow_pad) : 0;
     if (field == HK_PPO_CLIP) return t.clip ? 8 : 0;
     if (field == HK_PPO_NORM_MEAN || field == HK_PPO_NORM_STD) return h->policy[t.policy].q.normalize ? h->policy[t.policy].q.in_dim : 0;

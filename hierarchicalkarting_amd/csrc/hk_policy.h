@@ -88,6 +88,7 @@ struct PolicyDevice {
     PolicyBf16 bq{};
     PolicyLstm lq{};
     float* wlstm = nullptr;                  // the allocation behind lq's weights (hk_policy_attach_lstm)
+    float* braw = nullptr;                   // [8m] = b_ih | b_hh as attached or last published, in wlstm (a recurrent trainer's master copy reads them)
     float* weights = nullptr;                // one allocation behind every const float* above
     uint16_t* wbf = nullptr;                 // the second allocation, behind bq.Wf: made by the first switch to HK_POLICY_PREC_BF16
     int prec = HK_POLICY_PREC_F32;           // hk_policy_set_precision: which chain policy_launch_mlp runs

@@ -320,6 +320,9 @@ inline int policy_lstm_upload(PolicyDevice& pd, const hk_policy_lstm_desc* l, in
     };
     const size_t o_ih = lay(l->W_ih, H), o_hh = lay(l->W_hh, m), o_b = host.size();
     for (int k = 0; k < N; k++) host.push_back(l->b_ih[k] + l->b_hh[k]);
+    const size_t o_raw = host.size();                    // the two biases themselves, for hk_ppo_create_recurrent's master copy
+    host.insert(host.end(), l->b_ih, l->b_ih + N);
+    host.insert(host.end(), l->b_hh, l->b_hh + N);
     hipError_t e;
     if ((e = hipMalloc(&pd.wlstm, host.size() * sizeof(float))) != hipSuccess ||
         (e = hipMemcpyAsync(pd.wlstm, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, stream)) != hipSuccess ||
@@ -332,6 +335,7 @@ inline int policy_lstm_upload(PolicyDevice& pd, const hk_policy_lstm_desc* l, in
     q.Wq_ih = reinterpret_cast<const float4*>(pd.wlstm + o_ih);      // (hipMalloc's base and K * N floats: 16-byte aligned)
     q.Wq_hh = reinterpret_cast<const float4*>(pd.wlstm + o_hh);
     q.b = pd.wlstm + o_b;
+    pd.braw = pd.wlstm + o_raw;
     q.mem = nullptr;
     if (E > 0) {
         const size_t bytes = (size_t)E * pd.q.n_slots * 2 * m * sizeof(float);

@@ -9,6 +9,7 @@ and leaves updated weights in the attached policy, so that the next step() acts 
     tr.normalizer_init(); ...; tr.normalizer_update()     # the running input normaliser, folded from the closed rollout (hk.h "NORMALISER")
     tr.update(3, 512, 3e-4, max_grad_norm=0.5, target_kl=0.02); tr.last_report      # clip by the global norm, KL stop (hk.h "LONG RUNS")
     tr.save(path); ...; tr2.load(path)           # exact resume: masters, Adam moments, the two counters, precision, normaliser
+    tr = PPOTrainer(env, 0, sequence_length=64)  # a recurrent actor: truncated BPTT over windows of 64 rows; ids and `minibatch` count sequences
 
 Nothing is computed here: the arrays below only describe the flat parameter layout the library uses."""
 import ctypes as C
@@ -59,15 +60,37 @@ def gemm_bf16(env, epi, A, B, bias=None, aux=None):
     return c.cpu().numpy()
 
 
-def param_layout(in_dim, hidden, n_layers, n_branch):
-    """-> [(name, shape)] of one network in the flat vector's order (torch layout; n_branch 0: the critic, whose value head is W_mu / b_mu)"""
+def param_layout(in_dim, hidden, n_layers, n_branch, memory_size=0):
+    """-> [(name, shape)] of one network in the flat vector's order (torch layout; n_branch 0: the critic, whose value head is W_mu / b_mu).
+    memory_size > 0: a recurrent actor — the cell (W_ih, W_hh, b_ih, b_hh; gates i f g o) follows the trunk and the heads are m = memory_size / 2 wide"""
     out = []
     for l in range(n_layers):
         out += [("W%d" % l, (hidden, in_dim if l == 0 else hidden)), ("b%d" % l, (hidden,))]
-    out += [("W_mu", (hidden,)), ("b_mu", (1,))]
+    head = hidden
+    if memory_size:
+        if memory_size < 2 or memory_size % 2:
+            raise ValueError("memory_size: an even number >= 2 (it holds h and c)")
+        head = memory_size // 2
+        out += [("W_ih", (4 * head, hidden)), ("W_hh", (4 * head, head)), ("b_ih", (4 * head,)), ("b_hh", (4 * head,))]
+    out += [("W_mu", (head,)), ("b_mu", (1,))]
     if n_branch:
-        out += [("log_sigma", (1,)), ("W_branch", (n_branch, hidden)), ("b_branch", (n_branch,))]
+        out += [("log_sigma", (1,)), ("W_branch", (n_branch, head)), ("b_branch", (n_branch,))]
     return out
+
+
+def sequence_count(rows, sequence_length, n_envs, n_slots):
+    """n_seq = ceil(R / L) E S of a recurrent trainer (hk.h "PPO trainer" RECURRENT)"""
+    return -(-int(rows) // int(sequence_length)) * int(n_envs) * int(n_slots)
+
+
+def sequence_rows(sid, rows, sequence_length, n_envs, n_slots):
+    """sequence id s = (k E + e) S + j -> the row ids (t E + e) S + j of its window, t in [k L, min((k + 1) L, R)), time ascending; an id
+    outside [0, n_seq) -> []"""
+    R, L, ES = int(rows), int(sequence_length), int(n_envs) * int(n_slots)
+    if not 0 <= sid < sequence_count(R, L, n_envs, n_slots):
+        return []
+    k, rem = divmod(int(sid), ES)
+    return [t * ES + rem for t in range(k * L, min((k + 1) * L, R))]
 
 
 def split_params(flat, layout):
@@ -218,9 +241,9 @@ def _need(d, key, what="state"):
     return d[key]
 
 
-def check_state(d, kind, actor_shape, critic_shape):
-    """the host-only head of load_state_dict: a checkpoint's format, trainer kind (absent: "ppo") and the two network shapes against the
-    loading trainer's; ValueError names the field"""
+def check_state(d, kind, actor_shape, critic_shape, sequence_length=0):
+    """the host-only head of load_state_dict: a checkpoint's format, trainer kind (absent: "ppo"), the two network shapes and the sequence
+    length (absent: 0, not recurrent) against the loading trainer's; ValueError names the field"""
     if _need(d, "format") != CHECKPOINT_FORMAT:
         raise ValueError("state: format %r is not %d" % (d["format"], CHECKPOINT_FORMAT))
     if str(d.get("kind", "ppo")) != kind:
@@ -228,6 +251,8 @@ def check_state(d, kind, actor_shape, critic_shape):
     for key, want in (("actor_shape", actor_shape), ("critic_shape", critic_shape)):
         if not np.array_equal(np.asarray(_need(d, key)), np.asarray(want)):
             raise ValueError("state: %s %s differs from the trainer's %s" % (key, list(np.asarray(d[key])), list(np.asarray(want))))
+    if int(d.get("sequence_length", 0)) != int(sequence_length):
+        raise ValueError("state: sequence_length %d differs from the trainer's %d" % (int(d.get("sequence_length", 0)), int(sequence_length)))
 
 
 def _option(name, v, inf_ok):
@@ -242,10 +267,12 @@ def _option(name, v, inf_ok):
 
 class PPOTrainer:
     """One trainer of RacingEnv `env`'s attached policy `policy_index` (hk_ppo_create).  critic: a Policy with n_branch 0 semantics (its trunk and
-    W_mu / b_mu are used) or None for Policy.random-style weights of the actor's shape; precision: "f32" | "bf16" (set_precision); cfg: DEFAULTS' keys."""
+    W_mu / b_mu are used) or None for Policy.random-style weights of the actor's shape; precision: "f32" | "bf16" (set_precision); cfg: DEFAULTS' keys.
+    sequence_length: given for a recurrent actor (hk_ppo_create_recurrent): ids and `minibatch` then count sequences of that many rows."""
     KIND = "ppo"          # a checkpoint's "kind" entry (absent in a PPO checkpoint: it reads as "ppo"); poca.POCATrainer: "poca"
+    sequence_length = 0   # > 0: a recurrent trainer (set by __init__ when sequence_length is given)
 
-    def __init__(self, env, policy_index, critic=None, precision="f32", **cfg):
+    def __init__(self, env, policy_index, critic=None, precision="f32", sequence_length=None, **cfg):
         if precision not in PRECISIONS:
             raise ValueError("precision: one of %s" % sorted(PRECISIONS))
         bad = set(cfg) - set(DEFAULTS)
@@ -264,11 +291,16 @@ class PPOTrainer:
         d, _keep = critic.desc()
         d.n_branch = 0
         d.W_branch = d.b_branch = None
-        rc = env.L.hk_ppo_create(env.h, self.index, C.byref(d), C.byref(pc))
+        self.sequence_length = 0 if sequence_length is None else int(sequence_length)
+        if sequence_length is None:
+            rc = env.L.hk_ppo_create(env.h, self.index, C.byref(d), C.byref(pc))
+        else:
+            rd = _lib.PpoRecurrentDesc(self.sequence_length, 0)
+            rc = env.L.hk_ppo_create_recurrent(env.h, self.index, C.byref(d), C.byref(pc), C.byref(rd))
         if rc < 0:
             env._ck(rc)
         self.t = rc
-        self.actor_layout = param_layout(a.in_dim, a.hidden, len(a.W), a.n_branch)
+        self.actor_layout = param_layout(a.in_dim, a.hidden, len(a.W), a.n_branch, a.memory_size if self.sequence_length else 0)
         self.critic_layout = param_layout(a.in_dim, critic.hidden, len(critic.W), 0)
         self.n_actor = sum(int(np.prod(s)) for _, s in self.actor_layout)
         self.last_report = None           # of the last update(): a dict when it was given an option, else None
@@ -366,7 +398,7 @@ class PPOTrainer:
 
     # ---- buffers
     def _field(self, name):
-        idx = _lib.PPO_FIELDS[name]
+        idx = _lib.PPO_FIELDS[name] if name in _lib.PPO_FIELDS else _lib.PPO_RECURRENT_FIELDS[name]
         n = self.env.L.hk_ppo_count(self.env.h, self.t, idx)
         if n < 0:
             self._ck(n)
@@ -392,7 +424,7 @@ class PPOTrainer:
             def __init__(self, ptr, n, ts):
                 self.__cuda_array_interface__ = {"shape": (n,), "typestr": ts, "data": (int(ptr), False), "version": 3, "strides": None}
         out = {}
-        for name, idx in _lib.PPO_FIELDS.items():
+        for name, idx in list(_lib.PPO_FIELDS.items()) + (list(_lib.PPO_RECURRENT_FIELDS.items()) if self.sequence_length else []):
             n = self.env.L.hk_ppo_count(self.env.h, self.t, idx)
             ptr = self.env.L.hk_ppo_ptr(self.env.h, self.t, idx) if n > 0 else None
             if ptr:
@@ -436,13 +468,15 @@ class PPOTrainer:
         mean, std = a.norm_mean, a.norm_std
         if mean is not None:
             mean, std = self.read("norm_mean"), self.read("norm_std")
+        lstm = {k: p[k] for k in Policy.LSTM_KEYS} if self.sequence_length else None          # a recurrent trainer: a recurrent Policy
         return Policy([p["W%d" % l] for l in range(L)], [p["b%d" % l] for l in range(L)], p["W_mu"], p["b_mu"], p["log_sigma"], p["W_branch"],
-                      p["b_branch"], mean, std, a.stack, a.deterministic, a.seed)
+                      p["b_branch"], mean, std, a.stack, a.deterministic, a.seed, lstm)
 
     # ---- exact resume (hk.h "LONG RUNS"): a restored trainer fed the same rollout continues bit for bit
     def _shapes(self):
         a, c = self.actor_policy, self.critic_policy
-        return (np.array([a.in_dim, a.hidden, len(a.W), a.n_branch], np.int64), np.array([a.in_dim, c.hidden, len(c.W), 0], np.int64))
+        sa = [a.in_dim, a.hidden, len(a.W), a.n_branch] + ([a.memory_size] if self.sequence_length else [])
+        return (np.array(sa, np.int64), np.array([a.in_dim, c.hidden, len(c.W), 0], np.int64))
 
     def state_dict(self):
         """-> dict of numpy arrays and scalars: format, the two network shapes, params / adam_m / adam_v, adam_steps, epochs_done, precision, cfg
@@ -453,6 +487,8 @@ class PPOTrainer:
                  adam_v=self.read("adam_v"), adam_steps=steps, epochs_done=epochs, precision=self.precision,
                  cfg={k: (int(self.cfg[k]) & 0xFFFFFFFF if k == "seed" else int(bool(self.cfg[k])) if k == "normalize_advantages" else float(self.cfg[k]))
                       for k in DEFAULTS})
+        if self.sequence_length:
+            d["sequence_length"] = self.sequence_length
         if self.actor_policy.norm_mean is not None:
             try:
                 n, mean, m2 = self.normalizer_state()
@@ -464,7 +500,7 @@ class PPOTrainer:
     def load_state_dict(self, d):
         """validate (ValueError names the field: shapes, cfg — a differing shuffle seed would not continue the permutations), then restore the
         counters, the three vectors, the precision and the normaliser if present, and publish; the library refuses it while a rollout is open"""
-        check_state(d, self.KIND, *self._shapes())
+        check_state(d, self.KIND, *self._shapes(), sequence_length=self.sequence_length)
         cfg = _need(d, "cfg")
         for k in DEFAULTS:
             mine = int(self.cfg[k]) & 0xFFFFFFFF if k == "seed" else int(bool(self.cfg[k])) if k == "normalize_advantages" else float(self.cfg[k])

@@ -34,6 +34,7 @@ namespace KartGame.AI.Native
                          HK_PPO_PREC_F32 = 0, HK_PPO_PREC_BF16 = 1,
                          HK_POLICY_PREC_F32 = 0, HK_POLICY_PREC_BF16 = 1,      // hk_policy_precision
                          HK_PPO_STATS = 6;
+        public const int HK_PPO_MB_MEMORY = 32;      // hk_ppo_recurrent_field: a recurrent trainer's extra buffer, outside [0, HK_PPO_FIELDS)
         // hk_poca_field: the extra buffers of a POCA trainer (hk_poca_ptr / hk_poca_count); HK_POCA_STATS: L_b, reserved
         public const int HK_POCA_B_OLD = 0, HK_POCA_MB_BASELINE = 1, HK_POCA_TEAM_REWARD = 2, HK_POCA_FIELDS = 3, HK_POCA_STATS = 2,
                          HK_POCA_MAX_GROUP = 4, HK_POCA_HEADS = 4;
@@ -419,6 +420,14 @@ namespace KartGame.AI.Native
         public float* b_val;
     }
 
+    // hk_ppo_recurrent_desc: hk_ppo_create_recurrent's sequence length (hk.h "PPO trainer" RECURRENT)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HkPpoRecurrentDesc
+    {
+        public int sequence_length;
+        public int reserved;
+    }
+
     // hk_ppo_update_opts / hk_ppo_update_report: hk_ppo_update_opt's options (0: off) and what it did (hk.h "LONG RUNS")
     [StructLayout(LayoutKind.Sequential)]
     public struct HkPpoUpdateOpts
@@ -530,6 +539,7 @@ namespace KartGame.AI.Native
         [DllImport(Lib)] public static extern IntPtr hk_rollout_ptr(IntPtr h, int field);
         // PPO trainer: train an attached actor on the closed rollout, on the device (hk.h "PPO trainer")
         [DllImport(Lib)] public static extern int hk_ppo_create(IntPtr h, int policy, HkPolicyDesc* critic, HkPpoConfig* cfg);
+        [DllImport(Lib)] public static extern int hk_ppo_create_recurrent(IntPtr h, int policy, HkPolicyDesc* critic, HkPpoConfig* cfg, HkPpoRecurrentDesc* r);
         [DllImport(Lib)] public static extern int hk_ppo_advantages(IntPtr h, int trainer);
         [DllImport(Lib)] public static extern int hk_ppo_minibatch(IntPtr h, int trainer, IntPtr rowsDev, int m, float eps, float beta, float* stats);
         [DllImport(Lib)] public static extern int hk_ppo_adam(IntPtr h, int trainer, float lr);

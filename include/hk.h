@@ -503,9 +503,10 @@ int hk_policy_forward(hk_handle h, int policy, int rows, const float* obs /*[row
  * Refused with HK_ERR_INVALID, state as it was, hk_last_error naming the argument: memory_size odd; m not a multiple of 32 or outside
  * [32, 128]; a NULL weight pointer; reserved != 0; hk_policy_memory_set while a rollout is open; hk_policy_forward_mem, hk_policy_memory_get
  * or hk_policy_memory_set on a policy without memory or with a NULL array.  Refused with HK_ERR_UNSUPPORTED on a policy WITH memory:
- * hk_policy_forward (use hk_policy_forward_mem), hk_policy_set_precision(HK_POLICY_PREC_BF16), hk_ppo_create, hk_ppo_create_poca,
+ * hk_policy_forward (use hk_policy_forward_mem), hk_policy_set_precision(HK_POLICY_PREC_BF16), hk_ppo_create (use hk_ppo_create_recurrent), hk_ppo_create_poca,
  * hk_policy_pool_create / _save / _load.
- * Out of scope: recurrent training (see "PPO trainer"), bf16 for the cell, snapshot pools and self-play swaps of recurrent actors, m above
+ * Training: hk_ppo_create_recurrent ("PPO trainer" RECURRENT).
+ * Out of scope: bf16 for the cell, snapshot pools and self-play swaps of recurrent actors, m above
  * 128, stacked or bidirectional LSTMs, and a CPU-oracle restatement (the bit reference is the host build named above). */
 #define HK_POLICY_MAX_MEMORY 256          /* memory_size; m = memory_size / 2, a multiple of 32 in [32, 128] */
 typedef struct hk_policy_lstm_desc {
@@ -703,8 +704,43 @@ void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* 
  *                        valid as they were.  Either pointer of get may be NULL.
  * Refused with HK_ERR_INVALID and a message naming the argument, state as it was: a NULL opts, epochs < 1, minibatch < 1, max_grad_norm or target_kl
  * negative or NaN, target_kl infinite, reserved != 0, and whatever hk_ppo_update / hk_ppo_adam refuse.
- * Out of scope (self-play opponent swaps, episode statistics and ELO: "SELF-PLAY" below; POCA and group rewards: "POCA" below): training a recurrent actor (truncated BPTT over the recorder's MEMORY / FIRST rows, a recurrent critic, sequence_length minibatches: hk_ppo_create
- * refuses a policy with memory, "RECURRENT ACTORS" above), a normaliser for policies attached with normalize == 0,
+ * RECURRENT (hk_ppo_create_recurrent: PPO with truncated back-propagation through time for an actor with memory, "RECURRENT ACTORS" above; the
+ * reference's *-LSTM behaviours train with memory_size 256, sequence_length 64).  It returns a trainer index of the same table and every hk_ppo_*
+ * entry point takes it; a trainer made by hk_ppo_create or hk_ppo_create_poca computes what it computed, bit for bit, issues the launches it issued
+ * and allocates nothing more.  hk_ppo_create itself keeps refusing a policy with memory (HK_ERR_UNSUPPORTED), hk_ppo_config is as it was.
+ * The CRITIC stays the feed-forward critic above on the stacked input — ML-Agents gives the critic an LSTM of its own; not doing so is a
+ * documented departure — so hk_ppo_advantages, GAE and V_OLD are those of a plain trainer.
+ * SEQUENCES.  With L = sequence_length and R the completed rows, window k of agent (e, j) is the rows t in [k L, min((k + 1) L, R)); sequence id
+ * s = (k E + e) S + j, n_seq = ceil(R / L) E S.  The memory entering a window's first row is the recorder's MEMORY[k L], a constant: no gradient
+ * flows into it.  Inside a window the training forward carries the memory itself.  At a row with FIRST[t] == 1 the memory read is exactly zero
+ * and no gradient crosses that row backwards (gradients still flow within the row).  The rows tau of the last window with k L + tau >= R are
+ * dead: exact zeros in every loss term, delta and gradient contribution, like a skipped id.
+ * MINIBATCHES.  As for POCA's group ids, an id handed to hk_ppo_minibatch is a SEQUENCE id and m counts sequences; an id outside [0, n_seq) skips
+ * its sequence and stats[5] counts skipped sequences.  Under hk_ppo_update / hk_ppo_update_opt `minibatch` counts sequences, the permutation is
+ * over n_seq and PERM is int32 [n_seq].  Loss means are over the valid rows, as above.  The rows are gathered time-major: MB_MU, MB_LOGITS and
+ * MB_VALUE are [L][m], and HK_PPO_MB_MEMORY [L][m][2 m_cell] holds the memory [h' | c'] each row's cell wrote.
+ * PARAMS / GRAD / ADAM_M / ADAM_V, actor part: the trunk as above; then W_ih [4 m_cell][H], W_hh [4 m_cell][m_cell], b_ih [4 m_cell],
+ * b_hh [4 m_cell] in torch layout, gates i f g o; then the heads, m_cell wide; then the critic, unchanged.  The gate bias the forward uses is
+ * fp32(b_ih + b_hh), formed as at attach; both biases receive the same gradient.
+ * EXACTNESS.  A gate pre-activation is the inference chain: seeded with the summed bias, one ascending-k fmaf chain over a[0 .. H), then over
+ * h[0 .. m_cell), on v_mfma_f32_32x32x2_f32 (the partial chain is stored to fp32 memory between the two parts, which is lossless); the cell is
+ * hk_lstm_cell, the heads fmaf chains on h'.  At unchanged parameters in the exact order (advantages -> update -> normaliser): rho == 1, approx-KL
+ * and the clip fraction exactly 0, MB_MU / MB_LOGITS equal to the recorder's MU / LOGITS bit for bit, MB_MEMORY at row t equal to MEMORY[t + 1]
+ * wherever FIRST[t + 1] == 0 and to NEXT_MEMORY at the last row where DONE == 0.
+ * BACKWARD.  sigma' = s (1 - s) and tanh' = 1 - t^2 from the stored gate outputs.  With dh_tau the heads' delta at tau plus the recurrent delta
+ * from tau + 1, the cell backward gives the four gate deltas dG_tau and dc_{tau-1}; the recurrent delta to tau - 1 is dG_tau W_hh, zeroed (with dc)
+ * where FIRST of row tau is set, and at tau = 0.  Over all rows of the minibatch at once, in the fixed-order split-K forms above (chunks of 256 rows,
+ * combined in chunk order; no float atomics: the same call on the same state gives the same bits): dW_ih = dG^T a, dW_hh = dG^T h_prev (h_prev as
+ * read, after the reset), db = the fp64 column sum of dG, da = (dG W_ih) * swish'(Z_last), handed to the trunk's backward.
+ * hk_ppo_adam / hk_ppo_adam_clipped (one norm over everything, the cell included), hk_ppo_update(_opt) with clip and KL stop, the counters, the
+ * normaliser (it acts on inputs) and hk_ppo_ptr / hk_ppo_count work without a change of meaning.  hk_ppo_publish also rewrites the policy's
+ * group-major Wq_ih / Wq_hh copies and the summed bias.
+ * Refused with HK_ERR_INVALID, state as it was, the message naming the argument: a NULL r, sequence_length < 1, reserved != 0, a policy without
+ * memory (use hk_ppo_create) and whatever hk_ppo_create refuses.  HK_ERR_UNSUPPORTED: hk_ppo_set_precision(HK_PPO_PREC_BF16) on a recurrent trainer.
+ * Out of scope for recurrent training: a recurrent critic, recurrent POCA, bf16 for the cell or its training products, snapshot pools and
+ * self-play swaps of recurrent actors, m_cell above 128, burn-in rows.
+ * Out of scope (self-play opponent swaps, episode statistics and ELO: "SELF-PLAY" below; POCA and group rewards: "POCA" below):
+ * a normaliser for policies attached with normalize == 0,
  * multi-GPU gradient all-reduce and bf16 optimiser state.  Everything is asynchronous on hk_stream unless noted. */
 #define HK_PPO_STATS 6
 typedef struct hk_ppo_config {
@@ -727,6 +763,12 @@ typedef enum hk_ppo_field {
 } hk_ppo_field;
 typedef enum { HK_PPO_PREC_F32 = 0, HK_PPO_PREC_BF16 = 1 } hk_ppo_precision;
 int hk_ppo_create(hk_handle h, int policy, const hk_policy_desc* critic, const hk_ppo_config* cfg);
+/* the field a recurrent trainer adds (RECURRENT), taken by hk_ppo_ptr / hk_ppo_count beside hk_ppo_field; it lies outside [0, HK_PPO_FIELDS), which is as it was */
+typedef enum hk_ppo_recurrent_field {
+    HK_PPO_MB_MEMORY = 32      /* fp32 [L][m][2 m_cell]: the memory [h' | c'] each row's cell wrote in the last minibatch; count 0 on other trainers */
+} hk_ppo_recurrent_field;
+typedef struct hk_ppo_recurrent_desc { int32_t sequence_length, reserved; } hk_ppo_recurrent_desc;
+int hk_ppo_create_recurrent(hk_handle h, int policy, const hk_policy_desc* critic, const hk_ppo_config* cfg, const hk_ppo_recurrent_desc* r);
 int hk_ppo_advantages(hk_handle h, int trainer);
 int hk_ppo_minibatch(hk_handle h, int trainer, const int32_t* rows_dev, int m, float eps, float beta, float* stats /*[HK_PPO_STATS]*/);
 int hk_ppo_adam(hk_handle h, int trainer, float lr);
