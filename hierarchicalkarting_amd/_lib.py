@@ -37,6 +37,8 @@ HK_RO_FIELDS = len(RO_FIELDS)
 PPO_FIELDS = {n: i for i, n in enumerate(("params", "grad", "adam_m", "adam_v", "v_old", "adv", "ret", "mb_mu", "mb_logits", "mb_value", "perm", "shadow",
                                                "norm_mean", "norm_std", "clip"))}
 PPO_RECURRENT_FIELDS = {"mb_memory": 32}      # hk_ppo_recurrent_field: taken by hk_ppo_ptr / hk_ppo_count of a recurrent trainer, outside [0, HK_PPO_FIELDS)
+# hk_ppo_recurrent_critic_field: a recurrent critic's extra buffers (hk_ppo_create_recurrent_critic), count 0 on every other trainer
+PPO_RECURRENT_CRITIC_FIELDS = {"critic_memory": 33, "critic_mem_in": 34, "critic_mem_out": 35, "mb_critic_memory": 36}
 HK_PPO_FIELDS = len(PPO_FIELDS)
 HK_PPO_STATS = 6
 HK_PPO_PREC_F32, HK_PPO_PREC_BF16 = 0, 1
@@ -192,6 +194,10 @@ class PpoRecurrentDesc(C.Structure):
     _fields_ = [("sequence_length", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PpoRecurrentCriticDesc(C.Structure):
+    _fields_ = [("sequence_length", C.c_int32), ("value_chunk_steps", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class PpoUpdateOpts(C.Structure):
     _fields_ = [("epochs", C.c_int32), ("minibatch", C.c_int32), ("lr", C.c_float), ("eps", C.c_float), ("beta", C.c_float),
                 ("max_grad_norm", C.c_float), ("target_kl", C.c_float), ("reserved", C.c_int32)]
@@ -262,6 +268,8 @@ SYMBOLS = {
     "hk_rollout_ptr": (C.c_void_p, [_H, C.c_int]),
     "hk_ppo_create": (C.c_int, [_H, C.c_int, C.POINTER(PolicyDesc), C.POINTER(PpoConfig)]),
     "hk_ppo_create_recurrent": (C.c_int, [_H, C.c_int, C.POINTER(PolicyDesc), C.POINTER(PpoConfig), C.POINTER(PpoRecurrentDesc)]),
+    "hk_ppo_create_recurrent_critic": (C.c_int, [_H, C.c_int, C.POINTER(PolicyDesc), C.POINTER(PolicyLstmDesc), C.POINTER(PpoConfig),
+                                                 C.POINTER(PpoRecurrentCriticDesc)]),
     "hk_ppo_advantages": (C.c_int, [_H, C.c_int]),
     "hk_ppo_minibatch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, _fp]),
     "hk_ppo_adam": (C.c_int, [_H, C.c_int, C.c_float]),

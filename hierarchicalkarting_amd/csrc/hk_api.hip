@@ -17,6 +17,7 @@
 #include "hk_rollout.h"
 #include "hk_ppo.h"
 #include "hk_ppo_lstm.h"
+#include "hk_ppo_lstm_critic.h"
 #include "hk_poca.h"
 #include "hk_selfplay.h"
 #include <dlfcn.h>
@@ -252,6 +253,20 @@ struct hk_context {
         hk::PpoLstmNet lnet;
         void* rws = nullptr;
         int rcap = 0, last_ms = 0;
+        // ... with a recurrent critic (RECURRENT CRITIC; hk_ppo_create_recurrent_critic; nothing of this is touched for the other kinds): critic_m > 0,
+        // the critic's cell and value head at cnet's offsets (critic.oWmu / obmu are cnet's W_v / b_v), a minibatch workspace of its own for ccap
+        // rows, the memories cmem = MEM_IN | MEM_OUT | the value pass's carry, [E S][2 m_v] each, CRITIC_MEMORY [cmem_k][E S][2 m_v], and the
+        // value pass's Zx and summed bias for vcap rows
+        int critic_m = 0, value_chunk = 0;
+        hk::PpoLstmCriticNet cnet;
+        void* cws = nullptr;
+        int ccap = 0;
+        float* cmem = nullptr;
+        float* cmemk = nullptr;
+        size_t cmemk_n = 0;
+        int cmem_k = 0, cmem_gen = -1;          // windows of the last value pass; the rollout generation MEM_IN belongs to
+        float* vws = nullptr;
+        size_t vcap = 0;
     } ppo[HK_MAX_POLICIES];
     int n_ppo = 0;
     // self-play (hk.h "SELF-PLAY"; hk_selfplay.h); nothing is allocated before the first hk_policy_pool_create / hk_rollout_episode_stats
@@ -1992,6 +2007,36 @@ size_t ppo_lstm_ws_layout(const hk_context::Ppo& t, int M, PpoLstmWs* w)
 
 PpoLstmWs ppo_lstm_ws(const hk_context::Ppo& t) { PpoLstmWs w; ppo_lstm_ws_layout(t, t.rcap, &w); return w; }
 
+// the recurrent critic's workspace at a capacity of M rows (Ppo::cws): the same pieces for the critic's cell, m_v wide; the row ids and FIRST
+// words are the actor workspace's
+size_t ppo_lstm_cws_layout(const hk_context::Ppo& t, int M, PpoLstmWs* w)
+{
+    PpoBump a{w ? (char*)t.cws : nullptr};
+    auto fl = [&](size_t count) { return (float*)a.take(count * 4); };
+    const size_t Mz = (size_t)M, mc = (size_t)t.critic_m;
+    const size_t ms = (Mz + t.seq_len - 1) / t.seq_len;
+    const int Hc = t.critic.hidden, in = t.critic.in_dim;
+    const size_t mn = std::max(4 * mc * std::max((size_t)Hc, mc), (size_t)Hc * std::max(in, Hc));      // the cell's 4 m_v x max(Hc, m_v), or a trunk layer's
+    const size_t nz = (Mz + hk::PPO_KCH - 1) / hk::PPO_KCH;
+    PpoLstmWs d{};
+    d.mem0 = fl(ms * 2 * mc); d.bsum = fl(4 * mc);
+    d.GZ = fl(Mz * 4 * mc); d.hnew = fl(Mz * mc); d.mbmem = fl(Mz * 2 * mc); d.hprev = fl(Mz * mc); d.cprev = fl(Mz * mc); d.dH = fl(Mz * mc);
+    d.drec = fl(ms * mc); d.dcar = fl(ms * mc);
+    d.part = fl(nz * mn);
+    if (w) *w = d;
+    return a.off;
+}
+
+PpoLstmWs ppo_lstm_cws(const hk_context::Ppo& t) { PpoLstmWs w; ppo_lstm_cws_layout(t, t.ccap, &w); return w; }
+
+// the memories of a recurrent critic (Ppo::cmem): MEM_IN, MEM_OUT and the value pass's carry, [E S][2 m_v] each
+struct PpoCriticMem { float *in, *out, *carry; size_t each; };
+PpoCriticMem ppo_critic_mem(hk_handle h, const hk_context::Ppo& t)
+{
+    const size_t each = (size_t)h->cfg.num_envs * h->policy[t.policy].q.n_slots * 2 * t.critic_m;
+    return PpoCriticMem{t.cmem, t.cmem + each, t.cmem + 2 * each, each};
+}
+
 // one recurrent minibatch: ms sequence ids -> M = L ms time-major rows; loss, stats, gradient into GRAD
 int ppo_lstm_mb(hk_handle h, hk_context::Ppo& t, const int32_t* sids, int ms, float eps, float beta, bool acc)
 {
@@ -2003,6 +2048,10 @@ int ppo_lstm_mb(hk_handle h, hk_context::Ppo& t, const int32_t* sids, int ms, fl
     if (rc) return rc;
     if (M > t.rcap && (rc = dev_grow(h, &t.rws, &t.rcap, M, ppo_lstm_ws_layout(t, M, nullptr)))) return rc;
     const PpoLstmWs r = ppo_lstm_ws(t);
+    const int mv = t.critic_m, Nv = 4 * mv;          // a recurrent critic (mv > 0): its cell's leg beside the actor's
+    if (mv && M > t.ccap && (rc = dev_grow(h, &t.cws, &t.ccap, M, ppo_lstm_cws_layout(t, M, nullptr)))) return rc;
+    const PpoLstmWs c = mv ? ppo_lstm_cws(t) : PpoLstmWs{};
+    const hk::PpoLstmCriticNet& cn = t.cnet;
     hipStream_t s = h->stream;
     const hk::PpoRows P = ppo_rows(h, t);
     const auto& ro = h->ro;
@@ -2025,6 +2074,14 @@ int ppo_lstm_mb(hk_handle h, hk_context::Ppo& t, const int32_t* sids, int ms, fl
     const dim3 sgrid(nblk(mc, hk::PPO_TN), nblk(ms, hk::PPO_TM));
     for (int tau = 0; tau < L; tau++)
         hipLaunchKernelGGL(hk::ppo_lstm_step_kernel, sgrid, dim3(256), 0, s, tau, ms, mc, prm + ln.oWhh, r.mem0, r.first, r.GZ, r.hnew, r.mbmem, r.hprev, r.cprev);
+    if (mv) {          // the critic's cell over the window, from CRITIC_MEMORY[k]: the same three pieces
+        hipLaunchKernelGGL(hk::ppo_lstm_critic_mem0_kernel, dim3(nblk((size_t)ms * 2 * mv)), dim3(256), 0, s, t.cmemk, sids, ms, t.n_seq, mv, c.mem0);
+        hipLaunchKernelGGL(hk::ppo_lstm_bsum_kernel, dim3(nblk(Nv)), dim3(256), 0, s, prm + cn.obih, prm + cn.obhh, Nv, c.bsum);
+        ppo_product<0>(s, M, Nv, Hc, w.Ac[Lc], Hc, true, PpoMat(prm + cn.oWih), Hc, true, c.bsum, PpoMat(c.GZ), Nv, nullptr, Hc);
+        const dim3 cgrid(nblk(mv, hk::PPO_TN), nblk(ms, hk::PPO_TM));
+        for (int tau = 0; tau < L; tau++)
+            hipLaunchKernelGGL(hk::ppo_lstm_step_kernel, cgrid, dim3(256), 0, s, tau, ms, mv, prm + cn.oWhh, c.mem0, r.first, c.GZ, c.hnew, c.mbmem, c.hprev, c.cprev);
+    }
     // loss on h' (width m), per-row ids
     {
         const PpoRowBuf rows = ppo_rowbuf(h, t);
@@ -2034,6 +2091,7 @@ int ppo_lstm_mb(hk_handle h, hk_context::Ppo& t, const int32_t* sids, int ms, fl
         A.W_v = prm + nc.oWmu; A.b_v = prm + nc.obmu;
         A.v_old = rows.v_old; A.adv = rows.adv; A.ret = rows.ret;
         A.ids = r.rowids; A.valid = w.valid; A.n_valid = w.n_valid; A.m = M; A.n = t.n; A.Ha = mc; A.Hc = Hc; A.nb = nb;
+        if (mv) { A.Ac = c.hnew; A.Hc = mv; }          // (nc.oWmu / obmu are the m_v-wide W_v / b_v)
         A.eps = eps; A.beta = beta;
         A.dhead = w.dhead; A.dls = w.dls; A.dv = w.dv; A.rowstat = w.rowstat;
         A.mu_out = w.mb_mu; A.logit_out = w.mb_logits; A.v_out = w.mb_v;
@@ -2059,11 +2117,85 @@ int ppo_lstm_mb(hk_handle h, hk_context::Ppo& t, const int32_t* sids, int ms, fl
     HK_HIP(h, hipMemcpyAsync(grad + ln.obhh, grad + ln.obih, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));      // both biases: the same gradient
     ppo_product<2>(s, M, Ha, N, PpoMat(r.GZ), N, true, PpoMat(prm + ln.oWih), Ha, false, nullptr, w.d0, Ha, w.Za[La], N);
     ppo_trunk_backward(s, t, na, r.part, w.X0, M, w.Za, w.Aa, w.d0, w.d1);
-    // critic (feed-forward on the stacked input, as a plain trainer's)
-    ppo_value_head_back(s, t, r.part, M, Hc, w.dv, nc.oWmu, nc.obmu, w.Zc[Lc], w.Ac[Lc], w.d0);
-    ppo_trunk_backward(s, t, nc, r.part, w.X0, M, w.Zc, w.Ac, w.d0, w.d1);
+    if (mv) {
+        // the recurrent critic: the actor's backward above, applied to its cell — the value-head delta onto h', the L steps in reverse, the cell's
+        // weight gradients over all rows at once, da into the critic's trunk
+        ppo_wgrad(s, c.part, 1, mv, M, w.dv, 1, PpoMat(c.hnew), mv, grad + cn.oWv, nullptr);
+        ppo_colsum(s, w.dv, M, 1, 1, grad + cn.obv);
+        hipLaunchKernelGGL(hk::ppo_lstm_head_back_kernel, dim3(nblk((size_t)M * mv)), dim3(256), 0, s, M, mv, 1, w.dv, 1, prm + cn.oWv, (const float*)nullptr, c.dH);
+        for (int tau = L - 1; tau >= 0; tau--) {
+            hipLaunchKernelGGL(hk::ppo_lstm_back_kernel, dim3(nblk((size_t)ms * mv)), dim3(256), 0, s, tau, ms, mv, (int)(tau == L - 1), r.first, c.dH, c.drec,
+                               c.mbmem, c.cprev, c.GZ, c.dcar);
+            if (tau > 0)
+                ppo_product<0>(s, ms, mv, Nv, PpoMat(c.GZ + (size_t)tau * ms * Nv), Nv, true, PpoMat(prm + cn.oWhh), mv, false, nullptr, PpoMat(c.drec), mv, nullptr, Nv);
+        }
+        ppo_wgrad(s, c.part, Nv, Hc, M, PpoMat(c.GZ), Nv, w.Ac[Lc], Hc, grad + cn.oWih, nullptr);
+        ppo_wgrad(s, c.part, Nv, mv, M, PpoMat(c.GZ), Nv, PpoMat(c.hprev), mv, grad + cn.oWhh, nullptr);
+        ppo_colsum(s, PpoMat(c.GZ), M, Nv, Nv, grad + cn.obih);
+        HK_HIP(h, hipMemcpyAsync(grad + cn.obhh, grad + cn.obih, (size_t)Nv * sizeof(float), hipMemcpyDeviceToDevice, s));
+        ppo_product<2>(s, M, Hc, Nv, PpoMat(c.GZ), Nv, true, PpoMat(prm + cn.oWih), Hc, false, nullptr, w.d0, Hc, w.Zc[Lc], Nv);
+        ppo_trunk_backward(s, t, nc, c.part, w.X0, M, w.Zc, w.Ac, w.d0, w.d1);
+    } else {
+        // critic (feed-forward on the stacked input, as a plain trainer's)
+        ppo_value_head_back(s, t, r.part, M, Hc, w.dv, nc.oWmu, nc.obmu, w.Zc[Lc], w.Ac[Lc], w.d0);
+        ppo_trunk_backward(s, t, nc, r.part, w.X0, M, w.Zc, w.Ac, w.d0, w.d1);
+    }
     HK_HIP(h, hipGetLastError());
     t.last_m = M; t.last_ms = ms;
+    return HK_OK;
+}
+
+// hk_ppo_advantages of a trainer with a recurrent critic (hk.h RECURRENT CRITIC): the critic run sequentially over the rows t = 0 .. R - 1 and the
+// bootstrap step t = R of every (e, j), memory carried from MEM_IN; then GAE as a plain trainer's.  The R + 1 time steps go in chunks of T =
+// value_chunk_steps, the E S sequences in tiles of sq, T sq rows of the order of the plain trainer's 16 384 at a time: gather, trunk and Zx over
+// the chunk's rows at once (time-major), then ONE ppo_lstm_value_kernel launch for the chunk's T steps.  The bits depend on neither T nor sq:
+// every row's chains are its own, and the carry between launches is exact.
+int ppo_lstm_values_and_gae(hk_handle h, hk_context::Ppo& t, const hk::PpoRows& P)
+{
+    const auto& ro = h->ro;
+    const int ES = P.E * P.S, mv = t.critic_m, N = 4 * mv, L = t.seq_len, K = (P.R + L - 1) / L;
+    const PpoRowBuf rows = ppo_rowbuf(h, t);
+    const PpoCriticMem cm = ppo_critic_mem(h, t);
+    int rc;
+    if ((rc = dev_grow(h, &t.cmemk, &t.cmemk_n, (size_t)K * cm.each, (size_t)K * cm.each * sizeof(float)))) return rc;
+    t.cmem_k = K;
+    // the tile of sequences follows from value_chunk_steps as given (16 384 rows / steps, whole 32-sequence blocks, at least one); the steps per
+    // launch are at most the R + 1 there are
+    const int Treq = t.value_chunk > 0 ? t.value_chunk : 16, T = std::min(Treq, P.R + 1);
+    const int sq_cap = std::min(std::max(hk::PLV_TS, 16384 / Treq / hk::PLV_TS * hk::PLV_TS), ES);
+    const size_t cap = (size_t)T * sq_cap;
+    PpoWs w;
+    if ((rc = ppo_ensure_ws(h, t, (int)cap, w))) return rc;
+    if ((rc = dev_grow(h, &t.vws, &t.vcap, cap, (cap * N + N + cap) * sizeof(float)))) return rc;
+    float* Zx = t.vws;
+    float* bsum = t.vws + t.vcap * N;
+    int* flags = (int*)(bsum + N);
+    hipStream_t s = h->stream;
+    const hk::PpoNet& nc = t.critic;
+    const hk::PpoLstmCriticNet& cn = t.cnet;
+    const float* prm = t.param;
+    const int Hc = nc.hidden, Lc = nc.n_layers - 1;
+    if (t.cmem_gen != ro.gen) {          // a rollout this trainer has not seen: the memory its last value pass left is what this one starts from
+        HK_HIP(h, hipMemcpyAsync(cm.in, cm.out, cm.each * sizeof(float), hipMemcpyDeviceToDevice, s));
+        t.cmem_gen = ro.gen;
+    }
+    HK_HIP(h, hipMemcpyAsync(cm.carry, cm.in, cm.each * sizeof(float), hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(hk::ppo_lstm_bsum_kernel, dim3(nblk(N)), dim3(256), 0, s, prm + cn.obih, prm + cn.obhh, N, bsum);
+    const size_t lds = hk::ppo_lstm_value_lds_bytes(mv);
+    for (int t0 = 0; t0 <= P.R; t0 += T) {
+        const int Tc = std::min(T, P.R + 1 - t0);
+        for (int p0 = 0; p0 < ES; p0 += sq_cap) {
+            const int sq = std::min(sq_cap, ES - p0), m = Tc * sq;
+            hipLaunchKernelGGL(hk::ppo_lstm_value_ids_kernel, dim3(nblk(m)), dim3(256), 0, s, P, w.ids, flags, t0, Tc, p0, sq);
+            ppo_gather(s, P, w.ids, m, 1, w.X0, w.valid);
+            ppo_trunk_forward(s, t, nc, w.X0, m, w.Zc, w.Ac);
+            ppo_product<0>(s, m, N, Hc, w.Ac[Lc], Hc, true, PpoMat(const_cast<float*>(prm) + cn.oWih), Hc, true, bsum, PpoMat(Zx), N, nullptr, Hc);
+            hipLaunchKernelGGL(hk::ppo_lstm_value_kernel, dim3(nblk(sq, hk::PLV_TS)), dim3(64 * (mv / 32)), lds, s, P.R, ES, t0, Tc, p0, sq, mv, L, Zx, flags,
+                               prm + cn.oWhh,
+                               prm + cn.oWv, prm + cn.obv, cm.carry, t.cmemk, cm.out, rows.v_old, rows.v_boot);
+        }
+    }
+    hipLaunchKernelGGL(hk::ppo_gae_kernel, dim3(nblk(ES)), dim3(256), 0, s, P, rows.v_old, rows.v_boot, t.cfg.gamma, t.cfg.lambd, rows.adv, rows.ret);
     return HK_OK;
 }
 
@@ -2266,6 +2398,7 @@ static void ppo_release(hk_context::Ppo& t)
 {
     (void)dev_free(t.param); (void)dev_free(t.rowbuf); (void)dev_free(t.ws); (void)dev_free(t.shadow); (void)dev_free(t.norm);
     (void)dev_free(t.norm_part); (void)dev_free(t.clip); (void)dev_free(t.prow); (void)dev_free(t.pws); (void)dev_free(t.rws);
+    (void)dev_free(t.cws); (void)dev_free(t.cmem); (void)dev_free(t.cmemk); (void)dev_free(t.vws);
     t = hk_context::Ppo{};
 }
 
@@ -2314,6 +2447,66 @@ int hk_ppo_create_recurrent(hk_handle h, int policy, const hk_policy_desc* c, co
     return ppo_create_ff(h, "hk_ppo_create_recurrent", policy, c, cfg, r->sequence_length);
 }
 
+int hk_ppo_create_recurrent_critic(hk_handle h, int policy, const hk_policy_desc* c, const hk_policy_lstm_desc* cell, const hk_ppo_config* cfg,
+                                   const hk_ppo_recurrent_critic_desc* r)
+{
+    HK_NEED_ENV(h);
+    const std::string f = "hk_ppo_create_recurrent_critic: ";
+    if (!r) return fail(h, HK_ERR_INVALID, f + "NULL r (the hk_ppo_recurrent_critic_desc)");
+    if (!cell) return fail(h, HK_ERR_INVALID, f + "NULL critic_cell (the critic's hk_policy_lstm_desc)");
+    if (r->sequence_length < 1) return fail(h, HK_ERR_INVALID, f + "sequence_length < 1");
+    if (r->value_chunk_steps < 0) return fail(h, HK_ERR_INVALID, f + "value_chunk_steps < 0");
+    if (r->reserved[0] != 0 || r->reserved[1] != 0) return fail(h, HK_ERR_INVALID, f + "reserved != 0");
+    if (cell->reserved != 0) return fail(h, HK_ERR_INVALID, f + "critic_cell: reserved != 0");
+    if (cell->memory_size & 1) return fail(h, HK_ERR_INVALID, f + "critic_cell: memory_size is odd (it holds h and c, m_v = memory_size / 2 each)");
+    const int mv = cell->memory_size / 2;
+    if (mv < 32 || mv > HK_POLICY_MAX_MEMORY / 2 || mv % 32)
+        return fail(h, HK_ERR_INVALID, f + "critic_cell: memory_size: m_v = memory_size / 2 must be a multiple of 32 in [32, 128]");
+    if (!cell->W_ih || !cell->W_hh || !cell->b_ih || !cell->b_hh) return fail(h, HK_ERR_INVALID, f + "critic_cell: NULL W_ih / W_hh / b_ih / b_hh");
+    // the trunk's checks are the feed-forward critic's; the pack lays the cell and the m_v-wide value head behind the trunk
+    auto checks = [&](const hk::PolicyParams& q) {
+        if (c->in_dim != q.in_dim) return fail(h, HK_ERR_INVALID, f + "the critic's in_dim differs from the actor's");
+        if (c->hidden < 32 || c->hidden > HK_POLICY_MAX_HIDDEN || c->hidden % 32 || c->n_layers < 1 || c->n_layers > HK_POLICY_MAX_LAYERS || c->n_branch != 0)
+            return fail(h, HK_ERR_INVALID, f + "critic hidden / n_layers out of the actor's limits, or n_branch != 0");
+        for (int l = 0; l < c->n_layers; l++) if (!c->W[l] || !c->b[l]) return fail(h, HK_ERR_INVALID, f + "NULL critic layer weights");
+        if (!c->W_mu || !c->b_mu) return fail(h, HK_ERR_INVALID, f + "NULL critic value head");
+        return (int)HK_OK;
+    };
+    auto pack = [&](hk_context::Ppo& t, std::vector<float>& host) {
+        const size_t base = t.actor.count;
+        const int Hc = c->hidden, N = 4 * mv;
+        t.critic.layout(t.actor.in_dim, Hc, c->n_layers, 0, base);
+        t.cnet.layout(Hc, mv, t.critic.oWmu);
+        t.critic.oWmu = t.cnet.oWv; t.critic.obmu = t.cnet.obv;
+        t.critic.count = t.cnet.end - base;
+        t.critic_m = mv; t.value_chunk = r->value_chunk_steps;
+        host.resize(t.critic.count);
+        auto put = [&](size_t off, const float* src, size_t k) { std::memcpy(&host[off - base], src, k * 4); };
+        for (int l = 0; l < c->n_layers; l++) {
+            put(t.critic.oW[l], c->W[l], (size_t)Hc * (l == 0 ? c->in_dim : Hc));
+            put(t.critic.ob[l], c->b[l], Hc);
+        }
+        put(t.cnet.oWih, cell->W_ih, (size_t)N * Hc); put(t.cnet.oWhh, cell->W_hh, (size_t)N * mv);
+        put(t.cnet.obih, cell->b_ih, N); put(t.cnet.obhh, cell->b_hh, N);
+        put(t.cnet.oWv, c->W_mu, mv); put(t.cnet.obv, c->b_mu, 1);
+    };
+    const int idx = ppo_create(h, "hk_ppo_create_recurrent_critic", policy, c != nullptr, cfg, checks, pack, r->sequence_length);
+    if (idx < 0) return idx;
+    // MEM_IN, MEM_OUT and the carry, all zero; the value kernel's LDS (above 64 KB at m_v = 128)
+    auto& t = h->ppo[idx];
+    const size_t each = ppo_critic_mem(h, t).each;
+    hipError_t e = hipMalloc(&t.cmem, 3 * each * sizeof(float));
+    if (e == hipSuccess) e = hipMemsetAsync(t.cmem, 0, 3 * each * sizeof(float), h->stream);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)hk::ppo_lstm_value_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {          // (give the slot back)
+        ppo_release(t);
+        h->n_ppo--;
+        return fail(h, HK_ERR_HIP, f + hipGetErrorString(e));
+    }
+    return idx;
+}
+
 int hk_ppo_advantages(hk_handle h, int trainer)
 {
     HK_NEED_ENV(h);
@@ -2335,7 +2528,7 @@ int hk_ppo_advantages(hk_handle h, int trainer)
         const long long nseq = (long long)((P.R + t.seq_len - 1) / t.seq_len) * P.E * P.S;
         t.n_seq = (int)nseq;          // (<= n)
     }
-    if ((rc = t.poca ? poca_values_and_returns(h, t, P) : ppo_values_and_gae(h, t, P))) return rc;
+    if ((rc = t.poca ? poca_values_and_returns(h, t, P) : t.critic_m ? ppo_lstm_values_and_gae(h, t, P) : ppo_values_and_gae(h, t, P))) return rc;
     if (t.cfg.normalize_advantages) hipLaunchKernelGGL(hk::ppo_adv_norm_kernel, dim3(1), dim3(1024), 0, h->stream, ppo_rowbuf(h, t).adv, t.n);
     HK_HIP(h, hipGetLastError());
     t.adv_gen = ro.gen;
@@ -2676,7 +2869,19 @@ void* hk_ppo_ptr(hk_handle h, int trainer, int field)
     if (!h) { fail(nullptr, HK_ERR_INVALID, "NULL handle"); return nullptr; }
     if (trainer < 0 || trainer >= h->n_ppo) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: bad trainer index"); return nullptr; }
     const auto& t = h->ppo[trainer];
-    if ((field < 0 || field >= HK_PPO_FIELDS) && field != HK_PPO_MB_MEMORY) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: bad field"); return nullptr; }
+    const bool critic_field = field >= HK_PPO_CRITIC_MEMORY && field <= HK_PPO_MB_CRITIC_MEMORY;
+    if ((field < 0 || field >= HK_PPO_FIELDS) && field != HK_PPO_MB_MEMORY && !critic_field) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: bad field"); return nullptr; }
+    if (critic_field) {          // (RECURRENT CRITIC)
+        if (!t.critic_m) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: the HK_PPO_CRITIC_* fields belong to a trainer with a recurrent critic"); return nullptr; }
+        if (field == HK_PPO_CRITIC_MEM_IN) return ppo_critic_mem(h, t).in;
+        if (field == HK_PPO_CRITIC_MEM_OUT) return ppo_critic_mem(h, t).out;
+        if (field == HK_PPO_CRITIC_MEMORY) {
+            if (t.adv_gen < 0) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: hk_ppo_advantages has not run"); return nullptr; }
+            return t.cmemk;
+        }
+        if (t.last_m == 0) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: no minibatch yet"); return nullptr; }
+        return ppo_lstm_cws(t).mbmem;
+    }
     if (field <= HK_PPO_ADAM_V) return t.param + (size_t)field * t.P;
     if (field <= HK_PPO_RET) {
         if (t.adv_gen < 0) { fail(h, HK_ERR_INVALID, "hk_ppo_ptr: hk_ppo_advantages has not run"); return nullptr; }
@@ -2715,6 +2920,12 @@ int hk_ppo_count(hk_handle h, int trainer, int field)
     if (!h) return fail(nullptr, HK_ERR_INVALID, "NULL handle");
     if (trainer < 0 || trainer >= h->n_ppo) return fail(h, HK_ERR_INVALID, "hk_ppo_count: bad trainer index");
     const auto& t = h->ppo[trainer];
+    if (field >= HK_PPO_CRITIC_MEMORY && field <= HK_PPO_MB_CRITIC_MEMORY) {          // (RECURRENT CRITIC; 0 on every other trainer)
+        if (!t.critic_m) return 0;
+        const size_t each = ppo_critic_mem(h, t).each;
+        if (field == HK_PPO_CRITIC_MEMORY) return t.adv_gen < 0 ? 0 : (int)(t.cmem_k * each);
+        return field == HK_PPO_MB_CRITIC_MEMORY ? t.last_m * 2 * t.critic_m : (int)each;
+    }
     if ((field < 0 || field >= HK_PPO_FIELDS) && field != HK_PPO_MB_MEMORY) return fail(h, HK_ERR_INVALID, "hk_ppo_count: bad field");
     if (field <= HK_PPO_ADAM_V) return (int)t.P;
     if (field <= HK_PPO_RET) return t.adv_gen < 0 ? 0 : t.n;

@@ -357,7 +357,8 @@ class RacingEnv:
 
     def ppo_trainer(self, policy_index, critic=None, **cfg):
         """-> ppo.PPOTrainer of an attached policy (hk_ppo_create): it trains on this handle's closed rollouts and publishes into the policy.
-        sequence_length=64 (PPOTrainer's named argument, passed through): a recurrent actor's trainer (hk_ppo_create_recurrent), truncated BPTT over windows of that many rows"""
+        sequence_length=64 (PPOTrainer's named argument, passed through): a recurrent actor's trainer (hk_ppo_create_recurrent), truncated BPTT over windows of that many rows;
+        critic_memory_size=256 with it (passed through too): the critic gets an LSTM cell of its own (hk_ppo_create_recurrent_critic)"""
         from .ppo import PPOTrainer
         return PPOTrainer(self, policy_index, critic, **cfg)
 

@@ -10,6 +10,7 @@ and leaves updated weights in the attached policy, so that the next step() acts 
     tr.update(3, 512, 3e-4, max_grad_norm=0.5, target_kl=0.02); tr.last_report      # clip by the global norm, KL stop (hk.h "LONG RUNS")
     tr.save(path); ...; tr2.load(path)           # exact resume: masters, Adam moments, the two counters, precision, normaliser
     tr = PPOTrainer(env, 0, sequence_length=64)  # a recurrent actor: truncated BPTT over windows of 64 rows; ids and `minibatch` count sequences
+    tr = PPOTrainer(env, 0, sequence_length=64, critic_memory_size=256)     # ... with a recurrent critic: an LSTM cell of its own (hk.h RECURRENT CRITIC)
 
 Nothing is computed here: the arrays below only describe the flat parameter layout the library uses."""
 import ctypes as C
@@ -62,7 +63,8 @@ def gemm_bf16(env, epi, A, B, bias=None, aux=None):
 
 def param_layout(in_dim, hidden, n_layers, n_branch, memory_size=0):
     """-> [(name, shape)] of one network in the flat vector's order (torch layout; n_branch 0: the critic, whose value head is W_mu / b_mu).
-    memory_size > 0: a recurrent actor — the cell (W_ih, W_hh, b_ih, b_hh; gates i f g o) follows the trunk and the heads are m = memory_size / 2 wide"""
+    memory_size > 0: a recurrent actor — the cell (W_ih, W_hh, b_ih, b_hh; gates i f g o) follows the trunk and the heads are m = memory_size / 2 wide;
+    with n_branch 0: a recurrent critic — trunk, cell, then the value head W_mu [m], b_mu"""
     out = []
     for l in range(n_layers):
         out += [("W%d" % l, (hidden, in_dim if l == 0 else hidden)), ("b%d" % l, (hidden,))]
@@ -242,8 +244,9 @@ def _need(d, key, what="state"):
 
 
 def check_state(d, kind, actor_shape, critic_shape, sequence_length=0):
-    """the host-only head of load_state_dict: a checkpoint's format, trainer kind (absent: "ppo"), the two network shapes and the sequence
-    length (absent: 0, not recurrent) against the loading trainer's; ValueError names the field"""
+    """the host-only head of load_state_dict: a checkpoint's format, trainer kind (absent: "ppo"), the two network shapes (a recurrent critic's
+    carries its memory size as a fifth entry) and the sequence length (absent: 0, not recurrent) against the loading trainer's; a recurrent
+    critic's state must carry critic_mem_in / critic_mem_out; ValueError names the field"""
     if _need(d, "format") != CHECKPOINT_FORMAT:
         raise ValueError("state: format %r is not %d" % (d["format"], CHECKPOINT_FORMAT))
     if str(d.get("kind", "ppo")) != kind:
@@ -253,6 +256,11 @@ def check_state(d, kind, actor_shape, critic_shape, sequence_length=0):
             raise ValueError("state: %s %s differs from the trainer's %s" % (key, list(np.asarray(d[key])), list(np.asarray(want))))
     if int(d.get("sequence_length", 0)) != int(sequence_length):
         raise ValueError("state: sequence_length %d differs from the trainer's %d" % (int(d.get("sequence_length", 0)), int(sequence_length)))
+    if len(np.asarray(critic_shape)) > 4:
+        for key in ("critic_mem_in", "critic_mem_out"):
+            a = np.asarray(_need(d, key))
+            if a.dtype != np.float32 or a.ndim != 1 or a.size % int(np.asarray(critic_shape)[4]):
+                raise ValueError("state: %s is float32 [E S %d]" % (key, int(np.asarray(critic_shape)[4])))
 
 
 def _option(name, v, inf_ok):
@@ -268,11 +276,16 @@ def _option(name, v, inf_ok):
 class PPOTrainer:
     """One trainer of RacingEnv `env`'s attached policy `policy_index` (hk_ppo_create).  critic: a Policy with n_branch 0 semantics (its trunk and
     W_mu / b_mu are used) or None for Policy.random-style weights of the actor's shape; precision: "f32" | "bf16" (set_precision); cfg: DEFAULTS' keys.
-    sequence_length: given for a recurrent actor (hk_ppo_create_recurrent): ids and `minibatch` then count sequences of that many rows."""
+    sequence_length: given for a recurrent actor (hk_ppo_create_recurrent): ids and `minibatch` then count sequences of that many rows.
+    critic_memory_size (with sequence_length): the critic gets an LSTM cell of m_v = critic_memory_size / 2 units of its own
+    (hk_ppo_create_recurrent_critic); critic: then a recurrent Policy of that memory size (trunk, cell, W_mu [m_v] / b_mu) or None for a seeded
+    random one.  value_chunk_steps: time steps per value-pass launch (0: the default; the result does not depend on it)."""
     KIND = "ppo"          # a checkpoint's "kind" entry (absent in a PPO checkpoint: it reads as "ppo"); poca.POCATrainer: "poca"
     sequence_length = 0   # > 0: a recurrent trainer (set by __init__ when sequence_length is given)
 
-    def __init__(self, env, policy_index, critic=None, precision="f32", sequence_length=None, **cfg):
+    critic_memory_size = 0   # > 0: a recurrent critic
+
+    def __init__(self, env, policy_index, critic=None, precision="f32", sequence_length=None, critic_memory_size=None, value_chunk_steps=0, **cfg):
         if precision not in PRECISIONS:
             raise ValueError("precision: one of %s" % sorted(PRECISIONS))
         bad = set(cfg) - set(DEFAULTS)
@@ -281,8 +294,14 @@ class PPOTrainer:
         self.env, self.index = env, int(policy_index)
         self.actor_policy = env._policies[self.index]
         a = self.actor_policy
+        if critic_memory_size is not None and sequence_length is None:
+            raise ValueError("critic_memory_size: a recurrent critic needs sequence_length (a recurrent actor's trainer)")
+        self.critic_memory_size = 0 if critic_memory_size is None else int(critic_memory_size)
         if critic is None:
-            critic = Policy.random(a.in_dim, a.hidden, len(a.W), n_branch=1, stack=a.stack, seed=0xC417 + self.index, normalize=False)
+            critic = Policy.random(a.in_dim, a.hidden, len(a.W), n_branch=1, stack=a.stack, seed=0xC417 + self.index, normalize=False,
+                                   memory_size=self.critic_memory_size)
+        if critic_memory_size is not None and critic.memory_size != self.critic_memory_size:
+            raise ValueError("critic: a recurrent Policy with memory_size %d (it has %d)" % (self.critic_memory_size, critic.memory_size))
         self.critic_policy = critic
         c = dict(DEFAULTS, **cfg)
         self.cfg = c
@@ -294,6 +313,10 @@ class PPOTrainer:
         self.sequence_length = 0 if sequence_length is None else int(sequence_length)
         if sequence_length is None:
             rc = env.L.hk_ppo_create(env.h, self.index, C.byref(d), C.byref(pc))
+        elif critic_memory_size is not None:
+            rd = _lib.PpoRecurrentCriticDesc(self.sequence_length, int(value_chunk_steps), (C.c_int32 * 2)(0, 0))
+            cell = critic.lstm_desc()
+            rc = env.L.hk_ppo_create_recurrent_critic(env.h, self.index, C.byref(d), C.byref(cell) if cell is not None else None, C.byref(pc), C.byref(rd))
         else:
             rd = _lib.PpoRecurrentDesc(self.sequence_length, 0)
             rc = env.L.hk_ppo_create_recurrent(env.h, self.index, C.byref(d), C.byref(pc), C.byref(rd))
@@ -301,7 +324,7 @@ class PPOTrainer:
             env._ck(rc)
         self.t = rc
         self.actor_layout = param_layout(a.in_dim, a.hidden, len(a.W), a.n_branch, a.memory_size if self.sequence_length else 0)
-        self.critic_layout = param_layout(a.in_dim, critic.hidden, len(critic.W), 0)
+        self.critic_layout = param_layout(a.in_dim, critic.hidden, len(critic.W), 0, self.critic_memory_size)
         self.n_actor = sum(int(np.prod(s)) for _, s in self.actor_layout)
         self.last_report = None           # of the last update(): a dict when it was given an option, else None
         self.set_precision(precision)
@@ -398,7 +421,7 @@ class PPOTrainer:
 
     # ---- buffers
     def _field(self, name):
-        idx = _lib.PPO_FIELDS[name] if name in _lib.PPO_FIELDS else _lib.PPO_RECURRENT_FIELDS[name]
+        idx = next(f[name] for f in (_lib.PPO_FIELDS, _lib.PPO_RECURRENT_FIELDS, _lib.PPO_RECURRENT_CRITIC_FIELDS) if name in f)
         n = self.env.L.hk_ppo_count(self.env.h, self.t, idx)
         if n < 0:
             self._ck(n)
@@ -424,12 +447,30 @@ class PPOTrainer:
             def __init__(self, ptr, n, ts):
                 self.__cuda_array_interface__ = {"shape": (n,), "typestr": ts, "data": (int(ptr), False), "version": 3, "strides": None}
         out = {}
-        for name, idx in list(_lib.PPO_FIELDS.items()) + (list(_lib.PPO_RECURRENT_FIELDS.items()) if self.sequence_length else []):
+        for name, idx in (list(_lib.PPO_FIELDS.items()) + (list(_lib.PPO_RECURRENT_FIELDS.items()) if self.sequence_length else []) +
+                          (list(_lib.PPO_RECURRENT_CRITIC_FIELDS.items()) if self.critic_memory_size else [])):
             n = self.env.L.hk_ppo_count(self.env.h, self.t, idx)
             ptr = self.env.L.hk_ppo_ptr(self.env.h, self.t, idx) if n > 0 else None
             if ptr:
                 out[name] = torch.as_tensor(_Ext(ptr, n, {"perm": "<i4", "shadow": "<i2", "clip": "<f8"}.get(name, "<f4")), device="cuda:%d" % self.env.built.cfg.device_id)
         return out
+
+    def write(self, name, a):
+        """host array -> an HK_PPO_* field the contract calls writable (params, adam_m, adam_v, critic_mem_in, critic_mem_out); the size must fit"""
+        self.env.synchronize()
+        ptr, n = self._field(name)
+        a = np.ascontiguousarray(a, _DTYPES.get(name, np.float32)).reshape(-1)
+        if a.size != n:
+            raise ValueError("%s: %d elements (given %d)" % (name, n, a.size))
+        _lib.copy_host_to_device(ptr, a.ctypes.data, a.nbytes)
+
+    def reset_critic_memory(self):
+        """a recurrent critic: zero the carried critic memory — MEM_IN, which the next advantages() on the current rollout reads, and MEM_OUT,
+        which the first advantages() on the next rollout starts from"""
+        if not self.critic_memory_size:
+            raise ValueError("reset_critic_memory: the trainer has no recurrent critic")
+        for name in ("critic_mem_in", "critic_mem_out"):
+            self.write(name, np.zeros(self._field(name)[1], np.float32))
 
     def actor_params(self, flat=None):
         flat = self.read("params") if flat is None else flat
@@ -476,7 +517,7 @@ class PPOTrainer:
     def _shapes(self):
         a, c = self.actor_policy, self.critic_policy
         sa = [a.in_dim, a.hidden, len(a.W), a.n_branch] + ([a.memory_size] if self.sequence_length else [])
-        return (np.array(sa, np.int64), np.array([a.in_dim, c.hidden, len(c.W), 0], np.int64))
+        return (np.array(sa, np.int64), np.array([a.in_dim, c.hidden, len(c.W), 0] + ([self.critic_memory_size] if self.critic_memory_size else []), np.int64))
 
     def state_dict(self):
         """-> dict of numpy arrays and scalars: format, the two network shapes, params / adam_m / adam_v, adam_steps, epochs_done, precision, cfg
@@ -489,6 +530,8 @@ class PPOTrainer:
                       for k in DEFAULTS})
         if self.sequence_length:
             d["sequence_length"] = self.sequence_length
+        if self.critic_memory_size:
+            d["critic_mem_in"], d["critic_mem_out"] = self.read("critic_mem_in"), self.read("critic_mem_out")
         if self.actor_policy.norm_mean is not None:
             try:
                 n, mean, m2 = self.normalizer_state()
@@ -521,11 +564,20 @@ class PPOTrainer:
                                      _need(norm, "m2", "state normalizer"), self.actor_policy.in_dim)
             if self.actor_policy.norm_mean is None:
                 raise ValueError("state: normalizer given, but the policy was attached without statistics")
+        cmem = {}
+        if self.critic_memory_size:
+            for name in ("critic_mem_in", "critic_mem_out"):
+                n = self.env.L.hk_ppo_count(self.env.h, self.t, _lib.PPO_RECURRENT_CRITIC_FIELDS[name])
+                if np.asarray(d[name]).shape != (n,):
+                    raise ValueError("state: %s is float32 [%d]" % (name, n))
+                cmem[name] = np.ascontiguousarray(d[name])
         self.set_counters(_need(d, "adam_steps"), _need(d, "epochs_done"))          # (the library's refusals come first: nothing is written after one)
         self.env.synchronize()
         for name, a in vec.items():
             ptr, _ = self._field(name)
             _lib.copy_host_to_device(ptr, a.ctypes.data, a.nbytes)
+        for name, a in cmem.items():
+            self.write(name, a)
         self.set_precision(d["precision"])
         if norm is not None:
             self.normalizer_load(*norm)

@@ -35,6 +35,7 @@ namespace KartGame.AI.Native
                          HK_POLICY_PREC_F32 = 0, HK_POLICY_PREC_BF16 = 1,      // hk_policy_precision
                          HK_PPO_STATS = 6;
         public const int HK_PPO_MB_MEMORY = 32;      // hk_ppo_recurrent_field: a recurrent trainer's extra buffer, outside [0, HK_PPO_FIELDS)
+        public const int HK_PPO_CRITIC_MEMORY = 33, HK_PPO_CRITIC_MEM_IN = 34, HK_PPO_CRITIC_MEM_OUT = 35, HK_PPO_MB_CRITIC_MEMORY = 36;      // hk_ppo_recurrent_critic_field
         // hk_poca_field: the extra buffers of a POCA trainer (hk_poca_ptr / hk_poca_count); HK_POCA_STATS: L_b, reserved
         public const int HK_POCA_B_OLD = 0, HK_POCA_MB_BASELINE = 1, HK_POCA_TEAM_REWARD = 2, HK_POCA_FIELDS = 3, HK_POCA_STATS = 2,
                          HK_POCA_MAX_GROUP = 4, HK_POCA_HEADS = 4;
@@ -428,6 +429,15 @@ namespace KartGame.AI.Native
         public int reserved;
     }
 
+    // hk_ppo_recurrent_critic_desc: hk_ppo_create_recurrent_critic's sequence length and value-pass chunk (hk.h "PPO trainer" RECURRENT CRITIC)
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct HkPpoRecurrentCriticDesc
+    {
+        public int sequence_length;
+        public int value_chunk_steps;
+        public fixed int reserved[2];
+    }
+
     // hk_ppo_update_opts / hk_ppo_update_report: hk_ppo_update_opt's options (0: off) and what it did (hk.h "LONG RUNS")
     [StructLayout(LayoutKind.Sequential)]
     public struct HkPpoUpdateOpts
@@ -540,6 +550,7 @@ namespace KartGame.AI.Native
         // PPO trainer: train an attached actor on the closed rollout, on the device (hk.h "PPO trainer")
         [DllImport(Lib)] public static extern int hk_ppo_create(IntPtr h, int policy, HkPolicyDesc* critic, HkPpoConfig* cfg);
         [DllImport(Lib)] public static extern int hk_ppo_create_recurrent(IntPtr h, int policy, HkPolicyDesc* critic, HkPpoConfig* cfg, HkPpoRecurrentDesc* r);
+        [DllImport(Lib)] public static extern int hk_ppo_create_recurrent_critic(IntPtr h, int policy, HkPolicyDesc* critic, HkPolicyLstmDesc* criticCell, HkPpoConfig* cfg, HkPpoRecurrentCriticDesc* r);
         [DllImport(Lib)] public static extern int hk_ppo_advantages(IntPtr h, int trainer);
         [DllImport(Lib)] public static extern int hk_ppo_minibatch(IntPtr h, int trainer, IntPtr rowsDev, int m, float eps, float beta, float* stats);
         [DllImport(Lib)] public static extern int hk_ppo_adam(IntPtr h, int trainer, float lr);

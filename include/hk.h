@@ -708,8 +708,8 @@ void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* 
  * reference's *-LSTM behaviours train with memory_size 256, sequence_length 64).  It returns a trainer index of the same table and every hk_ppo_*
  * entry point takes it; a trainer made by hk_ppo_create or hk_ppo_create_poca computes what it computed, bit for bit, issues the launches it issued
  * and allocates nothing more.  hk_ppo_create itself keeps refusing a policy with memory (HK_ERR_UNSUPPORTED), hk_ppo_config is as it was.
- * The CRITIC stays the feed-forward critic above on the stacked input — ML-Agents gives the critic an LSTM of its own; not doing so is a
- * documented departure — so hk_ppo_advantages, GAE and V_OLD are those of a plain trainer.
+ * The CRITIC of a trainer made by hk_ppo_create_recurrent stays the feed-forward critic above on the stacked input, so its hk_ppo_advantages,
+ * GAE and V_OLD are those of a plain trainer; ML-Agents gives the critic an LSTM of its own: hk_ppo_create_recurrent_critic, RECURRENT CRITIC below.
  * SEQUENCES.  With L = sequence_length and R the completed rows, window k of agent (e, j) is the rows t in [k L, min((k + 1) L, R)); sequence id
  * s = (k E + e) S + j, n_seq = ceil(R / L) E S.  The memory entering a window's first row is the recorder's MEMORY[k L], a constant: no gradient
  * flows into it.  Inside a window the training forward carries the memory itself.  At a row with FIRST[t] == 1 the memory read is exactly zero
@@ -737,8 +737,45 @@ void* hk_rollout_ptr(hk_handle h, int field);   /* device pointer of an HK_RO_* 
  * group-major Wq_ih / Wq_hh copies and the summed bias.
  * Refused with HK_ERR_INVALID, state as it was, the message naming the argument: a NULL r, sequence_length < 1, reserved != 0, a policy without
  * memory (use hk_ppo_create) and whatever hk_ppo_create refuses.  HK_ERR_UNSUPPORTED: hk_ppo_set_precision(HK_PPO_PREC_BF16) on a recurrent trainer.
- * Out of scope for recurrent training: a recurrent critic, recurrent POCA, bf16 for the cell or its training products, snapshot pools and
- * self-play swaps of recurrent actors, m_cell above 128, burn-in rows.
+ * RECURRENT CRITIC (hk_ppo_create_recurrent_critic: the recurrent trainer above whose critic has an LSTM cell of its own, as ML-Agents' ValueNetwork
+ * built from the actor's network_settings; the reference's *-LSTM behaviours trained so).  Everything above holds for the actor side, unchanged;
+ * a trainer made by hk_ppo_create, hk_ppo_create_recurrent or hk_ppo_create_poca computes what it computed, bit for bit, issues the launches it
+ * issued and allocates nothing more.
+ * CRITIC.  The actor's normalised, clipped stacked input (the ACTOR's normaliser) -> n_layers x (Linear + Swish) of width Hc -> ONE LSTM cell of
+ * m_v = critic_cell.memory_size / 2 units (a multiple of 32 in [32, 128], gates i f g o) -> v = b_v + sum_k W_v[k] h'[k].  Its arithmetic is a
+ * recurrent actor's, bit for bit: a gate pre-activation is the fmaf chain seeded with fp32(b_ih + b_hh), ascending over a[0 .. Hc), then over
+ * h[0 .. m_v), on v_mfma_f32_32x32x2_f32; the cell is hk_lstm_cell; the value head is the ascending fmaf chain of the actor's mu head.  EXACTNESS:
+ * a recurrent POLICY whose trunk, cell and W_mu / b_mu are the critic's trunk, cell and W_v / b_v and whose normaliser is the actor's returns,
+ * through hk_policy_forward_mem, a mu that is V_OLD bit for bit.
+ * CRITIC MEMORY.  [h | c], 2 m_v floats per (e, j).  At a row with FIRST[t] == 1 the memory read is exactly zero (the actor's rule).  At row 0 of
+ * a rollout the memory read is HK_PPO_CRITIC_MEM_IN[e][j], subject to the FIRST rule; it is all zero at create.  The first hk_ppo_advantages on
+ * a rollout generation the trainer has not seen sets MEM_IN := MEM_OUT of its previous call (zero before any), then runs; a repeated call on
+ * the same rollout (after hk_ppo_normalizer_update, say) re-uses MEM_IN unchanged and gives the same bits.  HK_PPO_CRITIC_MEM_OUT is the memory
+ * after row R - 1, zero where DONE[R - 1] != 0.  Both are writable through hk_ppo_ptr, as PARAMS is: writing MEM_IN acts on the next call on
+ * the SAME rollout, writing MEM_OUT on the first call on the next one.  This is ML-Agents' critic_memory_dict: it is carried whatever happened
+ * between the rollouts (a reset, other steps), and it goes stale under parameter updates — it was computed by the parameters of the pass that
+ * wrote it, and is not recomputed.
+ * VALUE PASS.  hk_ppo_advantages runs the critic sequentially: for every (e, j), in time order t = 0 .. R - 1, one critic step per row gives
+ * V_OLD[t]; one more step on the bootstrap input (NEXT_OBS pushed into the stack) from the memory after row R - 1 gives the bootstrap value,
+ * unused where DONE[R - 1].  GAE and the advantage normalisation run exactly as for a plain trainer.  It records HK_PPO_CRITIC_MEMORY
+ * [ceil(R / L)][E][S][2 m_v]: the memory carried INTO row k L, before the FIRST rule (the training forward applies that rule itself) — the critic's
+ * twin of the recorder's MEMORY[k L].  The steps go value_chunk_steps at a time per launch (0: the default, 16) over tiles of sequences; the
+ * result depends on neither, bit for bit.
+ * TRAINING.  Windows, sequence ids, the time-major gather, dead rows and the skipped-id rule are those above.  The critic's forward over a window
+ * starts from CRITIC_MEMORY[k], a constant (no gradient flows into it), carries the memory itself and zeroes it at FIRST, in value and in
+ * gradient; the loss reads the critic's h' (m_v wide) under W_v.  The backward is BACKWARD above applied to the critic: the value-head delta
+ * onto h', the cell backward L times in reverse with the recurrent-delta product, dW_ih, dW_hh and the two biases (the same gradient) over all
+ * rows at once in the fixed-order split-K forms, da into the critic's trunk.  No float atomics.  At unchanged parameters: MB_VALUE == V_OLD bit
+ * for bit on every live row; HK_PPO_MB_CRITIC_MEMORY at row t equals CRITIC_MEMORY of the window starting at t + 1 wherever t + 1 is a window
+ * start, and MEM_OUT at the last row where DONE == 0.
+ * PARAMS, critic part: the trunk; W_ih [4 m_v][Hc], W_hh [4 m_v][m_v], b_ih, b_hh [4 m_v]; W_v [m_v], b_v.  Adam, the clip-aware step (one norm
+ * over everything), the KL stop, the counters, the normaliser and publish keep their meaning; the critic is never published.
+ * Refused with HK_ERR_INVALID, state as it was, the message naming the argument: a NULL r or critic_cell, sequence_length < 1,
+ * value_chunk_steps < 0, reserved != 0, a cell whose memory_size is odd or whose m_v is not a multiple of 32 in [32, 128], a NULL weight
+ * pointer, a policy without memory and whatever hk_ppo_create_recurrent refuses.  HK_ERR_UNSUPPORTED: hk_ppo_set_precision(HK_PPO_PREC_BF16).
+ * Out of scope for recurrent training: a recurrent critic with a feed-forward actor, recurrent POCA, bf16 for either cell or its training
+ * products, snapshot pools and self-play swaps of recurrent actors, m_cell above 128, ML-Agents' padding of a trajectory's first, short
+ * sequence, burn-in rows.
  * Out of scope (self-play opponent swaps, episode statistics and ELO: "SELF-PLAY" below; POCA and group rewards: "POCA" below):
  * a normaliser for policies attached with normalize == 0,
  * multi-GPU gradient all-reduce and bf16 optimiser state.  Everything is asynchronous on hk_stream unless noted. */
@@ -769,6 +806,22 @@ typedef enum hk_ppo_recurrent_field {
 } hk_ppo_recurrent_field;
 typedef struct hk_ppo_recurrent_desc { int32_t sequence_length, reserved; } hk_ppo_recurrent_desc;
 int hk_ppo_create_recurrent(hk_handle h, int policy, const hk_policy_desc* critic, const hk_ppo_config* cfg, const hk_ppo_recurrent_desc* r);
+/* the fields a recurrent critic adds (RECURRENT CRITIC); they continue hk_ppo_recurrent_field; count 0 and hk_ppo_ptr refusing on every other trainer */
+typedef enum hk_ppo_recurrent_critic_field {
+    HK_PPO_CRITIC_MEMORY = 33,       /* fp32 [ceil(R / L)][E][S][2 m_v]: the critic memory carried INTO row k L, before the FIRST rule; after hk_ppo_advantages */
+    HK_PPO_CRITIC_MEM_IN = 34,       /* fp32 [E][S][2 m_v]: the critic memory read at row 0 (writable) */
+    HK_PPO_CRITIC_MEM_OUT = 35,      /* fp32 [E][S][2 m_v]: the critic memory after row R - 1, zero where DONE[R - 1] (writable) */
+    HK_PPO_MB_CRITIC_MEMORY = 36     /* fp32 [L][m][2 m_v]: the memory [h' | c'] each row's critic cell wrote in the last minibatch */
+} hk_ppo_recurrent_critic_field;
+typedef struct hk_ppo_recurrent_critic_desc {
+    int32_t sequence_length;
+    int32_t value_chunk_steps;   /* time steps per value-pass launch; 0: the default */
+    int32_t reserved[2];         /* 0 */
+} hk_ppo_recurrent_critic_desc;
+int hk_ppo_create_recurrent_critic(hk_handle h, int policy,
+        const hk_policy_desc* critic,            /* trunk; W_mu [m_v], b_mu: the value head */
+        const hk_policy_lstm_desc* critic_cell,  /* the critic's own cell */
+        const hk_ppo_config* cfg, const hk_ppo_recurrent_critic_desc* r);
 int hk_ppo_advantages(hk_handle h, int trainer);
 int hk_ppo_minibatch(hk_handle h, int trainer, const int32_t* rows_dev, int m, float eps, float beta, float* stats /*[HK_PPO_STATS]*/);
 int hk_ppo_adam(hk_handle h, int trainer, float lr);
