@@ -261,6 +261,7 @@ SYMBOLS = {
     "hk_policy_forward_mem": (C.c_int, [_H, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
     "hk_policy_memory_get": (C.c_int, [_H, C.c_int, _fp]),
     "hk_policy_memory_set": (C.c_int, [_H, C.c_int, _fp]),
+    "hk_policy_memory_clear": (C.c_int, [_H, C.c_int]),
     "hk_get_actions": (C.c_int, [_H, _fp, C.POINTER(C.c_int32)]),
     "hk_rollout_begin": (C.c_int, [_H, C.c_int]),
     "hk_rollout_rows": (C.c_int, [_H]),
@@ -293,6 +294,7 @@ SYMBOLS = {
     "hk_poca_count": (C.c_int, [_H, C.c_int, C.c_int]),
     "hk_poca_stats": (C.c_int, [_H, C.c_int, _fp]),
     "hk_policy_pool_create": (C.c_int, [_H, C.c_int, C.c_int]),
+    "hk_policy_pool_create_recurrent": (C.c_int, [_H, C.c_int, C.c_int]),
     "hk_policy_pool_save": (C.c_int, [_H, C.c_int, C.c_int, C.c_int]),
     "hk_policy_pool_load": (C.c_int, [_H, C.c_int, C.c_int, C.c_int]),
     "hk_policy_pool_put": (C.c_int, [_H, C.c_int, C.c_int, _fp]),

@@ -273,6 +273,9 @@ struct hk_context {
     struct Pool {
         int in_dim = 0, stack = 0, hidden = 0, n_layers = 0, n_branch = 0, normalize = 0;    // the SHAPE
         hk::PpoNet net;                // the flat actor layout (base 0); a slot is net.count floats, then mean, std [in_dim] when normalize
+        int m = 0;                     // > 0: a recurrent pool (hk_policy_pool_create_recurrent) of memory_size 2m; net is then the trunk alone
+        hk::PpoLstmNet lnet;           // (it ends at lnet.oWih) and lnet the cell and the m-wide heads behind it; the actor is lnet.end floats
+        size_t actor = 0;              // floats of the actor part of a slot: net.count, or lnet.end for a recurrent pool
         int slots = 0;
         size_t count = 0;              // floats per slot
         float* buf = nullptr;          // [slots][count]
@@ -1371,6 +1374,23 @@ static int policy_memory_copy(hk_handle h, const char* fn, bool set, int policy,
 
 int hk_policy_memory_get(hk_handle h, int policy, float* mem) { return policy_memory_copy(h, "hk_policy_memory_get", false, policy, mem); }
 int hk_policy_memory_set(hk_handle h, int policy, const float* mem) { return policy_memory_copy(h, "hk_policy_memory_set", true, policy, const_cast<float*>(mem)); }
+
+// hk_policy_memory_set of an all-zero array without the host array: a device fill and the same epoch kernel, nothing waited for
+int hk_policy_memory_clear(hk_handle h, int policy)
+{
+    HK_NEED_ENV(h);
+    const std::string f = "hk_policy_memory_clear";
+    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, f + ": bad policy index");
+    const hk::PolicyDevice& pd = h->policy[policy];
+    if (pd.lq.m == 0) return fail(h, HK_ERR_INVALID, f + ": the policy has no memory (policy: attached without an LSTM)");
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, f + ": refused while a rollout is open (hk_rollout_close first)");
+    const int pairs = h->cfg.num_envs * pd.q.n_slots;
+    h->ep.moved = true;
+    HK_HIP(h, hipMemsetAsync(pd.lq.mem, 0, (size_t)pairs * 2 * pd.lq.m * sizeof(float), h->stream));
+    hipLaunchKernelGGL(hk::policy_epoch_current_kernel, dim3(nblk(pairs)), dim3(256), 0, h->stream, pd.q, h->cfg.num_envs, h->dev.envs, h->dev.slot_of);
+    HK_HIP(h, hipGetLastError());
+    return HK_OK;
+}
 
 int hk_policy_set_precision(hk_handle h, int policy, int precision)
 {
@@ -3044,15 +3064,58 @@ int pool_check(hk_handle h, const char* fn, int pool, int slot, int policy)
     if (slot < 0 || slot >= pl.slots) return fail(h, HK_ERR_INVALID, f + ": bad slot index");
     if (policy == -1) return HK_OK;
     if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, f + ": bad policy index");
-    if (h->policy[policy].lq.m > 0) return fail(h, HK_ERR_UNSUPPORTED, f + ": policy: a recurrent actor (snapshot pools of recurrent actors are out of scope)");
+    const int pm = h->policy[policy].lq.m;
+    if (pm > 0 && pl.m == 0) return fail(h, HK_ERR_UNSUPPORTED, f + ": policy: a recurrent actor (snapshot pools of recurrent actors are out of scope)");
+    if (pm == 0 && pl.m > 0) return fail(h, HK_ERR_INVALID, f + ": policy: an actor without memory (the pool holds recurrent actors: hk_policy_pool_create_recurrent)");
     const hk::PolicyParams& q = h->policy[policy].q;
     if (q.in_dim != pl.in_dim || q.stack != pl.stack || q.hidden != pl.hidden || q.n_layers != pl.n_layers || q.n_branch != pl.n_branch ||
         (q.normalize != 0) != (pl.normalize != 0))
         return fail(h, HK_ERR_INVALID, f + ": the policy's shape (in_dim, stack, hidden, n_layers, n_branch, normalize) differs from the pool's");
+    if (pm != pl.m) return fail(h, HK_ERR_INVALID, f + ": the policy's memory_size differs from the pool's");
     return HK_OK;
 }
 
 inline float* pool_slot(const hk_context::Pool& pl, int slot) { return pl.buf + (size_t)slot * pl.count; }
+
+// hk_policy_pool_create (recurrent false) and hk_policy_pool_create_recurrent: the checks, the SHAPE, the slot layout and the allocation
+int pool_create(hk_handle h, const char* fn, bool recurrent, int policy, int slots)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, f + "bad policy index");
+    if (slots < 1 || slots > HK_POOL_MAX_SLOTS) return fail(h, HK_ERR_INVALID, f + "slots outside [1, HK_POOL_MAX_SLOTS]");
+    if (h->n_pools >= HK_MAX_POOLS) return fail(h, HK_ERR_INVALID, f + "HK_MAX_POOLS pools already exist");
+    const int m = h->policy[policy].lq.m;
+    if (!recurrent && m > 0) return fail(h, HK_ERR_UNSUPPORTED, f + "policy: a recurrent actor (snapshot pools of recurrent actors are out of scope)");
+    if (recurrent && m == 0) return fail(h, HK_ERR_INVALID, f + "policy: an actor without memory (use hk_policy_pool_create)");
+    const hk::PolicyParams& q = h->policy[policy].q;
+    hk_context::Pool pl;
+    pl.in_dim = q.in_dim; pl.stack = q.stack; pl.hidden = q.hidden; pl.n_layers = q.n_layers; pl.n_branch = q.n_branch; pl.normalize = q.normalize != 0;
+    pl.net.layout(q.in_dim, q.hidden, q.n_layers, q.n_branch, 0);
+    pl.actor = pl.net.count;
+    if (recurrent) {          // the trunk through ppo_publish_kernel (a net that ends before the cell), the rest through ppo_lstm_publish_kernel: hk_ppo_publish's split
+        pl.m = m;
+        pl.lnet.layout(q.hidden, m, q.n_branch, pl.net.oWmu);
+        pl.actor = pl.lnet.end;
+        pl.net.count = pl.lnet.oWih;
+        pl.net.n_branch = 0;
+        pl.net.oWmu = pl.net.obmu = pl.net.ols = pl.net.oWbr = pl.net.obbr = pl.net.count;      // (no element of the trunk matches a head)
+    }
+    pl.slots = slots;
+    pl.count = pl.actor + (pl.normalize ? 2 * (size_t)q.in_dim : 0);
+    HK_HIP(h, hipMalloc(&pl.buf, (size_t)slots * pl.count * sizeof(float)));
+    h->pool[h->n_pools] = pl;
+    return h->n_pools++;
+}
+
+// the two launches that move an actor between a slot and a policy's inference copies (TO_POLICY: the load)
+template <bool TO_POLICY>
+void pool_move(hk_handle h, const hk_context::Pool& pl, hk::PolicyDevice& pd, float* slot)
+{
+    hipLaunchKernelGGL(hk::ppo_publish_kernel<TO_POLICY>, dim3(nblk(pl.net.count)), dim3(256), 0, h->stream, pd.q, pl.net, slot);
+    if (pl.m)
+        hipLaunchKernelGGL(hk::ppo_lstm_publish_kernel<TO_POLICY>, dim3(nblk(pl.lnet.end - pl.lnet.oWih)), dim3(256), 0, h->stream, pd.q, pd.lq, pd.braw,
+                           pl.lnet, slot);
+}
 
 }  // namespace
 }  // extern "C++"
@@ -3060,19 +3123,13 @@ inline float* pool_slot(const hk_context::Pool& pl, int slot) { return pl.buf + 
 int hk_policy_pool_create(hk_handle h, int policy, int slots)
 {
     HK_NEED_ENV(h);
-    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, "hk_policy_pool_create: bad policy index");
-    if (slots < 1 || slots > HK_POOL_MAX_SLOTS) return fail(h, HK_ERR_INVALID, "hk_policy_pool_create: slots outside [1, HK_POOL_MAX_SLOTS]");
-    if (h->n_pools >= HK_MAX_POOLS) return fail(h, HK_ERR_INVALID, "hk_policy_pool_create: HK_MAX_POOLS pools already exist");
-    if (h->policy[policy].lq.m > 0) return fail(h, HK_ERR_UNSUPPORTED, "hk_policy_pool_create: policy: a recurrent actor (snapshot pools of recurrent actors are out of scope)");
-    const hk::PolicyParams& q = h->policy[policy].q;
-    hk_context::Pool pl;
-    pl.in_dim = q.in_dim; pl.stack = q.stack; pl.hidden = q.hidden; pl.n_layers = q.n_layers; pl.n_branch = q.n_branch; pl.normalize = q.normalize != 0;
-    pl.net.layout(q.in_dim, q.hidden, q.n_layers, q.n_branch, 0);
-    pl.slots = slots;
-    pl.count = pl.net.count + (pl.normalize ? 2 * (size_t)q.in_dim : 0);
-    HK_HIP(h, hipMalloc(&pl.buf, (size_t)slots * pl.count * sizeof(float)));
-    h->pool[h->n_pools] = pl;
-    return h->n_pools++;
+    return pool_create(h, "hk_policy_pool_create", false, policy, slots);
+}
+
+int hk_policy_pool_create_recurrent(hk_handle h, int policy, int slots)
+{
+    HK_NEED_ENV(h);
+    return pool_create(h, "hk_policy_pool_create_recurrent", true, policy, slots);
 }
 
 int hk_policy_pool_count(hk_handle h, int pool)
@@ -3089,14 +3146,14 @@ int hk_policy_pool_save(hk_handle h, int pool, int slot, int policy)
     int rc = pool_check(h, "hk_policy_pool_save", pool, slot, policy);
     if (rc) return rc;
     auto& pl = h->pool[pool];
-    const hk::PolicyParams& q = h->policy[policy].q;
+    hk::PolicyDevice& pd = h->policy[policy];
     float* dst = pool_slot(pl, slot);
-    hipLaunchKernelGGL(hk::ppo_publish_kernel<false>, dim3(nblk(pl.net.count)), dim3(256), 0, h->stream, q, pl.net, dst);
+    pool_move<false>(h, pl, pd, dst);
     HK_HIP(h, hipGetLastError());
     if (pl.normalize) {
         const size_t nb = (size_t)pl.in_dim * sizeof(float);
-        HK_HIP(h, hipMemcpyAsync(dst + pl.net.count, q.mean, nb, hipMemcpyDeviceToDevice, h->stream));
-        HK_HIP(h, hipMemcpyAsync(dst + pl.net.count + pl.in_dim, q.std, nb, hipMemcpyDeviceToDevice, h->stream));
+        HK_HIP(h, hipMemcpyAsync(dst + pl.actor, pd.q.mean, nb, hipMemcpyDeviceToDevice, h->stream));
+        HK_HIP(h, hipMemcpyAsync(dst + pl.actor + pl.in_dim, pd.q.std, nb, hipMemcpyDeviceToDevice, h->stream));
     }
     pl.filled |= 1ull << slot;
     return HK_OK;
@@ -3116,12 +3173,12 @@ int hk_policy_pool_load(hk_handle h, int pool, int slot, int policy)
             return fail(h, HK_ERR_INVALID, "hk_policy_pool_load: the policy has a PPO trainer (its master weights would disagree with what plays)");
     hk::PolicyDevice& pd = h->policy[policy];
     float* src = pool_slot(pl, slot);
-    hipLaunchKernelGGL(hk::ppo_publish_kernel<true>, dim3(nblk(pl.net.count)), dim3(256), 0, h->stream, pd.q, pl.net, src);
+    pool_move<true>(h, pl, pd, src);
     HK_HIP(h, hipGetLastError());
     if (pl.normalize) {
         const size_t nb = (size_t)pl.in_dim * sizeof(float);
-        HK_HIP(h, hipMemcpyAsync(const_cast<float*>(pd.q.mean), src + pl.net.count, nb, hipMemcpyDeviceToDevice, h->stream));
-        HK_HIP(h, hipMemcpyAsync(const_cast<float*>(pd.q.std), src + pl.net.count + pl.in_dim, nb, hipMemcpyDeviceToDevice, h->stream));
+        HK_HIP(h, hipMemcpyAsync(const_cast<float*>(pd.q.mean), src + pl.actor, nb, hipMemcpyDeviceToDevice, h->stream));
+        HK_HIP(h, hipMemcpyAsync(const_cast<float*>(pd.q.std), src + pl.actor + pl.in_dim, nb, hipMemcpyDeviceToDevice, h->stream));
     }
     // the bf16 inference copies, when the policy has them: rebuilt from the fp32 copies just written, whichever precision the policy is in now
     if (pd.wbf) HK_HIP(h, hk::policy_bf16_refresh(pd.q, pd.bq, h->stream));

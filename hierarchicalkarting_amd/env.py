@@ -195,6 +195,11 @@ class RacingEnv:
             raise ValueError("memory: expected shape %s" % ((self.E, len(self._policy_slots[index]), pol.memory_size),))
         self._ck(self.L.hk_policy_memory_set(self.h, int(index), a.ctypes.data_as(C.POINTER(C.c_float))))
 
+    def policy_memory_clear(self, index):
+        """zero the memory of a recurrent actor's agents on the device: set_policy_memory of zeros without the host array, asynchronous on the
+        handle's stream (hk.h hk_policy_memory_clear); refused while a rollout is open"""
+        self._ck(self.L.hk_policy_memory_clear(self.h, int(index)))
+
     def lq_debug(self, env, ego):
         d = _lib.LqDebug()
         self._ck(self.L.hk_get_lq_debug(self.h, env, ego, C.byref(d)))
@@ -351,7 +356,7 @@ class RacingEnv:
         return {n: getattr(st, n) for n, _ in _lib.EpisodeStats._fields_}
 
     def snapshot_pool(self, policy_index, slots):
-        """-> selfplay.SnapshotPool of the policy's shape (hk_policy_pool_create)"""
+        """-> selfplay.SnapshotPool of the policy's shape (hk_policy_pool_create; hk_policy_pool_create_recurrent for a policy with memory)"""
         from .selfplay import SnapshotPool
         return SnapshotPool(self, policy_index, slots)
 

@@ -10,7 +10,9 @@ bookkeeping on top of three device facilities — the snapshot pool (hk_policy_p
     ppo.checkpoint_write(path, sp.state_dict()); ...; sp2.load_state_dict(ppo.checkpoint_read(path))     # ratings, cursor, generator, pool slots
 
 Nothing is computed on the host but ratings, schedules and which slot plays next.  Out of scope: team_change (a trainer is bound to one
-policy), per-env opponents, bf16 POCA and LSTM.  The trainer may be a poca.POCATrainer: nothing here is bound to the critic's kind."""
+policy), per-env opponents, bf16 POCA.  The trainer may be a poca.POCATrainer: nothing here is bound to the critic's kind.  It may be a
+recurrent PPOTrainer (sequence_length, with or without critic_memory_size): the pool is then a recurrent one (hk_policy_pool_create_recurrent,
+DESIGN §19), whose slots carry the LSTM cell; a swap keeps the opponent's memory unless reset_opponent_memory is set."""
 import ctypes as C
 import json
 import numpy as np
@@ -50,10 +52,13 @@ def linear_schedule(initial, minimum, step, max_steps):
 
 
 def policy_to_flat(pol):
-    """Policy -> the flat float32 vector of a pool slot: the actor in the trainer's torch layout, then norm_mean, norm_std when it normalises"""
+    """Policy -> the flat float32 vector of a pool slot: the actor in the trainer's torch layout, then norm_mean, norm_std when it normalises.
+    A Policy with memory: the cell (W_ih, W_hh, b_ih, b_hh) between the trunk and the heads, as param_layout(..., memory_size) orders it"""
     parts = []
     for l in range(len(pol.W)):
         parts += [pol.W[l].reshape(-1), pol.b[l]]
+    if pol.lstm:
+        parts += [pol.lstm[k].reshape(-1) for k in Policy.LSTM_KEYS]
     parts += [pol.W_mu, pol.b_mu, pol.log_sigma, pol.W_branch.reshape(-1), pol.b_branch]
     if pol.norm_mean is not None:
         parts += [pol.norm_mean, pol.norm_std]
@@ -61,26 +66,29 @@ def policy_to_flat(pol):
 
 
 def flat_to_policy(flat, like):
-    """a slot's flat vector -> Policy with the stack, seed and mode of `like` (whose shape it must have)"""
-    layout = param_layout(like.in_dim, like.hidden, len(like.W), like.n_branch)
+    """a slot's flat vector -> Policy with the stack, seed and mode of `like` (whose shape, memory size included, it must have)"""
+    layout = param_layout(like.in_dim, like.hidden, len(like.W), like.n_branch, like.memory_size)
     n = sum(int(np.prod(s)) for _, s in layout)
     p = split_params(flat[:n], layout)
     mean = std = None
     if like.norm_mean is not None:
         mean, std = flat[n:n + like.in_dim], flat[n + like.in_dim:n + 2 * like.in_dim]
     L = len(like.W)
+    lstm = {k: p[k] for k in Policy.LSTM_KEYS} if like.memory_size else None
     return Policy([p["W%d" % l] for l in range(L)], [p["b%d" % l] for l in range(L)], p["W_mu"], p["b_mu"], p["log_sigma"], p["W_branch"],
-                  p["b_branch"], mean, std, like.stack, like.deterministic, like.seed)
+                  p["b_branch"], mean, std, like.stack, like.deterministic, like.seed, lstm)
 
 
 class SnapshotPool:
-    """`slots` device slots of attached policy `policy_index`'s shape (hk_policy_pool_create).  save / load move a slot from / into an
-    attached policy of that shape on the device; put / get exchange it with a host Policy."""
+    """`slots` device slots of attached policy `policy_index`'s shape (hk_policy_pool_create; hk_policy_pool_create_recurrent when that policy
+    has memory, whose size is then part of the shape).  save / load move a slot from / into an attached policy of that shape on the device;
+    put / get exchange it with a host Policy.  A load never touches the policy's memory (env.policy_memory_clear does)."""
 
     def __init__(self, env, policy_index, slots):
         self.env, self.index, self.slots = env, int(policy_index), int(slots)
         self.like = env._policies[self.index]
-        rc = env.L.hk_policy_pool_create(env.h, self.index, self.slots)
+        create = env.L.hk_policy_pool_create_recurrent if self.like.memory_size else env.L.hk_policy_pool_create
+        rc = create(env.h, self.index, self.slots)
         if rc < 0:
             env._ck(rc)
         self.pool = rc
@@ -98,7 +106,7 @@ class SnapshotPool:
 
     def put(self, slot, policy):
         flat = policy_to_flat(policy)
-        if flat.size != self.count:
+        if flat.size != self.count or policy.memory_size != self.like.memory_size:
             raise ValueError("SnapshotPool.put: the Policy has %d parameters, a slot of this pool %d" % (flat.size, self.count))
         self.env._ck(self.env.L.hk_policy_pool_put(self.env.h, self.pool, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float))))
 
@@ -128,13 +136,17 @@ class SelfPlay:
     into slot cursor % window with its rating; every swap_steps the opponent is redrawn from numpy.random.default_rng(seed): with
     probability play_against_latest_model_ratio the latest learner (whose rating is the learner's own and is not decremented), otherwise
     uniformly one of the filled window slots.  Until the first swap the opponent plays the weights it was attached with, rated initial_elo.
-    pool: a SnapshotPool-like object (save(slot), load(slot, policy_index)); None: a SnapshotPool of the learner's shape."""
+    pool: a SnapshotPool-like object (save(slot), load(slot, policy_index)); None: a SnapshotPool of the learner's shape.
+    The trainer may be recurrent (sequence_length, with or without critic_memory_size): the pool is then a recurrent one, `minibatch` of
+    iteration() counts sequences as PPOTrainer.update defines, and steps are still learner rows.  A swap keeps the opponent's memory, as
+    ML-Agents' ghost swap does; reset_opponent_memory=True clears it on the device after every load (env.policy_memory_clear)."""
 
     def __init__(self, env, trainer, opponent_index, window=10, play_against_latest_model_ratio=0.5, save_steps=20000, swap_steps=10000,
-                 initial_elo=400.0, max_steps=None, seed=0, pool=None):
+                 initial_elo=400.0, max_steps=None, seed=0, pool=None, reset_opponent_memory=False):
         if window < 1 or save_steps < 1 or swap_steps < 1 or not 0.0 <= play_against_latest_model_ratio <= 1.0:
             raise ValueError("SelfPlay: window, save_steps, swap_steps >= 1 and 0 <= play_against_latest_model_ratio <= 1")
         self.env, self.trainer, self.opponent_index = env, trainer, int(opponent_index)
+        self.reset_opponent_memory = bool(reset_opponent_memory)
         self.window, self.ratio = int(window), float(play_against_latest_model_ratio)
         self.save_steps, self.swap_steps, self.max_steps = int(save_steps), int(swap_steps), max_steps
         self.pool = SnapshotPool(env, trainer.index, self.window + 1) if pool is None else pool
@@ -156,15 +168,20 @@ class SelfPlay:
         self.cursor += 1
         return slot
 
+    def _load(self, slot):
+        self.pool.load(slot, self.opponent_index)
+        if self.reset_opponent_memory:
+            self.env.policy_memory_clear(self.opponent_index)
+
     def _swap(self):
         filled = min(self.cursor, self.window)
         if self.rng.random() < self.ratio:
             pick = "latest"
             self.pool.save(self.window)
-            self.pool.load(self.window, self.opponent_index)
+            self._load(self.window)
         else:
             pick = int(self.rng.integers(filled))
-            self.pool.load(pick, self.opponent_index)
+            self._load(pick)
         self.opponent = pick
         self.history.append(pick)
         return pick
@@ -218,7 +235,8 @@ class SelfPlay:
         code = lambda x: self._PICK.get(x, x)
         d = dict(format=CHECKPOINT_FORMAT, window=self.window, elo=self.elo, ratings=np.asarray(self.ratings, np.float64), attached_elo=self.attached_elo,
                  cursor=self.cursor, opponent=int(code(self.opponent)), steps=self.steps, last_save=self.last_save, last_swap=self.last_swap,
-                 history=np.asarray([code(x) for x in self.history], np.int64), rng=json.dumps(self.rng.bit_generator.state))
+                 history=np.asarray([code(x) for x in self.history], np.int64), rng=json.dumps(self.rng.bit_generator.state),
+                 reset_opponent_memory=int(self.reset_opponent_memory))
         if include_pool:
             slots = list(range(min(self.cursor, self.window))) + ([self.window] if "latest" in self.history else [])
             d["pool"] = {"slot%d" % s: self.pool.get_flat(s) for s in slots}
@@ -226,7 +244,9 @@ class SelfPlay:
 
     def load_state_dict(self, d):
         """restore what state_dict stored; the slots are put back, and an opponent that is not None is loaded into the opponent policy (None, "as
-        attached", is the caller's to restore, as it is at construction).  ValueError: a missing key, another format or window"""
+        attached", is the caller's to restore, as it is at construction; so is the opponent's memory, which this load does not clear whatever
+        the flag says: a resume continues the episode in progress).  reset_opponent_memory is taken from the state when it has the key.
+        ValueError: a missing key, another format or window, a slot of another length than the pool's (nothing is put then)"""
         for k in ("format", "window", "elo", "ratings", "attached_elo", "cursor", "opponent", "steps", "last_save", "last_swap", "history", "rng"):
             if k not in d:
                 raise ValueError("SelfPlay state: missing key %r" % k)
@@ -238,8 +258,14 @@ class SelfPlay:
         rng_state = json.loads(str(d["rng"]))
         if rng_state.get("bit_generator") != type(self.rng.bit_generator).__name__:
             raise ValueError("SelfPlay state: rng is a %r state" % rng_state.get("bit_generator"))
+        count = getattr(self.pool, "count", None)
+        for name, flat in sorted(d.get("pool", {}).items()):
+            if count is not None and np.asarray(flat).size != count:
+                raise ValueError("SelfPlay state: %s has %d floats, a slot of this pool %d (another shape or memory size)" % (name, np.asarray(flat).size, count))
         for name, flat in sorted(d.get("pool", {}).items()):
             self.pool.put_flat(int(name[4:]), flat)
+        if "reset_opponent_memory" in d:
+            self.reset_opponent_memory = bool(int(d["reset_opponent_memory"]))
         self.elo, self.attached_elo = float(d["elo"]), float(d["attached_elo"])
         self.ratings = [float(x) for x in d["ratings"]]
         self.cursor, self.steps, self.last_save, self.last_swap = int(d["cursor"]), int(d["steps"]), int(d["last_save"]), int(d["last_swap"])

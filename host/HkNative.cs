@@ -541,6 +541,7 @@ namespace KartGame.AI.Native
         [DllImport(Lib)] public static extern int hk_policy_forward_mem(IntPtr h, int policy, int rows, float* obs, float* memIn, float* mu, float* logits, float* memOut);
         [DllImport(Lib)] public static extern int hk_policy_memory_get(IntPtr h, int policy, float* mem);
         [DllImport(Lib)] public static extern int hk_policy_memory_set(IntPtr h, int policy, float* mem);
+        [DllImport(Lib)] public static extern int hk_policy_memory_clear(IntPtr h, int policy);
         [DllImport(Lib)] public static extern int hk_get_actions(IntPtr h, float* steer, int* branch);
         // rollout recorder: every decision of the attached actors writes a row of device buffers (fields: hk.h hk_rollout_field)
         [DllImport(Lib)] public static extern int hk_rollout_begin(IntPtr h, int rows);
@@ -578,6 +579,8 @@ namespace KartGame.AI.Native
         [DllImport(Lib)] public static extern int hk_poca_stats(IntPtr h, int trainer, float* stats);
         // self-play (hk.h "SELF-PLAY"): device slots of saved actors, loaded into an attached opponent; episode statistics of the closed rollout
         [DllImport(Lib)] public static extern int hk_policy_pool_create(IntPtr h, int policy, int slots);
+        // a pool of recurrent actors (the policy must have memory): an index of the same table, a slot in the recurrent trainer's layout
+        [DllImport(Lib)] public static extern int hk_policy_pool_create_recurrent(IntPtr h, int policy, int slots);
         [DllImport(Lib)] public static extern int hk_policy_pool_save(IntPtr h, int pool, int slot, int policy);
         [DllImport(Lib)] public static extern int hk_policy_pool_load(IntPtr h, int pool, int slot, int policy);
         [DllImport(Lib)] public static extern int hk_policy_pool_put(IntPtr h, int pool, int slot, float* flat);

@@ -500,13 +500,16 @@ int hk_policy_forward(hk_handle h, int policy, int rows, const float* obs /*[row
  *   hk_policy_memory_set     ... from the host.  What is set belongs to the episode each env is in NOW: the next decision keeps it (and does
  *                            not clear the observation stack) unless the episode changes first, which is what lets a race with a recurrent
  *                            actor resume on another handle after hk_set_agent_state / hk_set_env_state.
+ *   hk_policy_memory_clear   hk_policy_memory_set of an all-zero array, on the device: a fill of [E][n_slots][2m] with +0.0 and the same epoch
+ *                            words made current; asynchronous on hk_stream, no host round trip (a self-play driver that wants a swapped-in
+ *                            opponent to start from a clean memory calls it after hk_policy_pool_load)
  * Refused with HK_ERR_INVALID, state as it was, hk_last_error naming the argument: memory_size odd; m not a multiple of 32 or outside
- * [32, 128]; a NULL weight pointer; reserved != 0; hk_policy_memory_set while a rollout is open; hk_policy_forward_mem, hk_policy_memory_get
- * or hk_policy_memory_set on a policy without memory or with a NULL array.  Refused with HK_ERR_UNSUPPORTED on a policy WITH memory:
+ * [32, 128]; a NULL weight pointer; reserved != 0; hk_policy_memory_set / _clear while a rollout is open; hk_policy_forward_mem, hk_policy_memory_get,
+ * hk_policy_memory_set or _clear on a policy without memory or (the first three) with a NULL array.  Refused with HK_ERR_UNSUPPORTED on a policy WITH memory:
  * hk_policy_forward (use hk_policy_forward_mem), hk_policy_set_precision(HK_POLICY_PREC_BF16), hk_ppo_create (use hk_ppo_create_recurrent), hk_ppo_create_poca,
- * hk_policy_pool_create / _save / _load.
- * Training: hk_ppo_create_recurrent ("PPO trainer" RECURRENT).
- * Out of scope: bf16 for the cell, snapshot pools and self-play swaps of recurrent actors, m above
+ * hk_policy_pool_create, and hk_policy_pool_save / _load with a feed-forward pool (use hk_policy_pool_create_recurrent: "SELF-PLAY" RECURRENT POOLS).
+ * Training: hk_ppo_create_recurrent ("PPO trainer" RECURRENT).  Snapshot pools and opponent swaps: hk_policy_pool_create_recurrent.
+ * Out of scope: bf16 for the cell, m above
  * 128, stacked or bidirectional LSTMs, and a CPU-oracle restatement (the bit reference is the host build named above). */
 #define HK_POLICY_MAX_MEMORY 256          /* memory_size; m = memory_size / 2, a multiple of 32 in [32, 128] */
 typedef struct hk_policy_lstm_desc {
@@ -519,6 +522,7 @@ int hk_policy_forward_mem(hk_handle h, int policy, int rows, const float* obs /*
                           float* mu, float* logits, float* mem_out /*[rows][2m] or NULL*/);
 int hk_policy_memory_get(hk_handle h, int policy, float* mem /*[E][n_slots][2m]*/);
 int hk_policy_memory_set(hk_handle h, int policy, const float* mem);
+int hk_policy_memory_clear(hk_handle h, int policy);
 /* The actions currently latched for every agent (what the policies / hk_set_actions wrote): steer[E][A], branch[E][A] */
 int hk_get_actions(hk_handle h, float* steer, int32_t* branch);
 
@@ -932,6 +936,21 @@ int hk_poca_stats(hk_handle h, int trainer, float* out /*[HK_POCA_STATS]*/);   /
  * Refused with HK_ERR_INVALID and a message, state as it was: a bad pool, slot or policy index; a policy whose shape differs from the pool's;
  * a load or get of a slot never written; a load while a rollout is open (the rows of one rollout come from one chain); a load into a policy
  * that has a PPO trainer (its master weights would silently disagree with what plays: train the learner, swap the opponent); a NULL host pointer.
+ * RECURRENT POOLS (hk_policy_pool_create_recurrent).  hk_policy_pool_create refuses a policy with memory (HK_ERR_UNSUPPORTED), and so do save and
+ * load of such a policy with a pool it made; pools of recurrent actors come from this entry point, which returns an index of the SAME table
+ * (HK_MAX_POOLS and HK_POOL_MAX_SLOTS are shared, every hk_policy_pool_* call takes the index).  `policy` must HAVE memory (HK_ERR_INVALID
+ * otherwise: use hk_policy_pool_create).  The SHAPE is the feed-forward shape plus the cell's memory_size.  A slot is the actor in the
+ * recurrent trainer's torch layout — the actor part of HK_PPO_PARAMS of hk_ppo_create_recurrent: the trunk W[0], b[0], ..., then
+ * W_ih [4m][hidden], W_hh [4m][m], b_ih [4m], b_hh [4m] (gates i f g o), then the m-wide heads W_mu [m], b_mu, log_sigma, W_branch [n_branch][m],
+ * b_branch — followed by mean and std [in_dim] when the shape normalises.
+ *   save   reads the policy's current inference copies: the transposed trunk weights, the group-major Wq_ih / Wq_hh, the RAW b_ih / b_hh that
+ *          hk_policy_attach_lstm keeps beside their sum, the heads and the published statistics.  Asynchronous on hk_stream.
+ *   load   writes exactly what hk_ppo_publish of a recurrent trainer whose actor parameters equal the slot would write, the summed bias
+ *          fp32(b_ih + b_hh) and the raw biases included, then mean / std.  Asynchronous.  The only float operation is that one sum.
+ *          It leaves the policy's MEMORY as it was (ML-Agents' ghost swap: load_weights keeps the memories), and as for every load the
+ *          observation ring, seed, deterministic, agent slots and decision counters.  hk_policy_memory_clear after it starts the new
+ *          weights from a zero memory.
+ * Refused with HK_ERR_INVALID as above, and: a policy without memory, of another memory_size, or with another feed-forward shape field.
  * EPISODE STATISTICS (hk_rollout_episode_stats; synchronises) of the COMPLETED rows of the closed rollout, over the agent slots (e, j) of
  * `policy`.  Per (e, j), t ascending, every operation one fp32 operation (no fused multiply-add), so a numpy fp32 loop restates it bit for bit:
  *   acc = carry_ret; gacc = carry_gret; len = carry_len           (0 where there is no valid carry)
@@ -957,11 +976,11 @@ int hk_poca_stats(hk_handle h, int trainer, float* out /*[HK_POCA_STATS]*/);   /
  * here and have no order, so a rollout's W wins, D draws and L losses are applied as n = W + D + L sequential steps of the MEAN result
  * s = (W + D / 2) / n: change = k (s - 1 / (1 + 10^((r_opp - r_learner) / 400))), r_learner += change, r_opp -= change.  Order-free, equal to
  * ML-Agents' sequence when all results agree, and self-limiting where a one-shot change of n (s - e) would move ratings by thousands of points.
- * Out of scope: team_change (a trainer is bound to one policy), per-env opponents, bf16 POCA, and snapshot pools or swaps of
- * recurrent actors (hk_policy_pool_create / _save / _load refuse a policy with memory). */
+ * Out of scope: team_change (a trainer is bound to one policy), per-env opponents, bf16 POCA. */
 #define HK_MAX_POOLS 8
 #define HK_POOL_MAX_SLOTS 64
 int hk_policy_pool_create(hk_handle h, int policy, int slots);
+int hk_policy_pool_create_recurrent(hk_handle h, int policy, int slots);
 int hk_policy_pool_save(hk_handle h, int pool, int slot, int policy);
 int hk_policy_pool_load(hk_handle h, int pool, int slot, int policy);
 int hk_policy_pool_put(hk_handle h, int pool, int slot, const float* flat /*host [hk_policy_pool_count]*/);
