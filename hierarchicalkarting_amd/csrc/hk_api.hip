@@ -1751,38 +1751,48 @@ void ppo_value_head_back(hipStream_t s, const hk_context::Ppo& t, float* part, i
 // What differs between the trainers under ppo_loss_kernel: what stands in for the critic's last activation [m][Hc], the value head, the row ids
 struct PpoValueIn { const float* Ac; int Hc; const float *W_v, *b_v; const int* ids; };
 
-// the actor half of a minibatch, first part: ppo_loss_kernel and ppo_stats_kernel on the actor's last activations and the value input c
-// (acc: into the update's stats accumulator too)
-void ppo_actor_loss(hk_handle h, const hk_context::Ppo& t, const hk::PpoRows& P, const PpoWs& w, const PpoValueIn& c, int m, float eps, float beta, bool acc)
+// the actor half of a minibatch, first part: ppo_loss_kernel and the stats kernel on what the heads read — Aa [m][Ha], the trunk's last
+// activations or a recurrent actor's h' (t.actor's head offsets are the m-wide heads' then) — and the value input c (acc: into the update's
+// stats accumulator too).  sids: a recurrent minibatch's ms sequence ids, whose stats count skipped SEQUENCES
+void ppo_actor_loss(hk_handle h, const hk_context::Ppo& t, const hk::PpoRows& P, const PpoWs& w, const float* Aa, int Ha, const PpoValueIn& c, int m, float eps,
+                    float beta, bool acc, const int32_t* sids = nullptr, int ms = 0)
 {
     const PpoRowBuf rows = ppo_rowbuf(h, t);
     const float* prm = t.param;
     const hk::PpoNet& na = t.actor;
     hk::PpoLossArgs L{};
-    L.Aa = w.Aa[na.n_layers - 1].f; L.Ac = c.Ac;
+    L.Aa = Aa; L.Ac = c.Ac;
     L.W_mu = prm + na.oWmu; L.b_mu = prm + na.obmu; L.log_sigma = prm + na.ols; L.W_br = prm + na.oWbr; L.b_br = prm + na.obbr;
     L.W_v = c.W_v; L.b_v = c.b_v;
     L.v_old = rows.v_old; L.adv = rows.adv; L.ret = rows.ret;
-    L.ids = c.ids; L.valid = w.valid; L.n_valid = w.n_valid; L.m = m; L.n = t.n; L.Ha = na.hidden; L.Hc = c.Hc; L.nb = na.n_branch;
+    L.ids = c.ids; L.valid = w.valid; L.n_valid = w.n_valid; L.m = m; L.n = t.n; L.Ha = Ha; L.Hc = c.Hc; L.nb = na.n_branch;
     L.eps = eps; L.beta = beta;
     L.dhead = w.dhead; L.dls = w.dls; L.dv = w.dv; L.rowstat = w.rowstat;
     L.mu_out = w.mb_mu; L.logit_out = w.mb_logits; L.v_out = w.mb_v;
     hipLaunchKernelGGL(hk::ppo_loss_kernel, dim3(nblk(m)), dim3(256), 0, h->stream, P, L);
-    hipLaunchKernelGGL(hk::ppo_stats_kernel, dim3(1), dim3(256), 0, h->stream, w.rowstat, m, w.stats, acc ? w.acc : nullptr);
+    if (sids) hipLaunchKernelGGL(hk::ppo_lstm_stats_kernel, dim3(1), dim3(256), 0, h->stream, w.rowstat, m, sids, ms, t.n_seq, w.stats, acc ? w.acc : nullptr);
+    else hipLaunchKernelGGL(hk::ppo_stats_kernel, dim3(1), dim3(256), 0, h->stream, w.rowstat, m, w.stats, acc ? w.acc : nullptr);
 }
 
-// ... second part: the heads' backward (vector ALU; their gradients fp32 in both precisions), then the trunk's
+// the gradients of the actor's heads (fp32 in both precisions) on what they read, A [m][H]: W_mu / W_branch through part, the biases and log_sigma
+void ppo_head_grads(hipStream_t s, const hk_context::Ppo& t, float* part, const PpoWs& w, int m, int H, PpoMat A)
+{
+    float* grad = t.param + t.P;
+    const hk::PpoNet& na = t.actor;
+    ppo_wgrad(s, part, 1 + na.n_branch, H, m, w.dhead, hk::PM_MAX_OUT, A, H, grad + na.oWmu, grad + na.oWbr);
+    ppo_colsum(s, w.dhead, m, hk::PM_MAX_OUT, 1, grad + na.obmu);
+    ppo_colsum(s, w.dhead + 1, m, hk::PM_MAX_OUT, na.n_branch, grad + na.obbr);
+    ppo_colsum(s, w.dls, m, 1, 1, grad + na.ols);
+}
+
+// ... second part: the heads' backward (vector ALU), then the trunk's
 void ppo_actor_backward(hipStream_t s, const hk_context::Ppo& t, const PpoWs& w, int m)
 {
     const float* prm = t.param;
-    float* grad = t.param + t.P;
     const hk::PpoNet& na = t.actor;
-    const int Ha = na.hidden, nb = na.n_branch, La = na.n_layers - 1;
-    ppo_head_back(s, m, Ha, 1 + nb, w.dhead, hk::PM_MAX_OUT, prm + na.oWmu, prm + na.oWbr, w.Za[La], w.d0);
-    ppo_wgrad(s, w.part, 1 + nb, Ha, m, w.dhead, hk::PM_MAX_OUT, w.Aa[La], Ha, grad + na.oWmu, grad + na.oWbr);
-    ppo_colsum(s, w.dhead, m, hk::PM_MAX_OUT, 1, grad + na.obmu);
-    ppo_colsum(s, w.dhead + 1, m, hk::PM_MAX_OUT, nb, grad + na.obbr);
-    ppo_colsum(s, w.dls, m, 1, 1, grad + na.ols);
+    const int Ha = na.hidden, La = na.n_layers - 1;
+    ppo_head_back(s, m, Ha, 1 + na.n_branch, w.dhead, hk::PM_MAX_OUT, prm + na.oWmu, prm + na.oWbr, w.Za[La], w.d0);
+    ppo_head_grads(s, t, w.part, w, m, Ha, w.Aa[La]);
     ppo_trunk_backward(s, t, na, w.part, w.X0, m, w.Za, w.Aa, w.d0, w.d1);
 }
 
@@ -1905,7 +1915,7 @@ int poca_mb(hk_handle h, hk_context::Ppo& t, const int32_t* gids, int mg, float 
     hipLaunchKernelGGL(hk::ppo_count_kernel, dim3(1), dim3(256), 0, s, w.valid, m, w.n_valid);
     ppo_trunk_forward(s, t, t.actor, w.X0, m, w.Za, w.Aa);
     // ppo_loss_kernel as it is: its "critic activation" is the row's group value, one wide, under the head (1, 0), so v = fmaf(V, 1, 0) = V
-    ppo_actor_loss(h, t, P, w, PpoValueIn{pw.vrow, 1, pw.consts, pw.consts + 1, pw.rid}, m, eps, beta, acc);
+    ppo_actor_loss(h, t, P, w, w.Aa[t.actor.n_layers - 1].f, t.actor.hidden, PpoValueIn{pw.vrow, 1, pw.consts, pw.consts + 1, pw.rid}, m, eps, beta, acc);
     hipLaunchKernelGGL(hk::poca_loss_kernel, dim3(nblk(mg)), dim3(256), 0, s, pw.brow, pw.rid, w.valid, w.n_valid, prows.b_old, rows.ret, w.dv, mg, S, t.n, eps,
                        pw.dout, pw.rowstat_b);
     hipLaunchKernelGGL(hk::poca_stats_kernel, dim3(1), dim3(256), 0, s, pw.rowstat_b, m, S, w.n_valid, w.stats, acc ? w.acc : nullptr, pw.pstats,
@@ -1996,27 +2006,36 @@ int ppo_values_and_gae(hk_handle h, hk_context::Ppo& t, const hk::PpoRows& P)
 // ---- recurrent training (hk.h "PPO trainer" RECURRENT; device side in hk_ppo_lstm.h).  Everything below is reached only through a
 // trainer made by hk_ppo_create_recurrent.
 
-// the recurrent workspace at a capacity of M = L ms rows (Ppo::rws; sized by the minibatch, never by the rollout)
+// a cell as the host sees it, the actor's (t.lnet) or a recurrent critic's (t.cnet): m wide on a trunk whose last layer is H wide, and the PARAMS
+// offsets of W_ih [4m][H], W_hh [4m][m], b_ih and b_hh [4m].  Host only: the kernels take pointers and widths
+struct PpoCell { int m, H; size_t oWih, oWhh, obih, obhh; };
+template <typename Net> PpoCell ppo_cell(const Net& n) { return PpoCell{n.m, n.hidden, n.oWih, n.oWhh, n.obih, n.obhh}; }
+
+// a cell's workspace at a capacity of M = L ms rows (sized by the minibatch, never by the rollout): the actor's (Ppo::rws), or a recurrent
+// critic's (Ppo::cws) — the same pieces m_v wide, without the row ids and FIRST words, which are the actor workspace's for both
 struct PpoLstmWs {
     int *rowids, *first;
     float *mem0, *bsum, *GZ, *hnew, *mbmem, *hprev, *cprev, *dH, *drec, *dcar, *part;
 };
 
-size_t ppo_lstm_ws_layout(const hk_context::Ppo& t, int M, PpoLstmWs* w)
+enum PpoCellOf { PPO_ACTOR_CELL, PPO_CRITIC_CELL };          // whose cell a workspace serves
+
+size_t ppo_lstm_ws_layout(const hk_context::Ppo& t, PpoCellOf of, int M, PpoLstmWs* w)
 {
-    PpoBump a{w ? (char*)t.rws : nullptr};
+    const bool critic = of == PPO_CRITIC_CELL;
+    PpoBump a{w ? (char*)(critic ? t.cws : t.rws) : nullptr};
     auto fl = [&](size_t count) { return (float*)a.take(count * 4); };
-    const size_t Mz = (size_t)M, mc = (size_t)t.lnet.m;
+    const PpoCell c = critic ? ppo_cell(t.cnet) : ppo_cell(t.lnet);
+    const size_t Mz = (size_t)M, mc = (size_t)c.m;
     const size_t ms = (Mz + t.seq_len - 1) / t.seq_len;          // sequences at this capacity: M = L ms
     const int Ha = t.actor.hidden, Hc = t.critic.hidden, in = t.actor.in_dim, nb = t.actor.n_branch;
-    // the largest weight gradient: the cell's 4m x max(H, m), a trunk layer's, or the heads'; a sequence is at least one row, so ms <= M
-    size_t mn = 4 * mc * std::max((size_t)Ha, mc);
-    mn = std::max(mn, (size_t)(1 + nb) * mc);
-    mn = std::max(mn, (size_t)Ha * std::max(in, Ha));
-    mn = std::max(mn, (size_t)Hc * std::max(in, Hc));
+    // the largest weight gradient that goes through part: the cell's 4m x max(H, m) or a layer of the critic's trunk (a feed-forward critic's
+    // goes through the actor's part) and, for the actor, the heads' or a layer of its own trunk; a sequence is at least one row, so ms <= M
+    size_t mn = std::max(4 * mc * std::max((size_t)c.H, mc), (size_t)Hc * std::max(in, Hc));
+    if (!critic) mn = std::max({mn, (size_t)(1 + nb) * mc, (size_t)Ha * std::max(in, Ha)});
     const size_t nz = (Mz + hk::PPO_KCH - 1) / hk::PPO_KCH;
     PpoLstmWs d{};
-    d.rowids = (int*)a.take(Mz * 4); d.first = (int*)a.take(Mz * 4);
+    if (!critic) { d.rowids = (int*)a.take(Mz * 4); d.first = (int*)a.take(Mz * 4); }
     d.mem0 = fl(ms * 2 * mc); d.bsum = fl(4 * mc);
     d.GZ = fl(Mz * 4 * mc); d.hnew = fl(Mz * mc); d.mbmem = fl(Mz * 2 * mc); d.hprev = fl(Mz * mc); d.cprev = fl(Mz * mc); d.dH = fl(Mz * mc);
     d.drec = fl(ms * mc); d.dcar = fl(ms * mc);
@@ -2025,29 +2044,9 @@ size_t ppo_lstm_ws_layout(const hk_context::Ppo& t, int M, PpoLstmWs* w)
     return a.off;
 }
 
-PpoLstmWs ppo_lstm_ws(const hk_context::Ppo& t) { PpoLstmWs w; ppo_lstm_ws_layout(t, t.rcap, &w); return w; }
-
-// the recurrent critic's workspace at a capacity of M rows (Ppo::cws): the same pieces for the critic's cell, m_v wide; the row ids and FIRST
-// words are the actor workspace's
-size_t ppo_lstm_cws_layout(const hk_context::Ppo& t, int M, PpoLstmWs* w)
-{
-    PpoBump a{w ? (char*)t.cws : nullptr};
-    auto fl = [&](size_t count) { return (float*)a.take(count * 4); };
-    const size_t Mz = (size_t)M, mc = (size_t)t.critic_m;
-    const size_t ms = (Mz + t.seq_len - 1) / t.seq_len;
-    const int Hc = t.critic.hidden, in = t.critic.in_dim;
-    const size_t mn = std::max(4 * mc * std::max((size_t)Hc, mc), (size_t)Hc * std::max(in, Hc));      // the cell's 4 m_v x max(Hc, m_v), or a trunk layer's
-    const size_t nz = (Mz + hk::PPO_KCH - 1) / hk::PPO_KCH;
-    PpoLstmWs d{};
-    d.mem0 = fl(ms * 2 * mc); d.bsum = fl(4 * mc);
-    d.GZ = fl(Mz * 4 * mc); d.hnew = fl(Mz * mc); d.mbmem = fl(Mz * 2 * mc); d.hprev = fl(Mz * mc); d.cprev = fl(Mz * mc); d.dH = fl(Mz * mc);
-    d.drec = fl(ms * mc); d.dcar = fl(ms * mc);
-    d.part = fl(nz * mn);
-    if (w) *w = d;
-    return a.off;
-}
-
-PpoLstmWs ppo_lstm_cws(const hk_context::Ppo& t) { PpoLstmWs w; ppo_lstm_cws_layout(t, t.ccap, &w); return w; }
+// the two workspaces as they are allocated now
+PpoLstmWs ppo_lstm_ws(const hk_context::Ppo& t) { PpoLstmWs w; ppo_lstm_ws_layout(t, PPO_ACTOR_CELL, t.rcap, &w); return w; }
+PpoLstmWs ppo_lstm_cws(const hk_context::Ppo& t) { PpoLstmWs w; ppo_lstm_ws_layout(t, PPO_CRITIC_CELL, t.ccap, &w); return w; }
 
 // the memories of a recurrent critic (Ppo::cmem): MEM_IN, MEM_OUT and the value pass's carry, [E S][2 m_v] each
 struct PpoCriticMem { float *in, *out, *carry; size_t each; };
@@ -2057,21 +2056,70 @@ PpoCriticMem ppo_critic_mem(hk_handle h, const hk_context::Ppo& t)
     return PpoCriticMem{t.cmem, t.cmem + each, t.cmem + 2 * each, each};
 }
 
+// a cell's summed bias b_ih + b_hh [4m] ...
+void ppo_cell_bsum(hipStream_t s, const hk_context::Ppo& t, const PpoCell& c, float* bsum)
+{
+    hipLaunchKernelGGL(hk::ppo_lstm_bsum_kernel, dim3(nblk(4 * c.m)), dim3(256), 0, s, t.param + c.obih, t.param + c.obhh, 4 * c.m, bsum);
+}
+
+// ... and its input projection over M rows of the trunk's last activations A: Zx [M][4m] = bsum + A W_ih^T (k ascending; fp32).  The two are
+// apart because the value pass sums the bias once and projects every chunk
+void ppo_cell_project(hipStream_t s, const hk_context::Ppo& t, const PpoCell& c, int M, PpoMat A, const float* bsum, float* Zx)
+{
+    ppo_product<0>(s, M, 4 * c.m, c.H, A, c.H, true, PpoMat(t.param + c.oWih), c.H, true, bsum, PpoMat(Zx), 4 * c.m, nullptr, c.H);
+}
+
+// a cell's forward over a minibatch's ms windows (M = L ms time-major rows) in its workspace r: the input projection over all rows at once, then
+// the L steps from r.mem0
+void ppo_cell_forward(hipStream_t s, const hk_context::Ppo& t, const PpoCell& c, const PpoLstmWs& r, PpoMat A, const int* first, int ms)
+{
+    const int L = t.seq_len;
+    ppo_cell_bsum(s, t, c, r.bsum);
+    ppo_cell_project(s, t, c, L * ms, A, r.bsum, r.GZ);
+    const dim3 grid(nblk(c.m, hk::PPO_TN), nblk(ms, hk::PPO_TM));
+    for (int tau = 0; tau < L; tau++)
+        hipLaunchKernelGGL(hk::ppo_lstm_step_kernel, grid, dim3(256), 0, s, tau, ms, c.m, t.param + c.oWhh, r.mem0, first, r.GZ, r.hnew, r.mbmem, r.hprev, r.cprev);
+}
+
+// a cell's backward from r.dH = dL / dh' as the heads left it: the L steps in reverse, the cell's weight gradients over all rows at once (through
+// r.part), the delta into the last layer of the trunk below (net, with its Z and A of the minibatch workspace), then that trunk
+int ppo_cell_backward(hk_handle h, const hk_context::Ppo& t, const PpoCell& c, const PpoLstmWs& r, const hk::PpoNet& net, const PpoWs& w, float* const* Z,
+                      const PpoMat* A, const int* first, int ms)
+{
+    hipStream_t s = h->stream;
+    const int L = t.seq_len, M = L * ms, m = c.m, N = 4 * m, H = c.H, top = net.n_layers - 1;
+    float* prm = t.param;
+    float* grad = t.param + t.P;
+    for (int tau = L - 1; tau >= 0; tau--) {
+        hipLaunchKernelGGL(hk::ppo_lstm_back_kernel, dim3(nblk((size_t)ms * m)), dim3(256), 0, s, tau, ms, m, (int)(tau == L - 1), first, r.dH, r.drec, r.mbmem,
+                           r.cprev, r.GZ, r.dcar);
+        if (tau > 0)          // the recurrent delta to tau - 1: dG_tau [ms][4m] W_hh [4m][m]
+            ppo_product<0>(s, ms, m, N, PpoMat(r.GZ + (size_t)tau * ms * N), N, true, PpoMat(prm + c.oWhh), m, false, nullptr, PpoMat(r.drec), m, nullptr, N);
+    }
+    ppo_wgrad(s, r.part, N, H, M, PpoMat(r.GZ), N, A[top], H, grad + c.oWih, nullptr);
+    ppo_wgrad(s, r.part, N, m, M, PpoMat(r.GZ), N, PpoMat(r.hprev), m, grad + c.oWhh, nullptr);
+    ppo_colsum(s, PpoMat(r.GZ), M, N, N, grad + c.obih);
+    HK_HIP(h, hipMemcpyAsync(grad + c.obhh, grad + c.obih, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));      // both biases: the same gradient
+    ppo_product<2>(s, M, H, N, PpoMat(r.GZ), N, true, PpoMat(prm + c.oWih), H, false, nullptr, w.d0, H, Z[top], N);
+    ppo_trunk_backward(s, t, net, r.part, w.X0, M, Z, A, w.d0, w.d1);
+    return HK_OK;
+}
+
 // one recurrent minibatch: ms sequence ids -> M = L ms time-major rows; loss, stats, gradient into GRAD
 int ppo_lstm_mb(hk_handle h, hk_context::Ppo& t, const int32_t* sids, int ms, float eps, float beta, bool acc)
 {
-    const int L = t.seq_len, mc = t.lnet.m, N = 4 * mc;
+    const int L = t.seq_len, mc = t.lnet.m;
     if ((long long)L * ms > 0x3FFFFFFF) return fail(h, HK_ERR_INVALID, "hk_ppo_minibatch: m x sequence_length rows do not fit");
     const int M = L * ms;
     PpoWs w;
     int rc = ppo_ensure_ws(h, t, M, w);
     if (rc) return rc;
-    if (M > t.rcap && (rc = dev_grow(h, &t.rws, &t.rcap, M, ppo_lstm_ws_layout(t, M, nullptr)))) return rc;
+    if (M > t.rcap && (rc = dev_grow(h, &t.rws, &t.rcap, M, ppo_lstm_ws_layout(t, PPO_ACTOR_CELL, M, nullptr)))) return rc;
     const PpoLstmWs r = ppo_lstm_ws(t);
-    const int mv = t.critic_m, Nv = 4 * mv;          // a recurrent critic (mv > 0): its cell's leg beside the actor's
-    if (mv && M > t.ccap && (rc = dev_grow(h, &t.cws, &t.ccap, M, ppo_lstm_cws_layout(t, M, nullptr)))) return rc;
+    const int mv = t.critic_m;          // a recurrent critic (mv > 0): its cell's leg beside the actor's
+    if (mv && M > t.ccap && (rc = dev_grow(h, &t.cws, &t.ccap, M, ppo_lstm_ws_layout(t, PPO_CRITIC_CELL, M, nullptr)))) return rc;
     const PpoLstmWs c = mv ? ppo_lstm_cws(t) : PpoLstmWs{};
-    const hk::PpoLstmCriticNet& cn = t.cnet;
+    const PpoCell la = ppo_cell(t.lnet), lc = ppo_cell(t.cnet);
     hipStream_t s = h->stream;
     const hk::PpoRows P = ppo_rows(h, t);
     const auto& ro = h->ro;
@@ -2079,82 +2127,33 @@ int ppo_lstm_mb(hk_handle h, hk_context::Ppo& t, const int32_t* sids, int ms, fl
     float* grad = t.param + t.P;
     const hk::PpoNet& na = t.actor;
     const hk::PpoNet& nc = t.critic;
-    const hk::PpoLstmNet& ln = t.lnet;
-    const int Ha = na.hidden, nb = na.n_branch, La = na.n_layers - 1, Hc = nc.hidden, Lc = nc.n_layers - 1;
+    const int La = na.n_layers - 1, Hc = nc.hidden, Lc = nc.n_layers - 1;
     // rows
     hipLaunchKernelGGL(hk::ppo_lstm_expand_kernel, dim3(nblk((size_t)M + (size_t)ms * 2 * mc)), dim3(256), 0, s, P, ro.at<float>(HK_RO_MEMORY), ro.mem_max, sids,
                        ms, L, t.n_seq, mc, r.rowids, r.first, r.mem0);
     ppo_gather(s, P, r.rowids, M, 0, w.X0, w.valid);
     hipLaunchKernelGGL(hk::ppo_count_kernel, dim3(1), dim3(256), 0, s, w.valid, M, w.n_valid);
-    // forward: the trunks over all rows, the input projection, then the L steps
+    // forward: the trunks over all rows, then the actor's cell and, from CRITIC_MEMORY[k], a recurrent critic's
     ppo_trunk_forward(s, t, na, w.X0, M, w.Za, w.Aa);
     ppo_trunk_forward(s, t, nc, w.X0, M, w.Zc, w.Ac);
-    hipLaunchKernelGGL(hk::ppo_lstm_bsum_kernel, dim3(nblk(N)), dim3(256), 0, s, prm + ln.obih, prm + ln.obhh, N, r.bsum);
-    ppo_product<0>(s, M, N, Ha, w.Aa[La], Ha, true, PpoMat(prm + ln.oWih), Ha, true, r.bsum, PpoMat(r.GZ), N, nullptr, Ha);
-    const dim3 sgrid(nblk(mc, hk::PPO_TN), nblk(ms, hk::PPO_TM));
-    for (int tau = 0; tau < L; tau++)
-        hipLaunchKernelGGL(hk::ppo_lstm_step_kernel, sgrid, dim3(256), 0, s, tau, ms, mc, prm + ln.oWhh, r.mem0, r.first, r.GZ, r.hnew, r.mbmem, r.hprev, r.cprev);
-    if (mv) {          // the critic's cell over the window, from CRITIC_MEMORY[k]: the same three pieces
-        hipLaunchKernelGGL(hk::ppo_lstm_critic_mem0_kernel, dim3(nblk((size_t)ms * 2 * mv)), dim3(256), 0, s, t.cmemk, sids, ms, t.n_seq, mv, c.mem0);
-        hipLaunchKernelGGL(hk::ppo_lstm_bsum_kernel, dim3(nblk(Nv)), dim3(256), 0, s, prm + cn.obih, prm + cn.obhh, Nv, c.bsum);
-        ppo_product<0>(s, M, Nv, Hc, w.Ac[Lc], Hc, true, PpoMat(prm + cn.oWih), Hc, true, c.bsum, PpoMat(c.GZ), Nv, nullptr, Hc);
-        const dim3 cgrid(nblk(mv, hk::PPO_TN), nblk(ms, hk::PPO_TM));
-        for (int tau = 0; tau < L; tau++)
-            hipLaunchKernelGGL(hk::ppo_lstm_step_kernel, cgrid, dim3(256), 0, s, tau, ms, mv, prm + cn.oWhh, c.mem0, r.first, c.GZ, c.hnew, c.mbmem, c.hprev, c.cprev);
-    }
-    // loss on h' (width m), per-row ids
-    {
-        const PpoRowBuf rows = ppo_rowbuf(h, t);
-        hk::PpoLossArgs A{};
-        A.Aa = r.hnew; A.Ac = w.Ac[Lc].f;
-        A.W_mu = prm + ln.oWmu; A.b_mu = prm + ln.obmu; A.log_sigma = prm + ln.ols; A.W_br = prm + ln.oWbr; A.b_br = prm + ln.obbr;
-        A.W_v = prm + nc.oWmu; A.b_v = prm + nc.obmu;
-        A.v_old = rows.v_old; A.adv = rows.adv; A.ret = rows.ret;
-        A.ids = r.rowids; A.valid = w.valid; A.n_valid = w.n_valid; A.m = M; A.n = t.n; A.Ha = mc; A.Hc = Hc; A.nb = nb;
-        if (mv) { A.Ac = c.hnew; A.Hc = mv; }          // (nc.oWmu / obmu are the m_v-wide W_v / b_v)
-        A.eps = eps; A.beta = beta;
-        A.dhead = w.dhead; A.dls = w.dls; A.dv = w.dv; A.rowstat = w.rowstat;
-        A.mu_out = w.mb_mu; A.logit_out = w.mb_logits; A.v_out = w.mb_v;
-        hipLaunchKernelGGL(hk::ppo_loss_kernel, dim3(nblk(M)), dim3(256), 0, s, P, A);
-        hipLaunchKernelGGL(hk::ppo_lstm_stats_kernel, dim3(1), dim3(256), 0, s, w.rowstat, M, sids, ms, t.n_seq, w.stats, acc ? w.acc : nullptr);
-    }
-    // backward: the heads (on h'), the L steps in reverse, the cell's weight gradients over all rows at once, then the trunk
-    ppo_wgrad(s, r.part, 1 + nb, mc, M, w.dhead, hk::PM_MAX_OUT, PpoMat(r.hnew), mc, grad + ln.oWmu, grad + ln.oWbr);
-    ppo_colsum(s, w.dhead, M, hk::PM_MAX_OUT, 1, grad + ln.obmu);
-    ppo_colsum(s, w.dhead + 1, M, hk::PM_MAX_OUT, nb, grad + ln.obbr);
-    ppo_colsum(s, w.dls, M, 1, 1, grad + ln.ols);
-    hipLaunchKernelGGL(hk::ppo_lstm_head_back_kernel, dim3(nblk((size_t)M * mc)), dim3(256), 0, s, M, mc, 1 + nb, w.dhead, hk::PM_MAX_OUT, prm + ln.oWmu,
-                       prm + ln.oWbr, r.dH);
-    for (int tau = L - 1; tau >= 0; tau--) {
-        hipLaunchKernelGGL(hk::ppo_lstm_back_kernel, dim3(nblk((size_t)ms * mc)), dim3(256), 0, s, tau, ms, mc, (int)(tau == L - 1), r.first, r.dH, r.drec, r.mbmem,
-                           r.cprev, r.GZ, r.dcar);
-        if (tau > 0)          // the recurrent delta to tau - 1: dG_tau [ms][4m] W_hh [4m][m]
-            ppo_product<0>(s, ms, mc, N, PpoMat(r.GZ + (size_t)tau * ms * N), N, true, PpoMat(prm + ln.oWhh), mc, false, nullptr, PpoMat(r.drec), mc, nullptr, N);
-    }
-    ppo_wgrad(s, r.part, N, Ha, M, PpoMat(r.GZ), N, w.Aa[La], Ha, grad + ln.oWih, nullptr);
-    ppo_wgrad(s, r.part, N, mc, M, PpoMat(r.GZ), N, PpoMat(r.hprev), mc, grad + ln.oWhh, nullptr);
-    ppo_colsum(s, PpoMat(r.GZ), M, N, N, grad + ln.obih);
-    HK_HIP(h, hipMemcpyAsync(grad + ln.obhh, grad + ln.obih, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));      // both biases: the same gradient
-    ppo_product<2>(s, M, Ha, N, PpoMat(r.GZ), N, true, PpoMat(prm + ln.oWih), Ha, false, nullptr, w.d0, Ha, w.Za[La], N);
-    ppo_trunk_backward(s, t, na, r.part, w.X0, M, w.Za, w.Aa, w.d0, w.d1);
+    ppo_cell_forward(s, t, la, r, w.Aa[La], r.first, ms);
     if (mv) {
-        // the recurrent critic: the actor's backward above, applied to its cell — the value-head delta onto h', the L steps in reverse, the cell's
-        // weight gradients over all rows at once, da into the critic's trunk
-        ppo_wgrad(s, c.part, 1, mv, M, w.dv, 1, PpoMat(c.hnew), mv, grad + cn.oWv, nullptr);
-        ppo_colsum(s, w.dv, M, 1, 1, grad + cn.obv);
-        hipLaunchKernelGGL(hk::ppo_lstm_head_back_kernel, dim3(nblk((size_t)M * mv)), dim3(256), 0, s, M, mv, 1, w.dv, 1, prm + cn.oWv, (const float*)nullptr, c.dH);
-        for (int tau = L - 1; tau >= 0; tau--) {
-            hipLaunchKernelGGL(hk::ppo_lstm_back_kernel, dim3(nblk((size_t)ms * mv)), dim3(256), 0, s, tau, ms, mv, (int)(tau == L - 1), r.first, c.dH, c.drec,
-                               c.mbmem, c.cprev, c.GZ, c.dcar);
-            if (tau > 0)
-                ppo_product<0>(s, ms, mv, Nv, PpoMat(c.GZ + (size_t)tau * ms * Nv), Nv, true, PpoMat(prm + cn.oWhh), mv, false, nullptr, PpoMat(c.drec), mv, nullptr, Nv);
-        }
-        ppo_wgrad(s, c.part, Nv, Hc, M, PpoMat(c.GZ), Nv, w.Ac[Lc], Hc, grad + cn.oWih, nullptr);
-        ppo_wgrad(s, c.part, Nv, mv, M, PpoMat(c.GZ), Nv, PpoMat(c.hprev), mv, grad + cn.oWhh, nullptr);
-        ppo_colsum(s, PpoMat(c.GZ), M, Nv, Nv, grad + cn.obih);
-        HK_HIP(h, hipMemcpyAsync(grad + cn.obhh, grad + cn.obih, (size_t)Nv * sizeof(float), hipMemcpyDeviceToDevice, s));
-        ppo_product<2>(s, M, Hc, Nv, PpoMat(c.GZ), Nv, true, PpoMat(prm + cn.oWih), Hc, false, nullptr, w.d0, Hc, w.Zc[Lc], Nv);
-        ppo_trunk_backward(s, t, nc, c.part, w.X0, M, w.Zc, w.Ac, w.d0, w.d1);
+        hipLaunchKernelGGL(hk::ppo_lstm_critic_mem0_kernel, dim3(nblk((size_t)ms * 2 * mv)), dim3(256), 0, s, t.cmemk, sids, ms, t.n_seq, mv, c.mem0);
+        ppo_cell_forward(s, t, lc, c, w.Ac[Lc], r.first, ms);
+    }
+    // loss on h' (width m), per-row ids; a recurrent critic's value head reads its h' (nc.oWmu / obmu are the m_v-wide W_v / b_v)
+    ppo_actor_loss(h, t, P, w, r.hnew, mc, PpoValueIn{mv ? c.hnew : w.Ac[Lc].f, mv ? mv : Hc, prm + nc.oWmu, prm + nc.obmu, r.rowids}, M, eps, beta, acc, sids, ms);
+    // backward: the actor's heads (on h'), its cell and trunk
+    ppo_head_grads(s, t, r.part, w, M, mc, PpoMat(r.hnew));
+    hipLaunchKernelGGL(hk::ppo_lstm_head_back_kernel, dim3(nblk((size_t)M * mc)), dim3(256), 0, s, M, mc, 1 + na.n_branch, w.dhead, hk::PM_MAX_OUT, prm + na.oWmu,
+                       prm + na.oWbr, r.dH);
+    if ((rc = ppo_cell_backward(h, t, la, r, na, w, w.Za, w.Aa, r.first, ms))) return rc;
+    if (mv) {
+        // the recurrent critic: the value head's gradients and its delta onto h', then its cell and trunk
+        ppo_wgrad(s, c.part, 1, mv, M, w.dv, 1, PpoMat(c.hnew), mv, grad + nc.oWmu, nullptr);
+        ppo_colsum(s, w.dv, M, 1, 1, grad + nc.obmu);
+        hipLaunchKernelGGL(hk::ppo_lstm_head_back_kernel, dim3(nblk((size_t)M * mv)), dim3(256), 0, s, M, mv, 1, w.dv, 1, prm + nc.oWmu, (const float*)nullptr, c.dH);
+        if ((rc = ppo_cell_backward(h, t, lc, c, nc, w, w.Zc, w.Ac, r.first, ms))) return rc;
     } else {
         // critic (feed-forward on the stacked input, as a plain trainer's)
         ppo_value_head_back(s, t, r.part, M, Hc, w.dv, nc.oWmu, nc.obmu, w.Zc[Lc], w.Ac[Lc], w.d0);
@@ -2192,15 +2191,14 @@ int ppo_lstm_values_and_gae(hk_handle h, hk_context::Ppo& t, const hk::PpoRows& 
     int* flags = (int*)(bsum + N);
     hipStream_t s = h->stream;
     const hk::PpoNet& nc = t.critic;
-    const hk::PpoLstmCriticNet& cn = t.cnet;
+    const PpoCell lc = ppo_cell(t.cnet);
     const float* prm = t.param;
-    const int Hc = nc.hidden, Lc = nc.n_layers - 1;
     if (t.cmem_gen != ro.gen) {          // a rollout this trainer has not seen: the memory its last value pass left is what this one starts from
         HK_HIP(h, hipMemcpyAsync(cm.in, cm.out, cm.each * sizeof(float), hipMemcpyDeviceToDevice, s));
         t.cmem_gen = ro.gen;
     }
     HK_HIP(h, hipMemcpyAsync(cm.carry, cm.in, cm.each * sizeof(float), hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(hk::ppo_lstm_bsum_kernel, dim3(nblk(N)), dim3(256), 0, s, prm + cn.obih, prm + cn.obhh, N, bsum);
+    ppo_cell_bsum(s, t, lc, bsum);
     const size_t lds = hk::ppo_lstm_value_lds_bytes(mv);
     for (int t0 = 0; t0 <= P.R; t0 += T) {
         const int Tc = std::min(T, P.R + 1 - t0);
@@ -2209,10 +2207,9 @@ int ppo_lstm_values_and_gae(hk_handle h, hk_context::Ppo& t, const hk::PpoRows& 
             hipLaunchKernelGGL(hk::ppo_lstm_value_ids_kernel, dim3(nblk(m)), dim3(256), 0, s, P, w.ids, flags, t0, Tc, p0, sq);
             ppo_gather(s, P, w.ids, m, 1, w.X0, w.valid);
             ppo_trunk_forward(s, t, nc, w.X0, m, w.Zc, w.Ac);
-            ppo_product<0>(s, m, N, Hc, w.Ac[Lc], Hc, true, PpoMat(const_cast<float*>(prm) + cn.oWih), Hc, true, bsum, PpoMat(Zx), N, nullptr, Hc);
+            ppo_cell_project(s, t, lc, m, w.Ac[nc.n_layers - 1], bsum, Zx);
             hipLaunchKernelGGL(hk::ppo_lstm_value_kernel, dim3(nblk(sq, hk::PLV_TS)), dim3(64 * (mv / 32)), lds, s, P.R, ES, t0, Tc, p0, sq, mv, L, Zx, flags,
-                               prm + cn.oWhh,
-                               prm + cn.oWv, prm + cn.obv, cm.carry, t.cmemk, cm.out, rows.v_old, rows.v_boot);
+                               prm + lc.oWhh, prm + nc.oWmu, prm + nc.obmu, cm.carry, t.cmemk, cm.out, rows.v_old, rows.v_boot);
         }
     }
     hipLaunchKernelGGL(hk::ppo_gae_kernel, dim3(nblk(ES)), dim3(256), 0, s, P, rows.v_old, rows.v_boot, t.cfg.gamma, t.cfg.lambd, rows.adv, rows.ret);
@@ -2236,7 +2233,7 @@ int ppo_mb(hk_handle h, hk_context::Ppo& t, const int32_t* ids, int m, float eps
     hipLaunchKernelGGL(hk::ppo_count_kernel, dim3(1), dim3(256), 0, s, w.valid, m, w.n_valid);
     ppo_trunk_forward(s, t, t.actor, w.X0, m, w.Za, w.Aa);
     ppo_trunk_forward(s, t, nc, w.X0, m, w.Zc, w.Ac);
-    ppo_actor_loss(h, t, P, w, PpoValueIn{w.Ac[Lc].f, Hc, prm + nc.oWmu, prm + nc.obmu, ids}, m, eps, beta, acc);
+    ppo_actor_loss(h, t, P, w, w.Aa[t.actor.n_layers - 1].f, t.actor.hidden, PpoValueIn{w.Ac[Lc].f, Hc, prm + nc.oWmu, prm + nc.obmu, ids}, m, eps, beta, acc);
     ppo_actor_backward(s, t, w, m);
     // critic
     ppo_value_head_back(s, t, w.part, m, Hc, w.dv, nc.oWmu, nc.obmu, w.Zc[Lc], w.Ac[Lc], w.d0);
@@ -2353,6 +2350,25 @@ void ppo_norm_stale(hk_handle h, int policy)
     for (int i = 0; i < h->n_ppo; i++) if (h->ppo[i].policy == policy) h->ppo[i].adv_stale = true;
 }
 
+// a recurrent actor's trunk as ppo_publish_kernel takes it: the net cut before the cell ln
+hk::PpoNet ppo_trunk_only(hk::PpoNet net, const hk::PpoLstmNet& ln)
+{
+    net.count = ln.oWih;
+    net.n_branch = 0;
+    net.oWmu = net.obmu = net.ols = net.oWbr = net.obbr = net.count;      // (no element of the trunk matches a head)
+    return net;
+}
+
+// the launches that move an actor between a flat copy (a trainer's PARAMS, a pool's slot) and a policy's inference copies (TO_POLICY: towards
+// the policy): the whole net through ppo_publish_kernel or, of a recurrent actor (ln.m > 0), its trunk, then the cell and the m-wide heads
+template <bool TO_POLICY>
+void ppo_publish_actor(hipStream_t s, hk::PolicyDevice& pd, hk::PpoNet net, const hk::PpoLstmNet& ln, float* flat)
+{
+    if (ln.m) net = ppo_trunk_only(net, ln);
+    hipLaunchKernelGGL(hk::ppo_publish_kernel<TO_POLICY>, dim3(nblk(net.count)), dim3(256), 0, s, pd.q, net, flat);
+    if (ln.m) hipLaunchKernelGGL(hk::ppo_lstm_publish_kernel<TO_POLICY>, dim3(nblk(ln.end - ln.oWih)), dim3(256), 0, s, pd.q, pd.lq, pd.braw, ln, flat);
+}
+
 // hk_ppo_create and hk_ppo_create_poca (fn): the checks both start with, critic_checks() (the entry point's own refusals, in their place in the
 // order), the config, the slot and the actor's layout; pack_critic(t, host) lays the critic out behind the actor and packs its parameters in
 // that order; then PARAMS .. ADAM_V [4][P], zeroed, the critic uploaded and the actor's weights copied from the policy.  -> the trainer's index
@@ -2378,7 +2394,6 @@ int ppo_create(hk_handle h, const char* fn, int policy, bool have_critic, const 
     t = hk_context::Ppo{};
     t.policy = policy; t.cfg = d;
     t.actor.layout(q.in_dim, q.hidden, q.n_layers, q.n_branch, 0);
-    hk::PpoNet trunk = t.actor;          // what ppo_publish_kernel moves
     if (seq_len) {
         // the trunk as laid out; the cell and the m-wide heads behind it (PpoLstmNet); the actor's head offsets follow
         hk::PpoLstmNet& ln = t.lnet;
@@ -2386,9 +2401,6 @@ int ppo_create(hk_handle h, const char* fn, int policy, bool have_critic, const 
         t.seq_len = seq_len;
         t.actor.oWmu = ln.oWmu; t.actor.obmu = ln.obmu; t.actor.ols = ln.ols; t.actor.oWbr = ln.oWbr; t.actor.obbr = ln.obbr;
         t.actor.count = ln.end;
-        trunk.count = ln.oWih;
-        trunk.n_branch = 0;
-        trunk.oWmu = trunk.obmu = trunk.ols = trunk.oWbr = trunk.obbr = trunk.count;      // (no element of the trunk matches a head)
     }
     std::vector<float> host;
     pack_critic(t, host);
@@ -2397,10 +2409,7 @@ int ppo_create(hk_handle h, const char* fn, int policy, bool have_critic, const 
     if (e == hipSuccess) e = hipMemsetAsync(t.param, 0, 4 * t.P * sizeof(float), h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(t.param + t.actor.count, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(hk::ppo_publish_kernel<false>, dim3(nblk(trunk.count)), dim3(256), 0, h->stream, q, trunk, t.param);
-        if (seq_len)
-            hipLaunchKernelGGL(hk::ppo_lstm_publish_kernel<false>, dim3(nblk(t.lnet.end - t.lnet.oWih)), dim3(256), 0, h->stream, q, h->policy[policy].lq,
-                               h->policy[policy].braw, t.lnet, t.param);
+        ppo_publish_actor<false>(h->stream, h->policy[policy], t.actor, t.lnet, t.param);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -2424,26 +2433,37 @@ static void ppo_release(hk_context::Ppo& t)
 
 extern "C++" {
 namespace {
+// what hk_ppo_create, hk_ppo_create_recurrent and hk_ppo_create_recurrent_critic refuse of the critic's trunk and value head (f: the entry
+// point's name and ": ") ...
+int ppo_critic_checks(hk_handle h, const std::string& f, const hk_policy_desc* c, const hk::PolicyParams& q)
+{
+    if (c->in_dim != q.in_dim) return fail(h, HK_ERR_INVALID, f + "the critic's in_dim differs from the actor's");
+    if (c->hidden < 32 || c->hidden > HK_POLICY_MAX_HIDDEN || c->hidden % 32 || c->n_layers < 1 || c->n_layers > HK_POLICY_MAX_LAYERS || c->n_branch != 0)
+        return fail(h, HK_ERR_INVALID, f + "critic hidden / n_layers out of the actor's limits, or n_branch != 0");
+    for (int l = 0; l < c->n_layers; l++) if (!c->W[l] || !c->b[l]) return fail(h, HK_ERR_INVALID, f + "NULL critic layer weights");
+    if (!c->W_mu || !c->b_mu) return fail(h, HK_ERR_INVALID, f + "NULL critic value head");
+    return HK_OK;
+}
+
+// ... and the trunk's layers packed at t.critic's offsets into host, the critic's part of PARAMS (it starts at offset t.actor.count)
+void ppo_pack_critic_trunk(const hk_context::Ppo& t, const hk_policy_desc* c, std::vector<float>& host)
+{
+    for (int l = 0; l < c->n_layers; l++) {
+        const size_t nw = (size_t)c->hidden * (l == 0 ? c->in_dim : c->hidden);
+        std::memcpy(&host[t.critic.oW[l] - t.actor.count], c->W[l], nw * 4);
+        std::memcpy(&host[t.critic.ob[l] - t.actor.count], c->b[l], (size_t)c->hidden * 4);
+    }
+}
+
 // hk_ppo_create and hk_ppo_create_recurrent: the feed-forward critic's checks and packing (fn names the entry point in the messages)
 int ppo_create_ff(hk_handle h, const char* fn, int policy, const hk_policy_desc* c, const hk_ppo_config* cfg, int seq_len)
 {
     const std::string f = std::string(fn) + ": ";
-    auto checks = [&](const hk::PolicyParams& q) {
-        if (c->in_dim != q.in_dim) return fail(h, HK_ERR_INVALID, f + "the critic's in_dim differs from the actor's");
-        if (c->hidden < 32 || c->hidden > HK_POLICY_MAX_HIDDEN || c->hidden % 32 || c->n_layers < 1 || c->n_layers > HK_POLICY_MAX_LAYERS || c->n_branch != 0)
-            return fail(h, HK_ERR_INVALID, f + "critic hidden / n_layers out of the actor's limits, or n_branch != 0");
-        for (int l = 0; l < c->n_layers; l++) if (!c->W[l] || !c->b[l]) return fail(h, HK_ERR_INVALID, f + "NULL critic layer weights");
-        if (!c->W_mu || !c->b_mu) return fail(h, HK_ERR_INVALID, f + "NULL critic value head");
-        return (int)HK_OK;
-    };
+    auto checks = [&](const hk::PolicyParams& q) { return ppo_critic_checks(h, f, c, q); };
     auto pack = [&](hk_context::Ppo& t, std::vector<float>& host) {
         t.critic.layout(t.actor.in_dim, c->hidden, c->n_layers, 0, t.actor.count);
         host.resize(t.critic.count);
-        for (int l = 0; l < c->n_layers; l++) {
-            const size_t nw = (size_t)c->hidden * (l == 0 ? c->in_dim : c->hidden);
-            std::memcpy(&host[t.critic.oW[l] - t.actor.count], c->W[l], nw * 4);
-            std::memcpy(&host[t.critic.ob[l] - t.actor.count], c->b[l], (size_t)c->hidden * 4);
-        }
+        ppo_pack_critic_trunk(t, c, host);
         std::memcpy(&host[t.critic.oWmu - t.actor.count], c->W_mu, (size_t)c->hidden * 4);
         host[t.critic.obmu - t.actor.count] = c->b_mu[0];
     };
@@ -2484,28 +2504,20 @@ int hk_ppo_create_recurrent_critic(hk_handle h, int policy, const hk_policy_desc
         return fail(h, HK_ERR_INVALID, f + "critic_cell: memory_size: m_v = memory_size / 2 must be a multiple of 32 in [32, 128]");
     if (!cell->W_ih || !cell->W_hh || !cell->b_ih || !cell->b_hh) return fail(h, HK_ERR_INVALID, f + "critic_cell: NULL W_ih / W_hh / b_ih / b_hh");
     // the trunk's checks are the feed-forward critic's; the pack lays the cell and the m_v-wide value head behind the trunk
-    auto checks = [&](const hk::PolicyParams& q) {
-        if (c->in_dim != q.in_dim) return fail(h, HK_ERR_INVALID, f + "the critic's in_dim differs from the actor's");
-        if (c->hidden < 32 || c->hidden > HK_POLICY_MAX_HIDDEN || c->hidden % 32 || c->n_layers < 1 || c->n_layers > HK_POLICY_MAX_LAYERS || c->n_branch != 0)
-            return fail(h, HK_ERR_INVALID, f + "critic hidden / n_layers out of the actor's limits, or n_branch != 0");
-        for (int l = 0; l < c->n_layers; l++) if (!c->W[l] || !c->b[l]) return fail(h, HK_ERR_INVALID, f + "NULL critic layer weights");
-        if (!c->W_mu || !c->b_mu) return fail(h, HK_ERR_INVALID, f + "NULL critic value head");
-        return (int)HK_OK;
-    };
+    auto checks = [&](const hk::PolicyParams& q) { return ppo_critic_checks(h, f, c, q); };
     auto pack = [&](hk_context::Ppo& t, std::vector<float>& host) {
         const size_t base = t.actor.count;
         const int Hc = c->hidden, N = 4 * mv;
         t.critic.layout(t.actor.in_dim, Hc, c->n_layers, 0, base);
         t.cnet.layout(Hc, mv, t.critic.oWmu);
+        // from here on the value head is addressed through t.critic.oWmu / obmu alone (the loss, the value pass and the head's gradients read
+        // them, as they do a feed-forward critic's); cnet.oWv / obv are read by this pack only
         t.critic.oWmu = t.cnet.oWv; t.critic.obmu = t.cnet.obv;
         t.critic.count = t.cnet.end - base;
         t.critic_m = mv; t.value_chunk = r->value_chunk_steps;
         host.resize(t.critic.count);
         auto put = [&](size_t off, const float* src, size_t k) { std::memcpy(&host[off - base], src, k * 4); };
-        for (int l = 0; l < c->n_layers; l++) {
-            put(t.critic.oW[l], c->W[l], (size_t)Hc * (l == 0 ? c->in_dim : Hc));
-            put(t.critic.ob[l], c->b[l], Hc);
-        }
+        ppo_pack_critic_trunk(t, c, host);
         put(t.cnet.oWih, cell->W_ih, (size_t)N * Hc); put(t.cnet.oWhh, cell->W_hh, (size_t)N * mv);
         put(t.cnet.obih, cell->b_ih, N); put(t.cnet.obhh, cell->b_hh, N);
         put(t.cnet.oWv, c->W_mu, mv); put(t.cnet.obv, c->b_mu, 1);
@@ -2589,22 +2601,12 @@ int hk_ppo_publish(hk_handle h, int trainer)
     if (rc) return rc;
     if ((rc = ppo_refuse_open(h, "hk_ppo_publish"))) return rc;
     auto& t = h->ppo[trainer];
-    if (t.seq_len) {          // the trunk through ppo_publish_kernel (a net that ends before the cell), then the cell and the m-wide heads
-        hk::PpoNet trunk = t.actor;
-        trunk.count = t.lnet.oWih;
-        trunk.n_branch = 0;
-        trunk.oWmu = trunk.obmu = trunk.ols = trunk.oWbr = trunk.obbr = trunk.count;
-        hipLaunchKernelGGL(hk::ppo_publish_kernel<true>, dim3(nblk(trunk.count)), dim3(256), 0, h->stream, h->policy[t.policy].q, trunk, t.param);
-        hipLaunchKernelGGL(hk::ppo_lstm_publish_kernel<true>, dim3(nblk(t.lnet.end - t.lnet.oWih)), dim3(256), 0, h->stream, h->policy[t.policy].q,
-                           h->policy[t.policy].lq, h->policy[t.policy].braw, t.lnet, t.param);
-        HK_HIP(h, hipGetLastError());
-        return HK_OK;
-    }
-    hipLaunchKernelGGL(hk::ppo_publish_kernel<true>, dim3(nblk(t.actor.count)), dim3(256), 0, h->stream, h->policy[t.policy].q, t.actor, t.param);
+    hk::PolicyDevice& pd = h->policy[t.policy];
+    ppo_publish_actor<true>(h->stream, pd, t.actor, t.lnet, t.param);
     HK_HIP(h, hipGetLastError());
-    // the bf16 inference copies, when the policy has them: rebuilt from the fp32 copies just written (each an exact copy of its master, so every
-    // weight is the master rounded once by ppo_bf16_rne: HK_PPO_SHADOW's element), whichever precision the policy is in now
-    if (h->policy[t.policy].wbf) HK_HIP(h, hk::policy_bf16_refresh(h->policy[t.policy].q, h->policy[t.policy].bq, h->stream));
+    // the bf16 inference copies, when a plain actor's policy has them: rebuilt from the fp32 copies just written (each an exact copy of its master,
+    // so every weight is the master rounded once by ppo_bf16_rne: HK_PPO_SHADOW's element), whichever precision the policy is in now
+    if (!t.seq_len && pd.wbf) HK_HIP(h, hk::policy_bf16_refresh(pd.q, pd.bq, h->stream));
     return HK_OK;
 }
 
@@ -3096,25 +3098,13 @@ int pool_create(hk_handle h, const char* fn, bool recurrent, int policy, int slo
         pl.m = m;
         pl.lnet.layout(q.hidden, m, q.n_branch, pl.net.oWmu);
         pl.actor = pl.lnet.end;
-        pl.net.count = pl.lnet.oWih;
-        pl.net.n_branch = 0;
-        pl.net.oWmu = pl.net.obmu = pl.net.ols = pl.net.oWbr = pl.net.obbr = pl.net.count;      // (no element of the trunk matches a head)
+        pl.net = ppo_trunk_only(pl.net, pl.lnet);          // (kept cut; ppo_publish_actor cuts whatever it is handed, which changes nothing here)
     }
     pl.slots = slots;
     pl.count = pl.actor + (pl.normalize ? 2 * (size_t)q.in_dim : 0);
     HK_HIP(h, hipMalloc(&pl.buf, (size_t)slots * pl.count * sizeof(float)));
     h->pool[h->n_pools] = pl;
     return h->n_pools++;
-}
-
-// the two launches that move an actor between a slot and a policy's inference copies (TO_POLICY: the load)
-template <bool TO_POLICY>
-void pool_move(hk_handle h, const hk_context::Pool& pl, hk::PolicyDevice& pd, float* slot)
-{
-    hipLaunchKernelGGL(hk::ppo_publish_kernel<TO_POLICY>, dim3(nblk(pl.net.count)), dim3(256), 0, h->stream, pd.q, pl.net, slot);
-    if (pl.m)
-        hipLaunchKernelGGL(hk::ppo_lstm_publish_kernel<TO_POLICY>, dim3(nblk(pl.lnet.end - pl.lnet.oWih)), dim3(256), 0, h->stream, pd.q, pd.lq, pd.braw,
-                           pl.lnet, slot);
 }
 
 }  // namespace
@@ -3148,7 +3138,7 @@ int hk_policy_pool_save(hk_handle h, int pool, int slot, int policy)
     auto& pl = h->pool[pool];
     hk::PolicyDevice& pd = h->policy[policy];
     float* dst = pool_slot(pl, slot);
-    pool_move<false>(h, pl, pd, dst);
+    ppo_publish_actor<false>(h->stream, pd, pl.net, pl.lnet, dst);
     HK_HIP(h, hipGetLastError());
     if (pl.normalize) {
         const size_t nb = (size_t)pl.in_dim * sizeof(float);
@@ -3173,7 +3163,7 @@ int hk_policy_pool_load(hk_handle h, int pool, int slot, int policy)
             return fail(h, HK_ERR_INVALID, "hk_policy_pool_load: the policy has a PPO trainer (its master weights would disagree with what plays)");
     hk::PolicyDevice& pd = h->policy[policy];
     float* src = pool_slot(pl, slot);
-    pool_move<true>(h, pl, pd, src);
+    ppo_publish_actor<true>(h->stream, pd, pl.net, pl.lnet, src);
     HK_HIP(h, hipGetLastError());
     if (pl.normalize) {
         const size_t nb = (size_t)pl.in_dim * sizeof(float);
