@@ -1,4 +1,4 @@
-// hk_poca.h — device side of the POCA trainer (contract in include/hk.h "POCA", host side in hk_api.hip).
+// hk_poca.h — device side of the POCA trainer (contract in include/hk.h "POCA", host side in hk_train.hip).
 // A POCA trainer is a PPO trainer whose critic is a centralised attention critic over the S agents of a group (the policy's slots in one env).
 // Per minibatch of mg groups (m = mg S agent rows, E2 = 2 m entities, NS = (S + 1) mg sequences, SR = NS S sequence rows):
 //   poca_rows_kernel        group ids -> the agent row ids ppo_gather_kernel reads (a bootstrap group -> the bootstrap rows; any other id -> -1)

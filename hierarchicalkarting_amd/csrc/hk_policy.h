@@ -160,6 +160,7 @@ inline void pm_wq_fill(float* wq, const float* W, int N, int K)
 // barrier — the epoch word is read by every lane before lane 0 rewrites it, the zero fill precedes the copy in program order — and a pair moves
 // obs_dim <= 126 floats: with 128 threads and two __syncthreads per pair the kernel took 1.9 ms per decision beside the planner's searches.)
 // rec_obs / rec_first (an open rollout's row, [E][A][obs_dim] / [E][A]; nullptr: not recording): the slice pushed and the clear
+#ifdef HK_POLICY_KERNELS      // the non-template kernels and the launchers, here and in hk_policy_bf16.h / hk_policy_lstm.h: ONE unit (hk_api.hip) defines them
 __global__ __launch_bounds__(256) void policy_stack_kernel(PolicyParams Q, int E, int A, const hk_env_state* envs_by_slot, const int* slot_of,
                                                            const float* obs, int w, float* rec_obs, int* rec_first)
 {
@@ -193,7 +194,7 @@ __global__ __launch_bounds__(256) void policy_invalidate_kernel(PolicyParams Q, 
     const int env = env_ids ? env_ids[idx / Q.n_slots] : idx / Q.n_slots;
     Q.epoch[(size_t)env * Q.n_slots + idx % Q.n_slots] = -1;
 }
-
+#endif  /* HK_POLICY_KERNELS */
 
 // One wave's share of a layer over kc inputs: acc0 (+ acc1 when HAS1) += A[32 rows][kc] * B[kc][32 cols], as MFMA
 // 32x32x2 f32 steps in ascending k.  a?p already point at this lane's first element of A (LDS, row stride PM_LD per k); B comes from
@@ -606,6 +607,7 @@ inline void policy_free(PolicyDevice& pd)
 // The actor kernels use ~68 KB of dynamic LDS and more, above the 64 KB default: raise the limit once per DEVICE (the attribute belongs to
 // the device's code object; a second handle on another device needs it too).  Guarded by a mutex: handles of different
 // devices may be driven from different host threads.
+#ifdef HK_POLICY_KERNELS
 inline void policy_raise_lds_limit_once()
 {
     static std::mutex mu;
@@ -647,5 +649,6 @@ inline int policy_launch_mlp(const PolicyDevice& pd, int rows, const float* src,
     }
     return launch(H <= 128 ? policy_mlp_kernel<0> : H == 256 ? policy_mlp_kernel<1> : policy_mlp_kernel<2>, "policy_mlp_kernel", policy_lds_bytes(pd.q));
 }
+#endif  /* HK_POLICY_KERNELS */
 
 }  // namespace hk

@@ -45,6 +45,7 @@ inline size_t policy_bf16_layer_elems(const PolicyParams& q, int l) { return (si
 
 // Wf[l] from the CURRENT fp32 inference copy Wt[l] ([k][hidden]), each weight rounded once: element ((cb * nsteps + s) * 64 + lane) * 8 + j
 // = W[k = 16 s + 8 (lane >> 5) + j][col = 32 cb + (lane & 31)], +0.0 where k >= K.  One thread per element.
+#ifdef HK_POLICY_KERNELS
 __global__ __launch_bounds__(256) void policy_bf16_build_kernel(PolicyParams Q, PolicyBf16 B, int l)
 {
     const int H = Q.hidden, K = l == 0 ? Q.in_dim : H;
@@ -58,7 +59,8 @@ __global__ __launch_bounds__(256) void policy_bf16_build_kernel(PolicyParams Q, 
 }
 
 // (re)build every layer's copy on `stream` — the switch to HK_POLICY_PREC_BF16 and hk_ppo_publish, after the fp32 copies are written
-inline hipError_t policy_bf16_refresh(const PolicyParams& q, const PolicyBf16& bq, hipStream_t stream)
+// (out of line, in the unit that has the kernel; hk_train.hip sees the declaration alone)
+__attribute__((visibility("hidden"))) hipError_t policy_bf16_refresh(const PolicyParams& q, const PolicyBf16& bq, hipStream_t stream)
 {
     for (int l = 0; l < q.n_layers; l++) {
         const size_t n = policy_bf16_layer_elems(q, l);
@@ -66,6 +68,9 @@ inline hipError_t policy_bf16_refresh(const PolicyParams& q, const PolicyBf16& b
     }
     return hipGetLastError();
 }
+#else
+__attribute__((visibility("hidden"))) hipError_t policy_bf16_refresh(const PolicyParams& q, const PolicyBf16& bq, hipStream_t stream);
+#endif  /* HK_POLICY_KERNELS */
 
 // One wave's share of a layer over ns k-steps (a multiple of 4): acc0 (+ acc1 when TWO) += A[32 rows][16 ns] * B[16 ns][32 cols].  a?p: this
 // lane's first 8 elements of its row of X; bp: this lane's 16 bytes of the first step's B operand (64 x 16 bytes per step).  The B loads run

@@ -65,6 +65,7 @@ inline size_t policy_lstm_lds_bytes(const PolicyParams& q, const PolicyLstm& l)
 // The first decision of an episode starts from zero memory: the `stale` test of policy_stack_kernel (pm_episode_word) on the epoch word that
 // kernel rewrites — so this one is issued BEFORE it, and FIRST == 1 if and only if the memory read is zero.  One wave per (env, slot).
 // rec_mem (an open rollout's MEMORY row, [E][A][mem_max]; nullptr: not recording): the memory the decision reads, after the clear.
+#ifdef HK_POLICY_KERNELS      // (hk_policy.h: the kernels, in the one unit that defines them)
 __global__ __launch_bounds__(256) void policy_memory_kernel(PolicyParams Q, PolicyLstm L, int E, int A, const hk_env_state* envs_by_slot, const int* slot_of,
                                                             float* rec_mem, int mem_max)
 {
@@ -294,6 +295,7 @@ __global__ __launch_bounds__(PM_THREADS, 2) void policy_lstm_kernel(PolicyParams
     __syncthreads();
     pm_tail(Q, Ht, head, rows, row0, decision, env_id_base, A, mu_out, logit_out, act_steer, act_branch, rec, tid, m);
 }
+#endif  /* HK_POLICY_KERNELS */
 
 // ---------------------------------------------------------------------------------------------------------------------
 inline int policy_lstm_validate(const hk_policy_lstm_desc* l, std::string& err)

@@ -1,4 +1,4 @@
-// hk_ppo.h — device side of the PPO trainer (contract in include/hk.h "PPO trainer", host side in hk_api.hip).
+// hk_ppo.h — device side of the PPO trainer (contract in include/hk.h "PPO trainer", host side in hk_train.hip).
 // Per minibatch of m rows (ids into the rollout's n = R * E * S rows):
 //   ppo_gather_kernel       the stacked input of every row rebuilt from OBS / FIRST / RING0 (NEXT_OBS for the bootstrap rows), normalised
 //                           and clipped exactly as policy_mlp_kernel's loader does: X0 [m][in_dim] (a workspace sized by the minibatch)

@@ -1,5 +1,5 @@
 // hk_ppo_lstm.h — device side of recurrent training: PPO with truncated BPTT through the actor's LSTM cell (contract in include/hk.h
-// "PPO trainer" RECURRENT, host side in hk_api.hip).  A minibatch is ms sequences of L = sequence_length rows, gathered
+// "PPO trainer" RECURRENT, host side in hk_train.hip).  A minibatch is ms sequences of L = sequence_length rows, gathered
 // TIME-MAJOR: row = tau ms + q, so the rows of one time step are a contiguous block and everything that is not recurrent — the gather, the
 // trunk, the critic, the loss, the weight gradients — runs once over all M = L ms rows on hk_ppo.h's kernels.  New here:
 //   ppo_lstm_expand_kernel      sequence ids -> per-row ids (-1: a dead row or a skipped sequence), the rows' FIRST words and the windows'

@@ -1,5 +1,5 @@
 // hk_ppo_lstm_critic.h — device side of the recurrent critic of recurrent PPO (contract in include/hk.h "PPO trainer" RECURRENT CRITIC, host
-// side in hk_api.hip).  The critic is the actor's normalised input -> n x (Linear + Swish) of width Hc -> ONE LSTM cell of m_v units
+// side in hk_train.hip).  The critic is the actor's normalised input -> n x (Linear + Swish) of width Hc -> ONE LSTM cell of m_v units
 // -> v = b_v + sum_k W_v[k] h'[k], in the arithmetic of a recurrent actor (hk_policy_lstm.h): its training forward and backward over a window
 // are hk_ppo_lstm.h's kernels on a second workspace.  New here:
 //   ppo_lstm_value_ids_kernel     the row ids of a chunk of the value pass, time-major: (t0 + tl) E S + p0 + q; t == R gives the bootstrap ids;

@@ -6,7 +6,7 @@
 //                            ppo_adv_norm_kernel does) into one hk_episode_stats.  No float atomics: the same call gives the same bits.
 // The snapshot pool needs no kernel of its own: it launches ppo_publish_kernel<false / true> and policy_bf16_build_kernel as they are.
 #pragma once
-#include "hk_policy.h"
+#include "hk_handle.h"      // EpisodeCarry, which the handle holds two of
 
 namespace hk {
 
@@ -16,13 +16,6 @@ struct EpisodeRows {
     const int* done;
     int R, E, A, S;
     int slots[HK_MAX_AGENTS];
-};
-
-// the state of the episode in progress, per [E][A]: what the rows after the last DONE have summed.  whole: the episode's first row lies
-// inside the chain of rollouts the carry has been handed along (0: it began before the chain; its end is a partial episode)
-struct EpisodeCarry {
-    float *ret, *gret;
-    int *len, *whole;
 };
 
 __device__ __forceinline__ void episode_stats_zero(hk_episode_stats& s)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""What a host-side refactor of the environment half of hk_api.hip must leave as it is: one fixed course through the entry points outside the
-trainers (LQ batch, reset / actions / step, policy attach / forward / memory, the rollout recorder, snapshot pools, episode statistics, the
+"""What a host-side refactor of hk_api.hip (the environment's unit) or of hk_handle.h must leave as it is: one fixed course through the entry
+points outside the trainers — the snapshot pools, which live in hk_train.hip, are on it too — (LQ batch, reset / actions / step, policy attach / forward / memory, the rollout recorder, snapshot pools, episode statistics, the
 state getters and setters, the RCCL gather, the device-pointer getters, the profiler), printed as one JSON document.  Run it once per
 library, each in a fresh process, and compare the two outputs byte for byte:
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What a host-side refactor of the trainers must leave bit for bit: one fixed course through the PPO trainer (f32, then bf16), the POCA
+"""What a host-side refactor of the trainers (hk_train.hip, and hk_handle.h under it) must leave bit for bit: one fixed course through the PPO trainer (f32, then bf16), the POCA
 trainer and the recurrent PPO trainer (feed-forward critic, then recurrent critic), with a SHA-256 of every readable trainer field, of the
 returned stats and of the update report after each step, printed as one JSON document.  Run it once per library, each in a fresh process, and
 compare the two outputs byte for byte:
