@@ -262,6 +262,9 @@ SYMBOLS = {
     "hk_policy_memory_get": (C.c_int, [_H, C.c_int, _fp]),
     "hk_policy_memory_set": (C.c_int, [_H, C.c_int, _fp]),
     "hk_policy_memory_clear": (C.c_int, [_H, C.c_int]),
+    "hk_policy_lstm_set_precision": (C.c_int, [_H, C.c_int, C.c_int]),
+    "hk_ppo_recurrent_set_precision": (C.c_int, [_H, C.c_int, C.c_int]),
+    "hk_ppo_lstm_gates_bf16": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hk_get_actions": (C.c_int, [_H, _fp, C.POINTER(C.c_int32)]),
     "hk_rollout_begin": (C.c_int, [_H, C.c_int]),
     "hk_rollout_rows": (C.c_int, [_H]),

@@ -1106,6 +1106,40 @@ int hk_policy_set_precision(hk_handle h, int policy, int precision)
     return HK_OK;
 }
 
+// hk_policy_set_precision for a policy with memory (hk.h "RECURRENT ACTORS IN BF16"): the trunk's copies as above, and the cell's beside them
+int hk_policy_lstm_set_precision(hk_handle h, int policy, int precision)
+{
+    HK_NEED_ENV(h);
+    if (policy < 0 || policy >= h->n_policies) return fail(h, HK_ERR_INVALID, "hk_policy_lstm_set_precision: bad policy index");
+    if (precision != HK_POLICY_PREC_F32 && precision != HK_POLICY_PREC_BF16) return fail(h, HK_ERR_INVALID, "hk_policy_lstm_set_precision: unknown precision");
+    if (h->ro.open) return fail(h, HK_ERR_INVALID, "hk_policy_lstm_set_precision: refused while a rollout is open (hk_rollout_close first)");
+    hk::PolicyDevice& pd = h->policy[policy];
+    if (pd.lq.m == 0) return fail(h, HK_ERR_INVALID, "hk_policy_lstm_set_precision: the policy has no memory (use hk_policy_set_precision)");
+    if (precision == HK_POLICY_PREC_BF16 && !pd.wlbf) {
+        // one allocation for the trunk's and one for the cell's fragment-major bf16 copies, built on the stream from the CURRENT fp32 copies
+        size_t off[HK_POLICY_MAX_LAYERS + 1] = {};
+        for (int l = 0; l < pd.q.n_layers; l++) off[l + 1] = off[l] + hk::policy_bf16_layer_elems(pd.q, l);
+        const size_t n_ih = hk::policy_lstm_bf16_ih_elems(pd.q, pd.lq), n_hh = hk::policy_lstm_bf16_hh_elems(pd.lq);
+        uint16_t *wbf = nullptr, *wlbf = nullptr;
+        hipError_t e = hipMalloc(&wbf, off[pd.q.n_layers] * sizeof(uint16_t));
+        if (e == hipSuccess) e = hipMalloc(&wlbf, (n_ih + n_hh) * sizeof(uint16_t));
+        hk::PolicyBf16 bq{};
+        for (int l = 0; l < pd.q.n_layers; l++) bq.Wf[l] = wbf + off[l];
+        const hk::PolicyLstmBf16 lbq{wlbf, wlbf + n_ih};
+        if (e == hipSuccess) e = hk::policy_bf16_refresh(pd.q, bq, h->stream);
+        if (e == hipSuccess) e = hk::policy_lstm_bf16_refresh(pd.q, pd.lq, lbq, h->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(wbf);
+            (void)hipFree(wlbf);
+            HK_HIP(h, e);
+        }
+        pd.wbf = wbf; pd.bq = bq;
+        pd.wlbf = wlbf; pd.lbq = lbq;
+    }
+    pd.prec = precision;
+    return HK_OK;
+}
+
 int hk_policy_get_precision(hk_handle h, int policy)
 {
     if (!h) return fail(nullptr, HK_ERR_INVALID, "NULL handle");

@@ -83,14 +83,22 @@ struct PolicyLstm {
     float* mem;                              // [E][n_slots][2m] = [h | c], indexed like the ring; nullptr for a forward-only policy
 };
 
+// HK_POLICY_PREC_BF16 of a policy with memory (hk_policy_lstm_bf16.h): the bf16 copies of the cell's weights, an argument of policy_lstm_bf16_kernel alone
+struct PolicyLstmBf16 {
+    const uint16_t* Wf_ih;                   // fragment-major [unit block][gate][k step][lane][8], K = hidden padded to 64; nullptr until the first switch
+    const uint16_t* Wf_hh;                   // likewise, K = m (m / 16 whole steps)
+};
+
 struct PolicyDevice {
     PolicyParams q{};
     PolicyBf16 bq{};
     PolicyLstm lq{};
+    PolicyLstmBf16 lbq{};
     float* wlstm = nullptr;                  // the allocation behind lq's weights (hk_policy_attach_lstm)
     float* braw = nullptr;                   // [8m] = b_ih | b_hh as attached or last published, in wlstm (a recurrent trainer's master copy reads them)
     float* weights = nullptr;                // one allocation behind every const float* above
     uint16_t* wbf = nullptr;                 // the second allocation, behind bq.Wf: made by the first switch to HK_POLICY_PREC_BF16
+    uint16_t* wlbf = nullptr;                // ... and behind lbq, made by the first hk_policy_lstm_set_precision(HK_POLICY_PREC_BF16)
     int prec = HK_POLICY_PREC_F32;           // hk_policy_set_precision: which chain policy_launch_mlp runs
     bool used = false;
 };
@@ -591,12 +599,14 @@ inline int policy_upload(PolicyDevice& pd, const hk_policy_desc* d, int index, i
 }  // namespace hk
 #include "hk_policy_bf16.h"      // policy_mlp_bf16_kernel: the same decision on the bf16 matrix cores (HK_POLICY_PREC_BF16)
 #include "hk_policy_lstm.h"      // policy_lstm_kernel: the trunk, then one LSTM cell, the heads on h' (a policy with memory)
+#include "hk_policy_lstm_bf16.h" // policy_lstm_bf16_kernel: that decision with the trunk and the gate chains on the bf16 matrix cores
 namespace hk {
 
 inline void policy_free(PolicyDevice& pd)
 {
     if (pd.weights) (void)hipFree(pd.weights);
     if (pd.wbf) (void)hipFree(pd.wbf);
+    if (pd.wlbf) (void)hipFree(pd.wlbf);
     if (pd.wlstm) (void)hipFree(pd.wlstm);
     if (pd.lq.mem) (void)hipFree(pd.lq.mem);
     if (pd.q.ring) (void)hipFree(pd.q.ring);
@@ -641,6 +651,11 @@ inline int policy_launch_mlp(const PolicyDevice& pd, int rows, const float* src,
         // a policy with memory: lstm_mem [rows][2m] (nullptr: the policy's own buffer), read and rewritten in place
         float* mem = lstm_mem ? lstm_mem : pd.lq.mem;
         if (!mem) { err = "policy_lstm_kernel: no memory buffer"; return HK_ERR_INVALID; }
+        if (pd.prec == HK_POLICY_PREC_BF16) {
+            if (!pd.wbf || !pd.wlbf) { err = "policy_lstm_bf16_kernel: the policy has no bf16 weights"; return HK_ERR_INVALID; }
+            return launch(H <= 128 ? policy_lstm_bf16_kernel<false> : policy_lstm_bf16_kernel<true>, "policy_lstm_bf16_kernel",
+                          policy_lstm_bf16_lds_bytes(pd.q, pd.lq), pd.bq, pd.lq, pd.lbq, mem);
+        }
         return launch(policy_lstm_kernel, "policy_lstm_kernel", policy_lstm_lds_bytes(pd.q, pd.lq), pd.lq, mem);
     }
     if (pd.prec == HK_POLICY_PREC_BF16) {

@@ -12,6 +12,7 @@
 #include "hk_handle.h"
 #include "hk_ppo.h"
 #include "hk_ppo_lstm.h"
+#include "hk_ppo_lstm_bf16.h"
 #include "hk_ppo_lstm_critic.h"
 #include "hk_poca.h"
 
@@ -149,7 +150,8 @@ size_t ppo_ws_layout(const hk_context::Ppo& t, int M, PpoWs* w)
     PpoWs d{};
     d.ids = (int*)a.take(Mz * 4); d.valid = (int*)a.take(Mz * 4); d.n_valid = (int*)a.take(16);
     d.X0 = mat(Mz * in, bf);
-    for (int l = 0; l < t.actor.n_layers; l++) { d.Za[l] = fl(Mz * Ha); d.Aa[l] = mat(Mz * Ha, bf && l < t.actor.n_layers - 1); }
+    // (a recurrent actor's last post-activation is bf16 too: it is an operand of the cell's product and no head reads it)
+    for (int l = 0; l < t.actor.n_layers; l++) { d.Za[l] = fl(Mz * Ha); d.Aa[l] = mat(Mz * Ha, bf && (l < t.actor.n_layers - 1 || t.seq_len)); }
     for (int l = 0; l < t.critic.n_layers; l++) { d.Zc[l] = fl(Mz * Hc); d.Ac[l] = mat(Mz * Hc, bf && l < t.critic.n_layers - 1); }
     d.d0 = mat(Mz * Hm, bf); d.d1 = mat(Mz * Hm, bf);
     d.dhead = fl(Mz * hk::PM_MAX_OUT); d.dls = fl(Mz); d.dv = fl(Mz);
@@ -574,6 +576,7 @@ template <typename Net> PpoCell ppo_cell(const Net& n) { return PpoCell{n.m, n.h
 struct PpoLstmWs {
     int *rowids, *first;
     float *mem0, *bsum, *GZ, *hnew, *mbmem, *hprev, *cprev, *dH, *drec, *dcar, *part;
+    uint16_t *GZb, *hprevb;          // HK_PPO_PREC_BF16 (the actor's cell): the gate deltas and h_prev as the products read them; nullptr otherwise
 };
 
 enum PpoCellOf { PPO_ACTOR_CELL, PPO_CRITIC_CELL };          // whose cell a workspace serves
@@ -598,6 +601,7 @@ size_t ppo_lstm_ws_layout(const hk_context::Ppo& t, PpoCellOf of, int M, PpoLstm
     d.GZ = fl(Mz * 4 * mc); d.hnew = fl(Mz * mc); d.mbmem = fl(Mz * 2 * mc); d.hprev = fl(Mz * mc); d.cprev = fl(Mz * mc); d.dH = fl(Mz * mc);
     d.drec = fl(ms * mc); d.dcar = fl(ms * mc);
     d.part = fl(nz * mn);
+    if (!critic && t.prec == HK_PPO_PREC_BF16) { d.GZb = (uint16_t*)a.take(Mz * 4 * mc * 2); d.hprevb = (uint16_t*)a.take(Mz * mc * 2); }
     if (w) *w = d;
     return a.off;
 }
@@ -624,7 +628,19 @@ void ppo_cell_bsum(hipStream_t s, const hk_context::Ppo& t, const PpoCell& c, fl
 // apart because the value pass sums the bias once and projects every chunk
 void ppo_cell_project(hipStream_t s, const hk_context::Ppo& t, const PpoCell& c, int M, PpoMat A, const float* bsum, float* Zx)
 {
-    ppo_product<0>(s, M, 4 * c.m, c.H, A, c.H, true, PpoMat(t.param + c.oWih), c.H, true, bsum, PpoMat(Zx), 4 * c.m, nullptr, c.H);
+    ppo_product<0>(s, M, 4 * c.m, c.H, A, c.H, true, ppo_weights(t, c.oWih), c.H, true, bsum, PpoMat(Zx), 4 * c.m, nullptr, c.H);
+}
+
+// step tau of a cell's forward over ms rows: GZ's Zx continued over h with W_hh (of h's kind: the step kernel of that precision), then the cell.
+// htap (hk_ppo_lstm_gates_bf16 only): h as given, no cell, GZ returns the pre-activations
+void ppo_cell_step(hipStream_t s, int tau, int ms, int m, PpoMat Whh, const PpoLstmWs& r, const int* first, const uint16_t* htap = nullptr)
+{
+    if (Whh.b)
+        hipLaunchKernelGGL(hk::ppo_lstm_step_bf16_kernel, dim3(nblk(m, hk::PB_TN), nblk(ms, hk::PB_TM)), dim3(256), 0, s, tau, ms, m, Whh.b, r.mem0, first, htap,
+                           r.GZ, r.hnew, r.mbmem, r.hprev, r.hprevb, r.cprev);
+    else
+        hipLaunchKernelGGL(hk::ppo_lstm_step_kernel, dim3(nblk(m, hk::PPO_TN), nblk(ms, hk::PPO_TM)), dim3(256), 0, s, tau, ms, m, Whh.f, r.mem0, first, r.GZ,
+                           r.hnew, r.mbmem, r.hprev, r.cprev);
 }
 
 // a cell's forward over a minibatch's ms windows (M = L ms time-major rows) in its workspace r: the input projection over all rows at once, then
@@ -634,9 +650,8 @@ void ppo_cell_forward(hipStream_t s, const hk_context::Ppo& t, const PpoCell& c,
     const int L = t.seq_len;
     ppo_cell_bsum(s, t, c, r.bsum);
     ppo_cell_project(s, t, c, L * ms, A, r.bsum, r.GZ);
-    const dim3 grid(nblk(c.m, hk::PPO_TN), nblk(ms, hk::PPO_TM));
-    for (int tau = 0; tau < L; tau++)
-        hipLaunchKernelGGL(hk::ppo_lstm_step_kernel, grid, dim3(256), 0, s, tau, ms, c.m, t.param + c.oWhh, r.mem0, first, r.GZ, r.hnew, r.mbmem, r.hprev, r.cprev);
+    const PpoMat Whh = A.b ? ppo_weights(t, c.oWhh) : PpoMat(t.param + c.oWhh);
+    for (int tau = 0; tau < L; tau++) ppo_cell_step(s, tau, ms, c.m, Whh, r, first);
 }
 
 // a cell's backward from r.dH = dL / dh' as the heads left it: the L steps in reverse, the cell's weight gradients over all rows at once (through
@@ -648,17 +663,26 @@ int ppo_cell_backward(hk_handle h, const hk_context::Ppo& t, const PpoCell& c, c
     const int L = t.seq_len, M = L * ms, m = c.m, N = 4 * m, H = c.H, top = net.n_layers - 1;
     float* prm = t.param;
     float* grad = t.param + t.P;
+    // the gate deltas, h_prev and the cell's weights as the products read them: of A[top]'s kind (bf16: rounded once by the kernels that make them)
+    const bool bf = A[top].b != nullptr;
+    const PpoMat dG = bf ? PpoMat(r.GZb) : PpoMat(r.GZ), hp = bf ? PpoMat(r.hprevb) : PpoMat(r.hprev);
+    const PpoMat Wih = bf ? ppo_weights(t, c.oWih) : PpoMat(prm + c.oWih), Whh = bf ? ppo_weights(t, c.oWhh) : PpoMat(prm + c.oWhh);
+    auto at = [](PpoMat x, size_t o) { return x.b ? PpoMat(x.b + o) : PpoMat(x.f + o); };
     for (int tau = L - 1; tau >= 0; tau--) {
-        hipLaunchKernelGGL(hk::ppo_lstm_back_kernel, dim3(nblk((size_t)ms * m)), dim3(256), 0, s, tau, ms, m, (int)(tau == L - 1), first, r.dH, r.drec, r.mbmem,
-                           r.cprev, r.GZ, r.dcar);
+        const dim3 grid(nblk((size_t)ms * m));
+        if (bf)
+            hipLaunchKernelGGL(hk::ppo_lstm_back_bf16_kernel, grid, dim3(256), 0, s, tau, ms, m, (int)(tau == L - 1), first, r.dH, r.drec, r.mbmem, r.cprev, r.GZ,
+                               r.GZb, r.dcar);
+        else
+            hipLaunchKernelGGL(hk::ppo_lstm_back_kernel, grid, dim3(256), 0, s, tau, ms, m, (int)(tau == L - 1), first, r.dH, r.drec, r.mbmem, r.cprev, r.GZ, r.dcar);
         if (tau > 0)          // the recurrent delta to tau - 1: dG_tau [ms][4m] W_hh [4m][m]
-            ppo_product<0>(s, ms, m, N, PpoMat(r.GZ + (size_t)tau * ms * N), N, true, PpoMat(prm + c.oWhh), m, false, nullptr, PpoMat(r.drec), m, nullptr, N);
+            ppo_product<0>(s, ms, m, N, at(dG, (size_t)tau * ms * N), N, true, Whh, m, false, nullptr, PpoMat(r.drec), m, nullptr, N);
     }
-    ppo_wgrad(s, r.part, N, H, M, PpoMat(r.GZ), N, A[top], H, grad + c.oWih, nullptr);
-    ppo_wgrad(s, r.part, N, m, M, PpoMat(r.GZ), N, PpoMat(r.hprev), m, grad + c.oWhh, nullptr);
-    ppo_colsum(s, PpoMat(r.GZ), M, N, N, grad + c.obih);
+    ppo_wgrad(s, r.part, N, H, M, dG, N, A[top], H, grad + c.oWih, nullptr);
+    ppo_wgrad(s, r.part, N, m, M, dG, N, hp, m, grad + c.oWhh, nullptr);
+    ppo_colsum(s, dG, M, N, N, grad + c.obih);
     HK_HIP(h, hipMemcpyAsync(grad + c.obhh, grad + c.obih, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));      // both biases: the same gradient
-    ppo_product<2>(s, M, H, N, PpoMat(r.GZ), N, true, PpoMat(prm + c.oWih), H, false, nullptr, w.d0, H, Z[top], N);
+    ppo_product<2>(s, M, H, N, dG, N, true, Wih, H, false, nullptr, w.d0, H, Z[top], N);
     ppo_trunk_backward(s, t, net, r.part, w.X0, M, Z, A, w.d0, w.d1);
     return HK_OK;
 }
@@ -1159,6 +1183,11 @@ int hk_ppo_publish(hk_handle h, int trainer)
     // the bf16 inference copies, when a plain actor's policy has them: rebuilt from the fp32 copies just written (each an exact copy of its master,
     // so every weight is the master rounded once by ppo_bf16_rne: HK_PPO_SHADOW's element), whichever precision the policy is in now
     if (!t.seq_len && pd.wbf) HK_HIP(h, hk::policy_bf16_refresh(pd.q, pd.bq, h->stream));
+    // ... and a recurrent actor's (hk_policy_lstm_set_precision made them): the trunk's and the cell's
+    if (t.seq_len && pd.wlbf) {
+        HK_HIP(h, hk::policy_bf16_refresh(pd.q, pd.bq, h->stream));
+        HK_HIP(h, hk::policy_lstm_bf16_refresh(pd.q, pd.lq, pd.lbq, h->stream));
+    }
     return HK_OK;
 }
 
@@ -1380,21 +1409,15 @@ int hk_ppo_normalizer_update(hk_handle h, int trainer)
     return HK_OK;
 }
 
-int hk_ppo_set_precision(hk_handle h, int trainer, int precision)
+// the switch itself, after the entry point's refusals (hk_ppo_set_precision, hk_ppo_recurrent_set_precision)
+static int ppo_switch_precision(hk_handle h, hk_context::Ppo& t, int precision)
 {
-    HK_NEED_ENV(h);
-    int rc = ppo_check(h, trainer, "hk_ppo_set_precision", false);
-    if (rc) return rc;
-    if (precision != HK_PPO_PREC_F32 && precision != HK_PPO_PREC_BF16) return fail(h, HK_ERR_INVALID, "hk_ppo_set_precision: unknown precision");
-    auto& t = h->train->ppo[trainer];
-    if (t.poca && precision != HK_PPO_PREC_F32) return fail(h, HK_ERR_UNSUPPORTED, "hk_ppo_set_precision: a POCA trainer has no bf16 products (hk.h \"POCA\")");
-    if (t.seq_len && precision != HK_PPO_PREC_F32)
-        return fail(h, HK_ERR_UNSUPPORTED, "hk_ppo_set_precision: precision: a recurrent trainer has no bf16 products (hk.h \"PPO trainer\" RECURRENT)");
     if (precision == t.prec) return HK_OK;
     // the workspace is laid out per precision: drop it once the stream is done with it (the next minibatch allocates the other layout)
     HK_HIP(h, hipStreamSynchronize(h->stream));
     t.cap = 0; t.last_m = 0;
     HK_HIP(h, dev_free(t.ws));
+    if (t.seq_len) { t.rcap = 0; t.last_ms = 0; HK_HIP(h, dev_free(t.rws)); }          // (a recurrent trainer's cell workspace likewise)
     if (precision == HK_PPO_PREC_BF16 && !t.shadow) {
         t.shadow_pad = (8 - t.actor.count % 8) % 8;
         HK_HIP(h, hipMalloc(&t.shadow, (t.P + t.shadow_pad) * sizeof(uint16_t)));
@@ -1406,11 +1429,57 @@ int hk_ppo_set_precision(hk_handle h, int trainer, int precision)
     return HK_OK;
 }
 
+int hk_ppo_set_precision(hk_handle h, int trainer, int precision)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_check(h, trainer, "hk_ppo_set_precision", false);
+    if (rc) return rc;
+    if (precision != HK_PPO_PREC_F32 && precision != HK_PPO_PREC_BF16) return fail(h, HK_ERR_INVALID, "hk_ppo_set_precision: unknown precision");
+    auto& t = h->train->ppo[trainer];
+    if (t.poca && precision != HK_PPO_PREC_F32) return fail(h, HK_ERR_UNSUPPORTED, "hk_ppo_set_precision: a POCA trainer has no bf16 products (hk.h \"POCA\")");
+    if (t.seq_len && precision != HK_PPO_PREC_F32)
+        return fail(h, HK_ERR_UNSUPPORTED, "hk_ppo_set_precision: precision: a recurrent trainer has no bf16 products (hk.h \"PPO trainer\" RECURRENT)");
+    return ppo_switch_precision(h, t, precision);
+}
+
 int hk_ppo_get_precision(hk_handle h, int trainer)
 {
     if (!h) return fail(nullptr, HK_ERR_INVALID, "NULL handle");
     if (trainer < 0 || trainer >= h->train->n_ppo) return fail(h, HK_ERR_INVALID, "hk_ppo_get_precision: bad trainer index");
     return h->train->ppo[trainer].prec;
+}
+
+// hk_ppo_set_precision for a trainer made by hk_ppo_create_recurrent (hk.h "RECURRENT ACTORS IN BF16")
+int hk_ppo_recurrent_set_precision(hk_handle h, int trainer, int precision)
+{
+    HK_NEED_ENV(h);
+    int rc = ppo_check(h, trainer, "hk_ppo_recurrent_set_precision", false);
+    if (rc) return rc;
+    if (precision != HK_PPO_PREC_F32 && precision != HK_PPO_PREC_BF16) return fail(h, HK_ERR_INVALID, "hk_ppo_recurrent_set_precision: unknown precision");
+    auto& t = h->train->ppo[trainer];
+    if (!t.seq_len) return fail(h, HK_ERR_INVALID, "hk_ppo_recurrent_set_precision: the trainer is not recurrent (use hk_ppo_set_precision)");
+    if (t.critic_m)
+        return fail(h, HK_ERR_UNSUPPORTED, "hk_ppo_recurrent_set_precision: a trainer with a recurrent critic has no bf16 products (the critic's cell is fp32)");
+    return ppo_switch_precision(h, t, precision);
+}
+
+// a debug tap: the recurrent bf16 trainer's own two launches of the gate pre-activations on the caller's device buffers
+int hk_ppo_lstm_gates_bf16(hk_handle h, int rows, int H, int m, const void* a_dev, const void* h_dev, const void* W_ih_dev, const void* W_hh_dev, const float* bsum_dev,
+                           float* z_dev)
+{
+    HK_NEED_ENV(h);
+    if (rows < 1 || H < 1 || m < 1) return fail(h, HK_ERR_INVALID, "hk_ppo_lstm_gates_bf16: rows, H, m must be positive");
+    if (H % 32 || m % 32) return fail(h, HK_ERR_INVALID, "hk_ppo_lstm_gates_bf16: H and m must be multiples of 32");
+    if ((long long)rows * 4 * m > 0x3FFFFFFF) return fail(h, HK_ERR_INVALID, "hk_ppo_lstm_gates_bf16: rows x 4m elements do not fit");
+    if (!a_dev || !h_dev || !W_ih_dev || !W_hh_dev || !bsum_dev || !z_dev) return fail(h, HK_ERR_INVALID, "hk_ppo_lstm_gates_bf16: NULL operand");
+    hipStream_t s = h->stream;
+    // Zx = bsum + a W_ih^T (ppo_cell_project's product), then one step's chains over h without the cell (ppo_cell_step)
+    ppo_product<0>(s, rows, 4 * m, H, PpoMat((uint16_t*)a_dev), H, true, PpoMat((uint16_t*)W_ih_dev), H, true, bsum_dev, PpoMat(z_dev), 4 * m, nullptr, H);
+    PpoLstmWs r{};
+    r.GZ = z_dev;
+    ppo_cell_step(s, 0, rows, m, PpoMat((uint16_t*)W_hh_dev), r, nullptr, (const uint16_t*)h_dev);
+    HK_HIP(h, hipGetLastError());
+    return HK_OK;
 }
 
 int hk_ppo_gemm_bf16(hk_handle h, int epi, int M, int N, int K, const void* A_dev, const void* B_dev, const float* bias_dev, const float* aux_dev, float* C_dev)
@@ -1724,6 +1793,7 @@ int hk_policy_pool_load(hk_handle h, int pool, int slot, int policy)
     }
     // the bf16 inference copies, when the policy has them: rebuilt from the fp32 copies just written, whichever precision the policy is in now
     if (pd.wbf) HK_HIP(h, hk::policy_bf16_refresh(pd.q, pd.bq, h->stream));
+    if (pd.wlbf) HK_HIP(h, hk::policy_lstm_bf16_refresh(pd.q, pd.lq, pd.lbq, h->stream));      // (a recurrent pool into a bf16 policy with memory: the cell's)
     return HK_OK;
 }
 

@@ -152,6 +152,13 @@ class RacingEnv:
             raise ValueError("precision: one of %s" % sorted(self.POLICY_PRECISIONS))
         self._ck(self.L.hk_policy_set_precision(self.h, int(index), self.POLICY_PRECISIONS[precision]))
 
+    def policy_lstm_set_precision(self, index, precision):
+        """policy_set_precision for a recurrent actor (hk_policy_lstm_set_precision; hk.h "RECURRENT ACTORS IN BF16"): "bf16" runs the trunk and the
+        cell's gate products on the bf16 matrix cores, the recurrent bf16 trainer's forward bit for bit; the cell, the memory and the heads stay fp32"""
+        if precision not in self.POLICY_PRECISIONS:
+            raise ValueError("precision: one of %s" % sorted(self.POLICY_PRECISIONS))
+        self._ck(self.L.hk_policy_lstm_set_precision(self.h, int(index), self.POLICY_PRECISIONS[precision]))
+
     def policy_precision(self, index):
         rc = self.L.hk_policy_get_precision(self.h, int(index))
         if rc < 0:

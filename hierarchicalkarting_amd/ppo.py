@@ -61,6 +61,27 @@ def gemm_bf16(env, epi, A, B, bias=None, aux=None):
     return c.cpu().numpy()
 
 
+def lstm_gates_bf16(env, a, h, W_ih, W_hh, bsum):
+    """The gate pre-activations of the recurrent bf16 chain (hk_ppo_lstm_gates_bf16, a debug tap: the trainer's Zx product, then one step kernel's
+    gate chains without the cell) on uint16 bf16 bit patterns -> float32 z [rows, 4m].  a [rows, H], h [rows, m], W_ih [4m, H], W_hh [4m, m]
+    (torch layout, gates i f g o), bsum [4m] float32"""
+    import torch
+    a, h, W_ih, W_hh = (np.ascontiguousarray(x, np.uint16) for x in (a, h, W_ih, W_hh))
+    bsum = np.ascontiguousarray(bsum, np.float32)
+    (rows, H), m = a.shape, h.shape[1]
+    if h.shape != (rows, m) or W_ih.shape != (4 * m, H) or W_hh.shape != (4 * m, m) or bsum.shape != (4 * m,):
+        raise ValueError("lstm_gates_bf16: a [rows, H], h [rows, m], W_ih [4m, H], W_hh [4m, m], bsum [4m]")
+    dev = "cuda:%d" % env.built.cfg.device_id
+    up = lambda x: torch.from_numpy(x.view(np.int16) if x.dtype == np.uint16 else x).to(dev)
+    ta, th, tw, tu, tb = up(a), up(h), up(W_ih), up(W_hh), up(bsum)
+    z = torch.empty((rows, 4 * m), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    env._ck(env.L.hk_ppo_lstm_gates_bf16(env.h, rows, H, m, ptr(ta), ptr(th), ptr(tw), ptr(tu), ptr(tb), ptr(z)))
+    env.synchronize()
+    return z.cpu().numpy()
+
+
 def param_layout(in_dim, hidden, n_layers, n_branch, memory_size=0):
     """-> [(name, shape)] of one network in the flat vector's order (torch layout; n_branch 0: the critic, whose value head is W_mu / b_mu).
     memory_size > 0: a recurrent actor — the cell (W_ih, W_hh, b_ih, b_hh; gates i f g o) follows the trunk and the heads are m = memory_size / 2 wide;
@@ -339,6 +360,14 @@ class PPOTrainer:
             raise ValueError("precision: one of %s" % sorted(PRECISIONS))
         self._ck(self.env.L.hk_ppo_set_precision(self.env.h, self.t, PRECISIONS[precision]))
 
+    def set_recurrent_precision(self, precision):
+        """set_precision for a recurrent actor's trainer (hk_ppo_recurrent_set_precision; hk.h "RECURRENT ACTORS IN BF16"): "bf16" puts the trunk, the
+        gate products and the products of the cell's backward on the bf16 matrix cores — with env.policy_lstm_set_precision(index, "bf16") the
+        training forward is the inference chain bit for bit; refused for a trainer with a recurrent critic"""
+        if precision not in PRECISIONS:
+            raise ValueError("precision: one of %s" % sorted(PRECISIONS))
+        self._ck(self.env.L.hk_ppo_recurrent_set_precision(self.env.h, self.t, PRECISIONS[precision]))
+
     @property
     def precision(self):
         rc = self.env.L.hk_ppo_get_precision(self.env.h, self.t)
@@ -578,7 +607,10 @@ class PPOTrainer:
             _lib.copy_host_to_device(ptr, a.ctypes.data, a.nbytes)
         for name, a in cmem.items():
             self.write(name, a)
-        self.set_precision(d["precision"])
+        if self.sequence_length and not self.critic_memory_size:
+            self.set_recurrent_precision(d["precision"])
+        else:
+            self.set_precision(d["precision"])
         if norm is not None:
             self.normalizer_load(*norm)
         self.publish()

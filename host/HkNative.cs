@@ -542,6 +542,10 @@ namespace KartGame.AI.Native
         [DllImport(Lib)] public static extern int hk_policy_memory_get(IntPtr h, int policy, float* mem);
         [DllImport(Lib)] public static extern int hk_policy_memory_set(IntPtr h, int policy, float* mem);
         [DllImport(Lib)] public static extern int hk_policy_memory_clear(IntPtr h, int policy);
+        // recurrent actors in bf16 (hk.h "RECURRENT ACTORS IN BF16"): the policy's switch, the recurrent trainer's, and the gate-product tap on device pointers
+        [DllImport(Lib)] public static extern int hk_policy_lstm_set_precision(IntPtr h, int policy, int precision);
+        [DllImport(Lib)] public static extern int hk_ppo_recurrent_set_precision(IntPtr h, int trainer, int precision);
+        [DllImport(Lib)] public static extern int hk_ppo_lstm_gates_bf16(IntPtr h, int rows, int H, int m, IntPtr aDev, IntPtr hDev, IntPtr wIhDev, IntPtr wHhDev, float* bsumDev, float* zDev);
         [DllImport(Lib)] public static extern int hk_get_actions(IntPtr h, float* steer, int* branch);
         // rollout recorder: every decision of the attached actors writes a row of device buffers (fields: hk.h hk_rollout_field)
         [DllImport(Lib)] public static extern int hk_rollout_begin(IntPtr h, int rows);

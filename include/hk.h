@@ -509,7 +509,7 @@ int hk_policy_forward(hk_handle h, int policy, int rows, const float* obs /*[row
  * hk_policy_forward (use hk_policy_forward_mem), hk_policy_set_precision(HK_POLICY_PREC_BF16), hk_ppo_create (use hk_ppo_create_recurrent), hk_ppo_create_poca,
  * hk_policy_pool_create, and hk_policy_pool_save / _load with a feed-forward pool (use hk_policy_pool_create_recurrent: "SELF-PLAY" RECURRENT POOLS).
  * Training: hk_ppo_create_recurrent ("PPO trainer" RECURRENT).  Snapshot pools and opponent swaps: hk_policy_pool_create_recurrent.
- * Out of scope: bf16 for the cell, m above
+ * bf16 for the trunk and the cell: hk_policy_lstm_set_precision (RECURRENT ACTORS IN BF16, below).  Out of scope: m above
  * 128, stacked or bidirectional LSTMs, and a CPU-oracle restatement (the bit reference is the host build named above). */
 #define HK_POLICY_MAX_MEMORY 256          /* memory_size; m = memory_size / 2, a multiple of 32 in [32, 128] */
 typedef struct hk_policy_lstm_desc {
@@ -523,6 +523,44 @@ int hk_policy_forward_mem(hk_handle h, int policy, int rows, const float* obs /*
 int hk_policy_memory_get(hk_handle h, int policy, float* mem /*[E][n_slots][2m]*/);
 int hk_policy_memory_set(hk_handle h, int policy, const float* mem);
 int hk_policy_memory_clear(hk_handle h, int policy);
+/* RECURRENT ACTORS IN BF16 (hk_policy_lstm_set_precision for the policy, hk_ppo_recurrent_set_precision for its trainer; opt-in, the default and
+ * every call above are untouched).  ONE chain, operand for operand, for inference and for the training forward:
+ *   trunk   the bf16 chain of PRECISION above — input normalised in fp32 and rounded once, weights rounded once, the fp32 accumulator seeded
+ *           with the fp32 bias and stepped by v_mfma_f32_32x32x16_bf16 in ascending k over K padded with +0.0 to whole chunks of 64 (the
+ *           all-zero steps are issued), post-activations rounded once — with one difference: the LAST layer's post-activation a is rounded to
+ *           bf16 too, because here it is an operand of the cell's product and no head reads it.
+ *   gates   one fp32 accumulator per unit and gate (i, f, g, o), seeded with fp32(b_ih + b_hh), stepped in ascending k over a[0 .. hidden) with
+ *           the padding steps of the 64-wide chunks (hidden = 32 or 96 is not a multiple of 64), then over h[0 .. m) in m / 16 whole steps.
+ *           W_ih and W_hh are rounded once from the fp32 copies (in the trainer: the HK_PPO_SHADOW elements); h is rounded once where it is read
+ *           as an operand.  The trainer stores Zx = bsum + a W_ih^T to fp32 between the two parts, which is lossless.
+ *   cell    hk_lstm_cell, fp32 and unchanged.  c, c' and h' are fp32; the memory buffer, the recorder's MEMORY / NEXT_MEMORY rows and
+ *           HK_PPO_MB_MEMORY stay fp32 [h | c]; where FIRST is set, h and c are exactly zero.
+ *   heads   the heads, sampling, log-probabilities and the recorder's stores are the fp32 tail on the fp32 h'.
+ *   trainer backward: both operands of every product the recurrent path adds are bf16 on the matrix cores with fp32 accumulation — the recurrent
+ *           delta dG_tau W_hh, da = dG W_ih, dW_ih = dG^T a and dW_hh = dG^T h_prev.  Each operand is rounded once by the kernel that makes it
+ *           (the cell backward rounds its gate deltas as it makes them, the step kernel stores the rounded h_prev).  A bias gradient is the fp64
+ *           column sum of the rounded gate deltas.  Masters, GRAD, the Adam moments, dc, the cell backward itself, dh' from the heads and the head
+ *           weight gradients stay fp32.  No float atomics: the same call on the same state gives the same bits.
+ * Given up while the mode is on: agreement with the host twin of the fp32 chain.  Switching back restores it bit for bit.  With policy and
+ * trainer both in bf16 the training forward IS the inference chain: rho == 1, approx-KL == clip fraction == 0 at unchanged parameters; mixed
+ * settings are allowed and give small non-zero statistics, as for plain actors.
+ *   hk_policy_lstm_set_precision   for a policy WITH memory (one without: HK_ERR_INVALID, use hk_policy_set_precision).  Refused with
+ *                            HK_ERR_INVALID while a rollout is open, for an unknown precision or a bad index; a refused call leaves the precision
+ *                            as it was.  The first switch to bf16 builds the bf16 copies of the trunk layers and of W_ih / W_hh in the matrix
+ *                            instruction's operand order on hk_stream from the CURRENT fp32 copies; hk_ppo_publish of a recurrent trainer and
+ *                            hk_policy_pool_load from a recurrent pool rebuild them in the same call.  hk_policy_get_precision reports it.
+ *   hk_ppo_recurrent_set_precision ("PPO trainer" RECURRENT)  hk_ppo_set_precision for a trainer made by hk_ppo_create_recurrent; its MLP critic
+ *                            goes on the bf16 trunk path.  A trainer with a recurrent critic: HK_ERR_UNSUPPORTED, state as it was (the critic's
+ *                            cell stays fp32).  Any other trainer: HK_ERR_INVALID (use hk_ppo_set_precision).  hk_ppo_get_precision reports it.
+ *   hk_ppo_lstm_gates_bf16   a debug tap in the spirit of hk_ppo_gemm_bf16, on raw bf16 bit patterns in the caller's DEVICE buffers: the trainer's
+ *                            own two launches — the Zx product, then one step kernel's gate chains without the cell — returning the fp32
+ *                            pre-activations z [rows][4m].  a [rows][H], h [rows][m], W_ih [4m][H], W_hh [4m][m] (torch layout), bsum [4m] fp32.
+ *                            HK_ERR_INVALID: a NULL operand, non-positive sizes, H or m not a multiple of 32.  Asynchronous on hk_stream.
+ * Out of scope: bf16 for a recurrent critic's cell, bf16 memory or recorder rows, m above 128. */
+int hk_policy_lstm_set_precision(hk_handle h, int policy, int precision);
+int hk_ppo_recurrent_set_precision(hk_handle h, int trainer, int precision);
+int hk_ppo_lstm_gates_bf16(hk_handle h, int rows, int H, int m, const void* a_dev, const void* h_dev, const void* W_ih_dev, const void* W_hh_dev,
+                           const float* bsum_dev, float* z_dev);
 /* The actions currently latched for every agent (what the policies / hk_set_actions wrote): steer[E][A], branch[E][A] */
 int hk_get_actions(hk_handle h, float* steer, int32_t* branch);
 
